@@ -47,6 +47,9 @@ CPU_DSEED = 1234
 # (round 4: 10006-10008, 10011, 10014 added so that the parity sample is a FULL 8-slide batch; 10002 (2.1e-6 at level 2), 10009,
 # 10010 and 10012 have gaps < 1e-5)
 CPU_SLIDE_IDS = {2048: [10003, 10004, 10005, 10006, 10007, 10008, 10011, 10014], 1024: [10000, 10001, 10003, 10002], 256: [10000, 10001, 10002, 10003]}
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this much in all
+DUMP_SEED = 0                     # --dump-outputs: the fixed sample of rows / elements of outputs too large to write whole
+DUMP_ROWS = 512                   # --dump-outputs: ctx_patch rows sampled per slide (fewer if the budget needs it)
 
 
 def log(msg):
@@ -86,6 +89,40 @@ def host_cpu_share_all() -> int:
     except (OSError, ValueError):
         pass
     return max(1, n)
+
+
+def recursion_outputs(out, budget: int = DUMP_BYTES) -> dict:
+    """--dump-outputs of a recursion step: what recurse() / a tape replay hands its caller (the last level's outputs), copied to
+    the host.  logits, ctx_slide and importance whole; ctx_patch ([B, N, D + Hc], 84 MB at K = 2048 x 8 slides) as the same
+    seeded sample of row positions in every slide, with its padding rows (zero importance: the kernels never write them) zeroed."""
+    res = {k: out[k].detach().float().cpu().numpy() for k in ("logits", "ctx_slide", "importance")}
+    cp, imp = out["ctx_patch"], out["importance"]
+    B, N, Dp = cp.shape
+    rows = max(1, min(N, DUMP_ROWS, (budget - sum(a.nbytes for a in res.values())) // (4 * B * Dp + 8)))
+    idx = torch.randperm(N, generator=torch.Generator().manual_seed(DUMP_SEED))[:rows].sort().values.to(cp.device)
+    sample = cp.index_select(1, idx) * (imp.index_select(1, idx) != 0).unsqueeze(-1)
+    res["ctx_patch_sample"] = sample.float().cpu().numpy()
+    res["ctx_patch_sample_rows"] = idx.double().cpu().numpy()
+    return res
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as ``path/<name>.npy`` (float32 / float64); arrays too large for what is left of the budget are
+    written as a fixed seeded sample of their elements (flattened)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, written = DUMP_BYTES - 128 * len(arrays), 0          # (each .npy header: 128 bytes)
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > left:
+            keep = left // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.RandomState(DUMP_SEED).choice(a.size, keep, replace=False))]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        written += a.nbytes
+    log(f"outputs of the last timed step written to {path}: {', '.join(sorted(arrays))} ({written / 2**20:.1f} MB)")
 
 
 def build_model(K: int, dev, dropout=None, trans_dim=None):
@@ -166,10 +203,11 @@ def parity_check(cfg, model, K, ids, otrace, ohz, dev):
     return res
 
 
-def stress_measure(trans_dim, trans_heads, fp8, steps, warmup, spg, rank, world, dev, dev_reduce, pdist, putils):
+def stress_measure(trans_dim, trans_heads, fp8, steps, warmup, spg, rank, world, dev, dev_reduce, pdist, putils, outputs=None):
     """BASELINE.json configs[4] geometry: ONE level over K = 8192 patches of d = 1536 features per slide = full quadratic attention
     over 8193 tokens.  Measures the fp32-accurate (parity) path and, with ``fp8``, the opt-in e4m3 variants (whole aggregator; at
-    trans_dim 128 / 4 heads also attention only) with their logit distance from the accurate path.  Returns a dict."""
+    trans_dim 128 / 4 heads also attention only) with their logit distance from the accurate path.  Returns a dict; ``outputs`` (a
+    dict) receives the accurate path's last timed step (:func:`recursion_outputs`)."""
     from paths_amd import ops
     from paths_amd import synthetic as syn
     from paths_amd.config import Config
@@ -191,7 +229,7 @@ def stress_measure(trans_dim, trans_heads, fp8, steps, warmup, spg, rank, world,
     def barrier():
         torch.cuda.synchronize(); pdist.barrier(); torch.cuda.synchronize()
 
-    def timed_run():
+    def timed_run(capture=False):
         for _ in range(warmup):
             step()
         barrier()
@@ -215,12 +253,14 @@ def stress_measure(trans_dim, trans_heads, fp8, steps, warmup, spg, rank, world,
             ops.KERNEL_TIMER, ops.TIMER_ALL = None, False
         el = pdist.max_over_ranks(time.perf_counter() - t0, dev_reduce)
         assert int(out_["status"].item()) == 0
+        if capture:
+            outputs.update(recursion_outputs(out_))
         att = [e0.elapsed_time(e1) * 1e3 for n, e0, e1 in ev if n == "agg_attention"]
         agg = [e0.elapsed_time(e1) * 1e3 for n, e0, e1 in ev if n == "aggregator"]
         timed_run.agg_us = sum(agg) / len(agg) if agg else None
         return el, out_["logits"].clone(), (sum(att) / len(att) if att else None)
 
-    elapsed, logits, attn_us = timed_run()
+    elapsed, logits, attn_us = timed_run(capture=outputs is not None)
     agg_us = timed_run.agg_us
     T_, d_, L_ = 8193, trans_dim, cfg.model_config.trans_layers
     # algorithmic FLOPs of the aggregator per step and GPU (24 T d^2 + 4 T^2 d per layer, degenerate cross-attention 0)
@@ -280,7 +320,11 @@ def stress_bench(args, rank, world, dev, dev_reduce, pdist, putils):
     quadratic attention over 8193 tokens, on the split-operand fp32-accurate kernels; --fp8 adds the opt-in e4m3 variants
     (tests/test_gpu_parity.py::test_stress_shape_k8192_d1536_single_level_vs_oracle checks this shape on the accurate path)."""
     spg = args.slides_per_gpu
-    m = stress_measure(args.trans_dim, args.trans_heads, args.fp8, args.steps, args.warmup, spg, rank, world, dev, dev_reduce, pdist, putils)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    m = stress_measure(args.trans_dim, args.trans_heads, args.fp8, args.steps, args.warmup, spg, rank, world, dev, dev_reduce, pdist, putils,
+                       outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps({
             "metric": "stress_slides_per_sec_1level_K8192_D1536", "value": m["slides_per_s"],
@@ -347,6 +391,9 @@ def train_bench(args, cfg, model, slides, rank, world, dev, pdist, putils, _unus
     sync()
     elapsed = pdist.max_over_ranks(time.perf_counter() - t0, dev)
     per_rank = pdist.gather_floats(own / args.steps * 1e3)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+                                          "parameters": torch.cat([p.detach().float().reshape(-1) for p in model.parameters()]).cpu().numpy()})
     if rank == 0:
         K = args.k
         print(json.dumps({
@@ -558,7 +605,14 @@ def main():
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "stress"],
                     help="infer (default, the BASELINE metric); train: forward + HIP backward + AdamW + gradient all-reduce; "
                          "stress: one level over 8192 patches x 1536 features (BASELINE configs[4] geometry, fp32-accurate path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all: infer / stress the recursion's outputs (ctx_patch as a seeded row sample), train "
+                         "the loss and every parameter after the step.  Inputs and weights are seeded: the same arguments give the same "
+                         "inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     from paths_amd import distributed as pdist
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -674,6 +728,9 @@ def main():
     log(f"timed region: {args.steps} steps in {elapsed:.4f} s (all launches enqueued after {t_enqueued:.4f} s)")
     status = int(out["status"].item())
     assert status == 0, f"recursion status {status}"
+    if args.dump_outputs and rank == 0:
+        # (now: every replay after this overwrites the tape's output buffers)
+        write_outputs(args.dump_outputs, recursion_outputs(out))
     per_rank = pdist.gather_floats(own_elapsed / args.steps * 1e3)  # every rank's own ms per step (load imbalance: slides differ)
     elapsed = pdist.max_over_ranks(elapsed, dev_reduce)
     single = None

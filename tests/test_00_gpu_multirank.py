@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_children(cmds_envs, timeout=900):
+def _run_children(cmds_envs, timeout=900, cores=None):
     """Start the child processes with stdout / stderr in temporary files (a full pipe cannot stall a rank that another rank is
     waiting for inside a collective), wait for all of them, and ALWAYS reap them: on a timeout or a failure the survivors are
     killed, so no orphan keeps the GPU."""
@@ -28,7 +28,8 @@ def _run_children(cmds_envs, timeout=900):
     procs = []
     try:
         for (cmd, env), (fo, fe) in zip(cmds_envs, files):
-            procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=fo, stderr=fe, text=True))
+            procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=fo, stderr=fe, text=True,
+                                          preexec_fn=None if cores is None else (lambda: os.sched_setaffinity(0, cores))))
         deadline = time.time() + timeout
         while any(p.poll() is None for p in procs):
             if time.time() > deadline or any(p.poll() not in (None, 0) for p in procs):
@@ -162,16 +163,32 @@ def test_training_step_on_two_host_cores():
     share.  (the 1 -> 8 curve itself needs the node.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "PATHS_DIST_BACKEND")}
     env.update(PATHS_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    ms = {}
-    for cores in (0, 2):
-        out = _run_children([([sys.executable, "bench.py", "--mode", "train", "--steps", "8", "--warmup", "3", "--cores-per-rank", str(cores)], env)])[0]
+    # Other work on a shared host keeps some of its cores busy: the pinned rank gets the two idlest cores of this process's set (what
+    # a rank of the N = 8 run has to itself), and each setting is measured twice, interleaved, best of two.
+    ms = {0: [], 2: []}
+    for cores in (0, 2, 0, 2):
+        out = _run_children([([sys.executable, "bench.py", "--mode", "train", "--steps", "8", "--warmup", "3", "--cores-per-rank", str(cores)], env)],
+                            cores=_idlest_cores(2) if cores else None)[0]
         rec = json.loads([l for l in out[0].splitlines() if l.startswith("{")][-1])
-        ms[cores] = rec["ms_per_step"]
+        ms[cores].append(rec["ms_per_step"])
         assert rec["per_rank_ms_per_step"] and rec["rank_imbalance_max_over_min"] == 1.0
         if cores:
             assert "pinned to host cores" in out[1] and rec["cores_per_rank"] == 2
     print("training step, whole CPU share vs two cores:", ms)
-    assert ms[2] <= 1.10 * ms[0], ms
+    assert min(ms[2]) <= 1.10 * min(ms[0]), ms
+
+
+def _idlest_cores(n, window=0.5):
+    """The ``n`` cores of this process's affinity set with the most idle time over ``window`` seconds (/proc/stat)."""
+    import time
+
+    def idle():
+        with open("/proc/stat") as fh:
+            return {int(f[0][3:]): int(f[4]) + int(f[5]) for f in (l.split() for l in fh) if f[0].startswith("cpu") and f[0] != "cpu"}
+    a = idle()
+    time.sleep(window)
+    b = idle()
+    return sorted(sorted(os.sched_getaffinity(0), key=lambda c: b.get(c, 0) - a.get(c, 0), reverse=True)[:n])
 
 
 RCCL_WORKER = r'''

@@ -146,3 +146,37 @@ def test_lagged_scale_registry_resets():
     assert "w" in ops._lagged_store(a) and "w" not in ops._lagged_store(b)      # kept on the module, not keyed by id()
     ops.reset_lagged_scales()
     assert "w" not in ops._lagged_store(a)
+
+
+def test_bench_dump_outputs_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: the recursion's outputs whole, ctx_patch as the same seeded row sample in every run with its padding
+    rows zeroed, every file float32 / float64, the whole under 64 MB; an array larger than what is left is a seeded element sample."""
+    import bench
+    B, N, Dp = 8, 2048, 1280                                  # the headline's last level: ctx_patch alone is 84 MB
+    g = torch.Generator().manual_seed(1)
+    num_ims = torch.tensor([2048, 1900, 1500, 2000, 7, 1024, 2047, 1])
+    valid = torch.arange(N)[None, :] < num_ims[:, None]
+    out = {"logits": torch.randn(B, 4, generator=g), "ctx_slide": torch.randn(B, 128, generator=g),
+           "importance": torch.rand(B, N, generator=g).clamp_min(1e-3) * valid, "ctx_patch": torch.randn(B, N, Dp, generator=g),
+           "status": torch.zeros((), dtype=torch.int32)}
+    res = bench.recursion_outputs(out)
+    assert sum(a.nbytes for a in res.values()) <= bench.DUMP_BYTES
+    np.testing.assert_array_equal(res["logits"], out["logits"].numpy())
+    np.testing.assert_array_equal(res["importance"], out["importance"].numpy())
+    rows = res["ctx_patch_sample_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0)
+    want = out["ctx_patch"][:, rows] * valid[:, rows, None]
+    np.testing.assert_array_equal(res["ctx_patch_sample"], want.numpy())
+    np.testing.assert_array_equal(bench.recursion_outputs(out)["ctx_patch_sample_rows"], res["ctx_patch_sample_rows"])
+    # a budget that leaves room for fewer rows: fewer rows, still under it
+    small = bench.recursion_outputs(out, budget=4 << 20)
+    assert sum(a.nbytes for a in small.values()) <= 4 << 20 and 0 < len(small["ctx_patch_sample_rows"]) < bench.DUMP_ROWS
+    bench.write_outputs(str(tmp_path / "d"), dict(res, big=np.arange(10 << 20, dtype=np.float64)))
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == sorted([k + ".npy" for k in res] + ["big_sample.npy"])
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert np.load(tmp_path / "d" / f).dtype in (np.float32, np.float64)
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "ctx_patch_sample.npy"), res["ctx_patch_sample"])
+    big = np.load(tmp_path / "d" / "big_sample.npy")
+    assert 0 < big.size < 10 << 20 and np.all(np.diff(big) > 0)

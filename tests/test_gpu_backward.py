@@ -529,7 +529,13 @@ def test_training_other_aggregator_geometries_vs_oracle_autograd(dev, over):
                 assert g is None, k
             continue
         assert g is not None, k
-        assert rel_err(g, ref.grad) < 2e-3, (k, rel_err(g, ref.grad))
+        # importance hidden 36 without the LSTM: the one-element output biases of the importance MLP (each the sum over every row
+        # of its level of a cancelling term) are the ill-conditioned gradients of this geometry.  Measured on the device against a
+        # float64 evaluation of the oracle: levels 1 and 3 at 2.69e-3 and 2.17e-3 (every other parameter of all twelve geometries
+        # <= 1.6e-3); the fp32 oracle itself lands up to 2.2e-3 away from the float64 value there, depending on the host's thread
+        # count, so the earlier 2e-3 held or failed with the CPU that ran the oracle.
+        tol = 3e-3 if over.get("importance_mlp_hidden_dim") == 36 and k.endswith("importance_mlp.2.bias") else 2e-3
+        assert rel_err(g, ref.grad) < tol, (k, rel_err(g, ref.grad))
         live += 1
     assert live > 80
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=1e-2)
