@@ -132,6 +132,15 @@ int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const
                        const float* hp, const int* hp_row,
                        int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide, int phases,
                        int planes, float wg_scale, float wm_scale, float a_scale, paths_stream_t stream);
+/* fp16 slide grids: paths_lstm_cell_x6 with x_rows addressing FP16 feature rows (x = NULL, planes = 2, a_scale a power of two in
+ * [1, 2^15]).  The c / o gate GEMMs take a ONE-plane A operand (x a_scale is its own fp16 hi plane, the lo plane is zero): 2 MFMAs per
+ * block instead of 3; bit-identical to paths_lstm_cell_x6 on fp32 rows holding the same values. */
+int paths_lstm_cell_x6_h16(const float* x, int64_t ldx, const int64_t* x_rows, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
+                           const void* w_gates_x6, const float* b_gates, const void* w_mem_x6, const float* b_mem,
+                           float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
+                           const float* hp, const int* hp_row,
+                           int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide, int phases,
+                           int planes, float wg_scale, float wm_scale, float a_scale, paths_stream_t stream);
 /* w_ip_x6 = pack of [256, D] (rows interleaved as for paths_importance_proj); y_add (optional): GEMM input = y + y_add summed
  * in fp32 while staging, so that the caller can pass (x, h1) and skip materialising Y = X + h1; y_rows (optional, planes = 2):
  * row addresses of y instead of (y, ldy) */
@@ -141,6 +150,14 @@ int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows,
                              const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
                              float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
                              int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, paths_stream_t stream);
+/* fp16 slide grids: paths_importance_proj_x6 with y_rows addressing FP16 rows (y = NULL; y_add and splitk_ws required, planes = 2):
+ * the rows are widened, summed with y_add in fp32 and split as in the fp32 form (split-K form only). */
+int paths_importance_proj_x6_h16(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6, const float* b1, const float* w2, const float* b2 /* device scalar */,
+                                 const float* bp, const float* special, const float* div_term, const float* pe_table, int pe_rows,
+                                 const int64_t* locs,
+                                 const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
+                                 float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
+                                 int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, paths_stream_t stream);
 /* splitk_ws (optional, paths_importance_proj_x6_workspace(M) bytes; used with planes = 2, y_add given, no training saves): the
  * [M/128 x 1]-block GEMM covers half the chip, so its k loop runs as two halves on twice the blocks (raw accumulators to the
  * workspace) and a second launch sums them and applies the epilogue on 64-row blocks.  null = one launch. */
@@ -169,6 +186,15 @@ int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, 
                             /* phase 8 (importance finish + top-K in one launch, instead of phase 2): the outputs of paths_topk_rows */
                             int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
                             const float* zero_row, int* counters /* 2 B int32, zero on entry, left zero */, int* status, paths_stream_t stream);
+/* fp16 slide grids: paths_importance_qkv_x6 whose GEMM phase (bit 1) reads y_rows as FP16 rows (y = NULL). */
+int paths_importance_qkv_x6_h16(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6,
+                                const float* b1, const float* w2, const float* b2 /* device scalar */, const float* bp, const float* special,
+                                const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
+                                int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
+                                float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
+                                float qscale, void* qkv_images, int phases, int alpha_from_importance,
+                                int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
+                                const float* zero_row, int* counters, int* status, paths_stream_t stream);
 /* out (+)= maskop(act(a W[:, k0:k0+K]^T + b)) + residual, W = pack of an [Npad, Kpacked] weight; Npad % 128 == 0
  * (256-column tiles when Npad % 256 == 0, else 128-column tiles) */
 int paths_gemm_nt_x6(const float* a, int64_t lda, const void* w_x6, int Kpacked, int k0, const float* b, float* out, int64_t ldo,
@@ -180,6 +206,10 @@ int paths_gemm_nt_x6(const float* a, int64_t lda, const void* w_x6, int Kpacked,
 int paths_gemm_add_nt_x6(const float* a, int64_t lda, const int64_t* a_rows, const float* a_add, int64_t ld_add, const void* w_x6, int Kpacked,
                          const float* b, float* out, int64_t ldo, int M, int N, int Npad, int K, int act, const int64_t* num_ims,
                          int rows_per_slide, float w_scale, float a_scale, paths_stream_t stream);
+/* fp16 slide grids: paths_gemm_add_nt_x6 with a_rows addressing FP16 rows (a = NULL). */
+int paths_gemm_add_nt_x6_h16(const float* a, int64_t lda, const int64_t* a_rows, const float* a_add, int64_t ld_add, const void* w_x6, int Kpacked,
+                             const float* b, float* out, int64_t ldo, int M, int N, int Npad, int K, int act, const int64_t* num_ims,
+                             int rows_per_slide, float w_scale, float a_scale, paths_stream_t stream);
 /* The same product without bias / activation, A given as row ADDRESSES (planes = 2 only): row m = the K floats at a_rows[m]. */
 int paths_gemm_rows_nt_x6(const int64_t* a_rows, const void* w_x6, int Kpacked, int k0, float* out, int64_t ldo,
                           int M, int Npad, int K, int planes, float w_scale, float a_scale, paths_stream_t stream);
@@ -522,6 +552,11 @@ int paths_gather_rows(const int64_t* grid_ptrs, const int* src_cell, int D, cons
                       int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
                       float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
                       paths_stream_t stream);
+/* paths_gather_rows over FP16 grids: row_ptrs address fp16 rows, fts_out (optional) receives fp32 copies; zero_row as above. */
+int paths_gather_rows_h16(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                          int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                          float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                          paths_stream_t stream);
 
 /* Compact table of the kept parents' rows: out[b*ldk + i] = src[b, keep_idx[b,i], 0:D] (zeros beyond keep_count). */
 int paths_gather_kept_rows(const float* src, int64_t n_cur, int64_t ld_src, const int* keep_idx, int64_t ldk, const int* keep_count,
@@ -546,6 +581,10 @@ int paths_scatter_kept_rows(const float* src, int64_t ldk, int64_t ld_src, const
 int paths_level0_batch(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
                        float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                        const float* zero_row, paths_stream_t stream);
+/* paths_level0_batch over FP16 grids (row_ptrs address fp16 rows, fts receives fp32 copies). */
+int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                           float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                           const float* zero_row, paths_stream_t stream);
 
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */
@@ -559,10 +598,15 @@ int paths_tissue_mask(const float* grid, int64_t cells, int D, uint8_t* mask, pa
  * floats order like their bit patterns, a NaN reads back above +inf.  Guards the fp16-split range contract of the default mode
  * (replaces nothing in the reference; its fp32 CPU path has no such limit). */
 int paths_tissue_mask_absmax(const float* grid, int64_t cells, int D, uint8_t* mask, uint32_t* absmax_bits, paths_stream_t stream);
+/* paths_tissue_mask_absmax over an FP16 grid [cells, D] (sums and max|x| in fp32: the same mask and bits as the fp32 grid of the same values). */
+int paths_tissue_mask_absmax_h16(const void* grid, int64_t cells, int D, uint8_t* mask, uint32_t* absmax_bits, paths_stream_t stream);
 
 /* Counter-based synthetic grid (paths_amd/synthetic.py). */
 int paths_synth_grid(float* grid, int X, int Y, int D, uint32_t slide_level_key, int level, uint64_t bg_threshold,
                      paths_stream_t stream);
+/* paths_synth_grid into an FP16 grid: the same values rounded to nearest even. */
+int paths_synth_grid_h16(void* grid, int X, int Y, int D, uint32_t slide_level_key, int level, uint64_t bg_threshold,
+                         paths_stream_t stream);
 
 /* lstm = false training (reference model/paths.py:95-109, Z = alpha X + hctx): gradient of the importance MLP through the row
  * scaling: dalpha = dZ . X per row, dz = valid dalpha alpha (1 - alpha); dh [M,128] = (hid > 0) dz w2, dah = dz hid, da = dz. */

@@ -100,16 +100,24 @@ uint64_t* g_x6_dbg = nullptr;
 // OCC = waves per SIMD the register allocation is sized for: 1 (the whole 512-register file: the 256-row tiles) or more for the
 // small-tile instantiations of epilogue-bound products (K = 256 mem_to_out: several workgroups per CU hide each other's
 // epilogue loads / stores, which one wave per SIMD cannot).
-template <int NP, int WTM, int WTN, int PF, bool ADD, bool ROWS, class Epi, int OCC = 1>
+// A16 (fp16 slide grids, NP == 2 and ROWS only): the A rows are fp16, 4 consecutive k = 8 bytes per thread and stage.  Without ADD
+// the A operand is ONE plane: x * a_scale (a power of two) is an fp16 value, i.e. exactly its own hi plane with a zero lo plane, so
+// the lo*hi product is dropped (2 MFMAs per block, hi*lo then hi*hi as in the two-plane order) and the stage holds 1 A + 2 W planes.
+// With ADD (Y = X + h1) the rows are widened to fp32, summed, and split into two planes as in the fp32 form.
+template <int NP, int WTM, int WTN, int PF, bool ADD, bool ROWS, class Epi, int OCC = 1, bool A16 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 gemm_x6_kernel(X6Operands g, Epi epi) {
   static_assert(NP == 2 || NP == 3 || NP == 4, "two fp16 planes, three bf16 planes or two bf16 planes");
-  constexpr int PL = planes_of<NP>();                  // planes per operand
-  constexpr int SUBT = subt<NP>();
-  constexpr int NPROD = NP == 3 ? 6 : 3;               // partial products kept per operand pair
+  static_assert(!A16 || (NP == 2 && ROWS), "fp16 A rows: two-plane fp16 split, row-pointer form");
+  constexpr int PL = planes_of<NP>();                  // planes per W operand (and per A operand unless A1P)
+  constexpr bool A1P = A16 && !ADD;                    // A is one fp16 plane
+  constexpr int PLA = A1P ? 1 : PL;
+  constexpr int SUBT = subt<NP>();                     // one W sub-tile
+  constexpr int SUBTA = PLA * FRAG;                    // one A sub-tile
+  constexpr int NPROD = NP == 3 ? 6 : A1P ? 2 : 3;     // partial products kept per operand pair
   constexpr int BM = WTM * 64, BN = WTN * 64;
   constexpr int SA = 2 * WTM, SB = 2 * WTN;            // 32-row sub-tiles per block
-  constexpr int STAGE = (SA + SB) * SUBT;
+  constexpr int STAGE = SA * SUBTA + SB * SUBT;
   constexpr int NA = BM / 64;                          // fp32 A chunks (4 floats) per thread per stage
   constexpr int NPB = SB * PL, NB = (NPB + 3) / 4;     // 1-KiB W pieces per stage, per wave
   static_assert(WTM % 2 == 0, "A fragment register slots alternate per accumulator row");
@@ -141,16 +149,19 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   const int arow = tid >> 2, ac = tid & 3;
   uint32_t aoff0[NA], aoff1[NA], aoffs[ADD ? NA : 1]; int awr[NA];
   typedef const f32x4 __attribute__((address_space(1))) * gptr_f4;
-  gptr_f4 rowp[ROWS ? NA : 1];                         // ROWS: this thread's piece of each of its rows, advanced one stage at a time
+  typedef const u32x2 __attribute__((address_space(1))) * gptr_h4;
+  gptr_f4 rowp[ROWS && !A16 ? NA : 1];                 // ROWS: this thread's piece of each of its rows, advanced one stage at a time
+  gptr_h4 rowh[A16 ? NA : 1];                          // (A16: 4 fp16 = 8 bytes of the row per stage)
 #pragma unroll
   for (int p = 0; p < NA; ++p) {
     const int row = p * 64 + arow;
     const int64_t grow = min(m0 + row, g.M - 1);
     aoff0[p] = ROWS ? 0u : (uint32_t)((grow * g.lda0 + 4 * ac) * 4);
-    if constexpr (ROWS) rowp[p] = reinterpret_cast<gptr_f4>(static_cast<uintptr_t>(g.A0rows[grow]) + 16 * ac);
+    if constexpr (A16) rowh[p] = reinterpret_cast<gptr_h4>(static_cast<uintptr_t>(g.A0rows[grow]) + 8 * ac);
+    else if constexpr (ROWS) rowp[p] = reinterpret_cast<gptr_f4>(static_cast<uintptr_t>(g.A0rows[grow]) + 16 * ac);
     aoff1[p] = (uint32_t)((grow * g.lda1 + 4 * ac) * 4);
     if constexpr (ADD) aoffs[p] = (uint32_t)((grow * g.ldadd + 4 * ac) * 4);
-    awr[p] = (row >> 5) * SUBT + (ac >> 1) * 512 + (row & 31) * 16 + (ac & 1) * 8;
+    awr[p] = (row >> 5) * SUBTA + (ac >> 1) * 512 + (row & 31) * 16 + (ac & 1) * 8;
   }
   // split-K launches: this block's k window of the single panel (A columns, Aadd columns, W stages all start kofs floats in)
   const int K0w = g.ksplit > 1 ? g.K0 / g.ksplit : g.K0;
@@ -159,7 +170,8 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
 #pragma unroll
     for (int p = 0; p < NA; ++p) {
       aoff0[p] += (uint32_t)kofs * 4u;
-      if constexpr (ROWS) rowp[p] += kofs >> 2;
+      if constexpr (A16) rowh[p] += kofs >> 2;
+      else if constexpr (ROWS) rowp[p] += kofs >> 2;
       if constexpr (ADD) aoffs[p] += (uint32_t)kofs * 4u;
     }
   }
@@ -171,10 +183,11 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
     if (pc >= NPB) pc -= 4;                            // re-stage this wave's previous piece (same bytes, same slot)
     const int sub = pc / PL, pl = pc % PL;
     bbase[i] = g.Wt + ((int64_t)(n0 >> 5) + sub) * g.w_group_stride + pl * FRAG;
-    bwr[i] = (SA + sub) * SUBT + pl * FRAG + lane * 16;
+    bwr[i] = (A1P ? SA * SUBTA + sub * SUBT : (SA + sub) * SUBT) + pl * FRAG + lane * 16;
   }
   static_assert(PF == 1 || PF == 2, "one or two register sets");
   f32x4 sa[PF][NA], sadd[ADD ? PF : 1][ADD ? NA : 1]; u32x4 sbr[PF][NB];
+  u32x2 sh[A16 ? PF : 1][A16 ? NA : 1];                // A16: the staged fp16 row piece
   uint32_t hi[NA][2], mid[NP != 2 ? NA : 1][2], lo[NA][2];
   // Loads go through buffer descriptors: a wave-uniform base (SGPRs), a scalar byte offset (stage, panel, W piece) and ONE
   // per-lane 32-bit offset computed once.  As 64-bit pointers hipcc strength-reduced each load's address into a VGPR pair it
@@ -196,7 +209,9 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
 #else
     const int soff = (first ? kt : kt - nk0) * 64;
 #endif
-    if constexpr (ROWS) {                              // single panel: 64-bit per-lane row address + the stage's 64 bytes
+    if constexpr (A16) {                               // single panel of fp16 rows: the stage's 32 bytes of the row
+      sh[set][q] = rowh[q][kt * 4];
+    } else if constexpr (ROWS) {                       // single panel: 64-bit per-lane row address + the stage's 64 bytes
       sa[set][q] = rowp[q][kt * 4];
     } else {
       const u32x4 raw = first ? __builtin_amdgcn_raw_buffer_load_b128(rsA0, (int)aoff0[q], soff, 0)
@@ -214,15 +229,30 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   // between two 32-cycle MFMAs hides about 24 cycles of other issue; the first version used 7 steps of 4 VALU + waits, every
   // such gap overflowed by ~15 cycles and idle gaps cannot win that back: ~500 cycles per stage (tools/x6_stages.py).
   //   NP == 3 (bf16): 12 micro-steps (+1 for the ADD sum);  NP == 2 (fp16): scale, hi, lo low halves, lo high halves, writes = 5 (+1).
-  constexpr int NS = (NP == 3 ? 12 : NP == 4 ? 7 : (PATHS_X6_MIX16 ? 5 : 6)) + (ADD ? 1 : 0);
+  //   A1P (one fp16 plane): scale (one v_pk_mul_f16 per register), write = 2.  A16 + ADD: two widening sums (k pairs) in front.
+  constexpr int PRE = ADD ? (A16 ? 2 : 1) : 0;
+  constexpr int NS = A1P ? 2 : (NP == 3 ? 12 : NP == 4 ? 7 : (PATHS_X6_MIX16 ? 5 : 6)) + PRE;
   float tf[NA][2];
+  const uint32_t s2 = A1P ? __builtin_bit_cast(uint32_t, f16x2{(_Float16)g.a_scale, (_Float16)g.a_scale}) : 0u;   // A1P: the packed fp16 scale
   auto a_step = [&](int set, int q, int st0, int buf) __attribute__((always_inline)) {
     f32x4& v = sa[set][q];
-    const int st = ADD ? st0 - 1 : st0;
-    if constexpr (ADD) {
+    const int st = st0 - PRE;
+    if constexpr (ADD && A16) {                        // fp16 x widened exactly, + h1 in fp32: the same sum as the fp32 form's
+      if (st0 == 0) { v[0] = h_lo(sh[set][q][0]) + sadd[set][q][0]; v[1] = h_hi(sh[set][q][0]) + sadd[set][q][1]; }
+      if (st0 == 1) { v[2] = h_lo(sh[set][q][1]) + sadd[set][q][2]; v[3] = h_hi(sh[set][q][1]) + sadd[set][q][3]; }
+    } else if constexpr (ADD) {
       if (st0 == 0) v += sadd[set][q];                 // the fp32 sum the reference materialises (Y = X + h1)
     }
-    if constexpr (NP == 3) {
+    if constexpr (A1P) {
+      // x * a_scale in fp16 is exact (power of two, |x| a_scale < 65504 by the range rule): the hi plane of the fp32 form, lo = 0
+      // (inline asm: written as a product of two f16x2 vectors, hipcc 7.2 merged the two registers' multiplies into one and wrote its
+      // result to both halves of the chunk)
+      if (st == 0) {
+        asm("v_pk_mul_f16 %0, %1, %2" : "=v"(hi[q][0]) : "v"(sh[set][q][0]), "v"(s2));
+        asm("v_pk_mul_f16 %0, %1, %2" : "=v"(hi[q][1]) : "v"(sh[set][q][1]), "v"(s2));
+      }
+      if (st == 1) *reinterpret_cast<u32x2*>(smem + buf * STAGE + awr[q]) = u32x2{hi[q][0], hi[q][1]};
+    } else if constexpr (NP == 3) {
       if (st == 0) { hi[q][0] = pk_bf16(v[0], v[1]); hi[q][1] = pk_bf16(v[2], v[3]); }
       if (st == 1) { tf[q][0] = bf_lo(hi[q][0]); tf[q][1] = bf_hi(hi[q][0]); }
       if (st == 2) { v[0] -= tf[q][0]; v[1] -= tf[q][1]; }
@@ -291,10 +321,10 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   f32x16 acc[WTM][WTN];
   epi.template init<WTM, WTN>(acc, m0 + wm * WTM * 32, n0 + wn * WTN * 32, lane, g.M);
 
-  const char* sA = smem + (wm * WTM) * SUBT + lane * 16;
-  const char* sB = smem + (SA + wn * WTN) * SUBT + lane * 16;
-  u32x4 fa[2][PL], fb[2][WTN][PL];                     // 8 x 16-bit per lane and plane
-  auto read_a = [&](int buf, int i, int slot, int p) { fa[slot][p] = *reinterpret_cast<const u32x4*>(sA + buf * STAGE + i * SUBT + p * FRAG); };
+  const char* sA = smem + (wm * WTM) * SUBTA + lane * 16;
+  const char* sB = A1P ? smem + SA * SUBTA + (wn * WTN) * SUBT + lane * 16 : smem + (SA + wn * WTN) * SUBT + lane * 16;
+  u32x4 fa[2][PLA], fb[2][WTN][PL];                    // 8 x 16-bit per lane and plane
+  auto read_a = [&](int buf, int i, int slot, int p) { fa[slot][p] = *reinterpret_cast<const u32x4*>(sA + buf * STAGE + i * SUBTA + p * FRAG); };
   auto read_b = [&](int buf, int j, int slot, int p) { fb[slot][j][p] = *reinterpret_cast<const u32x4*>(sB + buf * STAGE + j * SUBT + p * FRAG); };
   constexpr int RG = WTN * NPROD;                      // MFMA gaps per accumulator row
   auto one_mfma = [&](int gq, int sb) __attribute__((always_inline)) {
@@ -305,6 +335,9 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
     } else if constexpr (NP == 4) {
       constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};                     // mid*hi, hi*mid, hi*hi
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[sl][PA_[t]]), __builtin_bit_cast(bf16x8, fb[sb][j][PB_[t]]), acc[i][j], 0, 0, 0);
+    } else if constexpr (A1P) {
+      constexpr int PB_[2] = {1, 0};                                            // hi*lo, hi*hi (the two-plane order without lo*hi = 0)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[sl][0]), __builtin_bit_cast(f16x8, fb[sb][j][PB_[t]]), acc[i][j], 0, 0, 0);
     } else {
       constexpr int PA_[3] = {1, 0, 0}, PB_[3] = {0, 1, 0};                     // lo*hi, hi*lo, hi*hi
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[sl][PA_[t]]), __builtin_bit_cast(f16x8, fb[sb][j][PB_[t]]), acc[i][j], 0, 0, 0);
@@ -370,7 +403,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
     static_for<0, AG>([&](auto gc) __attribute__((always_inline)) {
       constexpr int gq = decltype(gc)::value, i = gq / RG, gr = gq % RG;
       one_mfma(gq, sb);
-      if constexpr (gr >= AR0 && gr < AR0 + PL) read_a(buf, i + 1, (i + 1) & 1, gr - AR0);
+      if constexpr (gr >= AR0 && gr < AR0 + PLA) read_a(buf, i + 1, (i + 1) & 1, gr - AR0);
       staging_slot(std::integral_constant<int, gq>{}, kt, bufc, m1c, m2c);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -388,8 +421,8 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
       if constexpr (more1) {
         static_for<2 * gr, 2 * gr + 2>([&](auto fc) __attribute__((always_inline)) {
           constexpr int f = decltype(fc)::value;
-          if constexpr (f < PL) read_a(buf ^ 1, 0, 0, f);
-          else if constexpr (f < PL + PL * WTN) read_b(buf ^ 1, (f - PL) / PL, sb ^ 1, (f - PL) % PL);
+          if constexpr (f < PLA) read_a(buf ^ 1, 0, 0, f);
+          else if constexpr (f < PLA + PL * WTN) read_b(buf ^ 1, (f - PLA) / PL, sb ^ 1, (f - PLA) % PL);
         });
       }
       staging_slot(std::integral_constant<int, gq>{}, kt, bufc, m1c, m2c);   // (reload slots of the PF == 2 layout)
@@ -424,7 +457,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   }
   __syncthreads();
 #pragma unroll
-  for (int p = 0; p < PL; ++p) read_a(0, 0, 0, p);
+  for (int p = 0; p < PLA; ++p) read_a(0, 0, 0, p);
 #pragma unroll
   for (int j = 0; j < WTN; ++j)
 #pragma unroll
@@ -511,10 +544,10 @@ __global__ void x6_pack_t_kernel(const float* __restrict__ w, int64_t ldw, uint1
   if constexpr (NP == 3) *reinterpret_cast<u16x8*>(o + FRAG) = u16x8{l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7]};
 }
 
-template <int NP, int WTM, int WTN, int PF, bool ADD, bool ROWS, class Epi, int OCC = 1>
+template <int NP, int WTM, int WTN, int PF, bool ADD, bool ROWS, class Epi, int OCC = 1, bool A16 = false>
 int launch_x6_np(const X6Operands& g, int Npad, const Epi& epi, hipStream_t stream, const char* name) {
   constexpr int BM = WTM * 64, BN = WTN * 64;
-  constexpr size_t lds = 2ull * (2 * WTM + 2 * WTN) * subt<NP>();
+  constexpr size_t lds = 2ull * (2 * WTM * ((A16 && !ADD) ? FRAG : subt<NP>()) + 2 * WTN * subt<NP>());
   const int K = g.K0 + g.K1;
   PATHS_REQUIRE(g.M > 0, "%s: M must be > 0", name);
   PATHS_REQUIRE(g.K0 > 0 && g.K0 % 16 == 0 && g.K1 % 16 == 0 && K % 32 == 0 && K >= 128, "%s: K panels (%d,%d): multiples of 16, total a multiple of 32, >= 128", name, g.K0, g.K1);
@@ -523,7 +556,7 @@ int launch_x6_np(const X6Operands& g, int Npad, const Epi& epi, hipStream_t stre
   PATHS_REQUIRE(((uintptr_t)g.A0 % 16 == 0) && ((uintptr_t)g.A1 % 16 == 0) && ((uintptr_t)g.Wt % 16 == 0), "%s: operands must be 16-byte aligned", name);
   PATHS_REQUIRE(ROWS == (g.A0rows != nullptr) && (!ROWS || g.K1 == 0), "%s: row-pointer form is single-panel", name);
   PATHS_REQUIRE((int64_t)g.M * (g.lda0 > g.lda1 ? (g.lda0 > g.ldadd ? g.lda0 : g.ldadd) : (g.lda1 > g.ldadd ? g.lda1 : g.ldadd)) * 4 < (int64_t)1 << 32, "%s: A panel larger than 4 GiB", name);
-  auto kern = gemm_x6_kernel<NP, WTM, WTN, PF, ADD, ROWS, Epi, OCC>;
+  auto kern = gemm_x6_kernel<NP, WTM, WTN, PF, ADD, ROWS, Epi, OCC, A16>;
   PATHS_LDS_OPT_IN(kern, lds, name);
   PATHS_REQUIRE(g.ksplit == 1 || (g.ksplit > 1 && g.K1 == 0 && g.K0 % (32 * g.ksplit) == 0 && g.K0 / g.ksplit >= 128), "%s: split-K needs a single panel and k windows that are multiples of 32, >= 128", name);
   dim3 grid(Npad / BN, (g.M + BM - 1) / BM, g.ksplit);
@@ -628,6 +661,8 @@ static const bool H_SMALL_TILES = getenv("PATHS_H_SMALL_TILES") == nullptr || at
 inline int plane_count(int planes) { return planes == 4 ? 2 : planes; }      // API mode 4 = two bf16 planes
 inline int64_t group_stride(int planes, int Kpacked) { return (int64_t)(Kpacked / 16) * plane_count(planes) * FRAG; }
 inline bool pow2(float x) { int e; return x > 0.f && frexpf(x, &e) == 0.5f; }
+// fp16 A rows: the activation scale is applied in fp16 (exact for a power of two >= 1 while |x| a_scale < 65504)
+inline bool h16_scale_ok(float a_scale) { return pow2(a_scale) && a_scale >= 1.0f && a_scale <= 32768.0f; }
 
 }  // namespace
 
@@ -675,15 +710,20 @@ int paths_x6_pack_weights_t(const float* w, int64_t ldw, void* out, int N, int N
   return PATHS_OK;
 }
 
-// paths_lstm_cell with the gate / mem_to_out weights given as split images (planes, scales as in paths_x6_pack_weights;
-// a_scale: power of two applied to the fp32 activations before the fp16 split - |activation| * a_scale must stay < 65504):
-//   w_gates_x6 = pack([3Hc + D, 2D] packed gate rows, see paths_lstm_cell), w_mem_x6 = pack([D, Hc])
-int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
-                       const void* w_gates_x6, const float* b_gates, const void* w_mem_x6, const float* b_mem,
-                       float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
-                       const float* hp, const int* hp_row, int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide,
-                       int phases, int planes, float wg_scale, float wm_scale, float a_scale, hipStream_t stream) {
+}  // extern "C"
+namespace {
+// paths_lstm_cell_x6 (A16 = false) and paths_lstm_cell_x6_h16 (A16: x_rows address fp16 rows; the gate GEMMs take the one-plane A operand)
+template <bool A16>
+int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
+                 const void* w_gates_x6, const float* b_gates, const void* w_mem_x6, const float* b_mem,
+                 float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
+                 const float* hp, const int* hp_row, int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide,
+                 int phases, int planes, float wg_scale, float wm_scale, float a_scale, hipStream_t stream) {
   PATHS_REQUIRE(D % 256 == 0 && Hc % 64 == 0, "lstm_cell_x6: D (%d) must be a multiple of 256 and Hc (%d) of 64", D, Hc);
+  if constexpr (A16) {
+    PATHS_REQUIRE(x_rows != nullptr && x == nullptr && planes == 2, "lstm_cell_x6_h16: fp16 rows are given as x_rows (planes = 2)");
+    PATHS_REQUIRE(h16_scale_ok(a_scale), "lstm_cell_x6_h16: a_scale must be a power of two in [1, 2^15]");
+  }
   PATHS_REQUIRE(hp != nullptr || (h0 == nullptr) == (c0 == nullptr), "lstm_cell_x6: h0 and c0 must both be given or both be null");
   PATHS_REQUIRE((hp == nullptr) == (hp_row == nullptr) && (hp == nullptr || h0 == nullptr),
                 "lstm_cell_x6: hp/hp_row come together and replace h0 (the h half of the gate GEMM was done per parent)");
@@ -703,7 +743,10 @@ int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const
   if (phases & 1) {   // c-part: N = 3Hc, block 256 x 192
     EpiLstmC e{b_gates, c0, ldc0, state_out + D, ldso, save_frm, (int64_t)3 * Hc, hp, (int64_t)3 * Hc + D, hp_row, sg};
     int rc;
-    if (small_m) rc = x_rows ? launch_x6_np<2, 2, 3, 2, false, true>(g, 3 * Hc, e, stream, "lstm_cell_x6(c, 128-row tiles)")
+    if constexpr (A16) {
+      rc = small_m ? launch_x6_np<2, 2, 3, 2, false, true, decltype(e), 1, true>(g, 3 * Hc, e, stream, "lstm_cell_x6_h16(c, 128-row tiles)")
+                   : launch_x6_np<2, 4, 3, 1, false, true, decltype(e), 1, true>(g, 3 * Hc, e, stream, "lstm_cell_x6_h16(c)");
+    } else if (small_m) rc = x_rows ? launch_x6_np<2, 2, 3, 2, false, true>(g, 3 * Hc, e, stream, "lstm_cell_x6(c, 128-row tiles)")
                              : launch_x6_np<2, 2, 3, 2, false, false>(g, 3 * Hc, e, stream, "lstm_cell_x6(c, 128-row tiles)");
     else rc = launch_x6<4, 3, 1, false>(planes, g, 3 * Hc, e, stream, "lstm_cell_x6(c)");
     if (rc) return rc;
@@ -716,12 +759,16 @@ int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const
     int rc;
     if (o_raw) {
       EpiLstmORaw e{b_gates + 3 * Hc, ws_o, D, D, hp, (int64_t)3 * Hc + D, hp_row, 3 * Hc, sg};
-      if (small_m) rc = x_rows ? launch_x6_np<2, 2, 4, 2, false, true>(go, D, e, stream, "lstm_cell_x6(o, raw, 128-row tiles)")
+      if constexpr (A16) {
+        rc = small_m ? launch_x6_np<2, 2, 4, 2, false, true, decltype(e), 1, true>(go, D, e, stream, "lstm_cell_x6_h16(o, raw, 128-row tiles)")
+                     : launch_x6_np<2, 4, 4, 1, false, true, decltype(e), 1, true>(go, D, e, stream, "lstm_cell_x6_h16(o, raw)");
+      } else if (small_m) rc = x_rows ? launch_x6_np<2, 2, 4, 2, false, true>(go, D, e, stream, "lstm_cell_x6(o, raw, 128-row tiles)")
                                : launch_x6_np<2, 2, 4, 2, false, false>(go, D, e, stream, "lstm_cell_x6(o, raw, 128-row tiles)");
       else rc = launch_x6<4, 4, 1, false>(planes, go, D, e, stream, "lstm_cell_x6(o, raw)");
     } else {
       EpiLstmO e{b_gates + 3 * Hc, ws_o, D, D, hp, (int64_t)3 * Hc + D, hp_row, 3 * Hc, sg};
-      rc = launch_x6<4, 4, 1, false>(planes, go, D, e, stream, "lstm_cell_x6(o)");
+      if constexpr (A16) rc = launch_x6_np<2, 4, 4, 1, false, true, decltype(e), 1, true>(go, D, e, stream, "lstm_cell_x6_h16(o)");
+      else rc = launch_x6<4, 4, 1, false>(planes, go, D, e, stream, "lstm_cell_x6(o)");
     }
     if (rc) return rc;
   }
@@ -752,6 +799,31 @@ int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const
   }
   return PATHS_OK;
 }
+}  // namespace
+extern "C" {
+
+// paths_lstm_cell with the gate / mem_to_out weights given as split images (planes, scales as in paths_x6_pack_weights;
+// a_scale: power of two applied to the fp32 activations before the fp16 split - |activation| * a_scale must stay < 65504):
+//   w_gates_x6 = pack([3Hc + D, 2D] packed gate rows, see paths_lstm_cell), w_mem_x6 = pack([D, Hc])
+int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
+                       const void* w_gates_x6, const float* b_gates, const void* w_mem_x6, const float* b_mem,
+                       float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
+                       const float* hp, const int* hp_row, int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide,
+                       int phases, int planes, float wg_scale, float wm_scale, float a_scale, hipStream_t stream) {
+  return lstm_cell_x6<false>(x, ldx, x_rows, h0, ldh0, c0, ldc0, w_gates_x6, b_gates, w_mem_x6, b_mem, state_out, ldso, y, ldy, ws_o, save_frm,
+                             save_tc, hp, hp_row, M, D, Hc, num_ims, rows_per_slide, phases, planes, wg_scale, wm_scale, a_scale, stream);
+}
+
+// The same with x_rows addressing FP16 feature rows (fp16 slide grids; x must be NULL, planes = 2): the c / o gate GEMMs run on the
+// one-plane A operand (2 MFMAs per block); bit-identical to paths_lstm_cell_x6 on fp32 rows holding the same values.
+int paths_lstm_cell_x6_h16(const float* x, int64_t ldx, const int64_t* x_rows, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
+                           const void* w_gates_x6, const float* b_gates, const void* w_mem_x6, const float* b_mem,
+                           float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
+                           const float* hp, const int* hp_row, int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide,
+                           int phases, int planes, float wg_scale, float wm_scale, float a_scale, hipStream_t stream) {
+  return lstm_cell_x6<true>(x, ldx, x_rows, h0, ldh0, c0, ldc0, w_gates_x6, b_gates, w_mem_x6, b_mem, state_out, ldso, y, ldy, ws_o, save_frm,
+                            save_tc, hp, hp_row, M, D, Hc, num_ims, rows_per_slide, phases, planes, wg_scale, wm_scale, a_scale, stream);
+}
 
 #endif
 #if PATHS_X6_PART == 0 || PATHS_X6_PART == 2
@@ -761,11 +833,19 @@ int paths_lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const
 // bytes of the optional split-K workspace of paths_importance_proj_x6 (two k halves of raw [M_pad, 256] accumulators)
 int64_t paths_importance_proj_x6_workspace(int M) { return 2ll * ((M + 127) / 128 * 4) * 8 * 1024 * 4; }
 
-int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6, const float* b1, const float* w2, const float* b2,
-                             const float* bp, const float* special, const float* div_term, const float* pe_table, int pe_rows, const int64_t* locs,
-                             const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
-                             float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
-                             int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, hipStream_t stream) {
+}  // extern "C"
+namespace {
+// paths_importance_proj_x6 (A16 = false) and paths_importance_proj_x6_h16 (A16: y_rows address fp16 rows; split-K form only)
+template <bool A16>
+int importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6, const float* b1, const float* w2, const float* b2,
+                       const float* bp, const float* special, const float* div_term, const float* pe_table, int pe_rows, const int64_t* locs,
+                       const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
+                       float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
+                       int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, hipStream_t stream) {
+  if constexpr (A16) {
+    PATHS_REQUIRE(y == nullptr && y_rows != nullptr && y_add != nullptr && splitk_ws != nullptr && planes == 2 && D % 64 == 0 && D >= 256,
+                  "importance_proj_x6_h16: fp16 rows (y_rows) + y_add on the split-K form (splitk_ws, planes = 2, D %% 64 == 0, D >= 256)");
+  }
   PATHS_REQUIRE(Hi == 128 && d == 128, "importance_proj_x6: this build supports importance_mlp_hidden_dim=128, trans_dim=128 (got %d, %d)", Hi, d);
   PATHS_REQUIRE(pe_mode == 1 || pe_mode == 2, "importance_proj_x6: pe_mode must be 1 (1d) or 2 (2d)");
   PATHS_REQUIRE(pe_mode == 1 || locs != nullptr, "importance_proj_x6: 2d positional encoding needs locs");
@@ -790,11 +870,16 @@ int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows,
         const int mt = (M + 127) / 128 * 4;                         // 32-row tiles, padded to the GEMM's 128-row blocks
         const int64_t zstride = (int64_t)mt * 8 * 1024;
         int rc;
-        const bool tile128 = IP_TILE128 && y_add != nullptr;
+        const bool tile128 = IP_TILE128 && y_add != nullptr && !A16;
         if (tile128) {
+          if constexpr (A16) return paths_set_error(PATHS_EUNSUPPORTED, "importance_proj_x6_h16: no 128 x 128 tile form");
           EpiRaw raw{splitk_ws, zstride, 8};
           rc = y_rows ? launch_x6_np<2, 2, 2, 2, true, true, EpiRaw, 2>(g, 256, raw, stream, "importance_proj_x6(raw, 128x128)")
                       : launch_x6_np<2, 2, 2, 2, true, false, EpiRaw, 2>(g, 256, raw, stream, "importance_proj_x6(raw, 128x128)");
+        } else if constexpr (A16) {
+          X6Operands gs = g; gs.ksplit = 2;
+          EpiRaw raw{splitk_ws, zstride, 8};
+          rc = launch_x6_np<2, 2, 4, 2, true, true, EpiRaw, 1, true>(gs, 256, raw, stream, "importance_proj_x6_h16(split-k)");
         } else {
           X6Operands gs = g; gs.ksplit = 2;
           EpiRaw raw{splitk_ws, zstride, 8};
@@ -818,11 +903,39 @@ int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows,
         return PATHS_OK;
       }
     }
-    if (y_add != nullptr) return launch_x6<2, 4, 2, true>(planes, g, 256, e, stream, "importance_proj_x6(sum)");
-    return launch_x6<2, 4, 2, false>(planes, g, 256, e, stream, "importance_proj_x6");
+    if constexpr (A16) {
+      return paths_set_error(PATHS_EUNSUPPORTED, "importance_proj_x6_h16: split-K form only");
+    } else {
+      if (y_add != nullptr) return launch_x6<2, 4, 2, true>(planes, g, 256, e, stream, "importance_proj_x6(sum)");
+      return launch_x6<2, 4, 2, false>(planes, g, 256, e, stream, "importance_proj_x6");
+    }
   };
   if (pe_table != nullptr) return save_hid ? go(EpiImpProj<true, true>{}) : go(EpiImpProj<true, false>{});
   return save_hid ? go(EpiImpProj<false, true>{}) : go(EpiImpProj<false, false>{});
+}
+}  // namespace
+extern "C" {
+
+int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6, const float* b1, const float* w2, const float* b2,
+                             const float* bp, const float* special, const float* div_term, const float* pe_table, int pe_rows, const int64_t* locs,
+                             const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
+                             float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
+                             int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, hipStream_t stream) {
+  return importance_proj_x6<false>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, div_term, pe_table, pe_rows, locs, num_ims,
+                                   rows_per_slide, patch_size, pe_mode, imp_mul, importance, tokens, save_hid, save_pproj, M, D, Hi, d,
+                                   skip_padding, planes, w_scale, a_scale, splitk_ws, stream);
+}
+
+// The same with y_rows addressing FP16 feature rows (y = NULL; y_add and splitk_ws required): the split-K GEMM widens the fp16 rows,
+// adds y_add in fp32 and splits the sum as the fp32 form does - bit-identical to it on fp32 rows holding the same values.
+int paths_importance_proj_x6_h16(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6, const float* b1, const float* w2, const float* b2,
+                                 const float* bp, const float* special, const float* div_term, const float* pe_table, int pe_rows, const int64_t* locs,
+                                 const int64_t* num_ims, int rows_per_slide, int patch_size, int pe_mode, int imp_mul,
+                                 float* importance, float* tokens, float* save_hid, float* save_pproj, int M, int D, int Hi, int d,
+                                 int skip_padding, int planes, float w_scale, float a_scale, float* splitk_ws, hipStream_t stream) {
+  return importance_proj_x6<true>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, div_term, pe_table, pe_rows, locs, num_ims,
+                                  rows_per_slide, patch_size, pe_mode, imp_mul, importance, tokens, save_hid, save_pproj, M, D, Hi, d,
+                                  skip_padding, planes, w_scale, a_scale, splitk_ws, stream);
 }
 
 
@@ -844,14 +957,18 @@ int paths_importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows,
 //                 and the q | k | v operand images of paths_attention_h3_img in qkv_images (paths_attention_x6_workspace(B, N + 1, 4, 32, 2)).
 // Bits 2 and 4 are stop-event capable launches; they may be issued by separate calls on different streams (the caller orders them
 // behind bit 1).  pe_table is required (paths_pe_table; positions are clamped to its rows).  w_qkv: paths_tlayer_pack_ws part 1 image with scale s_wqkv.
-int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6,
-                            const float* b1, const float* w2, const float* b2, const float* bp, const float* special,
-                            const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
-                            int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
-                            float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
-                            float qscale, void* qkv_images, int phases, int alpha_from_importance,
-                            int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
-                            const float* zero_row, int* counters, int* status, hipStream_t stream) {
+}  // extern "C"
+namespace {
+template <bool A16>
+int importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6,
+                      const float* b1, const float* w2, const float* b2, const float* bp, const float* special,
+                      const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
+                      int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
+                      float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
+                      float qscale, void* qkv_images, int phases, int alpha_from_importance,
+                      int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
+                      const float* zero_row, int* counters, int* status, hipStream_t stream) {
+  PATHS_REQUIRE(!A16 || (phases & 1) == 0 || (y == nullptr && y_rows != nullptr), "importance_qkv_x6_h16: fp16 rows are given as y_rows");
   PATHS_REQUIRE(B > 0 && N > 0 && N % 64 == 0 && D % 64 == 0 && D >= 256, "importance_qkv_x6: bad shape B=%d N=%d (a multiple of 64) D=%d", B, N, D);
   PATHS_REQUIRE(pe_mode == 1 || pe_mode == 2, "importance_qkv_x6: pe_mode must be 1 (1d) or 2 (2d)");
   PATHS_REQUIRE(pe_table != nullptr && pe_rows > 0 && (pe_mode == 1 || locs != nullptr), "importance_qkv_x6: needs the positional-encoding table (and locs in 2d mode)");
@@ -869,8 +986,10 @@ int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, 
     X6Operands g{y, ldy, D, y_rows, nullptr, 0, 0, y_add, ldya, reinterpret_cast<const char*>(w_ip_x6), group_stride(2, D), M, skip_padding ? num_ims : nullptr, N, a_scale};
     g.ksplit = 2;
     EpiRaw raw{splitk_ws, zstride, 8};
-    const int rc = y_rows ? launch_x6_np<2, 2, 4, 2, true, true>(g, 256, raw, stream, "importance_qkv_x6(split-k)")
-                          : launch_x6_np<2, 2, 4, 2, true, false>(g, 256, raw, stream, "importance_qkv_x6(split-k)");
+    int rc;
+    if constexpr (A16) rc = launch_x6_np<2, 2, 4, 2, true, true, EpiRaw, 1, true>(g, 256, raw, stream, "importance_qkv_x6_h16(split-k)");
+    else rc = y_rows ? launch_x6_np<2, 2, 4, 2, true, true>(g, 256, raw, stream, "importance_qkv_x6(split-k)")
+                     : launch_x6_np<2, 2, 4, 2, true, false>(g, 256, raw, stream, "importance_qkv_x6(split-k)");
     if (rc != PATHS_OK) return rc;
   }
   if (phases & 14) {
@@ -896,6 +1015,37 @@ int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, 
     }
   }
   return PATHS_OK;
+}
+}  // namespace
+extern "C" {
+
+int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6,
+                            const float* b1, const float* w2, const float* b2, const float* bp, const float* special,
+                            const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
+                            int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
+                            float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
+                            float qscale, void* qkv_images, int phases, int alpha_from_importance,
+                            int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
+                            const float* zero_row, int* counters, int* status, hipStream_t stream) {
+  return importance_qkv_x6<false>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, pe_table, pe_rows, locs, num_ims, B, N, patch_size,
+                                  pe_mode, imp_mul, importance, tokens, D, skip_padding, w_scale, a_scale, splitk_ws, w_qkv, bqkv, s_wqkv, qscale,
+                                  qkv_images, phases, alpha_from_importance, keep, keep_idx, ldk, keep_count, row_base, row_ld, kept_rows, zero_row,
+                                  counters, status, stream);
+}
+
+// The same with y_rows addressing FP16 feature rows (y = NULL) in the GEMM phase (bit 1); the finish phases are the fp32 form's.
+int paths_importance_qkv_x6_h16(const float* y, int64_t ldy, const int64_t* y_rows, const float* y_add, int64_t ldya, const void* w_ip_x6,
+                                const float* b1, const float* w2, const float* b2, const float* bp, const float* special,
+                                const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
+                                int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
+                                float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
+                                float qscale, void* qkv_images, int phases, int alpha_from_importance,
+                                int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
+                                const float* zero_row, int* counters, int* status, hipStream_t stream) {
+  return importance_qkv_x6<true>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, pe_table, pe_rows, locs, num_ims, B, N, patch_size,
+                                 pe_mode, imp_mul, importance, tokens, D, skip_padding, w_scale, a_scale, splitk_ws, w_qkv, bqkv, s_wqkv, qscale,
+                                 qkv_images, phases, alpha_from_importance, keep, keep_idx, ldk, keep_count, row_base, row_ld, kept_rows, zero_row,
+                                 counters, status, stream);
 }
 
 #endif
@@ -951,6 +1101,20 @@ int paths_gemm_add_nt_x6(const float* a, int64_t lda, const int64_t* a_rows, con
   }
   return a_rows ? launch_x6_np<2, 2, 4, 2, true, true>(g, Npad, e, stream, "gemm_add_nt_x6(rows)")
                 : launch_x6_np<2, 2, 4, 2, true, false>(g, Npad, e, stream, "gemm_add_nt_x6");
+}
+
+// paths_gemm_add_nt_x6 with a_rows addressing FP16 feature rows (a = NULL): widened, summed with a_add in fp32 and split as there.
+int paths_gemm_add_nt_x6_h16(const float* a, int64_t lda, const int64_t* a_rows, const float* a_add, int64_t ld_add, const void* w_x6, int Kpacked,
+                             const float* b, float* out, int64_t ldo, int M, int N, int Npad, int K, int act, const int64_t* num_ims,
+                             int rows_per_slide, float w_scale, float a_scale, hipStream_t stream) {
+  PATHS_REQUIRE(a == nullptr && a_rows != nullptr, "gemm_add_nt_x6_h16: fp16 rows are given as a_rows");
+  PATHS_REQUIRE(a_add != nullptr && ld_add % 4 == 0 && (uintptr_t)a_add % 16 == 0, "gemm_add_nt_x6_h16: a_add must be 16-byte aligned with ld_add %% 4 == 0");
+  PATHS_REQUIRE(pow2(w_scale) && pow2(a_scale) && K == Kpacked && (Npad % 256 == 0 || Npad % 192 == 0),
+                "gemm_add_nt_x6_h16: power-of-two scales, whole-K image, Npad a multiple of 256 or of 192");
+  X6Operands g{nullptr, lda, K, a_rows, nullptr, 0, 0, a_add, ld_add, reinterpret_cast<const char*>(w_x6), group_stride(2, Kpacked), M, num_ims, rows_per_slide, a_scale};
+  EpiBias e{b, out, ldo, N, act, nullptr, 0, nullptr, 0, 0, 1.0f / (w_scale * a_scale)};
+  if (Npad % 256 != 0) return launch_x6_np<2, 2, 3, 2, true, true, EpiBias, 1, true>(g, Npad, e, stream, "gemm_add_nt_x6_h16(rows, 192-wide tiles)");
+  return launch_x6_np<2, 2, 4, 2, true, true, EpiBias, 1, true>(g, Npad, e, stream, "gemm_add_nt_x6_h16(rows)");
 }
 
 #endif

@@ -16,6 +16,19 @@ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   return h;
 }
 
+// Feature grids are fp32 or fp16 (DeviceSlide dtype).  Rows are read 4 values at a time (16 or 8 bytes per lane) and widened to fp32
+// exactly, so every pass below computes on an fp16 grid what it computes on an fp32 grid holding the same values.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <class T>
+__device__ __forceinline__ f32x4 load4(const T* row, int64_t i) {     // elements 4 i .. 4 i + 3 of a row
+  if constexpr (sizeof(T) == 4) {
+    return reinterpret_cast<const f32x4*>(row)[i];
+  } else {
+    const f16x4 h = reinterpret_cast<const f16x4*>(row)[i];
+    return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // top-K: indices of the `keep` largest scores, ordered by (score descending, index ascending).
 // torch.topk (slide.py:298) leaves tie order unspecified; this rule equals it whenever scores are distinct.
@@ -297,6 +310,7 @@ fallback_all_cells_kernel(const int* __restrict__ next_x, const int* __restrict_
 // (One 256-thread workgroup per row was 16,384 workgroups for 16 MB in the default path - only the 1-KiB memory-cell part of the
 // state is copied there, 64 of the 256 threads had anything to do: 14.6 us.)
 constexpr int GATHER_ROWS = 4;
+template <class T>
 __global__ void __launch_bounds__(256)
 gather_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ src_cell, int D,
               const float* __restrict__ state_cur /*already offset to the first copied column*/, int64_t n_cur, int64_t ld_state_cur,
@@ -311,9 +325,9 @@ gather_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ src
   f32x4* fo = fts_out ? reinterpret_cast<f32x4*>(fts_out + o * D) : nullptr;
   f32x4* so = state_out ? reinterpret_cast<f32x4*>(state_out + o * Dp) : nullptr;
   if (j < num_out[b]) {
-    const f32x4* fi = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(grid_ptrs[b]) + (int64_t)src_cell[o] * D);
+    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + (int64_t)src_cell[o] * D;
     if (row_ptrs && lane == 0) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(fi);     // consumers read the row where it lives
-    if (fo) for (int i = lane; i < D / 4; i += 64) fo[i] = fi[i];
+    if (fo) for (int i = lane; i < D / 4; i += 64) fo[i] = load4(fi, i);                    // (gathered copies are fp32)
     if (so) {
       const int sr = src_row[o];
       if (sr >= 0) {
@@ -412,6 +426,7 @@ scatter_kept_rows_kernel(const float* __restrict__ src, int64_t ldk, int64_t ld_
 }
 
 // Level 0: every grid cell, row-major, no background filter (slide.py:257-269).
+template <class T>
 __global__ void __launch_bounds__(256)
 level0_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ gx, const int* __restrict__ gy, int D,
               int patch_size, int64_t n0, float* __restrict__ fts, int64_t* __restrict__ locs,
@@ -426,8 +441,8 @@ level0_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ gx,
   f32x4* fo = fts ? reinterpret_cast<f32x4*>(fts + o * D) : nullptr;
   if (j == 0 && tid == 0) num_ims[b] = n;
   if (j < n) {
-    const f32x4* fi = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(grid_ptrs[b]) + j * D);
-    if (fo) for (int i = tid; i < D / 4; i += 256) fo[i] = fi[i];
+    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + j * D;
+    if (fo) for (int i = tid; i < D / 4; i += 256) fo[i] = load4(fi, i);
     if (tid == 0) {
       locs[2 * o] = (j / Y) * patch_size; locs[2 * o + 1] = (j % Y) * patch_size; parent[o] = j;
       if (row_ptrs) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(fi);
@@ -460,16 +475,17 @@ tissue_mask_kernel(const float* __restrict__ grid, int64_t cells, int D, uint8_t
 // fp16).  absmax_bits holds the fp32 BIT PATTERN of the running maximum: non-negative floats order like their bit patterns and a
 // NaN's pattern is above +inf's, so a NaN anywhere reads back as "not finite".  The atomic is only issued by waves that beat the
 // value they last saw, i.e. a handful of times per grid.
+template <class T>
 __global__ void __launch_bounds__(256)
-tissue_mask_absmax_kernel(const float* __restrict__ grid, int64_t cells, int D, uint8_t* __restrict__ mask, unsigned* __restrict__ absmax_bits) {
+tissue_mask_absmax_kernel(const T* __restrict__ grid, int64_t cells, int D, uint8_t* __restrict__ mask, unsigned* __restrict__ absmax_bits) {
   const int lane = threadIdx.x & 63;
   const int64_t cell = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (cell >= cells) return;
-  const f32x4* row = reinterpret_cast<const f32x4*>(grid + cell * D);
+  const T* row = grid + cell * D;
   float s = 0.f;
   unsigned m = 0;
   for (int i = lane; i < D / 4; i += 64) {
-    const f32x4 v = row[i];
+    const f32x4 v = load4(row, i);
     s += (v[0] + v[1]) + (v[2] + v[3]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
@@ -503,9 +519,10 @@ scale_add_rows_kernel(const float* __restrict__ x, const float* __restrict__ alp
   }
 }
 
-// Synthetic grid (paths_amd/synthetic.py): one thread per 4 channels.
+// Synthetic grid (paths_amd/synthetic.py): one thread per 4 channels.  fp16 grids: the fp32 values rounded to nearest even.
+template <class T>
 __global__ void __launch_bounds__(256)
-synth_grid_kernel(float* __restrict__ grid, int X, int Y, int D, uint32_t k2, int level, unsigned long long bg_thr) {
+synth_grid_kernel(T* __restrict__ grid, int X, int Y, int D, uint32_t k2, int level, unsigned long long bg_thr) {
   const int64_t cell = blockIdx.x;
   const int x = (int)(cell / Y), y = (int)(cell % Y);
   const uint32_t k3 = fmix32(k2 + (uint32_t)x * 0xC2B2AE3Du);
@@ -519,7 +536,14 @@ synth_grid_kernel(float* __restrict__ grid, int X, int Y, int D, uint32_t k2, in
       const float f = ((float)(u >> 8) * 0x1p-23f - 1.0f) * 1.7320508075688772f;
       v[e] = bg ? 0.f : f;
     }
-    *reinterpret_cast<f32x4*>(grid + cell * D + 4 * c4) = v;
+    if constexpr (sizeof(T) == 4) {
+      *reinterpret_cast<f32x4*>(grid + cell * D + 4 * c4) = v;
+    } else {
+      // round the fp32 VALUES (the host replica's double step): without the barrier the last multiply and the conversion fuse into
+      // one mixed-precision FMA that rounds the exact product to fp16 once - 1 ulp apart from fp32-then-fp16 in rare cases
+      asm volatile("" : "+v"(v));
+      *reinterpret_cast<f16x4*>(grid + cell * D + 4 * c4) = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+    }
   }
 }
 
@@ -583,9 +607,25 @@ int paths_gather_rows(const int64_t* grid_ptrs, const int* src_cell, int D, cons
   PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "gather_rows: features must go somewhere (a copy or row pointers)");
   PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "gather_rows: row_ptrs needs a zero row for padding");
   PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "gather_rows: state in/out must both be given or null");
-  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D, state_cur,
+  hipLaunchKernelGGL(gather_kernel<float>, dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D, state_cur,
                      n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row);
   PATHS_LAUNCH_CHECK("gather_rows");
+  return PATHS_OK;
+}
+
+// paths_gather_rows over FP16 grids: row_ptrs address fp16 rows, fts_out (if given) receives fp32 copies.  zero_row: D floats of zero
+// (valid padding for either row width).
+int paths_gather_rows_h16(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                          int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                          float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                          hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n_next > 0 && D % 4 == 0 && Dp % 4 == 0 && ld_state_cur % 4 == 0, "gather_rows_h16: bad shape");
+  PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "gather_rows_h16: features must go somewhere (a copy or row pointers)");
+  PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "gather_rows_h16: row_ptrs needs a zero row for padding");
+  PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "gather_rows_h16: state in/out must both be given or null");
+  hipLaunchKernelGGL(gather_kernel<_Float16>, dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D,
+                     state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row);
+  PATHS_LAUNCH_CHECK("gather_rows_h16");
   return PATHS_OK;
 }
 
@@ -633,9 +673,21 @@ int paths_level0_batch(const int64_t* grid_ptrs, const int* gx, const int* gy, i
                        const float* zero_row, hipStream_t stream) {
   PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "level0_batch: bad shape");
   PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "level0_batch: features need a destination (copy or row pointers + zero row)");
-  hipLaunchKernelGGL(level0_kernel, dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
+  hipLaunchKernelGGL(level0_kernel<float>, dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
                      fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row);
   PATHS_LAUNCH_CHECK("level0_batch");
+  return PATHS_OK;
+}
+
+// paths_level0_batch over FP16 grids (row_ptrs address fp16 rows; fts receives fp32 copies)
+int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                           float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                           const float* zero_row, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "level0_batch_h16: bad shape");
+  PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "level0_batch_h16: features need a destination (copy or row pointers + zero row)");
+  hipLaunchKernelGGL(level0_kernel<_Float16>, dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
+                     fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row);
+  PATHS_LAUNCH_CHECK("level0_batch_h16");
   return PATHS_OK;
 }
 
@@ -656,15 +708,33 @@ int paths_tissue_mask(const float* grid, int64_t cells, int D, uint8_t* mask, hi
 
 int paths_tissue_mask_absmax(const float* grid, int64_t cells, int D, uint8_t* mask, uint32_t* absmax_bits, hipStream_t stream) {
   PATHS_REQUIRE(cells > 0 && D % 4 == 0 && absmax_bits != nullptr, "tissue_mask_absmax: bad arguments");
-  hipLaunchKernelGGL(tissue_mask_absmax_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, stream, grid, cells, D, mask, absmax_bits);
+  hipLaunchKernelGGL(tissue_mask_absmax_kernel<float>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, stream, grid, cells, D, mask, absmax_bits);
   PATHS_LAUNCH_CHECK("tissue_mask_absmax");
+  return PATHS_OK;
+}
+
+// the same pass over an FP16 grid (grid: [cells, D] fp16; sums and max|x| in fp32, identical to the fp32 grid of the same values)
+int paths_tissue_mask_absmax_h16(const void* grid, int64_t cells, int D, uint8_t* mask, uint32_t* absmax_bits, hipStream_t stream) {
+  PATHS_REQUIRE(cells > 0 && D % 4 == 0 && absmax_bits != nullptr, "tissue_mask_absmax_h16: bad arguments");
+  hipLaunchKernelGGL(tissue_mask_absmax_kernel<_Float16>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, stream,
+                     reinterpret_cast<const _Float16*>(grid), cells, D, mask, absmax_bits);
+  PATHS_LAUNCH_CHECK("tissue_mask_absmax_h16");
   return PATHS_OK;
 }
 
 int paths_synth_grid(float* grid, int X, int Y, int D, uint32_t slide_level_key, int level, uint64_t bg_threshold, hipStream_t stream) {
   PATHS_REQUIRE(X > 0 && Y > 0 && D % 4 == 0 && (int64_t)X * Y < ((int64_t)1 << 31), "synth_grid: bad shape");
-  hipLaunchKernelGGL(synth_grid_kernel, dim3((unsigned)((int64_t)X * Y)), dim3(256), 0, stream, grid, X, Y, D, slide_level_key, level, (unsigned long long)bg_threshold);
+  hipLaunchKernelGGL(synth_grid_kernel<float>, dim3((unsigned)((int64_t)X * Y)), dim3(256), 0, stream, grid, X, Y, D, slide_level_key, level, (unsigned long long)bg_threshold);
   PATHS_LAUNCH_CHECK("synth_grid");
+  return PATHS_OK;
+}
+
+// paths_synth_grid into an FP16 grid: the same values rounded to nearest even (synthetic.SyntheticSlide feature_dtype "float16")
+int paths_synth_grid_h16(void* grid, int X, int Y, int D, uint32_t slide_level_key, int level, uint64_t bg_threshold, hipStream_t stream) {
+  PATHS_REQUIRE(X > 0 && Y > 0 && D % 4 == 0 && (int64_t)X * Y < ((int64_t)1 << 31), "synth_grid_h16: bad shape");
+  hipLaunchKernelGGL(synth_grid_kernel<_Float16>, dim3((unsigned)((int64_t)X * Y)), dim3(256), 0, stream, reinterpret_cast<_Float16*>(grid), X, Y, D,
+                     slide_level_key, level, (unsigned long long)bg_threshold);
+  PATHS_LAUNCH_CHECK("synth_grid_h16");
   return PATHS_OK;
 }
 

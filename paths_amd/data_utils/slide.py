@@ -6,6 +6,10 @@ background cell, preprocess/preprocess.py:89,172-175) kept RESIDENT in HBM, plus
 mask computed once on upload (``sum(dim=1) != 0``, reference data_utils/slide.py:324).  The per-level host
 gather + H2D copy of the reference disappears: child rows are gathered on the device straight from these grids.
 At K=2048 one slide is 2.9 GB (level-4 grid alone 2.1 GB); 288 GB of HBM holds ~90 of them.
+
+Grids may also be kept in fp16 (``dtype=torch.float16``, opt-in): half the HBM per slide (~180 K=2048 slides per MI355X).  The
+device kernels read fp16 rows where they live and widen them exactly; the host conversion goes through :func:`to_float16`, which
+refuses values an fp16 grid cannot hold.  bf16 is not supported.
 """
 from __future__ import annotations
 
@@ -16,10 +20,54 @@ import torch
 
 from .. import _lib, synthetic
 
+GRID_DTYPES = (torch.float32, torch.float16)
+FP16_MAX = 65504.0
+
+
+def check_grid_dtype(dtype) -> torch.dtype:
+    """The storage dtype of resident grids: torch.float32 (default) or torch.float16."""
+    if dtype == torch.bfloat16:
+        raise NotImplementedError("bfloat16 feature grids are not supported (torch.float32 or torch.float16)")
+    if dtype not in GRID_DTYPES:
+        raise ValueError(f"feature grids must be torch.float32 or torch.float16, got {dtype}")
+    return dtype
+
+
+def to_float16(grid, chunk_rows: int = 1 << 16) -> Tuple[torch.Tensor, float]:
+    """Host grid [..., D] (numpy or CPU tensor, any float dtype; taken as fp32 first) -> (fp16 CPU tensor rounded to nearest even,
+    max |fp16 - fp32| rounding error).  Raises ValueError when a value is not finite or |x| > 65504, or when a tissue row (nonzero
+    fp32 values) rounds to all zeros - the cell would silently turn into background."""
+    g = torch.as_tensor(grid, dtype=torch.float32)
+    assert g.device.type == "cpu", "to_float16 converts host grids"
+    D = g.shape[-1]
+    flat = g.reshape(-1, D)
+    out = torch.empty(flat.shape, dtype=torch.float16)
+    err = 0.0
+    for r0 in range(0, flat.shape[0], chunk_rows):
+        x = flat[r0:r0 + chunk_rows]
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("to_float16: the grid holds inf or NaN")
+        amax = float(x.abs().max()) if x.numel() else 0.0
+        if amax > FP16_MAX:
+            raise ValueError(f"to_float16: |x| = {amax:g} exceeds the fp16 range ({FP16_MAX:g})")
+        h = x.to(torch.float16)
+        lost = (x != 0).any(dim=1) & ~(h != 0).any(dim=1)
+        if bool(lost.any()):
+            row = r0 + int(torch.nonzero(lost)[0])
+            raise ValueError(f"to_float16: tissue row {row} rounds to all zeros in fp16 (it would become background)")
+        if x.numel():
+            err = max(err, float((h.to(torch.float32) - x).abs().max()))
+        out[r0:r0 + chunk_rows] = h
+    return out.reshape(g.shape), err
+
 
 class DeviceSlide:
     def __init__(self, grids: Sequence[torch.Tensor], patch_size: int = 256, slide_id: str = "", subtype=None):
+        """``grids``: device tensors [X, Y, D], all torch.float32 or all torch.float16 (kept as they are: no fp32 copy is made)."""
         assert len(grids) >= 1
+        self.dtype = check_grid_dtype(grids[0].dtype)
+        if any(g.dtype != self.dtype for g in grids):
+            raise ValueError("DeviceSlide: all levels of a slide must have the same dtype")
         self.patch_size = patch_size
         self.slide_id = slide_id
         self.subtype = subtype
@@ -29,13 +77,14 @@ class DeviceSlide:
         self._absmax: Optional[float] = None
         for g in grids:
             _lib.require_cuda(g)
-            assert g.dim() == 3 and g.dtype == torch.float32
+            assert g.dim() == 3
             g = g.contiguous()
             X, Y, D = g.shape
             m = torch.empty((X, Y), dtype=torch.uint8, device=g.device)
             if self._absmax_bits is None:
                 self._absmax_bits = torch.zeros((1,), dtype=torch.int32, device=g.device)
-            _lib.call("paths_tissue_mask_absmax", g.data_ptr(), X * Y, D, m.data_ptr(), self._absmax_bits.data_ptr(), _lib.stream())
+            _lib.call("paths_tissue_mask_absmax_h16" if self.dtype == torch.float16 else "paths_tissue_mask_absmax", g.data_ptr(), X * Y, D,
+                      m.data_ptr(), self._absmax_bits.data_ptr(), _lib.stream())
             self.grids.append(g)
             self.masks.append(m)
 
@@ -58,40 +107,48 @@ class DeviceSlide:
         return self.grids[0].shape[2]
 
     @staticmethod
-    def from_host(grids: Sequence, device, **kw) -> "DeviceSlide":
-        """Upload host grids (numpy or CPU tensors, e.g. ``torch.load('<slide>_<power:.3f>.pt')``)."""
+    def from_host(grids: Sequence, device, dtype=torch.float32, **kw) -> "DeviceSlide":
+        """Upload host grids (numpy or CPU tensors, e.g. ``torch.load('<slide>_<power:.3f>.pt')``) as ``dtype`` grids
+        (torch.float16: converted on the host by :func:`to_float16`, which raises on values fp16 cannot hold)."""
+        if check_grid_dtype(dtype) == torch.float16:
+            return DeviceSlide([to_float16(g)[0].to(device) for g in grids], **kw)
         return DeviceSlide([torch.as_tensor(g, dtype=torch.float32).to(device) for g in grids], **kw)
 
     @staticmethod
     def from_preprocessed(root: str, slide_id: str, powers: Sequence[float], device="cuda", patch_size: int = 256,
-                          subtype=None) -> "DeviceSlide":
+                          subtype=None, dtype=torch.float32) -> "DeviceSlide":
         """Load the reference's preprocessed-grid files ``<root>/<slide_id>_<power:.3f>.pt`` (one ``[X, Y, D]`` float
         tensor per magnification, all-zero row = background; written by reference preprocess/preprocess.py:89,134 and
-        read by preprocess/loader.py:14-18 / data_utils/slide.py:247-253) and make them resident in HBM."""
+        read by preprocess/loader.py:14-18 / data_utils/slide.py:247-253) and make them resident in HBM as ``dtype`` grids
+        (see :meth:`from_host`)."""
         import os
+        check_grid_dtype(dtype)                 # before any file is read or the device is touched
         grids = []
         for power in powers:
             path = os.path.join(root, slide_id + f"_{power:.3f}.pt")
             assert os.path.isfile(path), f"Pre-process load: path '{path}' not found!"
             g = torch.load(path, map_location="cpu")
             assert g.dim() == 3, f"{path}: expected a [X, Y, D] grid, got {tuple(g.shape)}"
-            grids.append(g.float())
-        return DeviceSlide.from_host(grids, device, patch_size=patch_size, slide_id=slide_id, subtype=subtype)
+            grids.append(g.float() if dtype == torch.float32 else g)
+        return DeviceSlide.from_host(grids, device, dtype=dtype, patch_size=patch_size, slide_id=slide_id, subtype=subtype)
 
     @staticmethod
     def synthetic(seed: int, slide: int, base_shape: Tuple[int, int], dim: int = 1024, num_levels: int = 5,
-                  p_bg: float = 0.1, device="cuda", patch_size: int = 256) -> "DeviceSlide":
-        """Generate the counter-based synthetic pyramid directly in HBM (paths_synth_grid)."""
+                  p_bg: float = 0.1, device="cuda", patch_size: int = 256, dtype=torch.float32) -> "DeviceSlide":
+        """Generate the counter-based synthetic pyramid directly in HBM (paths_synth_grid; torch.float16: paths_synth_grid_h16, the same
+        values rounded to nearest even)."""
+        h16 = check_grid_dtype(dtype) == torch.float16
         grids = []
         thr = synthetic.bg_threshold(p_bg)
         for l in range(num_levels):
             X, Y = base_shape[0] << l, base_shape[1] << l
-            g = torch.empty((X, Y, dim), dtype=torch.float32, device=device)
+            g = torch.empty((X, Y, dim), dtype=dtype, device=device)
             key = int(synthetic.slide_level_key(seed, slide, l))
-            _lib.call("paths_synth_grid", g.data_ptr(), X, Y, dim, key, l, thr, _lib.stream())
+            _lib.call("paths_synth_grid_h16" if h16 else "paths_synth_grid", g.data_ptr(), X, Y, dim, key, l, thr, _lib.stream())
             grids.append(g)
         s = DeviceSlide(grids, patch_size=patch_size, slide_id=f"synthetic-{seed}-{slide}")
-        s.synthetic_spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg)
+        s.synthetic_spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg,
+                                                    feature_dtype="float16" if h16 else "float32")
         return s
 
 
@@ -110,6 +167,10 @@ class DeviceSlideBatch:
         self.device, self.num_levels = dev, L
         self.dim = self.slides[0].dim
         assert all(s.dim == self.dim for s in self.slides)
+        self.dtype = self.slides[0].dtype            # grid dtype of the whole batch: the recursion picks its kernels by it
+        if any(s.dtype != self.dtype for s in self.slides):
+            raise ValueError("DeviceSlideBatch: slides of one batch must share the grid dtype (got "
+                             + ", ".join(sorted({str(s.dtype) for s in self.slides})) + ")")
 
         def table(fn, dtype):
             return [torch.tensor([fn(s, l) for s in self.slides], device=dev, dtype=dtype) for l in range(L)]

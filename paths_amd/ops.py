@@ -576,7 +576,7 @@ def importance_proj_generic(mc, lvl_pack, src, ld_src: int, locs, num_ims, B: in
 
 
 def importance_proj_generic_add(mc, lvl_pack, src, x_rows, add, locs, num_ims, B: int, N: int, D: int, imp_mul: int, imp_out, tokens, skip_padding: bool,
-                                pe_tab=None):
+                                pe_tab=None, x_rows_h16: bool = False):
     """:func:`importance_proj_generic` on the split-operand kernel with the GEMM input ``src + add`` summed while it is staged (the
     Y = X + h1 form of the tuned path: Y is never stored, ``src`` may be row addresses into the resident grids): the LSTM part of the
     selection chain does not depend on the aggregator's geometry, so every geometry gets the tuned gate kernels."""
@@ -602,7 +602,7 @@ def importance_proj_generic_add(mc, lvl_pack, src, x_rows, add, locs, num_ims, B
     # paths_tokens_assemble selects on that 0 - only when the importance does not multiply the tokens does the buffer need a fill;
     # _lib.zeros: the fill is repeated when a recorded launch tape is replayed)
     hp_ = (_lib.zeros if (skip_padding and not imp_mul) else torch.empty)((M, n), device=dev, dtype=torch.float32)
-    _lib.call("paths_gemm_add_nt_x6", p(src) if x_rows is None else None, D, p(x_rows), p(add), add.stride(1), img.data_ptr(), D, p(gp["b1p"]), p(hp_), n,
+    _lib.call("paths_gemm_add_nt_x6_h16" if x_rows_h16 else "paths_gemm_add_nt_x6", p(src) if x_rows is None else None, D, p(x_rows), p(add), add.stride(1), img.data_ptr(), D, p(gp["b1p"]), p(hp_), n,
               M, n, n_pad, D, 0, nim, N, ws, a_scale(), st)
     pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
     if pe_tab is not None and FUSE_IMPORTANCE_TOKENS:
@@ -870,7 +870,7 @@ def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor
 def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, skip_padding: bool,
                       parent=None, max_pos: int = 0, x_rows=None, feat_dim: Optional[int] = None,
                       importance_out: Optional[torch.Tensor] = None, last_level: bool = False,
-                      topk: Optional[Dict[str, object]] = None) -> Dict[str, torch.Tensor]:
+                      topk: Optional[Dict[str, object]] = None, x_rows_h16: bool = False) -> Dict[str, torch.Tensor]:
     """The part of a level that decides the NEXT level: LSTM state update, importance, token projection
     (reference model/paths.py:71-124).  Returns ctx_patch (new state), importance, tokens, num_ims.
 
@@ -887,6 +887,8 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
 
     ``x_rows`` (device recursion only, default split mode): [B, N] int64 ADDRESSES of the feature rows (paths_gather_rows
     ``row_ptrs``); ``fts`` is then None, ``feat_dim`` = D, and the GEMMs read the rows where they live (no gathered copy).
+    ``x_rows_h16``: the rows are fp16 (fp16 slide grids): the row-addressed GEMMs take their ``_h16`` entry points (one-plane A operand
+    in the gate GEMMs, fp16 rows widened in the importance / projection GEMM's staging).
 
     ``parent`` (device recursion only) = {"hp": [rows, 3Hc+D], "hp_row": [B,N] int32, "c0": [B,N,Hc]}: the up-to-4 children
     of a kept patch share the parent's h, so the h half of the gate GEMM is computed once per kept PARENT
@@ -914,6 +916,8 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
 
     x6 = use_x6(D, lstm_pack["Hc"] if mc.lstm else 64)
     assert x_rows is None or (x6 and split_planes() == 2 and mc.lstm), "row pointers need the default split mode and lstm=true"
+    assert not x_rows_h16 or x_rows is not None, "x_rows_h16 describes x_rows"
+    h16 = "_h16" if x_rows_h16 else ""
     pe_rows = N if pe_mode == 1 else int(max_pos)
     if pe_rows == 0 and FUSE_QKV in (1, 2) and fast_path(mc) and N % 64 == 0 and not torch.is_grad_enabled():
         # a drop-in call (no grid size given): the fused finish reads its sin / cos values from the table only, so the table is sized
@@ -943,6 +947,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
         if x6:
             wip, wip_s = _x6_of(lvl_pack, "w_ip_fwd")
             splitk = SPLITK_IMPORTANCE and add is not None and split_planes() == 2 and (M + 127) // 128 <= 160
+            splitk = splitk or (x_rows_h16 and src is None)          # (the fp16-row form has the split-K kernel only)
             if splitk and fuse_qkv and imp_out is importance:
                 # GEMM rows in token order + a finish that also projects q | k | v of decoder layer 0 into the attention's operand images
                 lay0 = lvl_pack["layers"][0]
@@ -963,21 +968,21 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
                         fused["keep_idx"] = torch.empty((B, cap), device=dev, dtype=torch.int32)
                         fused["keep_count"] = torch.empty((B,), device=dev, dtype=torch.int32)
                         fused["kept_rows"] = torch.empty((B, cap), device=dev, dtype=torch.int64)
-                        _lib.call("paths_importance_qkv_x6", *args, 9, 0, keep, p(fused["keep_idx"]), cap, p(fused["keep_count"]), p(state_out), Dp,
+                        _lib.call("paths_importance_qkv_x6" + h16, *args, 9, 0, keep, p(fused["keep_idx"]), cap, p(fused["keep_count"]), p(state_out), Dp,
                                   p(fused["kept_rows"]), p(topk["zero_row"]), p(topk_counters(dev, B)), p(topk.get("status")), st)
                     else:
-                        _lib.call("paths_importance_qkv_x6", *args, 3, 0, *no_topk, st)
+                        _lib.call("paths_importance_qkv_x6" + h16, *args, 3, 0, *no_topk, st)
                     # (the aggregator stream finishes the tokens: ws / qkv_img travel with the closure)
                     fused["finish"] = lambda: _lib.call("paths_importance_qkv_x6", *args, 4, 1, *no_topk, _lib.stream())
                 else:
-                    _lib.call("paths_importance_qkv_x6", *args, 5, 0, *no_topk, st)
+                    _lib.call("paths_importance_qkv_x6" + h16, *args, 5, 0, *no_topk, st)
                 fused["qkv_img"], fused["ws"] = qkv_img, ws
                 return
             # M/128 blocks fill half the chip at K = 2048 x 8 slides: two k halves on twice the blocks + an epilogue launch
             splitk_ws = None
             if splitk:
                 splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=dev, dtype=torch.uint8)
-            _lib.call("paths_importance_proj_x6", p(src), D, p(x_rows) if src is None else None, p(add),
+            _lib.call("paths_importance_proj_x6" + (h16 if src is None else ""), p(src), D, p(x_rows) if src is None else None, p(add),
                       add.stride(1) if add is not None else 0,
                       p(wip), *common[:-1], split_planes(), wip_s, a_scale(), p(splitk_ws), common[-1])
         else:
@@ -1014,7 +1019,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
         def lstm(phases):
             if x6:
                 (wg, wg_s), (wm, wm_s) = _x6_of(lstm_pack, "w_gates"), _x6_of(lstm_pack, "w_mem")
-                _lib.call("paths_lstm_cell_x6", p(fts), D, p(x_rows), h0, ld, c0, ld, p(wg), p(lstm_pack["b_gates"]), p(wm), p(lstm_pack["b_mem"]),
+                _lib.call("paths_lstm_cell_x6" + h16, p(fts), D, p(x_rows), h0, ld, c0, ld, p(wg), p(lstm_pack["b_gates"]), p(wm), p(lstm_pack["b_mem"]),
                           p(state_out), Dp, p(y), D, p(ws_o), None, None, hp, hp_row, M, D, Hc, nim, N, phases,
                           split_planes(), wg_s, wm_s, a_scale(), st)
             else:
@@ -1031,7 +1036,8 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
             timed("lstm_mem_to_out", lambda: lstm(4))
         if generic_add:
             timed("importance_proj", lambda: importance_proj_generic_add(mc, lvl_pack, fts, x_rows, state_out, locs, num_ims, B, N, D,
-                                                                         1 if mc.importance_mode == "mul" else 0, importance, tokens, skip_padding, pe_tab=pe_tab))
+                                                                         1 if mc.importance_mode == "mul" else 0, importance, tokens, skip_padding, pe_tab=pe_tab,
+                                                                         x_rows_h16=x_rows_h16))
         elif x6 and not generic:
             timed("importance_proj", lambda: importance_proj(fts, 1 if mc.importance_mode == "mul" else 0, importance, add=state_out))
         else:

@@ -21,6 +21,8 @@ Definition (all arithmetic mod 2**32)::
 The grid format is the reference's preprocessed-grid format: ``[X, Y, D]`` float32 per level, an
 all-zero row marks a background cell (reference preprocess/preprocess.py:89,172-175); level ``l``
 has ``2**l`` times the level-0 cells per side (reference data_utils/slide.py:303-315).
+``SyntheticSlide(feature_dtype="float16")`` describes the same pyramid stored as fp16: every feature
+rounded to nearest even (``paths_synth_grid_h16``), served here widened back to float32.
 """
 from __future__ import annotations
 
@@ -93,21 +95,36 @@ def cell_features(seed: int, slide: int, level: int, x, y, dim: int, p_bg: float
     return f
 
 
+FEATURE_DTYPES = ("float32", "float16")
+
+
 @dataclass
 class SyntheticSlide:
-    """A lazily evaluated 5-level feature pyramid; ``grid(level)`` materialises a dense [X,Y,D]."""
+    """A lazily evaluated 5-level feature pyramid; ``grid(level)`` materialises a dense [X,Y,D].
+    ``feature_dtype`` = the storage dtype of the grids: "float32" (the generator's values) or "float16" (those values rounded to
+    nearest even; rows are still returned as float32 arrays)."""
     seed: int
     slide: int
     base_shape: Tuple[int, int]
     dim: int = 1024
     num_levels: int = 5
     p_bg: float = 0.1
+    feature_dtype: str = "float32"
+
+    def __post_init__(self):
+        if self.feature_dtype == "bfloat16":
+            raise NotImplementedError("bfloat16 feature grids are not supported (float32 or float16)")
+        if self.feature_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"feature_dtype must be one of {FEATURE_DTYPES}, got {self.feature_dtype!r}")
 
     def shape(self, level: int) -> Tuple[int, int]:
         return self.base_shape[0] << level, self.base_shape[1] << level
 
     def rows(self, level: int, x, y) -> np.ndarray:
-        return cell_features(self.seed, self.slide, level, x, y, self.dim, self.p_bg)
+        f = cell_features(self.seed, self.slide, level, x, y, self.dim, self.p_bg)
+        if self.feature_dtype == "float16":
+            f = f.astype(np.float16).astype(np.float32)          # numpy rounds to nearest even, like v_cvt_f16_f32
+        return f
 
     def is_background(self, level: int, x, y) -> np.ndarray:
         return cell_is_background(self.seed, self.slide, level, x, y, self.p_bg)

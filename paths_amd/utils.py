@@ -204,6 +204,8 @@ class TapedRecursion:
         on the current stream: no host sync).  Anything else drops the tape; the next replay records for the new batch."""
         new = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
         rec = self._rec_batch
+        if new.dtype != self.batch.dtype:           # (the launches differ by grid dtype: a tape never serves both)
+            raise ValueError(f"rebind: the tape serves {self.batch.dtype} grids, the new batch holds {new.dtype} grids")
         fits = (self.tape is not None and rec is not None and len(new) == len(rec) and new.dim == rec.dim and new.device == rec.device
                 and new.num_levels >= self.levels and new.n0 <= rec.n0
                 and all(new.max_dim[l] <= rec.max_dim[l] for l in range(self.levels))
@@ -400,6 +402,9 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
 
     grid_ptrs, mask_ptrs, gx, gy = batch.grid_ptrs, batch.mask_ptrs, batch.gx, batch.gy
     N = batch.n0
+    # fp16 grids: the selection-chain kernels and the row-addressed GEMMs take their _h16 forms; every gathered copy is fp32
+    h16 = batch.dtype == torch.float16
+    sfx = "_h16" if h16 else ""
     lstm_pack = ops.pack_lstm(model.lstm) if model.use_lstm else None
     share_parent = model.use_lstm          # siblings share the parent's h: h-half of the gate GEMM once per kept parent
     # default split mode: feature rows are read in place in the resident grids (row-pointer GEMM operands) instead of being
@@ -412,7 +417,7 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
     locs = torch.empty((B, N, 2), **i64)
     parent_inds = torch.empty((B, N), **i64)
     num_ims = torch.empty((B,), **i64)
-    _lib.call("paths_level0_batch", p(grid_ptrs[0]), p(gx[0]), p(gy[0]), B, D, mc.patch_size, N,
+    _lib.call("paths_level0_batch" + sfx, p(grid_ptrs[0]), p(gx[0]), p(gy[0]), B, D, mc.patch_size, N,
               p(fts), p(locs), p(parent_inds), p(num_ims), 0, p(x_rows), p(zero_row), st)
     state_prev, ctx_hist, parent = None, [], None
     out = None
@@ -455,7 +460,7 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                 (_lib.fork_behind(dsts, main_stream) if overlap else contextlib.nullcontext()):
             sel = ops.selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, True, parent=parent,
                                         max_pos=batch.max_dim[i], x_rows=x_rows, feat_dim=D, importance_out=imp_buf,
-                                        last_level=last,
+                                        last_level=last, x_rows_h16=h16 and rows_in_place,
                                         topk={"keep": keep, "zero_row": zero_row, "status": status} if want_topk else None)
         fused_topk = "keep_idx" in sel           # (else: the top-K launch below carries the expansion stream's fork, as before)
         def aggregate():
@@ -538,18 +543,18 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                     fts_next = None
                     x_rows_next = torch.empty((B, Nn), **i64)
                     ops.timed("gather", lambda: _lib.call(
-                        "paths_gather_rows", p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                        "paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
                         p(src_row), Hc, p(num_next), B, Nn, None, p(state_next), 0, p(x_rows_next), p(zero_row), st2))
                 else:
                     fts_next = torch.empty((B, Nn, D), **f32)
-                    _lib.call("paths_gather_rows", p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                    _lib.call("paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
                               p(src_row), Hc, p(num_next), B, Nn, p(fts_next), p(state_next), 0, None, None, st2)
                 parent = {"hp": hp, "hp_row": hp_row, "c0": state_next}
                 state_next = None
             else:
                 fts_next = torch.empty((B, Nn, D), **f32)
                 state_next = torch.empty((B, Nn, Dp), **f32)
-                _lib.call("paths_gather_rows", p(grid_ptrs[i + 1]), p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
+                _lib.call("paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
                           p(num_next), B, Nn, p(fts_next), p(state_next), 0, None, None, st2)
             if forked:
                 fork_pending = True
@@ -597,7 +602,8 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
     locs = torch.empty((B, N, 2), **i64)
     parent = torch.empty((B, N), **i64)
     num_ims = torch.empty((B,), **i64)
-    _lib.call("paths_level0_batch", p(batch.grid_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, mc.patch_size, N,
+    h16 = batch.dtype == torch.float16                     # fp16 grids: the gathers write fp32 copies, the training kernels are unchanged
+    _lib.call("paths_level0_batch_h16" if h16 else "paths_level0_batch", p(batch.grid_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, mc.patch_size, N,
               p(fts), p(locs), p(parent), p(num_ims), 1, None, None, st)
     state_prev, ctx_prev, ctx_hist = None, None, []
     logits = None
@@ -661,12 +667,12 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
                           B, Nn, p(num_next), p(locs_next), p(parent_next), p(src_row), p(src_cell), p(status), None, st)
         if parent_form:
             fts, c0, h_kept = pag.GatherParentFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx, keep_count,
-                                                       child_pos, D, Nn)
+                                                       child_pos, D, Nn, h16)
             par = {"c0": c0, "h_kept": h_kept, "hp_row": hp_row, "child_pos": child_pos, "keep_count": keep_count, "cap": cap_keep}
             state_prev = None
         else:
             fts, state_prev = pag.GatherFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx,
-                                                 keep_count, child_pos, D, Nn)
+                                                 keep_count, child_pos, D, Nn, h16)
         locs, parent, num_ims, N = locs_next, parent_next, num_next, Nn
     return {"logits": logits, "status": status}
 
