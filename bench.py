@@ -11,9 +11,13 @@ gather]) over one batch of synthetic slides that are ALREADY RESIDENT in HBM.  S
 shard the batch with no data-path collective (weak scaling: --slides-per-gpu slides per rank); the only
 collectives are the barriers around the timed region and a MAX-reduce of the elapsed time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-  roofline     dominant kernel (output-gate GEMM of the LSTM cell) timed live with events on the launch stream inside
-               the timed region; achieved = algorithmic FLOP (2 M N K) / measured duration.  Default build
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the run's shape and config).  A plain
+run does only what that line needs: set up, warm up, time the steps, write --dump-outputs, print.  Everything else the benchmark
+measures runs with --full, after the timed steps, and adds its objects to the line (infer mode: single_batch, sustained,
+launch_modes, serialized_breakdown, train, k1024, trans_dim_192, stress, parity_checked, and the two below):
+  roofline     dominant kernel (output-gate GEMM of the LSTM cell) timed with events on its launch stream over the same K
+               steps (an eager instrumented pass; --eager: the timed steps themselves); achieved = algorithmic FLOP (2 M N K) /
+               measured duration.  Default build
                (PATHS_GEMM_MODE=h3): the GEMM multiplies fp32 operands as 2 fp16 planes with 3 MFMAs per product block
                (csrc/gemm_x6.hip), so its ceiling is the dense 16-bit MFMA peak / 3; "x6": 3 bf16 planes, 6 MFMAs, peak / 6;
                "f32": the f32-input MFMA kernel (peak 157.3 TFLOP/s).
@@ -139,6 +143,31 @@ def build_model(K: int, dev, dropout=None, trans_dim=None):
     sd = syn.make_state_dict(0, shapes)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     return cfg, model.to(dev).eval(), sd
+
+
+def gemm_split(cfg, batch):
+    """(x6, planes) of the recursion's LSTM output-gate GEMM on ``batch``, as its launch reports them to the kernel timer
+    (paths_amd/ops.py level_forward), known without running a step: split-operand kernels or not, and 2 (fp16) / 3 (bf16) planes."""
+    from paths_amd import ops
+    mc = cfg.model_config
+    if not mc.lstm:                      # (no LSTM cell: no output-gate launch, the line says "f32")
+        return False, 0
+    with ops.range_guard(batch.feat_absmax):
+        x6 = ops.use_x6(batch.dim, mc.hierarchical_ctx_mlp_hidden_dim)
+        return x6, (ops.split_planes() if x6 else 0)
+
+
+def infer_dtype(x6: bool, planes: int) -> str:
+    return ("f32 (products as 2 fp16 planes per operand = 22 bits, 3 fp16 MFMAs per block, fp32 accumulate)" if planes == 2 else
+            "f32 (products as 3 exact bf16 planes per operand, 6 bf16 MFMAs per block, fp32 accumulate)" if x6 else "f32")
+
+
+def infer_gemm_mode(x6: bool, planes: int) -> str:
+    return (("h3: GEMM, attention and token-layer operands split into 2 fp16 planes (22 bits), 3 fp16 MFMAs per "
+             "product block, fp32 accumulate, power-of-two scaling of weights / GEMM activations (error of the "
+             "order of an fp32 FMA chain's); everything else fp32") if planes == 2 else
+            ("x6: operands split exactly into 3 bf16 planes, 6 bf16 MFMAs per product block, fp32 "
+             "accumulate (error <= an fp32 FMA chain's); everything else fp32") if x6 else "f32 MFMA")
 
 
 def cpu_baseline(cfg, sd, K: int, n_slides: int, reps: int):
@@ -561,6 +590,13 @@ def train_probe(cfg, model, slides, world, dev_reduce, pdist, putils, steps: int
     return out
 
 
+def close_process_group():
+    import torch.distributed as dist
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -568,19 +604,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--slides-per-gpu", type=int, default=8)
     ap.add_argument("--k", type=int, default=2048, choices=sorted(BASE_SHAPES))
-    ap.add_argument("--cpu-slides", type=int, default=8, help="slides of the cpu_baseline / parity_checked sample (a full batch at K=2048; "
-                    "capped at the number of screened ids of the K)")
-    ap.add_argument("--cpu-reps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="infer mode: after the timed steps, also measure and check everything "
+                    "beyond the headline (the options below marked --full) and add it to the line; off: the line carries the timed steps only")
+    ap.add_argument("--cpu-slides", type=int, default=8, help="--full: slides of the cpu_baseline / parity_checked sample (a full batch at "
+                    "K=2048; capped at the number of screened ids of the K)")
+    ap.add_argument("--cpu-reps", type=int, default=2, help="--full: timed repetitions of the cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline / parity_checked")
     ap.add_argument("--eager", action="store_true", help="timed region issues every launch through the Python launch path instead of "
                     "replaying the recorded launch tape (paths_amd.utils.TapedRecursion)")
     ap.add_argument("--graph", action="store_true", help="timed region replays the captured HIP graph of the recursion "
                     "(paths_amd.utils.GraphedRecursion) instead of issuing every launch from Python.  Measured on ROCm 7.2: the host "
                     "share drops from 0.65 to 0.13 of the step but the replay executes the three captured streams with far less "
                     "overlap (3.92 ms per step against 2.43 ms eager), so eager launches stay the default")
-    ap.add_argument("--sustain", type=float, default=6.0, help="seconds of the extra DVFS-steady loop (0 = skip); >= 6 s so that a 5-s "
+    ap.add_argument("--sustain", type=float, default=6.0, help="--full: seconds of the extra DVFS-steady loop (0 = skip); >= 6 s so that a 5-s "
                     "utilisation sampler beside the run lands inside GPU work")
-    ap.add_argument("--breakdown-steps", type=int, default=3, help="steps of the serialised per-kernel breakdown pass (0 = skip)")
+    ap.add_argument("--breakdown-steps", type=int, default=3, help="--full: steps of the serialised per-kernel breakdown pass (0 = skip)")
     ap.add_argument("--dropout", type=float, default=None, help="train mode: dropout probability (default: the shipped config's 0.05)")
     ap.add_argument("--trans-dim", type=int, default=128, help="stress mode: aggregator width (BASELINE configs[4] reports 128 and 1536; "
                     "1536 with --trans-heads 24 = head_dim 64 runs on the flash-style kernels, with the reference's own 4 heads = head_dim "
@@ -590,14 +628,14 @@ def main():
                     "its logit distance from the fp32-accurate path")
     ap.add_argument("--rotate", type=int, default=3, help="infer mode: distinct resident slide batches (21 GiB each at K=2048) cycled "
                     "through the timed region, one recorded launch tape each; the headline is measured on the rotation (every step works "
-                    "on different rows than the step before), the single-batch replay figure is reported beside it")
-    ap.add_argument("--train-steps", type=int, default=10, help="infer mode: timed steps of the short training measurement added to the "
+                    "on different rows than the step before); --full reports the single-batch replay figure beside it")
+    ap.add_argument("--train-steps", type=int, default=10, help="--full: timed steps of the short training measurement added to the "
                     "line as 'train' (0 = skip); 3 warm-up steps")
-    ap.add_argument("--stress-steps", type=int, default=4, help="infer mode, N=1: timed steps of the 'stress' object (BASELINE configs[4]: one level, "
+    ap.add_argument("--stress-steps", type=int, default=4, help="--full, N=1: timed steps of the 'stress' object (BASELINE configs[4]: one level, "
                     "K = 8192 x d = 1536, fp32-accurate path and the opt-in e4m3 variants at trans_dim 128 / 4 heads, 1536 / 24 heads and 1536 / 4 heads); 0 = skip")
-    ap.add_argument("--k1024-steps", type=int, default=20, help="infer mode: timed steps of the 'k1024' object (BASELINE configs[1]: the same "
+    ap.add_argument("--k1024-steps", type=int, default=20, help="--full: timed steps of the 'k1024' object (BASELINE configs[1]: the same "
                     "5-level recursion at K = 1024 patches per level on one GPU's 8 resident slides); 0 = skip")
-    ap.add_argument("--td192-steps", type=int, default=20, help="infer mode: timed steps of the 'trans_dim_192' object (the headline workload at the "
+    ap.add_argument("--td192-steps", type=int, default=20, help="--full: timed steps of the 'trans_dim_192' object (the headline workload at the "
                     "reference's dataclass-default aggregator width, config.py:30); 0 = skip")
     ap.add_argument("--cores-per-rank", type=int, default=0, help="pin this rank to N host cores (cores [rank N, rank N + N) of the "
                     "process's allowed set) BEFORE anything touches the GPU: what a rank gets when 8 ranks share one host's CPU share "
@@ -733,6 +771,27 @@ def main():
         write_outputs(args.dump_outputs, recursion_outputs(out))
     per_rank = pdist.gather_floats(own_elapsed / args.steps * 1e3)  # every rank's own ms per step (load imbalance: slides differ)
     elapsed = pdist.max_over_ranks(elapsed, dev_reduce)
+    x6, planes = gemm_split(cfg, slides)
+    line = {
+        "metric": "slides_per_sec_5level_K%d_D1024" % K, "value": round(spg * world * args.steps / elapsed, 2), "unit": "slides/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "per_rank_ms_per_step": [round(v, 3) for v in per_rank], "rank_imbalance_max_over_min": round(max(per_rank) / max(min(per_rank), 1e-9), 4),
+        "vs_baseline": None, "dtype": infer_dtype(x6, planes), "data": "synthetic",
+        "config": {"workload": f"5-level PATHS recursion (forward, eval): K={K} patches/level (level-0 grid "
+                               f"{BASE_SHAPES[K][0]}x{BASE_SHAPES[K][1]}, top_k {K // 4}, 10% background), D=1024 "
+                               f"features, trans_dim 128 x 4 heads x 2 layers, LSTM ctx 256; {spg} HBM-resident slides per GPU",
+                   "slides_per_gpu": spg, "global_batch": spg * world, "levels": cfg.num_levels,
+                   "resident_batches_rotated": nrot,
+                   "parallelism": f"slide-sharded x{world} (no data-path collective)",
+                   "gemm_mode": infer_gemm_mode(x6, planes)},
+        "host": {"launch_mode": launch_mode, "t_enqueued_over_elapsed": round(t_enqueued / max(elapsed, 1e-9), 3)},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        close_process_group()
+        return
     single = None
     if nrot > 1:
         # the same K steps on ONE batch (the round-2 headline): every step re-reads the rows the previous one touched
@@ -924,6 +983,8 @@ def main():
     meta0 = samples_o[0][1] if samples_o else {}
     x6 = bool(meta0.get("x6"))
     planes = int(meta0.get("planes", 3)) if x6 else 0
+    if samples_o and (x6, planes) != gemm_split(cfg, slides):
+        log(f"the instrumented output-gate launches ran x6={x6} planes={planes}; the line's dtype follows {gemm_split(cfg, slides)}")
     traffic = None            # HBM-side bytes per launch from the committed PMC passes (separate --pmc runs, profiles/)
     prof = {2: PMC_PROFILE_H3, 3: "r01e_pmc_traffic.json"}.get(planes, "r01_pmc_traffic.json")
     try:
@@ -1119,42 +1180,18 @@ def main():
             log(f"stress probe FAILED: {stress['error']}")
     per_rank_valid = pdist.gather_floats(float(sum(valid)))      # valid patches per step of every rank (what its step time follows)
     if rank == 0:
-        total_slides = spg * world * args.steps
-        line = {
-            "metric": "slides_per_sec_5level_K%d_D1024" % K, "value": round(total_slides / elapsed, 2), "unit": "slides/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "per_rank_ms_per_step": [round(v, 3) for v in per_rank], "rank_imbalance_max_over_min": round(max(per_rank) / max(min(per_rank), 1e-9), 4),
-            "per_rank_valid_patches_per_step": [int(v) for v in per_rank_valid],
-            "vs_baseline": None,
-            "dtype": ("f32 (products as 2 fp16 planes per operand = 22 bits, 3 fp16 MFMAs per block, fp32 accumulate)" if planes == 2 else
-                      "f32 (products as 3 exact bf16 planes per operand, 6 bf16 MFMAs per block, fp32 accumulate)" if x6 else "f32"),
-            "data": "synthetic",
-            "config": {"workload": f"5-level PATHS recursion (forward, eval): K={K} patches/level (level-0 grid "
-                                   f"{BASE_SHAPES[K][0]}x{BASE_SHAPES[K][1]}, top_k {K // 4}, 10% background), D=1024 "
-                                   f"features, trans_dim 128 x 4 heads x 2 layers, LSTM ctx 256; {spg} HBM-resident slides per GPU",
-                       "slides_per_gpu": spg, "global_batch": spg * world, "levels": cfg.num_levels,
-                       "resident_batches_rotated": nrot,
-                       "parallelism": f"slide-sharded x{world} (no data-path collective)",
-                       "gemm_mode": ("h3: GEMM, attention and token-layer operands split into 2 fp16 planes (22 bits), 3 fp16 MFMAs per "
-                                     "product block, fp32 accumulate, power-of-two scaling of weights / GEMM activations (error of the "
-                                     "order of an fp32 FMA chain's); everything else fp32") if planes == 2 else
-                                    ("x6: operands split exactly into 3 bf16 planes, 6 bf16 MFMAs per product block, fp32 "
-                                     "accumulate (error <= an fp32 FMA chain's); everything else fp32") if x6 else "f32 MFMA"},
-            "roofline": dict(roofline, attn_ffn=None if roofline_attn is None else {
-                k: roofline_attn.get(k) for k in ("achieved", "peak", "unit", "frac", "avg_span_us", "serialized_span_us", "serialized_frac",
-                                                   "serialized_span_replayed_us", "serialized_frac_replayed", "serialized_note",
-                                                   "serialized_frac_of_measured_peak", "algorithmic_gflop_per_level_launch",
-                                                   "in_proj_fused_into_finish", "algorithmic_gflop_in_proj0_excluded", "fuse_qkv_mode",
-                                                   "event_bracket_overhead", "serialized_frac_net_of_bracket", "serialized_span_by_level_us",
-                                                   "serialized_frac_by_level", "valid_patches_by_level")}),
-            "roofline_attn_ffn": roofline_attn,
-            "host": {"launch_mode": launch_mode,
-                     "t_enqueued_over_elapsed": round(t_enqueued / max(elapsed, 1e-9), 3), "eager_instrumented_pass": eager,
-                     "launch_modes": launch_modes,
-                     "note": "roofline / roofline_attn_ffn event timings come from the eager instrumented pass of the same K steps "
-                             "(the replayed launch sequence carries no events)" if replayed_launches else None},
-        }
+        line["per_rank_valid_patches_per_step"] = [int(v) for v in per_rank_valid]
+        line["roofline"] = dict(roofline, attn_ffn=None if roofline_attn is None else {
+            k: roofline_attn.get(k) for k in ("achieved", "peak", "unit", "frac", "avg_span_us", "serialized_span_us", "serialized_frac",
+                                               "serialized_span_replayed_us", "serialized_frac_replayed", "serialized_note",
+                                               "serialized_frac_of_measured_peak", "algorithmic_gflop_per_level_launch",
+                                               "in_proj_fused_into_finish", "algorithmic_gflop_in_proj0_excluded", "fuse_qkv_mode",
+                                               "event_bracket_overhead", "serialized_frac_net_of_bracket", "serialized_span_by_level_us",
+                                               "serialized_frac_by_level", "valid_patches_by_level")})
+        line["roofline_attn_ffn"] = roofline_attn
+        line["host"].update(eager_instrumented_pass=eager, launch_modes=launch_modes,
+                            note="roofline / roofline_attn_ffn event timings come from the eager instrumented pass of the same K steps "
+                                 "(the replayed launch sequence carries no events)" if replayed_launches else None)
         if single is not None:
             line["single_batch"] = single
         if train is not None:
@@ -1173,10 +1210,7 @@ def main():
             line["cpu_baseline"], ids, otrace, ohz = cpu_baseline(cfg, sd, K, args.cpu_slides, args.cpu_reps)
             line["parity_checked"] = parity_check(cfg, model, K, ids, otrace, ohz, dev)
         print(json.dumps(line), flush=True)
-    import torch.distributed as dist
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+    close_process_group()
 
 
 if __name__ == "__main__":

@@ -59,7 +59,7 @@ def _spawn(argv, port, extra_env=None, timeout=900):
 @pytest.mark.parametrize("mode", ["infer", "train"])
 def test_bench_two_ranks_one_device(mode):
     outs = _spawn(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--slides-per-gpu", "2", "--k", "256",
-                   "--no-cpu-baseline", "--mode", mode], 29741 + (mode == "train"))
+                   "--no-cpu-baseline", "--mode", mode] + (["--full"] if mode == "infer" else []), 29741 + (mode == "train"))
     lines = [l for l in outs[0][0].splitlines() if l.startswith("{")]
     assert len(lines) == 1 and not [l for l in outs[1][0].splitlines() if l.startswith("{")]      # rank 0 prints THE line
     rec = json.loads(lines[0])
@@ -145,7 +145,7 @@ def test_bench_self_launch_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "PATHS_DIST_BACKEND")}
     env.update(PATHS_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = _run_children([([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--slides-per-gpu", "2", "--k", "256",
-                           "--no-cpu-baseline", "--train-steps", "1", "--sustain", "0", "--breakdown-steps", "0"], env)])[0]
+                           "--full", "--no-cpu-baseline", "--train-steps", "1", "--sustain", "0", "--breakdown-steps", "0"], env)])[0]
     lines = [l for l in out[0].splitlines() if l.startswith("{")]
     assert len(lines) == 1, out
     rec = json.loads(lines[0])
@@ -154,6 +154,37 @@ def test_bench_self_launch_without_a_launcher():
     # a WORLD_SIZE that contradicts --gpus is an error message, not a bare assert
     bad = subprocess.run([sys.executable, "bench.py", "--gpus", "8"], env=dict(env, WORLD_SIZE="1", RANK="0"), cwd=ROOT, capture_output=True, text=True)
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr
+
+
+FULL_ONLY = ("per_rank_valid_patches_per_step", "roofline", "roofline_attn_ffn", "single_batch", "train", "sustained", "k1024", "trans_dim_192",
+             "stress", "serialized_breakdown", "cpu_baseline", "parity_checked")
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain ``bench.py`` run prints the headline line from its timed steps alone (no further measurement) and writes
+    --dump-outputs; ``--full`` prints the same headline fields plus the instrumented measurements, and the dtype a plain run
+    states without an instrumented pass is the one the instrumented output-gate launches report."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "PATHS_DIST_BACKEND")}
+    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--slides-per-gpu", "2", "--k", "256"]
+    recs = {}
+    for kind, extra in (("plain", ["--dump-outputs", str(tmp_path / "d")]),
+                        ("full", ["--full", "--no-cpu-baseline", "--train-steps", "0", "--stress-steps", "0", "--sustain", "0", "--breakdown-steps", "0"])):
+        out = _run_children([([sys.executable] + args + extra, env)])[0]
+        lines = [l for l in out[0].splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out
+        recs[kind] = json.loads(lines[0])
+    plain, full = recs["plain"], recs["full"]
+    assert not set(FULL_ONLY) & set(plain), sorted(set(FULL_ONLY) & set(plain))
+    assert set(plain["host"]) == {"launch_mode", "t_enqueued_over_elapsed"}
+    assert plain["metric"] == "slides_per_sec_5level_K256_D1024" and plain["unit"] == "slides/s" and plain["higher_is_better"] is True
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["n_gpus"] == 1
+    assert abs(plain["value"] - 2 * 2 / (plain["ms_per_step"] * 2e-3)) / plain["value"] < 0.01
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in ("logits", "ctx_slide", "importance", "ctx_patch_sample",
+                                                                            "ctx_patch_sample_rows"))
+    assert "roofline" in full and full["roofline"]["avg_launch_us"] > 0 and "eager_instrumented_pass" in full["host"]
+    for k in plain:
+        if k not in ("value", "ms_per_step", "per_rank_ms_per_step", "rank_imbalance_max_over_min", "host"):
+            assert full[k] == plain[k], (k, full[k], plain[k])
 
 
 def test_training_step_on_two_host_cores():

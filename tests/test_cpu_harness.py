@@ -180,3 +180,26 @@ def test_bench_dump_outputs_sample_and_budget(tmp_path):
     np.testing.assert_array_equal(np.load(tmp_path / "d" / "ctx_patch_sample.npy"), res["ctx_patch_sample"])
     big = np.load(tmp_path / "d" / "big_sample.npy")
     assert 0 < big.size < 10 << 20 and np.all(np.diff(big) > 0)
+
+
+def test_bench_line_dtype_follows_the_gemm_split(monkeypatch):
+    """bench.py states the recursion's dtype without running an instrumented step: gemm_split() gives what the LSTM output-gate
+    launch reports to the kernel timer for each PATHS_GEMM_MODE, the exact bf16 split for a batch outside the fp16 range, and
+    plain f32 without an LSTM cell."""
+    import types
+    import bench
+    from paths_amd import ops
+    from paths_amd.config import Config
+    cfg = Config.load(os.path.join(os.path.dirname(__file__), "golden", "sample"), test_mode=True)
+    batch = types.SimpleNamespace(feat_absmax=3.0, dim=1024)
+    fallbacks = list(ops.RANGE_FALLBACKS)
+    for mode, want in (("h3", (True, 2)), ("x6", (True, 3)), ("f32", (False, 0))):
+        monkeypatch.setattr(ops, "GEMM_MODE", mode)
+        assert bench.gemm_split(cfg, batch) == want, mode
+    monkeypatch.setattr(ops, "GEMM_MODE", "h3")
+    assert bench.gemm_split(cfg, types.SimpleNamespace(feat_absmax=1e6, dim=1024)) == (True, 3)
+    assert ops.GEMM_MODE == "h3"                                 # (the range guard restores the mode)
+    ops.RANGE_FALLBACKS[:] = fallbacks
+    cfg.model_config.lstm = False
+    assert bench.gemm_split(cfg, batch) == (False, 0)
+    assert bench.infer_dtype(True, 2).startswith("f32 (products as 2 fp16 planes") and bench.infer_dtype(False, 0) == "f32"

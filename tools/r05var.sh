@@ -11,7 +11,7 @@ for v in "$@"; do
   python3 $R/tools/agg_gaps.py /tmp/gaps_ser | grep -v "^gap"
 done
 for rep in 1 2; do for v in "$@"; do
-  PATHS_HIP_LIB=$(lib_of $v) python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --train-steps 0 --stress-steps 0 --k1024-steps 0 --td192-steps 0 --sustain 4 2>/dev/null | python3 -c "
+  PATHS_HIP_LIB=$(lib_of $v) python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --train-steps 0 --stress-steps 0 --k1024-steps 0 --td192-steps 0 --sustain 4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); a=d['roofline']['attn_ffn']; print('$v', d['value'], 'sustained', d['sustained']['slides_per_s'], 'span', a['serialized_span_us'], a['serialized_span_replayed_us'], a['serialized_frac_replayed'])"
 done; done

@@ -10,7 +10,7 @@ for lib in "" $R/tools/_bin/v/wt0.so; do
   python3 $R/tools/seq_gaps.py /tmp/gaps_ser 100
 done
 for rep in 1 2; do for lib in "" $R/tools/_bin/v/wt0.so; do
-  PATHS_HIP_LIB=$lib python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --train-steps 0 --stress-steps 0 --k1024-steps 0 --td192-steps 0 --sustain 4 2>/dev/null | python3 -c "
+  PATHS_HIP_LIB=$lib python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --train-steps 0 --stress-steps 0 --k1024-steps 0 --td192-steps 0 --sustain 4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); a=d['roofline']['attn_ffn']; print('lib=$lib', d['value'], 'sustained', d['sustained']['slides_per_s'], 'span', a['serialized_span_us'], a['serialized_span_replayed_us'], a['serialized_frac_replayed'])"
 done; done
