@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PATHS_HIP_LIB") or os.path.join(_HERE, "libpaths_hip.
 
 _i64, _i32, _f32, _vp, _u32, _u64 = C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_uint32, C.c_uint64
 
-# name -> argtypes (mirrors include/paths_hip.h; tests/test_cpu_surface.py::test_library_exports_every_declared_symbol checks both against the .so exports)
+# name -> argtypes (mirrors include/paths_hip.h; tests/test_cpu_surface.py::test_library_exports_every_declared_symbol_at_abi_3 checks both against the .so exports)
 SIGNATURES = {
     "paths_lstm_cell": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                         _i32, _i32, _i32, _vp, _i32, _i32, _vp],
@@ -32,8 +32,7 @@ SIGNATURES = {
     "paths_importance_proj_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
                                  _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp],
     "paths_importance_qkv_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
-                                _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _f32, _f32, _vp, _i32, _i32,
-                                _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+                                _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _f32, _f32, _vp, _i32, _i32, _vp],
     "paths_gemm_nt_x6": [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
                          _i32, _f32, _f32, _vp],
     "paths_gemm_add_nt_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _f32, _vp],
@@ -132,7 +131,7 @@ for _n in ("paths_lstm_cell_x6", "paths_importance_proj_x6", "paths_importance_q
     SIGNATURES[_n + "_h16"] = SIGNATURES[_n]
 _PLAIN = {"paths_gemm_tn_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_x6_packed_bytes": (C.c_int64, [_i32, _i32, _i32]), "paths_tlayer_h3_image_bytes": (C.c_int64, [_i32]), "paths_tlayer_ws_image_bytes": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes": (C.c_int64, []), "paths_token0_ws_partials": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes_d": (C.c_int64, [_i32]), "paths_token0_ws_partials_d": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_ws_supported": (_i32, [_i32, _i32, _i32, _i32]), "paths_attention_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]), "paths_attention_fp8_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_bwd_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_token0_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_attention_h3_any_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_importance_proj_x6_workspace": (C.c_int64, [_i32]), "paths_last_error": (C.c_char_p, []), "paths_build_info": (C.c_char_p, []), "paths_abi_version": (_i32, []), "paths_stop_event_pending": (_i32, []), "paths_clear_stop_event": (_i32, []), "paths_adamw_chunk": (_i32, []), "paths_attention_wide_workspace": (C.c_int64, [_i32, _i32]), "paths_event_create": (_vp, []), "paths_stream_create_masked": (_vp, [_vp, _i32])}
 
-ABI_VERSION = 2     # include/paths_hip.h: paths_abi_version() of the library this binding was written against
+ABI_VERSION = 3     # include/paths_hip.h: paths_abi_version() of the library this binding was written against
 _lib: Optional[C.CDLL] = None
 
 

@@ -30,7 +30,7 @@ PACK_T = os.environ.get("PATHS_PACK_T", "1") != "0"        # dX products image W
 # Module constants so that tests can force the split kernels onto the small shapes of the reference's trajectory fixtures.
 NT_X6_MIN_M = int(os.environ.get("PATHS_NT_X6_MIN_M", "1024"))
 TN_X6_MIN_M = int(os.environ.get("PATHS_TN_X6_MIN_M", "512"))
-# attention backward: "x6q" = the split-bf16 kernels (csrc/attn_bwd_x6.hip: dQ, and dK / dV unless PATHS_ATTN_BWD_KV_X6=0), "f32" = all of it on the f32 MFMA (csrc/attn_bwd.hip)
+# attention backward: "x6q" = the split-bf16 kernels (csrc/attn_bwd_x6.hip: dQ, dK and dV), "f32" = all of it on the f32 MFMA (csrc/attn_bwd.hip)
 ATTN_BWD_MODE = os.environ.get("PATHS_ATTN_BWD_MODE", "x6q")
 
 
@@ -1050,7 +1050,7 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
         ws = torch.empty((B * H * T,), **f32)
         if not fast:
             _attention_bwd_generic(lv["qkv"], lv["attn"], dattn, lv["lse"], num_ims, dqkv, ws, B, T, H, hd, d, qscale, 0, dk(l))
-        elif ATTN_BWD_MODE == "x6q":    # dQ, dK and dV on the split-bf16 kernels (csrc/attn_bwd_x6.hip; PATHS_ATTN_BWD_KV_X6=0 in the C library keeps dK / dV on the f32 MFMA)
+        elif ATTN_BWD_MODE == "x6q":    # dQ, dK and dV on the split-bf16 kernels (csrc/attn_bwd_x6.hip)
             img = torch.empty((int(_lib.load().paths_attention_bwd_x6_workspace(B, T, H, hd)),), device=dqkv.device, dtype=torch.uint8)
             # operand split as the other gradient products of the step (ops.TRAIN_PLANES: 4 = two bf16 planes, 3 = the exact three)
             _lib.call("paths_attention_bwd_x6_planes", P(lv["q"]), P(lv["k"]), P(lv["v"]), P(lv["attn"]), P(dattn), P(lv["lse"]),

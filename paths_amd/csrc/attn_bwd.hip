@@ -299,11 +299,9 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, co
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, o, d_o, ws_dsum, rows, T, H);
   PATHS_LAUNCH_CHECK("attention_bwd(prep)");
   dim3 grid((T + 63) / 64, H, B);
-  static const int x6_kv = getenv("PATHS_ATTN_BWD_KV_X6") == nullptr || atoi(getenv("PATHS_ATTN_BWD_KV_X6")) != 0;   // A/B switch
-  if (images != nullptr && x6_kv) return paths_attention_bwd_x6_launch(q, k, v, d_o, lse, ws_dsum, num_ims, dqkv, images, B, T, H, site, 1, planes, stream);
+  if (images != nullptr) return paths_attention_bwd_x6_launch(q, k, v, d_o, lse, ws_dsum, num_ims, dqkv, images, B, T, H, site, 1, planes, stream);
   hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(256), 0, stream, q, k, v, d_o, lse, ws_dsum, num_ims, dqkv, T, H, site);
   PATHS_LAUNCH_CHECK("attention_bwd(kv)");
-  if (images != nullptr) return paths_attention_bwd_x6_launch(q, k, v, d_o, lse, ws_dsum, num_ims, dqkv, images, B, T, H, site, 0, planes, stream);
   hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(256), 0, stream, q, k, v, d_o, lse, ws_dsum, num_ims, dqkv, T, H, site);
   PATHS_LAUNCH_CHECK("attention_bwd(q)");
   return PATHS_OK;

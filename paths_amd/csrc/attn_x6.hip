@@ -22,27 +22,6 @@
 #include "dropout.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
-#if defined(PATHS_ATTN_STAMPS) && !defined(PATHS_ATTN_DEBUG)
-#define PATHS_ATTN_DEBUG 1
-#endif
-#ifdef PATHS_M32P_STAMPS
-unsigned long long* g_m32p_dbg = nullptr;     // diagnostic builds only (tools/attn_pair_stamps.py): segment / barrier cycles per wave
-#define M32P_T(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc[i] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define M32P_T(i) do { } while (0)
-#endif
-#ifdef PATHS_ATTN_DEBUG
-unsigned long long* g_attn_dbg = nullptr;
-#endif
-// PATHS_ATTN_STAMPS = n (diagnostic builds only, tools/attn_stamps.py): s_memtime stamps between the phases of a key step, summed
-// per wave 0 of every workgroup into the debug buffer (16 words per workgroup).  1: around the barrier only (the schedule of the
-// step stays hipcc's), 2: every phase (pins the phases apart: shares, never quoted as run time).
-#ifdef PATHS_ATTN_STAMPS
-#define ATTN_STAMP(i, lvl) do { if (PATHS_ATTN_STAMPS >= (lvl)) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[i] += (unsigned)(t_ - st_prev); st_prev = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define ATTN_STAMP(i, lvl) do { } while (0)
-#endif
 
 namespace {
 
@@ -175,9 +154,6 @@ __device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[3], const u32x4 (&b
   return c;
 }
 __device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4 c) {   // hi, lo: all but lo*lo
-#if PATHS_ATTN_WHATIF & 4
-  return mfma_f16(a[0], b[0], c);
-#endif
   c = mfma_f16(a[1], b[0], c);
   c = mfma_f16(a[0], b[1], c);
   c = mfma_f16(a[0], b[0], c);
@@ -190,66 +166,19 @@ __device__ __forceinline__ float rows_sum(float x) { x += __shfl_xor(x, 16); ret
 // DROP (training with dropout > 0, reference nn.MultiheadAttention(dropout=p)): the softmax probabilities that enter the PV product
 // are multiplied by the regenerated mask / (1 - p) (element ((slide*H + head)*T + query)*T + key of the site, csrc/dropout.h); the
 // normaliser l and the saved log-sum-exp stay those of the un-dropped softmax, as in the reference.
-#ifndef PATHS_ATTN_OCC
-#define PATHS_ATTN_OCC 2
-#endif
-// PATHS_ATTN_OCC = waves per SIMD the kernel is built for.  2: the software-pipelined loop (S of the next step computed before the
-// softmax of this one; two score buffers).  3: one score buffer (32 registers less: fits 168), three workgroups per CU - the same
-// work on two thirds of the CUs, which leaves more of the chip to the selection chain's GEMMs running beside it.
-constexpr int ATTN_OCC = PATHS_ATTN_OCC;
-#ifndef PATHS_ATTN_QT
-#define PATHS_ATTN_QT 2
-#endif
-// QT = 16-query tiles per wave (a workgroup = 4 waves = 64 QT queries).  2: every K / V^T fragment read from LDS feeds two query
-// tiles.  1 (with ATTN_OCC >= 3): twice the workgroups at half the registers - four or more waves per SIMD hide each other's
-// LDS / softmax latencies (the loop is latency-bound at two), at twice the LDS fragment traffic per MFMA.
-constexpr int QT = PATHS_ATTN_QT;
-#ifndef PATHS_ATTN_P1
-#define PATHS_ATTN_P1 0
-#endif
-constexpr bool ATTN_P1 = PATHS_ATTN_P1 != 0;      // P as one fp16 plane (see the kernel)
-#ifndef PATHS_ATTN_DEFER
-#define PATHS_ATTN_DEFER 8
-#endif
-constexpr float ATTN_DEFER = (float)(PATHS_ATTN_DEFER);   // deferred-rescale threshold in log2 units (0 = rescale every step)
-#ifndef PATHS_ATTN_WHATIF
-#define PATHS_ATTN_WHATIF 0
-#endif
-// PATHS_ATTN_WHATIF (diagnostic builds, WRONG results, tools/attn_time.py): 1 no exp2, 2 no lo plane of P, 4 one MFMA per product
-// block, 8 no PV products, 16 no score products, 32 no LDS fragment reads (one fragment set re-used), 64 no staging (loads, LDS writes)
-constexpr int WHATIF = PATHS_ATTN_WHATIF;
-#ifndef PATHS_ATTN_DELAY_PV
-#define PATHS_ATTN_DELAY_PV 0
-#endif
-// DELAY_PV (FAST path): the PV product of key step k is issued in step k+1, in the same basic block as the score product of step k+2
-// and the exp2 / split work of step k+1 - every MFMA of the loop then has vector work to hide behind (before, the 24 PV MFMAs of a
-// step ran bare, after the step's vector work: the probabilities they multiply did not exist earlier).  V^T tiles live one step
-// longer (ring of three LDS buffers instead of two); a revision of the running maximum in step k+1 happens AFTER the pending product
-// was added, so one rescale covers it.  MEASURED (round 4) and OFF: hipcc does interleave the 48 MFMAs with ~100 vector instructions
-// then, results are bit-identical, and the kernel takes 57.6 us against 56.6 (A/B/A/B on one box) - the SIMD's aggregate issue
-// capacity, not the order inside one wave, is what bounds the step (tools/simd_probe.hip).
-constexpr bool ATTN_DELAY_PV = PATHS_ATTN_DELAY_PV != 0;
-#ifndef PATHS_ATTN_FAST
-#define PATHS_ATTN_FAST 1
-#endif
+// QT = 16-query tiles per wave (a workgroup = 4 waves = 64 QT queries): every K / V^T fragment read from LDS feeds two query tiles.
+constexpr int QT = 2;
+constexpr float ATTN_DEFER = 8.f;                     // deferred-rescale threshold in log2 units
 // FAST (two fp16 planes, no dropout): the running maximum is SUBTRACTED INSIDE the score product (the accumulators of S^T = K Q^T
 // start at -m_run instead of 0) and is only revised when a probability sum says it has to be: the common key step has no maximum
 // chain, no subtraction, no vote on the scores - exp2, the sum, the fp16 hi | lo split and nothing else (VALU instructions per
 // score element 6.7 -> ~4.5; the kernel is VALU-issue bound: round-4 measurement).
-constexpr bool ATTN_FAST = PATHS_ATTN_FAST != 0 && !ATTN_P1;
 template <int NP, bool DROP>
-__global__ void __launch_bounds__(256, ATTN_OCC)
+__global__ void __launch_bounds__(256, 2)
 attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const char* __restrict__ v6,
                float* __restrict__ o, float* __restrict__ lse, const int64_t* __restrict__ num_ims, int T, int Tp, int H,
-               int npairs_arg, int nqb_arg, DropSite drop, char* __restrict__ o_img
-#ifdef PATHS_ATTN_DEBUG
-               , unsigned long long* dbg
-#endif
-               ) {
+               int npairs_arg, int nqb_arg, DropSite drop, char* __restrict__ o_img) {
   constexpr int STEP_BYTES = step_bytes<NP>();
-#ifdef PATHS_ATTN_DEBUG
-  const unsigned long long dbg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];          // 2 x STEP_BYTES (+ occupancy padding, see the launcher)
   // XCD-aware placement (speed only): every workgroup of one (slide, head) pair streams that pair's whole K / V^T images (0.5 MB
   // at T = 2049), and blocks are dealt round-robin over the 8 XCDs.  With the query block as the fastest grid index each XCD's
@@ -284,7 +213,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < QT; ++j) oacc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr bool FAST = ATTN_FAST && NP == 2 && !DROP;
+  constexpr bool FAST = NP == 2 && !DROP;
   float m_run[QT], l_run[QT];
   f32x4 negm[QT];                                       // FAST: -m_run in all four elements = the C operand of the score products
 #pragma unroll
@@ -296,12 +225,8 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
   // them).  K therefore runs one step ahead of V in LDS: K(k+1), K(k+2 being written) | V(k), V(k+1 being written).
   const int nkt = (len + KSTEP - 1) / KSTEP;
   constexpr int HALF = 4 * NP * FRAG;                   // bytes of the K (or V) fragments of one step
-  constexpr bool FASTC = ATTN_FAST && NP == 2 && !DROP;
-  constexpr bool DELAY = FASTC && ATTN_DELAY_PV && ATTN_OCC < 3;
-  constexpr int NVB = DELAY ? 3 : 2;                    // V^T buffers (DELAY: a tile is read one step after its scores)
-  auto vbuf = [&](int kt) { return DELAY ? kt % 3 : (kt & 1); };
   char* const sKb = smem_raw;                           // [2][HALF]
-  char* const sVb = smem_raw + 2 * HALF;                // [NVB][HALF]
+  char* const sVb = smem_raw + 2 * HALF;                // [2][HALF]
   u32x4 st[2 * NP];
   auto gload_k = [&](int kt) {
 #pragma unroll
@@ -317,7 +242,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
   };
   auto swrite_v = [&](int kt) {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) *reinterpret_cast<u32x4*>(sVb + vbuf(kt) * HALF + (tid + 256 * i) * 16) = st[NP + i];
+    for (int i = 0; i < NP; ++i) *reinterpret_cast<u32x4*>(sVb + (kt & 1) * HALF + (tid + 256 * i) * 16) = st[NP + i];
   };
   auto qk = [&](int kt, f32x4 (&s)[QT][4]) __attribute__((always_inline)) {      // S^T = K Q^T for the 4 key tiles of step kt
     const char* sK = sKb + (kt & 1) * HALF + lane * 16;
@@ -325,12 +250,9 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
     for (int t = 0; t < 4; ++t) {
       u32x4 kf[NP];
 #pragma unroll
-      for (int p = 0; p < NP; ++p) kf[p] = *reinterpret_cast<const u32x4*>(sK + (((WHATIF & 32) ? 0 : t) * NP + p) * FRAG);
+      for (int p = 0; p < NP; ++p) kf[p] = *reinterpret_cast<const u32x4*>(sK + (t * NP + p) * FRAG);
 #pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        if constexpr ((WHATIF & 16) != 0) { s[qt][t] = negm[qt]; asm("" : "+v"(s[qt][t])); }
-        else s[qt][t] = mfma_split(kf, qf[qt], negm[qt]);      // (zero outside FAST)
-      }
+      for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split(kf, qf[qt], negm[qt]);      // (zero outside FAST)
     }
   };
   gload_k(0); gload_v(0);
@@ -338,24 +260,19 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
   if (nkt > 1) { gload_k(1); swrite_k(1); }
   __syncthreads();
   f32x4 sA[QT][4], sB[QT][4];                             // [query tile][key tile]: rows = keys 4 g4 .. +3, col = query ql
-  if constexpr (ATTN_OCC < 3) qk(0, sA);
+  qk(0, sA);
   // one step: s = S(kt) (ready), sn receives S(kt+1)
   // Fair share for the SECOND workgroup of a CU.  Issue arbitration on a SIMD is oldest-first: measured per workgroup
-  // (tools/attn_wg_times.py), the 256 first-dispatched workgroups ran 46 us and their 224 younger CU mates 58 us - the last
+  // the 256 first-dispatched workgroups ran 46 us and their 224 younger CU mates 58 us - the last
   // 12 us with a single workgroup per CU.  Alternating the priority between the two every few key steps lets both finish together.
-#ifndef PATHS_ATTN_PRIO_SHIFT
-#define PATHS_ATTN_PRIO_SHIFT 2
-#endif
+  constexpr int PRIO_SHIFT = 2;                         // key steps per priority phase: 2^PRIO_SHIFT
   const int prio_parity = (qb * npairs + pair) >= 256 ? 1 : 0;
   auto step = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], auto lastc) __attribute__((always_inline)) {
     constexpr bool LAST = decltype(lastc)::value;       // the masked step is peeled: 26 selects per step otherwise
-    if constexpr (PATHS_ATTN_PRIO_SHIFT >= 0) {
-      if ((((kt >> PATHS_ATTN_PRIO_SHIFT) ^ prio_parity) & 1) != 0) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-    }
+    if ((((kt >> PRIO_SHIFT) ^ prio_parity) & 1) != 0) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
     if (kt + 2 < nkt) gload_k(kt + 2);
     if (kt + 1 < nkt) gload_v(kt + 1);
-    if constexpr (ATTN_OCC >= 3) qk(kt, s);
     const char* sV = sVb + (kt & 1) * HALF + lane * 16;
     // ---- mask (last step only) + online softmax (lane: query ql of each tile; keys 16 t + 4 g4 + r)
     if constexpr (LAST) {
@@ -368,15 +285,8 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
           for (int r = 0; r < 4; ++r)
             if (kbase + 16 * t + r >= len) s[qt][t][r] = -INFINITY;
     }
-    if constexpr (ATTN_OCC < 3) qk(kt + 1, sn);         // (past the end: stale K fragments, finite garbage nobody reads)
-    // P1 (two-plane mode, no dropout): P enters the PV product as ONE fp16 plane (P^ = fp16(P), 11 bits) against V hi | lo: two
-    // MFMAs per block instead of three and no residual plane to build (1.5 of ~4.5 VALU per score element).  The normaliser sums
-    // the SAME rounded values (v_fma_mix reads them out of the packed register), so the result is an exact softmax-weighted mean
-    // with weights p^_k / sum p^: rounding perturbs each weight by <= 2^-12 relative and the perturbations largely cancel between
-    // numerator and denominator (error ~ 2^-12 |v - o| / sqrt(effective keys)).
-    constexpr bool P1 = ATTN_P1 && NP == 2 && !DROP;
-    constexpr int NPP = P1 ? 1 : NP;
-    u32x4 pf[QT][2][NPP];                               // [query tile][32-key group][plane]
+    qk(kt + 1, sn);                                     // (past the end: stale K fragments, finite garbage nobody reads)
+    u32x4 pf[QT][2][NP];                               // [query tile][32-key group][plane]
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       float mx = -INFINITY;
@@ -389,7 +299,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
       // maximum is kept - no cross-lane max, no exp2 of the correction, no pass over the output accumulators.  P then reaches
       // 2^ATTN_DEFER at most, far inside fp16 / fp32 range; the first step (m_run = -inf) always takes the full path.
       float m_new = m_run[qt];
-      const bool keep = ATTN_DEFER > 0.f && __all(mx - m_run[qt] <= ATTN_DEFER);
+      const bool keep = __all(mx - m_run[qt] <= ATTN_DEFER);
       if (!keep) {
         mx = rows_max(mx);
         m_new = fmaxf(m_run[qt], mx);                   // finite: key 0 (special token) is always valid
@@ -408,7 +318,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
           const f32x2 d = f32x2{s[qt][2 * kg + (j >> 2)][j & 3], s[qt][2 * kg + (j >> 2)][(j & 3) + 1]} - f32x2{m_new, m_new};   // v_pk_add_f32
           pv[j] = __builtin_amdgcn_exp2f(d[0]);
           pv[j + 1] = __builtin_amdgcn_exp2f(d[1]);
-          if constexpr (!P1) psum += pv[j] + pv[j + 1];
+          psum += pv[j] + pv[j + 1];
         }
         if constexpr (DROP) {
           const uint64_t row = drop_attn_row((uint64_t)pair, T, min(qw + 16 * qt + ql, T - 1));
@@ -419,17 +329,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
             pv[j] *= m0; pv[j + 1] *= m1;
           }
         }
-        if constexpr (P1) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint32_t h = pk_f16(pv[2 * i], pv[2 * i + 1]);
-            pf[qt][kg][0][i] = h;
-            asm("v_fma_mix_f32 %0, %1, 1.0, %0 op_sel_hi:[1,0,0]" : "+v"(psum) : "v"(h));                    // psum += (float)h.lo
-            asm("v_fma_mix_f32 %0, %1, 1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(psum) : "v"(h));      // psum += (float)h.hi
-          }
-        } else {
-          split_planes<NP>(pv, pf[qt][kg]);
-        }
+        split_planes<NP>(pv, pf[qt][kg]);
       }
       l_run[qt] += psum;
     }
@@ -442,14 +342,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
 #pragma unroll
         for (int p = 0; p < NP; ++p) vf[p] = *reinterpret_cast<const u32x4*>(sV + ((kg * 2 + dvt) * NP + p) * FRAG);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-          if constexpr (P1) {
-            oacc[dvt][qt] = mfma_f16(vf[1], pf[qt][kg][0], oacc[dvt][qt]);      // V lo * P^
-            oacc[dvt][qt] = mfma_f16(vf[0], pf[qt][kg][0], oacc[dvt][qt]);      // V hi * P^
-          } else {
-            oacc[dvt][qt] = mfma_split(vf, pf[qt][kg], oacc[dvt][qt]);
-          }
-        }
+        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pf[qt][kg], oacc[dvt][qt]);
       }
     if (kt + 2 < nkt) swrite_k(kt + 2);                 // over K(kt): read one step ago
     if (kt + 1 < nkt) swrite_v(kt + 1);                 // over V(kt-1)
@@ -460,10 +353,6 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
   // through the revision path: true maximum of the step, m_run += d, everything already computed relative to the old value
   // (l, O^T, these scores and the next step's, which are in flight) re-based, probabilities recomputed.  The first key step always
   // revises (m_run starts at 0; there d may be negative).  P <= 2^ATTN_DEFER keeps the fp16 planes far from their range.
-#ifdef PATHS_ATTN_STAMPS
-  unsigned st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_prev = __builtin_amdgcn_s_memtime();
-#endif
   auto pv_product = [&](const char* sV, u32x4 (&pfr)[QT][2][2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int kg = 0; kg < 2; ++kg)
@@ -471,28 +360,18 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
       for (int dvt = 0; dvt < 2; ++dvt) {
         u32x4 vf[2];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) vf[p] = *reinterpret_cast<const u32x4*>(sV + (((WHATIF & 32) ? 0 : (kg * 2 + dvt)) * NP + p) * FRAG);
+        for (int p = 0; p < 2; ++p) vf[p] = *reinterpret_cast<const u32x4*>(sV + ((kg * 2 + dvt) * NP + p) * FRAG);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-          if constexpr ((WHATIF & 8) != 0) { oacc[dvt][qt] += __builtin_bit_cast(f32x4, pfr[qt][kg][0]) + __builtin_bit_cast(f32x4, pfr[qt][kg][1]) + __builtin_bit_cast(f32x4, vf[0]); }
-          else oacc[dvt][qt] = mfma_split(vf, pfr[qt][kg], oacc[dvt][qt]);
-        }
+        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pfr[qt][kg], oacc[dvt][qt]);
       }
   };
-  // pf: receives this step's probability fragments; pfp (DELAY): the previous step's, whose PV product is issued here (pendc: there is one)
-  auto step_fast = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], u32x4 (&pf)[QT][2][2], u32x4 (&pfp)[QT][2][2], auto lastc, auto pendc) __attribute__((always_inline)) {
-    constexpr bool LAST = decltype(lastc)::value, PEND = decltype(pendc)::value;
-    if constexpr (PATHS_ATTN_PRIO_SHIFT >= 0) {
-      if ((((kt >> PATHS_ATTN_PRIO_SHIFT) ^ prio_parity) & 1) != 0) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-    }
-    ATTN_STAMP(0, 1);
-    if constexpr ((WHATIF & 64) == 0) {
+  auto step_fast = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], auto lastc) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(lastc)::value;
+    if ((((kt >> PRIO_SHIFT) ^ prio_parity) & 1) != 0) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
     if (kt + 2 < nkt) gload_k(kt + 2);
     if (kt + 1 < nkt) gload_v(kt + 1);
-    }
-    if constexpr (ATTN_OCC >= 3) qk(kt, s);
-    const char* sV = sVb + vbuf(DELAY ? kt - 1 : kt) * HALF + lane * 16;      // (DELAY: the tile of the pending product)
+    const char* sV = sVb + (kt & 1) * HALF + lane * 16;
     if constexpr (LAST) {
       const int kbase = kt * KSTEP + 4 * g4;
 #pragma unroll
@@ -503,9 +382,8 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
           for (int r = 0; r < 4; ++r)
             if (kbase + 16 * t + r >= len) s[qt][t][r] = -INFINITY;
     }
-    if constexpr (ATTN_OCC < 3) qk(kt + 1, sn);
-    if constexpr (DELAY && PEND) pv_product(sV, pfp);   // O^T += V^T(kt-1) P^T(kt-1): same basic block as the score product above and exp2 / split below
-    ATTN_STAMP(1, 2);
+    qk(kt + 1, sn);
+    u32x4 pf[QT][2][2];
     float psum[QT];
     auto probs = [&](int qt) __attribute__((always_inline)) {
       // four independent partial sums (a 16-deep dependent chain sat on the step's critical path: hipcc packed the two query tiles'
@@ -516,20 +394,16 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
         float pv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {                   // k-slot (g4, j) of the PV product = key 4 g4 + (j&3) + 16 (j>>2) of the group
-          pv[j] = (WHATIF & 1) ? s[qt][2 * kg + (j >> 2)][j & 3] : __builtin_amdgcn_exp2f(s[qt][2 * kg + (j >> 2)][j & 3]);
+          pv[j] = __builtin_amdgcn_exp2f(s[qt][2 * kg + (j >> 2)][j & 3]);
           ps[j & 3] += pv[j];
           asm("" : "+v"(ps[j & 3]));
         }
-        if constexpr ((WHATIF & 2) != 0) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) pf[qt][kg][0][i] = pf[qt][kg][1][i] = pk_f16(pv[2 * i], pv[2 * i + 1]);
-        } else split_planes<2>(pv, pf[qt][kg]);
+        split_planes<2>(pv, pf[qt][kg]);
       }
       psum[qt] = (ps[0] + ps[1]) + (ps[2] + ps[3]);
     };
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) probs(qt);
-    ATTN_STAMP(2, 2);
     float pmax = psum[0];
 #pragma unroll
     for (int qt = 1; qt < QT; ++qt) pmax = fmaxf(pmax, psum[qt]);
@@ -553,59 +427,41 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           s[qt][t] -= f32x4{d, d, d, d};
-          if constexpr (ATTN_OCC < 3) sn[qt][t] -= f32x4{d, d, d, d};
+          sn[qt][t] -= f32x4{d, d, d, d};
         }
         probs(qt);
       }
     }
-    ATTN_STAMP(3, 2);
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) l_run[qt] += psum[qt];
-    if constexpr (!DELAY) pv_product(sV, pf);
-    ATTN_STAMP(4, 2);
-    if constexpr ((WHATIF & 64) == 0) {
+    pv_product(sV, pf);
     if (kt + 2 < nkt) swrite_k(kt + 2);
     if (kt + 1 < nkt) swrite_v(kt + 1);
-    }
-    ATTN_STAMP(5, 1);
     __syncthreads();
-    ATTN_STAMP(6, 1);
   };
-  u32x4 pfA[QT][2][2], pfB[QT][2][2];                  // probability fragments of two consecutive steps (DELAY keeps one pending)
-  auto stepx = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], u32x4 (&pf)[QT][2][2], u32x4 (&pfp)[QT][2][2], auto lastc, auto pendc) __attribute__((always_inline)) {
-    if constexpr (FAST) step_fast(kt, s, sn, pf, pfp, lastc, pendc);
+  auto stepx = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], auto lastc) __attribute__((always_inline)) {
+    if constexpr (FAST) step_fast(kt, s, sn, lastc);
     else step(kt, s, sn, lastc);
   };
   {
     constexpr std::false_type MID{};
     constexpr std::true_type END{};
-    constexpr std::false_type NOPEND{};
-    constexpr std::true_type PEND{};
-    int kt = 0;
-    if constexpr (ATTN_OCC >= 3) {
-      for (; kt + 1 < nkt; ++kt) stepx(kt, sA, sA, pfA, pfA, MID, NOPEND);
-      stepx(kt, sA, sA, pfA, pfA, END, NOPEND);
+    // steps alternate the score buffers (sA, sB)
+    if (nkt == 1) {
+      stepx(0, sA, sB, END);
     } else {
-      // steps alternate the score buffers (sA, sB) and the fragment buffers (pfA, pfB); the first step has no pending product
-      if (nkt == 1) {
-        stepx(0, sA, sB, pfA, pfB, END, NOPEND);
-        if constexpr (DELAY) pv_product(sVb + vbuf(0) * HALF + lane * 16, pfA);
+      stepx(0, sA, sB, MID);
+      int kt = 1;
+      for (; kt + 2 < nkt; kt += 2) {
+        stepx(kt, sB, sA, MID);
+        stepx(kt + 1, sA, sB, MID);
+      }
+      // kt = first step not yet done (odd); one or two steps left
+      if (kt + 1 < nkt) {
+        stepx(kt, sB, sA, MID);
+        stepx(kt + 1, sA, sB, END);
       } else {
-        stepx(0, sA, sB, pfA, pfB, MID, NOPEND);
-        kt = 1;
-        for (; kt + 2 < nkt; kt += 2) {
-          stepx(kt, sB, sA, pfB, pfA, MID, PEND);
-          stepx(kt + 1, sA, sB, pfA, pfB, MID, PEND);
-        }
-        // kt = first step not yet done (odd); one or two steps left
-        if (kt + 1 < nkt) {
-          stepx(kt, sB, sA, pfB, pfA, MID, PEND);
-          stepx(kt + 1, sA, sB, pfA, pfB, END, PEND);
-          if constexpr (DELAY) pv_product(sVb + vbuf(kt + 1) * HALF + lane * 16, pfA);
-        } else {
-          stepx(kt, sB, sA, pfB, pfA, END, PEND);
-          if constexpr (DELAY) pv_product(sVb + vbuf(kt) * HALF + lane * 16, pfB);
-        }
+        stepx(kt, sB, sA, END);
       }
     }
   }
@@ -638,22 +494,6 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
       if (lse && g4 == 0) lse[((int64_t)b * H + head) * T + qi] = m_run[qt] + log2f(l);
     }
   }
-#ifdef PATHS_ATTN_DEBUG
-  if (dbg && threadIdx.x == 0) {
-    unsigned hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-#ifdef PATHS_ATTN_STAMPS
-    unsigned long long* d = dbg + 16 * blockIdx.x;
-    d[0] = dbg_t0; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = ((unsigned long long)xcc << 32) | hwid;
-    for (int i = 0; i < 8; ++i) d[3 + i] = st_acc[i];
-    d[11] = (unsigned long long)nkt;
-#else
-    dbg[3 * blockIdx.x] = dbg_t0; dbg[3 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime(); dbg[3 * blockIdx.x + 2] = ((unsigned long long)xcc << 32) | hwid;
-#endif
-  }
-#endif
 }
 
 
@@ -904,31 +744,13 @@ __device__ __forceinline__ void pair_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-#ifndef PATHS_M32P_PKADD
-#define PATHS_M32P_PKADD 0
-#endif
-#ifndef PATHS_M32P_EARLYPRE
-#define PATHS_M32P_EARLYPRE 1
-#endif
-#ifndef PATHS_M32P_PIPE
-#define PATHS_M32P_PIPE 0                 // explicit two-chunks-ahead fragment reads in M: over the 168-VGPR cap of three waves per SIMD (spills, 65 us)
-#endif
-#ifndef PATHS_M32P_LOADERS
-#define PATHS_M32P_LOADERS 1              // 1: four loader waves (768 threads); 0: waves 0-3 issue the DMAs at the head of their M segment (512 threads)
-#endif
-__global__ void __launch_bounds__(PATHS_M32P_LOADERS ? 768 : 512)
+// 768 threads: waves 0-7 compute, waves 8-11 are the loader waves (see below)
+__global__ void __launch_bounds__(768)
 attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const char* __restrict__ v6, float* __restrict__ o,
                  float* __restrict__ lse, const int64_t* __restrict__ num_ims, int T, int Tp, int H, int npairs_arg, int nqb_arg,
-                 char* __restrict__ o_img
-#ifdef PATHS_M32P_STAMPS
-                 , unsigned long long* __restrict__ dbg
-#endif
-                 ) {
+                 char* __restrict__ o_img) {
   constexpr int NP = 2;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-#ifdef PATHS_M32P_STAMPS
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
-#endif
   const int npairs = npairs_arg, nqb = nqb_arg;
   const int lin = blockIdx.x, xg = lin & 7, jx = lin >> 3;
   const int cnt = (npairs - xg + 7) >> 3;
@@ -962,12 +784,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
   for (int i = 0; i < 16; ++i) { oacc[i] = 0.f; negm[i] = 0.f; }
   float m_run = 0.f, l_run = 0.f;
   u32x4 pf[2][2][NP];                                   // P^T fragments [key tile][16-key step][plane]
-#if PATHS_M32P_PIPE
-  u32x4 fr[3][NP];                                      // operand fragments of M in flight (chunk c in fr[c % 3]); fr[0], fr[1] = V^T of key tile 0, read ahead of the barrier
-  auto& vpre = fr;
-#else
   u32x4 vpre[2][NP];                                    // V^T fragments of key tile 0, read ahead of the barrier that opens M
-#endif
 
   const int nkt = (len + KSTEP - 1) / KSTEP;
   constexpr int HALF = 4 * NP * FRAG;                   // one 64-key step of K or of V^T
@@ -1006,7 +823,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
     // images in global memory (they are stored in operand order), the (m, l, O) states merged through LDS by wave 0.  Run as a
     // ninth block at the pace of a full one (one active wave meeting every barrier of 33 key steps) this took ~35 us as a SECOND ROUND
     // of workgroups behind the 256 full blocks of eight full slides: 46 -> 82 us for the launch (tools/attn_full_slides.py).
-    constexpr int NWS = PATHS_M32P_LOADERS ? 12 : 8;    // every wave of the workgroup takes key steps (nothing is staged through LDS here)
+    constexpr int NWS = 12;                             // every wave of the workgroup takes key steps (nothing is staged through LDS here)
     const char* const kg = k6 + ibase;
     const char* const vg = v6 + ibase;
     bool first = true;
@@ -1128,7 +945,6 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
   const int wq = wave & 3;
   const uint32_t voff = wq * 1024 + lane * 16;
   auto dma_bundle = [&](int j) {
-#ifndef PATHS_M32P_NOSTAGE
     if (j >= nkt) return;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1138,21 +954,8 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
       for (int i = 0; i < 2; ++i)
         glds16(k6 + ibase + (int64_t)(j + 1) * HALF + 4096 * i, voff, lds0 + ((j + 1) & 3) * HALF + (wq + 4 * i) * 1024);
     }
-#endif
   };
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  auto fly_wait = [&](int kt) {                         // bundle kt + 1 has landed; kt + 2 and kt + 3 may fly
-    auto count = [&](int j) { return j >= nkt ? 0 : j + 1 < nkt ? 4 : 2; };
-    const int fly = count(kt + 2) + count(kt + 3);
-    if (fly == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (fly == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (fly == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (fly == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-#if !PATHS_M32P_LOADERS
-  if (grp == 0) { dma_bundle(1); dma_bundle(2); }
-#endif
   if (grp == 2) {
     // The loader waves (one per SIMD, at priority 3: they issue ~30 instructions per key step).  Issued by waves 4-7 themselves the
     // four DMAs of a step took 650-1000 cycles to ISSUE behind the partner's dense vector stream, in front of the wave's MFMAs.
@@ -1201,12 +1004,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
   };
   // V segment: (waves 4-7: DMA issue), softmax of s -> pf, l_run (and, rarely, a new running maximum), first V^T fragments of M(kt)
   auto vseg = [&](int kt) __attribute__((always_inline)) {
-    M32P_T(5);
-#ifdef PATHS_M32P_WHATIF
-    if (active && !((PATHS_M32P_WHATIF & 1) && grp == 0) && !((PATHS_M32P_WHATIF & 8) && grp == 1)) {
-#else
     if (active) {
-#endif
       if (kt == nkt - 1) {
         const int kbase = kt * KSTEP + 4 * h;
 #pragma unroll
@@ -1215,7 +1013,6 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
           for (int i = 0; i < 16; ++i)
             if (kbase + 32 * t + (i & 3) + 8 * (i >> 2) >= len) s[t][i] = -INFINITY;
       }
-#if PATHS_M32P_EARLYPRE
       {                                                 // first V^T fragments of M(kt): published one slot ago, read under the softmax
         const char* sV = sVb + (kt & 3) * HALF;
 #pragma unroll
@@ -1223,25 +1020,8 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
 #pragma unroll
           for (int p = 0; p < NP; ++p) vpre[u][p] = vfrag(sV, 0, u, p);
       }
-#endif
       float psum;
       auto probs = [&]() __attribute__((always_inline)) {
-#if PATHS_M32P_PKADD
-        f32x2 ps[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};     // four independent v_pk_add_f32 chains
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            float pv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pv[j] = __builtin_amdgcn_exp2f(s[t][4 * u + (j & 3) + 8 * (j >> 2)]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ps[j] += f32x2{pv[2 * j], pv[2 * j + 1]};
-            split8h(pv, pf[t][u][0], pf[t][u][1]);
-          }
-        const f32x2 q = (ps[0] + ps[1]) + (ps[2] + ps[3]);
-        psum = q[0] + q[1];
-#else
         float ps[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -1257,10 +1037,8 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
             split8h(pv, pf[t][u][0], pf[t][u][1]);
           }
         psum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
-#endif
       };
       probs();
-      M32P_T(6);
       if (kt == 0 || __any(!(psum <= 256.0f))) {
         float mx = -INFINITY;
 #pragma unroll
@@ -1281,53 +1059,13 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
         probs();
       }
       l_run += psum;
-#if !PATHS_M32P_EARLYPRE
-      const char* sV = sVb + (kt & 3) * HALF;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) vpre[u][p] = vfrag(sV, 0, u, p);
-#endif
     }
   };
   // M segment: O^T += V^T(kt) P^T(kt), then S(kt+1)
   auto mseg = [&](int kt, auto morec) __attribute__((always_inline)) {
     constexpr bool more = decltype(morec)::value;       // S(kt+1) wanted: all but the last step
-    M32P_T(7);
     if (!active) return;
-#ifdef PATHS_M32P_WHATIF
-    if ((PATHS_M32P_WHATIF & 4) && grp == 0) return;
-    if ((PATHS_M32P_WHATIF & 16) && grp == 1) return;
-#endif
     const char* sV = sVb + (kt & 3) * HALF;
-#if PATHS_M32P_PIPE
-    // 12 chunks of 3 MFMAs: 0-3 = V^T (tile, step), 4-11 = K (tile, k-step); chunk c + 2 is read while chunk c multiplies (chunks 0, 1
-    // came in before the barrier): the fragment reads run two chunks = 192+ matrix cycles ahead of their use
-    const char* sK = sKb + ((kt + 1) & 3) * HALF;
-    auto rd = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        if (c < 4) fr[c % 3][p] = vfrag(sV, c >> 1, c & 1, p);
-        else { const int t = (c - 4) >> 1, ks = (c - 4) & 1;
-               fr[c % 3][p] = *reinterpret_cast<const u32x4*>(sK + ((2 * t + sub) * NP + p) * FRAG + (l15 + 16 * (2 * ks + h)) * 16); }
-      }
-    };
-#pragma unroll
-    for (int c = 0; c < 12; ++c) {
-      if (c + 2 < 4 || (c + 2 < 12 && more)) rd(c + 2);
-      if (c < 4) oacc = mfma32_split(fr[c % 3], pf[c >> 1][c & 1], oacc);
-      else if (more) {
-        const int t = (c - 4) >> 1, ks = (c - 4) & 1;
-        if (ks == 0)
-          asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(s[t]) : "v"(fr[c % 3][1]), "v"(qf[0][0]), "v"(negm));
-        else
-          s[t] = mfma32_f16(fr[c % 3][1], qf[ks][0], s[t]);
-        s[t] = mfma32_f16(fr[c % 3][0], qf[ks][1], s[t]);
-        s[t] = mfma32_f16(fr[c % 3][0], qf[ks][0], s[t]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#else
 #pragma unroll
     for (int u = 0; u < 2; ++u) oacc = mfma32_split(vpre[u], pf[0][u], oacc);
 #pragma unroll
@@ -1338,43 +1076,21 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
       oacc = mfma32_split(vf, pf[1][u], oacc);
     }
     if (more) qk(sKb + ((kt + 1) & 3) * HALF);
-#endif
   };
   if (grp) pair_barrier();                              // (slot -1: waves 0-3 compute S(0))
   if (active) qk(sKb);
   pair_barrier();
-  M32P_T(0);
   for (int kt = 0; kt < nkt; ++kt) {
     vseg(kt);
-    M32P_T(1);
     pair_barrier();
-    M32P_T(2);
-#if !PATHS_M32P_LOADERS
-    if (grp == 0) dma_bundle(kt + 3);                   // (slot 2kt+1, like the loader waves)
-#endif
     if (kt + 1 < nkt) mseg(kt, std::true_type{}); else mseg(kt, std::false_type{});
-#if !PATHS_M32P_LOADERS
-    if (grp == 0) fly_wait(kt);
-#endif
-    M32P_T(3);
     pair_barrier();
-    M32P_T(4);
   }
   if (!grp) pair_barrier();                             // (the last slot belongs to waves 4-7)
-#ifdef PATHS_M32P_STAMPS
-  if (dbg != nullptr && lane == 0) {
-    unsigned long long* d = dbg + ((int64_t)blockIdx.x * 8 + wave) * 8;
-    for (int i = 0; i < 5; ++i) d[i] = tacc[i];
-    d[5] = tacc[5]; d[6] = nkt; d[7] = tacc[6]; d[4] = tacc[7];
-  }
-#endif
   if (!active) return;
   write_out();
 }
 
-#ifndef PATHS_ATTN_M32
-#define PATHS_ATTN_M32 2
-#endif
 static int attn_num_cus() {                 // CUs of the current device (asked once per device)
   static int cached[64] = {0};
   int dev = 0;
@@ -1407,19 +1123,15 @@ int attention_split(const float* q, const float* k, const float* v, float* o, fl
   // Workgroups per CU: registers allow 2, LDS would allow more.  The dispatcher fills a CU to its limit before it moves on, so
   // small grids ask for more LDS than needed to spread out: depth ~ grid / 256.
   const int nblk = ((nq + 64 * QT - 1) / (64 * QT)) * H * B;
-  static const int depth_env = getenv("PATHS_ATTN_DEPTH") ? atoi(getenv("PATHS_ATTN_DEPTH")) : 0;   // experiment
-  const int depth = depth_env ? depth_env : ATTN_OCC >= 3 ? (nblk <= 256 ? 1 : nblk <= 512 ? 2 : 3) : nblk <= 256 ? 1 : nblk <= 640 ? 2 : 3;    // (544 workgroups at K = 2048 x 8 slides: 2 per CU on every CU beat 3 per CU on 2/3 of them by 2 %)
-  const int lds = depth == 1 ? 96 * 1024 : depth == 2 ? 64 * 1024 : (5 * step_bytes<NP>()) / 2;     // (K ring of two + V^T ring of up to three half-step buffers)
+  const int depth = nblk <= 256 ? 1 : nblk <= 640 ? 2 : 3;    // (544 workgroups at K = 2048 x 8 slides: 2 per CU on every CU beat 3 per CU on 2/3 of them by 2 %)
+  const int lds = depth == 1 ? 96 * 1024 : depth == 2 ? 64 * 1024 : (5 * step_bytes<NP>()) / 2;     // (K and V^T rings of two half-step buffers each, and one spare)
   PATHS_LDS_OPT_IN((attn_x6_kernel<NP, false>), 96 * 1024, "attention_x6");
   PATHS_LDS_OPT_IN((attn_x6_kernel<NP, true>), 96 * 1024, "attention_x6(dropout)");
   const int nqb = (nq + 64 * QT - 1) / (64 * QT), npairs = H * B;
   const DropSite site = paths_make_drop_site(drop_key, drop_p);
   // 1-D grid walked in XCD-aware order (see the kernel)
-#ifdef PATHS_ATTN_DEBUG
-  hipLaunchKernelGGL((attn_x6_kernel<NP, false>), dim3(8 * ((npairs + 7) / 8) * nqb, 1, 1), dim3(256), lds, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb, site, o_img, g_attn_dbg);
-#else
   const char* m32_env = getenv("PATHS_ATTN_M32");       // (read per call: the tests switch kernels inside one process)
-  const int m32 = m32_env ? atoi(m32_env) : PATHS_ATTN_M32;     // 0: 16x16x32 kernel, 1: 32x32x16, 2: 32x32x16 wave pairs, 3: wave pairs on any grid
+  const int m32 = m32_env ? atoi(m32_env) : 2;          // 0: 16x16x32 kernel, 1: 32x32x16, 2: 32x32x16 wave pairs, 3: wave pairs on any grid
   // The wave-pair kernel puts 256 queries on one CU: it wins where its grid covers most of the chip (K = 2048 x 8 slides: 256
   // workgroups, 50.9 us against 55.3; 1024 x 8: 160, 28.4 against 29.9) and loses on small grids, which the 128-query kernel spreads
   // over twice as many CUs (2048 x 4 slides: 43.6 against 36.3; 512 x 8: 17.3 against 13.2).
@@ -1430,30 +1142,18 @@ int attention_split(const float* q, const float* k, const float* v, float* o, fl
   else if (NP == 2 && (m32 == 3 || (m32 == 2 && npairs * nqb2 >= pair_min))) {
     // one workgroup of 12 waves per CU (168 VGPRs a wave): 84 KiB of LDS asked for, 64 KiB used
     PATHS_LDS_OPT_IN(attn_m32p_kernel, 96 * 1024, "attention_x6(32x32x16, wave pairs)");
-#ifdef PATHS_M32P_STAMPS
-    hipLaunchKernelGGL(attn_m32p_kernel, dim3(8 * ((npairs + 7) / 8) * nqb2, 1, 1), dim3(PATHS_M32P_LOADERS ? 768 : 512), 84 * 1024, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb2, o_img, g_m32p_dbg);
-#else
-    hipLaunchKernelGGL(attn_m32p_kernel, dim3(8 * ((npairs + 7) / 8) * nqb2, 1, 1), dim3(PATHS_M32P_LOADERS ? 768 : 512), 84 * 1024, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb2, o_img);
-#endif
-  } else if (NP == 2 && QT == 2 && m32 == 1) {
+    hipLaunchKernelGGL(attn_m32p_kernel, dim3(8 * ((npairs + 7) / 8) * nqb2, 1, 1), dim3(768), 84 * 1024, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb2, o_img);
+  } else if (NP == 2 && m32 == 1) {
     PATHS_LDS_OPT_IN(attn_m32_kernel, 96 * 1024, "attention_x6(32x32x16)");
     hipLaunchKernelGGL(attn_m32_kernel, dim3(8 * ((npairs + 7) / 8) * nqb, 1, 1), dim3(256), lds, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb, o_img);
   } else
     hipLaunchKernelGGL((attn_x6_kernel<NP, false>), dim3(8 * ((npairs + 7) / 8) * nqb, 1, 1), dim3(256), lds, stream, q6, k6, v6, o, lse, num_ims, T, Tp, H, npairs, nqb, site, o_img);
-#endif
   PATHS_LAUNCH_CHECK("attention_x6");
   return PATHS_OK;
 }
 
 
 }  // namespace
-
-#ifdef PATHS_M32P_STAMPS
-extern "C" void paths_attn_pair_debug_buffer(unsigned long long* p) { g_m32p_dbg = p; }
-#endif
-#ifdef PATHS_ATTN_DEBUG
-extern "C" void paths_attn_debug_buffer(unsigned long long* p) { g_attn_dbg = p; }     // development hook (tools/attn_wg_times.py)
-#endif
 
 extern "C" {
 

@@ -26,8 +26,8 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 256, BN = 256;
-// k bytes per stage BK = 64 (any K % 128 == 0) or 128 (K % 256 == 0: two MFMA k-steps per barrier, whole 128-byte lines per row piece);
-// LDS rows of BK + 16 bytes: 80 / 144 bytes = 20 / 36 dwords, both conflict-free for the 16-byte fragment reads of 16 consecutive rows
+// k bytes per stage BK = 64 (any K % 128 == 0; a 128-byte stage needs more staging registers than the pipelined k-steps leave: it
+// spills); LDS rows of BK + 16 = 80 bytes = 20 dwords, conflict-free for the 16-byte fragment reads of 16 consecutive rows
 template <int BK> struct Fp8Tile { static constexpr int ROWB = BK + 16, TILE_B = BM * ROWB; };
 constexpr int SCALE_ONE = 0x7F7F7F7F;          // E8M0 127 = 2^0 in every byte
 
@@ -312,16 +312,9 @@ gemm_fp8_kernel(Fp8Gemm g) {
   }
 }
 
-static int launch_fp8(const Fp8Gemm& g, int blocks, int K, hipStream_t stream, const char* name) {
-  // (the 128-byte stage - half the barriers - needs 64 more staging registers than the pipelined k-steps leave: it spills; kept for A/B runs)
-  static const bool bk128 = getenv("PATHS_FP8_BK128") != nullptr && atoi(getenv("PATHS_FP8_BK128")) != 0;
-  if (K % 256 == 0 && bk128) {
-    PATHS_LDS_OPT_IN(gemm_fp8_kernel<128>, 4 * Fp8Tile<128>::TILE_B, name);
-    hipLaunchKernelGGL(gemm_fp8_kernel<128>, dim3(blocks), dim3(256), 4 * Fp8Tile<128>::TILE_B, stream, g);
-  } else {
-    PATHS_LDS_OPT_IN(gemm_fp8_kernel<64>, 4 * Fp8Tile<64>::TILE_B, name);
-    hipLaunchKernelGGL(gemm_fp8_kernel<64>, dim3(blocks), dim3(256), 4 * Fp8Tile<64>::TILE_B, stream, g);
-  }
+static int launch_fp8(const Fp8Gemm& g, int blocks, hipStream_t stream, const char* name) {
+  PATHS_LDS_OPT_IN(gemm_fp8_kernel<64>, 4 * Fp8Tile<64>::TILE_B, name);
+  hipLaunchKernelGGL(gemm_fp8_kernel<64>, dim3(blocks), dim3(256), 4 * Fp8Tile<64>::TILE_B, stream, g);
   PATHS_LAUNCH_CHECK(name);
   return PATHS_OK;
 }
@@ -379,7 +372,7 @@ int paths_gemm_nt_fp8(const uint8_t* a8, const uint8_t* w8, const float* a_scale
   const int MT = (M + BM - 1) / BM, NT = (N + BN - 1) / BN;
   Fp8Gemm g{a8, w8, a_scale, w_scale, bias, residual, ldr, out, ldo, M, N, K, act, MT, NT, nullptr, nullptr, nullptr};
   const int groups = ((MT + 7) / 8 + 3) / 4;            // groups of 4 row panels per XCD
-  const int rc_ = launch_fp8(g, 8 * groups * 4 * NT, K, stream, "gemm_nt_fp8");
+  const int rc_ = launch_fp8(g, 8 * groups * 4 * NT, stream, "gemm_nt_fp8");
   if (rc_ != PATHS_OK) return rc_;
   return PATHS_OK;
 }
@@ -397,7 +390,7 @@ int paths_gemm_nt_fp8_out8(const uint8_t* a8, const uint8_t* w8, const float* a_
   const int MT = (M + BM - 1) / BM, NT = (N + BN - 1) / BN;
   Fp8Gemm g{a8, w8, a_scale, w_scale, bias, nullptr, 0, nullptr, 0, M, N, K, act, MT, NT, out8, out_scale, out_absmax};
   const int groups = ((MT + 7) / 8 + 3) / 4;
-  const int rc_ = launch_fp8(g, 8 * groups * 4 * NT, K, stream, "gemm_nt_fp8_out8");
+  const int rc_ = launch_fp8(g, 8 * groups * 4 * NT, stream, "gemm_nt_fp8_out8");
   if (rc_ != PATHS_OK) return rc_;
   return PATHS_OK;
 }

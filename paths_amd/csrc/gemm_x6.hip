@@ -29,9 +29,6 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "finish_qkv.h"
-#ifndef PATHS_X6_MIX16
-#define PATHS_X6_MIX16 1
-#endif
 
 // PATHS_X6_PART = 1 / 2 / 3: this translation unit defines one third of the C entry points (LSTM cell + weight packing, importance /
 // projection, the gemm_nt family) - the file takes 4.5 minutes to compile whole, __graft_entry__.build() compiles the parts in
@@ -87,13 +84,7 @@ struct X6Operands {
   int rows_per_slide;
   float a_scale;                   // NP == 2: activations are multiplied by this power of two before the fp16 split
   int ksplit = 1;                  // > 1 (single-panel launches only): blockIdx.z owns the k window [z K0/ksplit, (z+1) K0/ksplit)
-#ifdef PATHS_X6_DEBUG
-  uint64_t* dbg;                   // tools/x6_stages.py only: per-wave {init, loop, epilogue} shader-clock ticks, 100 MHz ticks, start/end 100 MHz stamps
-#endif
 };
-#ifdef PATHS_X6_DEBUG
-uint64_t* g_x6_dbg = nullptr;
-#endif
 
 // PF = how many stages ahead of its LDS write a stage is loaded into registers (1 or 2 register sets).  Stages of the
 // 128-row tiles are only ~1,500 cycles long, shorter than a loaded-L2 round trip, so those run two stages ahead.
@@ -139,10 +130,6 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   const int by = grp * GM + in_grp % rows_in_grp, bx = in_grp / rows_in_grp;
   const int m0 = by * BM, n0 = bx * BN;
   if (block_all_padding(g.num_ims, g.rows_per_slide, m0, BM, g.M)) return;
-#ifdef PATHS_X6_DEBUG
-  const uint64_t dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_r0 = __builtin_amdgcn_s_memrealtime();
-  uint64_t dbg_t1 = 0, dbg_t2 = 0, dbg_s[4] = {0, 0, 0, 0};
-#endif
 
   // ---- staging addresses.  A: thread -> (row = 64 p + tid/4, floats 4 (tid%4) .. +3 of the stage); 32-bit byte offsets
   // against a wave-uniform panel base.  W: wave -> 1-KiB pieces wave + 4 i of the stage's SB x 3 fragments.
@@ -204,11 +191,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   for (int i = 0; i < NB; ++i) bsoff[i] = (int)(bbase[i] - g.Wt) + (kofs >> 4) * SUBT;
   auto gload_a = [&](int set, int q, int kt) {
     const bool first = kt < nk0;                       // wave-uniform panel select
-#ifdef PATHS_X6_EXP_HOTA
-    const int soff = 0;                                // experiment: every stage re-reads stage 0 of A (cache-hot): is the pre-barrier loss load latency?
-#else
     const int soff = (first ? kt : kt - nk0) * 64;
-#endif
     if constexpr (A16) {                               // single panel of fp16 rows: the stage's 32 bytes of the row
       sh[set][q] = rowh[q][kt * 4];
     } else if constexpr (ROWS) {                       // single panel: 64-bit per-lane row address + the stage's 64 bytes
@@ -227,11 +210,11 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   };
   // Split of one staged A chunk in NS micro-steps of at most 2 VALU instructions (the last one: the three LDS writes).  A gap
   // between two 32-cycle MFMAs hides about 24 cycles of other issue; the first version used 7 steps of 4 VALU + waits, every
-  // such gap overflowed by ~15 cycles and idle gaps cannot win that back: ~500 cycles per stage (tools/x6_stages.py).
+  // such gap overflowed by ~15 cycles and idle gaps cannot win that back: ~500 cycles per stage.
   //   NP == 3 (bf16): 12 micro-steps (+1 for the ADD sum);  NP == 2 (fp16): scale, hi, lo low halves, lo high halves, writes = 5 (+1).
   //   A1P (one fp16 plane): scale (one v_pk_mul_f16 per register), write = 2.  A16 + ADD: two widening sums (k pairs) in front.
   constexpr int PRE = ADD ? (A16 ? 2 : 1) : 0;
-  constexpr int NS = A1P ? 2 : (NP == 3 ? 12 : NP == 4 ? 7 : (PATHS_X6_MIX16 ? 5 : 6)) + PRE;
+  constexpr int NS = A1P ? 2 : (NP == 3 ? 12 : NP == 4 ? 7 : 5) + PRE;
   float tf[NA][2];
   const uint32_t s2 = A1P ? __builtin_bit_cast(uint32_t, f16x2{(_Float16)g.a_scale, (_Float16)g.a_scale}) : 0u;   // A1P: the packed fp16 scale
   auto a_step = [&](int set, int q, int st0, int buf) __attribute__((always_inline)) {
@@ -283,17 +266,11 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
         *reinterpret_cast<u32x2*>(d + FRAG) = u32x2{mid[q][0], mid[q][1]};
       }
     } else {
-#ifndef PATHS_X6_WHATIF_NOSPLIT
       if (st == 0) v *= g.a_scale;                      // power of two: exact
-#endif
       if (st == 1) { hi[q][0] = pk_f16(v[0], v[1]); hi[q][1] = pk_f16(v[2], v[3]); }
       // lo plane: residual AND its rounding to fp16 in one instruction per value (v_fma_mixlo_f16 / v_fma_mixhi_f16 write one half
       // of the packed register each; round 4: was 2 x v_fma_mix_f32 + v_cvt_pk per pair).  The two halves of a register go to
       // different micro-steps: a half-register write directly in front of the other half's costs a wait state.
-#if defined(PATHS_X6_WHATIF_NOSPLIT)   // diagnostic build, WRONG results: what a pre-split resident image could save at most (no scale, no lo plane work)
-      if (st == 2) { lo[q][0] = hi[q][0]; lo[q][1] = hi[q][1]; }
-      if (st == 4) {
-#elif PATHS_X6_MIX16
       if (st == 2) {
         asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo[q][0]) : "v"(hi[q][0]), "v"(v[0]));
         asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo[q][1]) : "v"(hi[q][1]), "v"(v[2]));
@@ -303,12 +280,6 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
         asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo[q][1]) : "v"(hi[q][1]), "v"(v[3]));
       }
       if (st == 4) {
-#else   // (round-3 form, kept for A/B builds: -DPATHS_X6_MIX16=0)
-      if (st == 2) f16_pair_residuals(hi[q][0], v[0], v[1], tf[q][0], tf[q][1]);
-      if (st == 3) { float r2, r3; f16_pair_residuals(hi[q][1], v[2], v[3], r2, r3); v[2] = r2; v[3] = r3; }
-      if (st == 4) { lo[q][0] = pk_f16(tf[q][0], tf[q][1]); lo[q][1] = pk_f16(v[2], v[3]); }
-      if (st == 5) {
-#endif
         char* d = smem + buf * STAGE + awr[q];
         *reinterpret_cast<u32x2*>(d) = u32x2{hi[q][0], hi[q][1]};
         *reinterpret_cast<u32x2*>(d + FRAG) = u32x2{lo[q][0], lo[q][1]};
@@ -397,9 +368,6 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
     constexpr int buf = decltype(bufc)::value, sb = buf;
     constexpr bool more1 = decltype(m1c)::value, more2 = decltype(m2c)::value;
     constexpr int set = PF == 2 ? (buf ^ 1) : 0;       // register set holding stage kt+1 (reloaded with stage kt+1+PF)
-#ifdef PATHS_X6_DEBUG
-    if (kt == 10) dbg_s[0] = __builtin_amdgcn_s_memtime();
-#endif
     static_for<0, AG>([&](auto gc) __attribute__((always_inline)) {
       constexpr int gq = decltype(gc)::value, i = gq / RG, gr = gq % RG;
       one_mfma(gq, sb);
@@ -407,13 +375,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
       staging_slot(std::integral_constant<int, gq>{}, kt, bufc, m1c, m2c);
       __builtin_amdgcn_sched_barrier(0);
     });
-#ifdef PATHS_X6_DEBUG
-    if (kt == 10) dbg_s[1] = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();
-#ifdef PATHS_X6_DEBUG
-    if (kt == 10) dbg_s[2] = __builtin_amdgcn_s_memtime();
-#endif
     __builtin_amdgcn_sched_barrier(0);
     static_for<AG, WTM * RG>([&](auto gc) __attribute__((always_inline)) {
       constexpr int gq = decltype(gc)::value, gr = gq % RG;
@@ -428,9 +390,6 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
       staging_slot(std::integral_constant<int, gq>{}, kt, bufc, m1c, m2c);   // (reload slots of the PF == 2 layout)
       __builtin_amdgcn_sched_barrier(0);
     });
-#ifdef PATHS_X6_DEBUG
-    if (kt == 10) dbg_s[3] = __builtin_amdgcn_s_memtime();
-#endif
   };
   constexpr std::integral_constant<int, 0> I0{};
   constexpr std::integral_constant<int, 1> I1{};
@@ -462,9 +421,6 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   for (int j = 0; j < WTN; ++j)
 #pragma unroll
     for (int p = 0; p < PL; ++p) read_b(0, j, 0, p);
-#ifdef PATHS_X6_DEBUG
-  dbg_t1 = __builtin_amdgcn_s_memtime();
-#endif
   for (int kt = 0; kt < nk - 2 * PF; kt += 2) {
     __builtin_amdgcn_sched_barrier(0);
     stage_body(kt, I0, T, T);
@@ -476,22 +432,8 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   }
   stage_body(nk - 2, I0, T, F);
   stage_body(nk - 1, I1, F, F);
-#ifdef PATHS_X6_DEBUG
-  dbg_t2 = __builtin_amdgcn_s_memtime();
-#endif
   __syncthreads();     // epilogues may reuse LDS
   epi.template run<WTM, WTN, 2, 2>(acc, m0 + wm * WTM * 32, n0 + wn * WTN * 32, lane, wm, wn, g.M, reinterpret_cast<float*>(smem));
-#ifdef PATHS_X6_DEBUG
-  if (g.dbg) {
-    __builtin_amdgcn_s_waitcnt(0);
-    const uint64_t t3 = __builtin_amdgcn_s_memtime(), r3 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {
-      uint64_t* d = g.dbg + 9 * ((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave);
-      d[0] = dbg_t1 - dbg_t0; d[1] = dbg_t2 - dbg_t1; d[2] = t3 - dbg_t2; d[3] = r3 - dbg_r0; d[4] = dbg_r0; d[5] = r3;
-      d[6] = dbg_s[1] - dbg_s[0]; d[7] = dbg_s[2] - dbg_s[1]; d[8] = dbg_s[3] - dbg_s[2];   // stage 10: pre-barrier, barrier wait, post-barrier
-    }
-  }
-#endif
 }
 
 // fp32 [N, K] (row stride ldw) -> split tiled image, rows >= N zero.  NP == 2: values are multiplied by wscale (a power of two) first.
@@ -560,12 +502,7 @@ int launch_x6_np(const X6Operands& g, int Npad, const Epi& epi, hipStream_t stre
   PATHS_LDS_OPT_IN(kern, lds, name);
   PATHS_REQUIRE(g.ksplit == 1 || (g.ksplit > 1 && g.K1 == 0 && g.K0 % (32 * g.ksplit) == 0 && g.K0 / g.ksplit >= 128), "%s: split-K needs a single panel and k windows that are multiples of 32, >= 128", name);
   dim3 grid(Npad / BN, (g.M + BM - 1) / BM, g.ksplit);
-#ifdef PATHS_X6_DEBUG
-  X6Operands gd = g; gd.dbg = g_x6_dbg;
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, gd, epi);
-#else
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, g, epi);
-#endif
   PATHS_LAUNCH_CHECK(name);
   return PATHS_OK;
 }
@@ -596,11 +533,7 @@ struct EpiRaw {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 v = f32x4{acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-#ifdef PATHS_RAW_NT
-          __builtin_nontemporal_store(v, t + 64 * q);     // experiment: streaming stores leave no dirty lines for the kernel-end write-back
-#else
           t[64 * q] = v;
-#endif
         }
       }
   }
@@ -644,19 +577,8 @@ int launch_x6(int planes, const X6Operands& g, int Npad, const Epi& epi, hipStre
   return paths_set_error(PATHS_EINVAL, "%s: planes must be 3 (bf16 x6) or 2 (fp16 x3), got %d", name, planes);
 }
 
-#ifndef PATHS_H_OCC
-#define PATHS_H_OCC 3
-#endif
-constexpr int H_OCC = PATHS_H_OCC;
-#ifndef PATHS_H_TRAIN_OCC
-#define PATHS_H_TRAIN_OCC 2
-#endif
-constexpr int H_TRAIN_OCC = PATHS_H_TRAIN_OCC;
-static const bool H_TRAIN_SMALL = getenv("PATHS_H_TRAIN_SMALL") == nullptr || atoi(getenv("PATHS_H_TRAIN_SMALL")) != 0;   // A/B switch
-static const bool FIN_XCD_ORDER = getenv("PATHS_FIN_XCD_ORDER") == nullptr || atoi(getenv("PATHS_FIN_XCD_ORDER")) != 0;   // A/B switch
-static const bool IP_TILE128 = getenv("PATHS_IP_TILE128") != nullptr && atoi(getenv("PATHS_IP_TILE128")) != 0;   // measured: 69 us vs 58 (split-K)
-static const bool O_RAW = getenv("PATHS_O_RAW") == nullptr || atoi(getenv("PATHS_O_RAW")) != 0;
-static const bool H_SMALL_TILES = getenv("PATHS_H_SMALL_TILES") == nullptr || atoi(getenv("PATHS_H_SMALL_TILES")) != 0;
+constexpr int H_OCC = 3;             // waves per SIMD of the 128 x 128 mem_to_out tiles: inference
+constexpr int H_TRAIN_OCC = 2;       // and training
 
 inline int plane_count(int planes) { return planes == 4 ? 2 : planes; }      // API mode 4 = two bf16 planes
 inline int64_t group_stride(int planes, int Kpacked) { return (int64_t)(Kpacked / 16) * plane_count(planes) * FRAG; }
@@ -670,11 +592,6 @@ inline bool h16_scale_ok(float a_scale) { return pow2(a_scale) && a_scale >= 1.0
 // C ABI
 // ================================================================================================
 extern "C" {
-
-#if defined(PATHS_X6_DEBUG) && (PATHS_X6_PART == 0 || PATHS_X6_PART == 1)
-// development hook (tools/x6_stages.py, debug build only): buffer of 9 uint64 per wave, or NULL
-void paths_x6_debug_buffer(uint64_t* p) { g_x6_dbg = p; }
-#endif
 
 #if PATHS_X6_PART == 0 || PATHS_X6_PART == 1
 // bytes of the packed image of an [Npad, K] weight: planes x 2 bytes per element
@@ -737,9 +654,8 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
   // Few rows (M <= 8192: K = 1024 x 8 slides, small batches, drop-in calls): 256-row blocks put ceil(M / 256) x 4 <= 128 workgroups on
   // 256 CUs - half the chip idles through the two biggest launches of a level.  128-row blocks (the parent GEMM's tile family) make it
   // one full round of workgroups with half the work each; above 8192 rows they would spill into a second round and lose (round 2:
-  // 165 against 280 TFLOP/s per workgroup pair).  Default split (two fp16 planes) only; PATHS_LSTM_SMALL_TILES=0 turns it off.
-  static const bool small_on = getenv("PATHS_LSTM_SMALL_TILES") == nullptr || atoi(getenv("PATHS_LSTM_SMALL_TILES")) != 0;
-  const bool small_m = small_on && planes == 2 && M <= 8192 && (h0 == nullptr);
+  // 165 against 280 TFLOP/s per workgroup pair).  Default split (two fp16 planes) only.
+  const bool small_m = planes == 2 && M <= 8192 && (h0 == nullptr);
   if (phases & 1) {   // c-part: N = 3Hc, block 256 x 192
     EpiLstmC e{b_gates, c0, ldc0, state_out + D, ldso, save_frm, (int64_t)3 * Hc, hp, (int64_t)3 * Hc + D, hp_row, sg};
     int rc;
@@ -752,7 +668,7 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
     if (rc) return rc;
   }
   // inference (no Y, no training saves): the gate travels to phase 4 as raw pre-activations in the accumulator layout (EpiLstmORaw)
-  const bool o_raw = y == nullptr && save_tc == nullptr && save_frm == nullptr && O_RAW;
+  const bool o_raw = y == nullptr && save_tc == nullptr && save_frm == nullptr;
   if (phases & 2) {   // o gate: N = D, block 256 x 256
     X6Operands go = g;
     go.Wt = wg + (int64_t)(3 * Hc / 32) * gs;
@@ -776,24 +692,25 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
     X6Operands gh{state_out + D, ldso, Hc, nullptr, nullptr, 0, 0, nullptr, 0, reinterpret_cast<const char*>(w_mem_x6), group_stride(planes, Hc), M, num_ims, rows_per_slide, a_scale};
     int rc;
     PATHS_REQUIRE(save_tc == nullptr || y != nullptr, "lstm_cell_x6: save_tc (training) needs y");
+    PATHS_REQUIRE(planes == 2 || planes == 3, "lstm_cell_x6: planes must be 3 (bf16 x6) or 2 (fp16 x3), got %d", planes);
     if (save_tc != nullptr) {
       EpiLstmH<true, true> e{b_mem, ws_o, D, x, ldx, state_out, ldso, y, ldy, D, save_tc, sm};
       // (round 5: the training form on the inference form's 128 x 128 tiles at H_TRAIN_OCC waves per SIMD: K = 256 is 16 k16 stages
       // of MFMA against ~250 MB of epilogue traffic - several workgroups per CU hide each other's epilogue loads / stores)
-      if (planes == 2 && H_SMALL_TILES && H_TRAIN_SMALL) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_TRAIN_OCC>(gh, D, e, stream, "lstm_cell_x6(h, save, 128x128)");
-      else rc = launch_x6<4, 4, 1, false>(planes, gh, D, e, stream, "lstm_cell_x6(h, save)");
+      if (planes == 2) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_TRAIN_OCC>(gh, D, e, stream, "lstm_cell_x6(h, save, 128x128)");
+      else rc = launch_x6_np<3, 4, 4, 1, false, false>(gh, D, e, stream, "lstm_cell_x6(h, save)");
     } else if (y != nullptr) {
       EpiLstmH<true, false> e{b_mem, ws_o, D, x, ldx, state_out, ldso, y, ldy, D, nullptr, sm};
       rc = launch_x6<4, 4, 1, false>(planes, gh, D, e, stream, "lstm_cell_x6(h)");
     } else if (o_raw) {
       EpiLstmH<false, false, true> e{b_mem, ws_o, D, x, ldx, state_out, ldso, nullptr, 0, D, nullptr, sm};
       // inference: 16 k16 stages of MFMA against 120 MB of epilogue traffic -> 128 x 128 tiles, several workgroups per CU
-      if (planes == 2 && H_SMALL_TILES) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_OCC>(gh, D, e, stream, "lstm_cell_x6(h, raw o, 128x128)");
-      else rc = launch_x6<4, 4, 1, false>(planes, gh, D, e, stream, "lstm_cell_x6(h, raw o)");
+      if (planes == 2) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_OCC>(gh, D, e, stream, "lstm_cell_x6(h, raw o, 128x128)");
+      else rc = launch_x6_np<3, 4, 4, 1, false, false>(gh, D, e, stream, "lstm_cell_x6(h, raw o)");
     } else {
       EpiLstmH<false, false> e{b_mem, ws_o, D, x, ldx, state_out, ldso, nullptr, 0, D, nullptr, sm};
-      if (planes == 2 && H_SMALL_TILES) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_OCC>(gh, D, e, stream, "lstm_cell_x6(h, no y, 128x128)");
-      else rc = launch_x6<4, 4, 1, false>(planes, gh, D, e, stream, "lstm_cell_x6(h, no y)");
+      if (planes == 2) rc = launch_x6_np<2, 2, 2, 2, false, false, decltype(e), H_OCC>(gh, D, e, stream, "lstm_cell_x6(h, no y, 128x128)");
+      else rc = launch_x6_np<3, 4, 4, 1, false, false>(gh, D, e, stream, "lstm_cell_x6(h, no y)");
     }
     if (rc) return rc;
   }
@@ -863,20 +780,12 @@ int importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows, const
                     save_hid, save_pproj, pe_table, pe_table ? pe_rows : 0, sc};
     {
       // two launches (default split): the GEMM stores RAW accumulators, the epilogue runs on 64-row blocks.  Default: split-K, two k
-      // halves of 128 x 256 tiles.  PATHS_IP_TILE128=1 (experiment, slower, Y = X + h1 form only): 128 x 128 tiles over the full k at two
-      // waves per SIMD - the x + h1 operand is then staged twice as often.  Round 5: also the training form (a stored Y, the SAVE
-      // epilogues): one launch of M / 128 blocks fills half the chip there too (115 us against ~60).
+      // halves of 128 x 256 tiles.  Round 5: also the training form (a stored Y, the SAVE epilogues): one launch of M / 128 blocks fills half the chip there too (115 us against ~60).
       if (splitk_ws != nullptr && planes == 2 && (y_add != nullptr || y_rows == nullptr) && D % 64 == 0 && D >= 256) {
         const int mt = (M + 127) / 128 * 4;                         // 32-row tiles, padded to the GEMM's 128-row blocks
         const int64_t zstride = (int64_t)mt * 8 * 1024;
         int rc;
-        const bool tile128 = IP_TILE128 && y_add != nullptr && !A16;
-        if (tile128) {
-          if constexpr (A16) return paths_set_error(PATHS_EUNSUPPORTED, "importance_proj_x6_h16: no 128 x 128 tile form");
-          EpiRaw raw{splitk_ws, zstride, 8};
-          rc = y_rows ? launch_x6_np<2, 2, 2, 2, true, true, EpiRaw, 2>(g, 256, raw, stream, "importance_proj_x6(raw, 128x128)")
-                      : launch_x6_np<2, 2, 2, 2, true, false, EpiRaw, 2>(g, 256, raw, stream, "importance_proj_x6(raw, 128x128)");
-        } else if constexpr (A16) {
+        if constexpr (A16) {
           X6Operands gs = g; gs.ksplit = 2;
           EpiRaw raw{splitk_ws, zstride, 8};
           rc = launch_x6_np<2, 2, 4, 2, true, true, EpiRaw, 1, true>(gs, 256, raw, stream, "importance_proj_x6_h16(split-k)");
@@ -892,13 +801,8 @@ int importance_proj_x6(const float* y, int64_t ldy, const int64_t* y_rows, const
         const int fblk = (M + 63) / 64, fdepth = (fblk + 255) / 256;
         const int flds = fdepth == 1 ? 84 * 1024 : fdepth == 2 ? 54 * 1024 : fdepth == 3 ? 41 * 1024 : 1024;
         PATHS_LDS_OPT_IN((x6_finish_kernel<2, decltype(epi)>), 84 * 1024, "importance_proj_x6(finish)");
-        PATHS_LDS_OPT_IN((x6_finish_kernel<1, decltype(epi)>), 84 * 1024, "importance_proj_x6(finish)");
-        if (tile128)
-          PATHS_LAUNCH_STOP((x6_finish_kernel<1, decltype(epi)>), dim3(fblk), dim3(256), flds, stream, splitk_ws, zstride, 8, M,
-                            skip_padding ? num_ims : nullptr, rows_per_slide, e);
-        else
-          PATHS_LAUNCH_STOP((x6_finish_kernel<2, decltype(epi)>), dim3(fblk), dim3(256), flds, stream, splitk_ws, zstride, 8, M,
-                            skip_padding ? num_ims : nullptr, rows_per_slide, e);
+        PATHS_LAUNCH_STOP((x6_finish_kernel<2, decltype(epi)>), dim3(fblk), dim3(256), flds, stream, splitk_ws, zstride, 8, M,
+                          skip_padding ? num_ims : nullptr, rows_per_slide, e);
         PATHS_LAUNCH_CHECK("importance_proj_x6(finish)");
         return PATHS_OK;
       }
@@ -949,10 +853,6 @@ int paths_importance_proj_x6_h16(const float* y, int64_t ldy, const int64_t* y_r
 // paths_token0_tail_ws with special_last = 1.  N % 64 == 0.
 //   phases bit 1: the split-K GEMM over (y | y_rows) + y_add into splitk_ws (paths_importance_proj_x6_workspace(B * N) bytes);
 //          bit 2: the importance-only finish (alpha -> importance [B, N]);
-//          bit 8: (instead of bit 2) the importance finish AND the top-K of every slide in one launch: keep_idx [B, ldk] (score descending,
-//                 index ascending; keep < 0: all, original order), keep_count [B], optionally kept_rows [B, ldk] = addresses of
-//                 row_base[b, keep_idx[b, i], :] (row stride row_ld floats, N rows per slide; zero_row beyond the count) - the outputs of
-//                 paths_topk_rows; counters: 2 B int32 words, zero on entry, left zero; status (optional): bit 4 on a timed-out arrival wait;
 //          bit 4: the tokens + in_proj finish: importance (computed, or read back when alpha_from_importance), tokens [B, N + 1, 128]
 //                 and the q | k | v operand images of paths_attention_h3_img in qkv_images (paths_attention_x6_workspace(B, N + 1, 4, 32, 2)).
 // Bits 2 and 4 are stop-event capable launches; they may be issued by separate calls on different streams (the caller orders them
@@ -965,15 +865,13 @@ int importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, const 
                       const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
                       int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
                       float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
-                      float qscale, void* qkv_images, int phases, int alpha_from_importance,
-                      int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
-                      const float* zero_row, int* counters, int* status, hipStream_t stream) {
+                      float qscale, void* qkv_images, int phases, int alpha_from_importance, hipStream_t stream) {
   PATHS_REQUIRE(!A16 || (phases & 1) == 0 || (y == nullptr && y_rows != nullptr), "importance_qkv_x6_h16: fp16 rows are given as y_rows");
   PATHS_REQUIRE(B > 0 && N > 0 && N % 64 == 0 && D % 64 == 0 && D >= 256, "importance_qkv_x6: bad shape B=%d N=%d (a multiple of 64) D=%d", B, N, D);
   PATHS_REQUIRE(pe_mode == 1 || pe_mode == 2, "importance_qkv_x6: pe_mode must be 1 (1d) or 2 (2d)");
   PATHS_REQUIRE(pe_table != nullptr && pe_rows > 0 && (pe_mode == 1 || locs != nullptr), "importance_qkv_x6: needs the positional-encoding table (and locs in 2d mode)");
   PATHS_REQUIRE(num_ims != nullptr && splitk_ws != nullptr && (uintptr_t)splitk_ws % 16 == 0, "importance_qkv_x6: num_ims and a 16-byte aligned workspace are required");
-  PATHS_REQUIRE(phases > 0 && (phases & ~15) == 0 && (phases & 10) != 10, "importance_qkv_x6: phases is a mask of 1 (GEMM), 2 (importance finish) or 8 (importance + top-K finish), 4 (tokens + in_proj finish)");
+  PATHS_REQUIRE(phases > 0 && (phases & ~7) == 0, "importance_qkv_x6: phases is a mask of 1 (GEMM), 2 (importance finish), 4 (tokens + in_proj finish)");
   PATHS_REQUIRE(pow2(w_scale) && pow2(a_scale), "importance_qkv_x6: scales must be powers of two");
   const int64_t M64 = (int64_t)B * N;
   PATHS_REQUIRE(M64 < (1ll << 24), "importance_qkv_x6: B * N must stay below 2^24 rows");
@@ -992,20 +890,13 @@ int importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, const 
                      : launch_x6_np<2, 2, 4, 2, true, false>(g, 256, raw, stream, "importance_qkv_x6(split-k)");
     if (rc != PATHS_OK) return rc;
   }
-  if (phases & 14) {
+  if (phases & 6) {
     PATHS_REQUIRE(b1 && w2 && b2 && importance, "importance_qkv_x6: b1, w2, b2 (device scalar) and importance are required");
     FinQkvParams f{splitk_ws, zstride, 2, b1, w2, b2, bp, special, pe_table, pe_rows, locs, num_ims, N, T, Tp, B, patch_size, pe_mode, imp_mul,
                    skip_padding, 1.0f / (w_scale * a_scale), alpha_from_importance, importance, tokens, w_qkv, bqkv, 1.0f / s_wqkv, qscale, qkv_images,
-                   (B % 8 == 0 && (M / 128) % 8 == 0 && M % 128 == 0 && FIN_XCD_ORDER) ? 1 : 0};
+                   (B % 8 == 0 && (M / 128) % 8 == 0 && M % 128 == 0) ? 1 : 0};
     if (phases & 2) {
       const int rc = paths_launch_finish_importance(f, stream);
-      if (rc != PATHS_OK) return rc;
-    }
-    if (phases & 8) {
-      PATHS_REQUIRE(keep_idx && keep_count && counters && ldk > 0 && ldk <= N && N <= 8192 && (kept_rows == nullptr || (row_base && zero_row)),
-                    "importance_qkv_x6: the importance + top-K finish needs keep_idx [B, ldk <= N], keep_count, counters (2 B zeroed int32), N <= 8192");
-      FinTopkParams tk{keep, keep_idx, ldk, keep_count, row_base, row_ld, kept_rows, zero_row, counters, status};
-      const int rc = paths_launch_finish_importance_topk(f, tk, stream);
       if (rc != PATHS_OK) return rc;
     }
     if (phases & 4) {
@@ -1024,13 +915,10 @@ int paths_importance_qkv_x6(const float* y, int64_t ldy, const int64_t* y_rows, 
                             const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
                             int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
                             float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
-                            float qscale, void* qkv_images, int phases, int alpha_from_importance,
-                            int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
-                            const float* zero_row, int* counters, int* status, hipStream_t stream) {
+                            float qscale, void* qkv_images, int phases, int alpha_from_importance, hipStream_t stream) {
   return importance_qkv_x6<false>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, pe_table, pe_rows, locs, num_ims, B, N, patch_size,
                                   pe_mode, imp_mul, importance, tokens, D, skip_padding, w_scale, a_scale, splitk_ws, w_qkv, bqkv, s_wqkv, qscale,
-                                  qkv_images, phases, alpha_from_importance, keep, keep_idx, ldk, keep_count, row_base, row_ld, kept_rows, zero_row,
-                                  counters, status, stream);
+                                  qkv_images, phases, alpha_from_importance, stream);
 }
 
 // The same with y_rows addressing FP16 feature rows (y = NULL) in the GEMM phase (bit 1); the finish phases are the fp32 form's.
@@ -1039,13 +927,10 @@ int paths_importance_qkv_x6_h16(const float* y, int64_t ldy, const int64_t* y_ro
                                 const float* pe_table, int pe_rows, const int64_t* locs, const int64_t* num_ims, int B, int N,
                                 int patch_size, int pe_mode, int imp_mul, float* importance, float* tokens, int D, int skip_padding,
                                 float w_scale, float a_scale, float* splitk_ws, const void* w_qkv, const float* bqkv, float s_wqkv,
-                                float qscale, void* qkv_images, int phases, int alpha_from_importance,
-                                int keep, int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t* kept_rows,
-                                const float* zero_row, int* counters, int* status, hipStream_t stream) {
+                                float qscale, void* qkv_images, int phases, int alpha_from_importance, hipStream_t stream) {
   return importance_qkv_x6<true>(y, ldy, y_rows, y_add, ldya, w_ip_x6, b1, w2, b2, bp, special, pe_table, pe_rows, locs, num_ims, B, N, patch_size,
                                  pe_mode, imp_mul, importance, tokens, D, skip_padding, w_scale, a_scale, splitk_ws, w_qkv, bqkv, s_wqkv, qscale,
-                                 qkv_images, phases, alpha_from_importance, keep, keep_idx, ldk, keep_count, row_base, row_ld, kept_rows, zero_row,
-                                 counters, status, stream);
+                                 qkv_images, phases, alpha_from_importance, stream);
 }
 
 #endif

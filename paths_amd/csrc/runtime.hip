@@ -20,7 +20,7 @@ const char* paths_build_info(void) { return "paths_hip gfx950 split-operand MFMA
 // 2 (round 5): dropout masks are one 16-bit hash half per element since round 4 (thr16 = round(p 65536), scale 1 / (1 - thr16 / 65536):
 // same (key, p) -> other masks than ABI 1), events of paths_event_create are device-side joins only (no system-scope fence: not for
 // host waits), paths_stop_event_pending / paths_record_event / paths_clear_stop_event added.
-int paths_abi_version(void) { return 2; }
+int paths_abi_version(void) { return 3; }
 
 // ---- stream plumbing for the launch tape (paths_amd/utils.py:TapedRecursion): the recorded launch sequence of a recursion is
 // replayed as a flat list of C calls, so its cross-stream joins and zero fills are C calls too.
@@ -28,10 +28,8 @@ int paths_abi_version(void) { return 2; }
 void* paths_event_create(void) {
   hipEvent_t ev = nullptr;
   // (device-side joins of streams of ONE device only: no system-scope fence when the event is recorded - the kernel that carries it as its
-  // stop event would otherwise end with a release to the system.  PATHS_EVENT_FLAGS overrides, for A/B runs.)
-  static const unsigned flags = getenv("PATHS_EVENT_FLAGS") ? (unsigned)strtoul(getenv("PATHS_EVENT_FLAGS"), nullptr, 0)
-                                                            : (hipEventDisableTiming | hipEventDisableSystemFence);
-  if (hipEventCreateWithFlags(&ev, flags) != hipSuccess) { paths_set_error(PATHS_ELAUNCH, "event_create failed"); return nullptr; }
+  // stop event would otherwise end with a release to the system.)
+  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { paths_set_error(PATHS_ELAUNCH, "event_create failed"); return nullptr; }
   return ev;
 }
 // Destroy an event made by paths_event_create (the launch tape destroys its events when it is closed / collected).

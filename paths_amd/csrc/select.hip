@@ -115,13 +115,10 @@ static int launch_topk(const float* scores, int64_t ld, const int64_t* num_ims, 
 // expansion: kept patch (x,y) -> blocks (2x,2y) | (2x,2y+1) | (2x+1,2y) | (2x+1,2y+1), each in top-K
 // order (slide.py:307-315); keep child iff in bounds and tissue (slide.py:320-325); stable compaction.
 // ------------------------------------------------------------------------------------------------
-#ifndef PATHS_EXPAND_THREADS
-#define PATHS_EXPAND_THREADS 512           // threads of the one workgroup per slide (a multiple of 64, <= 1024).  Alone the kernel is fastest at
-                                           // 1024 (11.7 us against 15.1 / 23.5 at 512 / 256), but a 16-wave workgroup has to wait for a CU with four free
-                                           // wave slots per SIMD beside the aggregator's kernels: in the recursion 512 gives 3,591-3,624 slides/s against
-                                           // 3,527-3,535 (sustained 3,717-3,731 against 3,609-3,616), 256 gives 3,589-3,618
-#endif
-constexpr int EXP_NT = PATHS_EXPAND_THREADS, EXP_NW = EXP_NT / 64;
+// threads of the one workgroup per slide.  Alone the kernel is fastest at 1024 (11.7 us against 15.1 / 23.5 at 512 / 256), but a
+// 16-wave workgroup has to wait for a CU with four free wave slots per SIMD beside the aggregator's kernels: in the recursion 512
+// gives 3,591-3,624 slides/s against 3,527-3,535 (sustained 3,717-3,731 against 3,609-3,616), 256 gives 3,589-3,618
+constexpr int EXP_NT = 512, EXP_NW = EXP_NT / 64;
 __global__ void __launch_bounds__(EXP_NT)
 expand_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restrict__ keep_count,
               const int64_t* __restrict__ locs, int64_t n_cur, int patch_size,

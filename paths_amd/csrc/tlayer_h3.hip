@@ -32,13 +32,10 @@ constexpr int FRAG = 1024;         // bytes of one 16-row x 32-k fragment of one
 constexpr int CHUNK = 32 * FRAG;   // one staged chunk: [64 out rows][128 k] or [128 out rows][64 k], 2 planes
 constexpr int N_POST = 18;         // chunks of the post-attention part: 0-1 Wo | 2+2h W1 rows 64h | 3+2h W2[:, 64h:64h+64]
 constexpr int N_QKV = 6;           // chunks of in_proj: rows 64 c
-#ifndef PATHS_TLAYER_WAVES
-#define PATHS_TLAYER_WAVES 8
-#endif
 // Waves per workgroup (16 tokens each).  8 = two waves per SIMD sharing every staged weight chunk: the chain is latency-bound (one
 // wave per SIMD re-reads a 32-KiB chunk from LDS per 48 MFMAs, MFMA pipe 11 % busy), a second wave on the SIMD runs under the
 // first one's LDS / barrier waits, the global -> LDS chunk traffic per token halves, and the launch needs half the CUs.
-constexpr int NWAVES = PATHS_TLAYER_WAVES;
+constexpr int NWAVES = 8;
 constexpr int NTHREADS = 64 * NWAVES, TOK_WG = 16 * NWAVES, NSTAGE = 2048 / NTHREADS;   // 16-byte pieces per thread and chunk
 
 __device__ __forceinline__ uint32_t pk_f16(float a, float b) {

@@ -32,16 +32,10 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FRAG = 1024;         // bytes of one 16-row x 32-k fragment of one plane
 constexpr int NW = 4;              // waves per workgroup
-#ifndef PATHS_WS_TT
-#define PATHS_WS_TT 4
-#endif
-constexpr int TT = PATHS_WS_TT;    // 16-token tiles per workgroup (4: 64 tokens, one workgroup per CU; 2: 32 tokens, two per CU)
+constexpr int TT = 4;              // 16-token tiles per workgroup (64 tokens, one workgroup per CU)
 constexpr int TOK = 16 * TT;
 constexpr int NFF = 4;             // feed-forward hidden chunks of DM features (dim_feedforward = 4 DM, reference aggregator.py:29)
-#ifndef PATHS_WS_NPF
-#define PATHS_WS_NPF 6
-#endif
-constexpr int NPF = PATHS_WS_NPF;  // weight prefetch ring: k32 steps in flight per wave (6: inside a level the weights come from beyond the L2 - it is
+constexpr int NPF = 6;             // weight prefetch ring: k32 steps in flight per wave (6: inside a level the weights come from beyond the L2 - it is
                                    // invalidated at every launch boundary; row chain 24.1 -> 22.9 us in the recursion, 4 = 8 in a hot loop)
 
 template <int DM> struct Geo {
@@ -94,27 +88,15 @@ __device__ __forceinline__ u32x4 ldg_u32x4(const char* p) {
 // add up to the pair sum in every lane.  Inline asm: through __builtin_amdgcn_permlane16_swap hipcc (ROCm 7.2) added result 0 to
 // itself here (v_add v, r0, r0: wrong sums).  s_nop 1 = the two wait states between a VALU write of an operand and the swap.
 __device__ __forceinline__ float sum_xor16(float x) {
-#ifdef PATHS_WS_LN_SHFL
-  return x + __shfl_xor(x, 16);
-#endif
   float a = x, b = x;
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   return a + b;
 }
 __device__ __forceinline__ float sum_xor32(float x) {
-#ifdef PATHS_WS_LN_SHFL
-  return x + __shfl_xor(x, 32);
-#endif
   float a = x, b = x;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   return a + b;
 }
-
-#ifdef PATHS_WS_STAMPS
-#define WS_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (p.stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = t_; } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WS_STAMP(i) do { } while (0)
-#endif
 
 struct WsParams {
   const float* x_in;            // [B][T][DM] residual stream (POST) / in_proj input (QKV only)
@@ -131,9 +113,6 @@ struct WsParams {
   int T, Tp, B, skip_padding;
   float qscale, eps;
   int* zero_words; int n_zero;  // optional: words zeroed by block (0, 0) (the arrival counters of the token-0 tail that follows)
-#ifdef PATHS_WS_STAMPS
-  unsigned long long* stamps;   // diagnostic build only: 16 s_memtime stamps per workgroup
-#endif
   FinQkvParams fin;             // FIN kernels only (finish_qkv.h): the input rows are BUILT here from the raw importance / projection GEMM result
 };
 
@@ -155,12 +134,7 @@ __device__ __forceinline__ void fin_tile_of_workgroup(const FinQkvParams& f, int
   t0 = (k % tiles) * TOK;
 }
 
-#ifdef PATHS_WS_STAMPS
-#define FIN_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = t_; } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define FIN_STAMP(i) do { } while (0)
-#endif
-__device__ __forceinline__ void fin_tokens(const FinQkvParams& f, int b, int t0, int tid, float* sTok, float* sAlpha, unsigned long long* stamps) {
+__device__ __forceinline__ void fin_tokens(const FinQkvParams& f, int b, int t0, int tid, float* sTok, float* sAlpha) {
   constexpr int d = 128, NZ = 2;                       // (two k halves: the only split the GEMM is launched with)
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
   const int u0 = 64 * wn;
@@ -247,7 +221,6 @@ __device__ __forceinline__ void fin_tokens(const FinQkvParams& f, int b, int t0,
     issue(2);
     reduce(std::integral_constant<int, 2>{});
   }
-  FIN_STAMP(2);
   if (!f.alpha_from_importance) {
     // ---- partial importance logits over this wave's 64 hidden units, summed over the 32 lanes of each half-wave by the halving
     // butterfly of EpiImpProj (gemm_epi.h): afterwards lane l holds the total of row index rho(l) = bits 4..1 of l
@@ -286,7 +259,6 @@ __device__ __forceinline__ void fin_tokens(const FinQkvParams& f, int b, int t0,
     if ((lane & 1) == 0) sAlpha[wn * TOK + 32 * wm + c32_row(rho, lane)] = p1;
   }
   __syncthreads();
-  FIN_STAMP(3);
   // ---- alpha of the tile's 64 slots, once each (64 threads; one coalesced store of the importance row piece)
   if (tid < TOK) {
     const int sl = t0 + tid;
@@ -310,7 +282,6 @@ __device__ __forceinline__ void fin_tokens(const FinQkvParams& f, int b, int t0,
       sTok[lt * TOK_LD + c] = sl == nim ? spv[j] : (sl < f.T ? av * pj + bpv[j] + pev[r][j] : 0.f);
     }
   }
-  FIN_STAMP(4);
 }
 
 // the tile's fp32 token rows from LDS to tokens [B, T, 128]: whole 512-byte rows, 16 bytes per lane (call after a barrier behind fin_tokens)
@@ -326,9 +297,9 @@ __device__ __forceinline__ void fin_store_tokens(const FinQkvParams& f, int b, i
 // tile ot, the features 16 (OT w + ot) + 4 g + r (r = 0..3) of token 16 tt + ql  -  the C layout of v_mfma_f32_16x16x32_f16 with the
 // weights as A (rows = output features) and the activations as B (columns = tokens).
 template <int DM, bool POST, bool QKV, bool ROWS = false, bool FIN = false>
-__global__ void __launch_bounds__(64 * NW, TT == 2 ? 2 : 1)
+__global__ void __launch_bounds__(64 * NW, 1)
 tlayer_ws_kernel(WsParams p) {
-  static_assert(!FIN || (DM == 128 && !POST && QKV && !ROWS && TT == 4), "FIN: the fused finish of the importance / projection GEMM (trans_dim 128, in_proj only)");
+  static_assert(!FIN || (DM == 128 && !POST && QKV && !ROWS), "FIN: the fused finish of the importance / projection GEMM (trans_dim 128, in_proj only)");
   using G = Geo<DM>;
   constexpr int KB = G::KB, OT = G::OT;
   constexpr int POST_STEPS = POST ? G::N_POST * KB : 0, NSTEPS = POST_STEPS + (QKV ? G::N_QKV * KB : 0);
@@ -348,7 +319,6 @@ tlayer_ws_kernel(WsParams p) {
   const int len = p.num_ims ? min((int)p.num_ims[b] + 1, p.T) : p.T;               // valid tokens: special token + patches
   if (p.skip_padding && t0 >= len) return;
   const int fbase = 16 * OT * wave + 4 * g;                                       // this lane's first feature (tile 0)
-  WS_STAMP(0);
 
   // ---- weight stream of this wave: [unit][wave][kb][ot][plane][64 lanes][16 B]; a k32 step = OT x 2 loads of 1 KiB
   u32x4 wr[NPF][OT][2];
@@ -419,11 +389,7 @@ tlayer_ws_kernel(WsParams p) {
     // the input rows are built HERE from the raw result of the importance / projection GEMM (finish_qkv.h); the weight loads and
     // the bias vector issued above land under it
     float* const sTok = sBqkv + 3 * DM;
-#ifdef PATHS_WS_STAMPS
-    fin_tokens(p.fin, b, t0, tid, sTok, sTok + TOK * TOK_LD, p.stamps);
-#else
-    fin_tokens(p.fin, b, t0, tid, sTok, sTok + TOK * TOK_LD, nullptr);
-#endif
+    fin_tokens(p.fin, b, t0, tid, sTok, sTok + TOK * TOK_LD);
     __syncthreads();
     fin_store_tokens(p.fin, b, t0, tid, sTok);
     for (int kb = wave; kb < KB; kb += NW) {
@@ -469,7 +435,6 @@ tlayer_ws_kernel(WsParams p) {
       if (tid + q * 64 * NW < 3 * DM) sBqkv[tid + q * 64 * NW] = vbq[q];
   }
   __syncthreads();
-  WS_STAMP(1);
 
   // acc[ot][tt] += W_unit[this wave's rows 16 ot ..][all DM k] . X[k][token tile tt]   (SWAP: the operands exchanged, rows = tokens)
   // The B fragments of k32 step kb + 1 are read from LDS while the MFMAs of step kb run (two register sets; a step's reads were
@@ -609,7 +574,6 @@ tlayer_ws_kernel(WsParams p) {
         for (int tt = 0; tt < TT; ++tt) xr[ot][tt] = xr[ot][tt] + (acc[ot][tt] * p.inv_wo + bo);
       }
     }
-    WS_STAMP(2);
     layernorm(xr, sVec + DM, sVec + 2 * DM, 0);
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
@@ -618,10 +582,8 @@ tlayer_ws_kernel(WsParams p) {
       for (int tt = 0; tt < TT; ++tt) xr[ot][tt] = xr[ot][tt] + cab;
     }
     layernorm(xr, sVec + 4 * DM, sVec + 5 * DM, 1);
-    WS_STAMP(3);
     put_act(xr, sAct);                      // (every wave has finished reading the attention image: two barriers ago)
     __syncthreads();
-    WS_STAMP(4);
 
     // ---- feed-forward in 4 hidden chunks of DM: hid = relu(W1_c x + b1_c) -> LDS -> y += W2[:, c] hid.  linear2 of chunk c and
     // linear1 of chunk c + 1 run back to back (no barrier between them): one 8-step pipelined sequence per chunk
@@ -651,7 +613,6 @@ tlayer_ws_kernel(WsParams p) {
         unit(std::integral_constant<int, (3 + 2 * c) * KB>{}, NO, YES, hid, sAct, nullptr);
         put_hidden(std::integral_constant<int, c + 1>{});
       }
-      WS_STAMP(5 + c);
     });
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
@@ -660,7 +621,6 @@ tlayer_ws_kernel(WsParams p) {
       for (int tt = 0; tt < TT; ++tt) xr[ot][tt] = xr[ot][tt] + (y[ot][tt] * p.inv_w2 + b2);
     }
     layernorm(xr, sVec + 7 * DM, sVec + 8 * DM, 0);
-    WS_STAMP(9);
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt)
       if (t0 + 16 * tt + ql < p.T) {
@@ -672,7 +632,6 @@ tlayer_ws_kernel(WsParams p) {
       put_act(xr, sAct);                    // (the last reader of the x1 image, linear1 of chunk 3, is two barriers back)
       __syncthreads();
     }
-    WS_STAMP(10);
   }
 
   if constexpr (QKV && ROWS) {
@@ -714,7 +673,6 @@ tlayer_ws_kernel(WsParams p) {
       zero(acc);
       if constexpr (which == 0) unit(std::integral_constant<int, POST_STEPS>{}, NO, NO, acc, sAct, sAct);
       else unit(std::integral_constant<int, POST_STEPS + KB>{}, NO, YES, acc, sAct, sAct);
-      WS_STAMP(11 + 2 * which);
       const float sc = which == 0 ? p.qscale : 1.0f;
       f32x4 bb[OT];
 #pragma unroll
@@ -740,7 +698,6 @@ tlayer_ws_kernel(WsParams p) {
           *reinterpret_cast<u32x4*>(dst + FRAG) = lo;
         }
       }
-      WS_STAMP(12 + 2 * which);
     });
     {
       f32x4 acc[OT][TT];                    // [dv tile][token tile]: column = dim 16 ot + ql, rows = tokens 16 tt + 4 g + r
@@ -766,7 +723,6 @@ tlayer_ws_kernel(WsParams p) {
       }
     }
   }
-  WS_STAMP(15);
 }
 
 // One fragment-pair chunk per workgroup: unit `blockIdx.x`, all of its [wave][kb][ot][plane] fragments.
@@ -803,7 +759,7 @@ int launch_ws(const WsParams& p, hipStream_t stream) {
   const size_t lds = ws_lds_bytes<DM>(POST, QKV);
   PATHS_LDS_OPT_IN((tlayer_ws_kernel<DM, POST, QKV, ROWS>), 160 * 1024, "token_layer_ws");
   // (> 80 KiB per workgroup: one workgroup per CU, so a grid of ~one workgroup per CU spreads over the whole chip)
-  const size_t ask = TT == 2 ? lds : (lds > 84 * 1024 ? lds : 84 * 1024);
+  const size_t ask = lds > 84 * 1024 ? lds : 84 * 1024;
   hipLaunchKernelGGL((tlayer_ws_kernel<DM, POST, QKV, ROWS>), dim3((p.T + TOK - 1) / TOK, p.B), dim3(64 * NW), ask, stream, p);
   PATHS_LAUNCH_CHECK("token_layer_ws");
   return PATHS_OK;
@@ -882,109 +838,7 @@ finish_importance_kernel(FinQkvParams f) {
   }
 }
 
-// ---- importance finish AND top-K in one launch (phase 8 of paths_importance_qkv_x6; reference model/paths.py:95 +
-// data_utils/slide.py:294-301).  The two were tiny latency-bound kernels back to back on the recursion's critical path (8 + 12 us
-// and two launch boundaries for ~0.3 us of arithmetic).  A workgroup owns 64 slots of one slide in both halves: it finishes their
-// alpha, publishes them (write-through stores, drained, then ONE release add on the slide's arrival counter), waits until the
-// slide's ceil(num_ims / 64) workgroups have arrived (bounded spin; the waited-for workgroups are part of this launch and small
-// enough - 20 KB of LDS - to be resident together even beside other kernels), then ranks its 64 elements against all scores of the
-// slide exactly as topk_rank_kernel (csrc/select.hip) does: 64-bit keys (score descending, index ascending), rank = number of
-// smaller keys, kept iff rank < count, output position = rank.  The last workgroup of a slide to leave zeroes its two counters.
-__device__ __forceinline__ unsigned long long fin_topk_key(float score, int idx) {
-  uint32_t u = __float_as_uint(score);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // monotone float -> uint
-  return ((unsigned long long)(~u) << 32) | (uint32_t)idx;
-}
-
-__global__ void __launch_bounds__(256)
-finish_importance_topk_kernel(FinQkvParams f, FinTopkParams k) {
-  extern __shared__ __attribute__((aligned(16))) char smem_tk[];
-  float* const sAlpha = reinterpret_cast<float*>(smem_tk);                                   // [2][TOK]
-  int* const part = reinterpret_cast<int*>(smem_tk + 2 * TOK * sizeof(float));              // [4][64] partial counts
-  int* const sFlag = part + 256;
-  unsigned long long* const keys = reinterpret_cast<unsigned long long*>(smem_tk + 2 * TOK * sizeof(float) + 260 * sizeof(int));   // (1552 bytes in: 16-byte aligned)
-  const int b = blockIdx.y, t0 = blockIdx.x * TOK;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = (int)f.num_ims[b];
-  const int count = k.keep < 0 ? n : min(n, k.keep);
-  const int i = t0 + lane;                              // this lane's element in the ranking
-  if (blockIdx.x == 0 && tid == 0) k.keep_count[b] = count;
-  auto row_addr = [&](int idx) { return (int64_t)reinterpret_cast<uintptr_t>(k.row_base + ((int64_t)b * f.N + idx) * k.row_ld); };
-  // entries [count, ldk) of the row table point at the zero row (every workgroup covers its own 64 positions)
-  if (k.kept_rows && wave == 0 && i >= count && i < k.ldk) k.kept_rows[(int64_t)b * k.ldk + i] = (int64_t)reinterpret_cast<uintptr_t>(k.zero_row);
-  if (t0 >= f.N || t0 >= n) return;                     // no valid slot here (workgroup-uniform; the importance buffer is zero there)
-  // ---- alpha of this tile
-  fin_alpha_partials(f, b, t0, tid, sAlpha);
-  __syncthreads();
-  if (tid < TOK) {
-    const int sl = t0 + tid;
-    if (sl < f.N) __hip_atomic_store(f.importance + (int64_t)b * f.N + sl, sl < n ? sigmoid_acc((sAlpha[tid] + sAlpha[TOK + tid]) + *f.b2) : 0.f,
-                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (k.keep < 0) {                                     // keep all, original order (slide.py:294 not taken): nothing to wait for
-    if (wave == 0 && i < n) {
-      k.keep_idx[(int64_t)b * k.ldk + i] = i;
-      if (k.kept_rows) k.kept_rows[(int64_t)b * k.ldk + i] = row_addr(i);
-    }
-    return;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // ---- arrival of the slide's workgroups
-  const int need = (n + TOK - 1) / TOK;
-  int* const cnt = k.counters + 2 * b;
-  if (tid == 0) {
-    __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    int spins = 0, ok = 1;
-    while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1 << 22)) {                        // give up loudly rather than hang: this slide's selection is garbage
-        if (k.status) atomicOr(k.status, 4);
-        ok = 0;
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    *sFlag = ok;
-  }
-  __syncthreads();
-  // ---- all n scores of the slide -> keys in LDS (agent-scope loads: other workgroups of this launch wrote them)
-  const int np = (n + 7) & ~7;
-  const float* s = f.importance + (int64_t)b * f.N;
-  for (int j = tid; j < np; j += 256) keys[j] = j < n ? fin_topk_key(__hip_atomic_load(s + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), j) : ~0ull;
-  __syncthreads();
-  const unsigned long long mine = i < n ? keys[i] : 0ull;
-  const int pairs = np >> 1, q0 = (pairs * wave) >> 2, q1 = (pairs * (wave + 1)) >> 2;
-  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-  const u64x2* kp = reinterpret_cast<const u64x2*>(keys);
-  int c = 0, q = q0;
-  for (; q + 4 <= q1; q += 4) {
-    const u64x2 a = kp[q], cc = kp[q + 1], d = kp[q + 2], e = kp[q + 3];
-    c += (a[0] < mine) + (a[1] < mine) + (cc[0] < mine) + (cc[1] < mine) + (d[0] < mine) + (d[1] < mine) + (e[0] < mine) + (e[1] < mine);
-  }
-  for (; q < q1; ++q) { const u64x2 a = kp[q]; c += (a[0] < mine) + (a[1] < mine); }
-  part[wave * 64 + lane] = c;
-  __syncthreads();
-  if (wave == 0 && i < n) {
-    const int rank = part[lane] + part[64 + lane] + part[128 + lane] + part[192 + lane];
-    if (rank < count) {
-      k.keep_idx[(int64_t)b * k.ldk + rank] = i;
-      if (k.kept_rows) k.kept_rows[(int64_t)b * k.ldk + rank] = row_addr(i);
-    }
-  }
-  // ---- the last workgroup of the slide to get here leaves the counters zero for the next launch
-  if (tid == 0 && __hip_atomic_fetch_add(cnt + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == need - 1) {
-    __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(cnt + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
 }  // namespace
-
-#ifdef PATHS_WS_STAMPS
-static unsigned long long* g_ws_stamps = nullptr;
-extern "C" void paths_ws_stamp_buffer(unsigned long long* p) { g_ws_stamps = p; }     // development hook (tools/ws_time.py)
-#endif
 
 // finish_qkv.h: phases bit 2 = the importance-only finish, bit 4 = tokens + in_proj images (alpha computed there unless
 // alpha_from_importance); both stop-event capable (the recursion's forks ride on them)
@@ -994,26 +848,13 @@ int paths_launch_finish_importance(const FinQkvParams& f, hipStream_t stream) {
   return PATHS_OK;
 }
 
-int paths_launch_finish_importance_topk(const FinQkvParams& f, const FinTopkParams& k, hipStream_t stream) {
-  const size_t lds = 2 * TOK * sizeof(float) + 260 * sizeof(int) + (size_t)(((f.N + 7) & ~7) + 2) * 8;
-  PATHS_LDS_OPT_IN(finish_importance_topk_kernel, 2 * TOK * sizeof(float) + 260 * sizeof(int) + (8192 + 2) * 8, "importance_qkv_x6(importance + top-K finish)");
-  // the grid covers every slot of the slide AND every position of the kept-row table (ldk <= N)
-  PATHS_LAUNCH_STOP(finish_importance_topk_kernel, dim3((f.N + TOK - 1) / TOK, f.B), dim3(256), lds, stream, f, k);
-  PATHS_LAUNCH_CHECK("importance_qkv_x6(importance + top-K finish)");
-  return PATHS_OK;
-}
-
 int paths_launch_finish_qkv(const FinQkvParams& f, hipStream_t stream) {
-  static_assert(TT == 4, "the fused finish owns 64-token tiles");
   WsParams p{};
   p.bqkv = f.bqkv; p.inv_wo = p.inv_w1 = p.inv_w2 = 1.0f; p.inv_wqkv = f.inv_wqkv;
   p.w_qkv = reinterpret_cast<const char*>(f.w_qkv);
   p.qkv_img = reinterpret_cast<char*>(f.qkv_img);
   p.num_ims = f.num_ims; p.T = f.T; p.Tp = f.Tp; p.B = f.B; p.skip_padding = f.skip_padding; p.qscale = f.qscale; p.eps = 0.f;
   p.fin = f;
-#ifdef PATHS_WS_STAMPS
-  p.stamps = g_ws_stamps;
-#endif
   const size_t lds = ws_lds_bytes<128>(false, true) + (size_t)(TOK * TOK_LD + 3 * TOK) * sizeof(float);
   PATHS_LDS_OPT_IN((tlayer_ws_kernel<128, false, true, false, true>), 160 * 1024, "importance_qkv_x6(finish)");
   // (> 80 KiB per workgroup: one workgroup per CU - a grid of ~one workgroup per CU spreads over the whole chip)
@@ -1081,11 +922,7 @@ int paths_token_layer_ws(const float* x_in, const float* attn, const void* attn_
   WsParams p{x_in, attn, reinterpret_cast<const char*>(attn_img), x_out, reinterpret_cast<const char*>(w_post), reinterpret_cast<const char*>(w_qkv),
              bo, ln1g, ln1b, cab, ln2g, ln2b, b1, b2, ln3g, ln3b, bqkv,
              do_post ? 1.0f / s_wo : 1.0f, do_post ? 1.0f / s_w1 : 1.0f, do_post ? 1.0f / s_w2 : 1.0f, do_qkv ? 1.0f / s_wqkv : 1.0f,
-             reinterpret_cast<char*>(qkv_images), nullptr, 0, num_ims, T, (T + 63) / 64 * 64, B, skip_padding, qscale, eps, zero_words, n_zero
-#ifdef PATHS_WS_STAMPS
-             , g_ws_stamps
-#endif
-  };
+             reinterpret_cast<char*>(qkv_images), nullptr, 0, num_ims, T, (T + 63) / 64 * 64, B, skip_padding, qscale, eps, zero_words, n_zero};
   if (d == 192) return do_qkv ? launch_ws<192, false, true>(p, stream) : launch_ws<192, true, false>(p, stream);
   if (do_post && do_qkv) return launch_ws<128, true, true>(p, stream);
   if (do_post) return launch_ws<128, true, false>(p, stream);
@@ -1111,11 +948,7 @@ int paths_token_layer_ws_rows(const float* x_in, const float* attn, float* x_out
   WsParams p{x_in, attn, nullptr, x_out, reinterpret_cast<const char*>(w_post), reinterpret_cast<const char*>(w_qkv),
              bo, ln1g, ln1b, cab, ln2g, ln2b, b1, b2, ln3g, ln3b, bqkv,
              do_post ? 1.0f / s_wo : 1.0f, do_post ? 1.0f / s_w1 : 1.0f, do_post ? 1.0f / s_w2 : 1.0f, do_qkv ? 1.0f / s_wqkv : 1.0f,
-             nullptr, qkv_rows, ld_qkv, num_ims, T, (T + 63) / 64 * 64, B, skip_padding, 1.0f, eps, nullptr, 0
-#ifdef PATHS_WS_STAMPS
-             , g_ws_stamps
-#endif
-  };
+             nullptr, qkv_rows, ld_qkv, num_ims, T, (T + 63) / 64 * 64, B, skip_padding, 1.0f, eps, nullptr, 0};
   if (do_post && do_qkv) return launch_ws<192, true, true, true>(p, stream);
   if (do_post) return launch_ws<192, true, false>(p, stream);
   return launch_ws<192, false, true, true>(p, stream);

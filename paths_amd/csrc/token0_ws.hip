@@ -36,11 +36,6 @@ constexpr int OFF_W2 = OFF_W1 + DFF * DM;                // [128 k4][128 f][4]
 constexpr int OFF_OB = OFF_W2 + DM * DFF;                // [128] Wo bv + bo  (distributed form: the bias of out_proj(attention output))
 constexpr int IMG_FLOATS = OFF_OB + DM;
 
-#ifdef PATHS_T0_STAMPS
-#define T0_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (p.stamps && tid == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = t_; } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define T0_STAMP(i) do { } while (0)
-#endif
 
 struct T0Params {
   const float* x1;                 // [B][T][128] input rows of the last layer
@@ -55,9 +50,6 @@ struct T0Params {
   int* status;                     // optional: bit 4 is set when a bounded hand-off wait of the distributed form gives up
   int T, nts; float eps, eps_f;
   int special_last;                // 0: the special token is row 0 (the reference's order); 1: it is row num_ims[b] (paths_importance_qkv_x6's order)
-#ifdef PATHS_T0_STAMPS
-  unsigned long long* stamps;
-#endif
 };
 
 // sum over the 16 lanes of a row (DPP: two quad permutes, two mirrors), over 32 (+ v_permlane16_swap) and over 64 lanes
@@ -111,7 +103,6 @@ token0_ws_kernel(T0Params p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* xb = p.x1 + (int64_t)b * p.T * DM;
 
-  T0_STAMP(0);
   // ---- phase 0: qt = A_head x0 + a0_head
   if (tid < DM) sX0[tid] = xb[(p.special_last ? (int64_t)min((int)p.num_ims[b], p.T - 1) * DM : 0) + tid];
   __syncthreads();
@@ -130,7 +121,6 @@ token0_ws_kernel(T0Params p) {
   if (tid < DM) sQ[tid] = ((sRed[tid] + sRed[DM + tid]) + (sRed[2 * DM + tid] + sRed[3 * DM + tid])) + p.img[OFF_A0 + head * DM + tid];
   __syncthreads();
 
-  T0_STAMP(1);
   // ---- phase 1: this workgroup's token range, one token per half-wave and iteration, 4 features per lane
   const int len = min((int)p.num_ims[b] + 1, p.T);
   const int chunk = (len + p.nts - 1) / p.nts;
@@ -168,7 +158,6 @@ token0_ws_kernel(T0Params p) {
     l = l * alpha + ps;
     m = mx;
   }
-  T0_STAMP(2);
   *reinterpret_cast<f32x4*>(sZ + slot * DM + 4 * l5) = z;
   if (l5 == 0) { sML[2 * slot] = m; sML[2 * slot + 1] = l; }
   __syncthreads();
@@ -205,7 +194,6 @@ token0_ws_kernel(T0Params p) {
     *sFlag = last;
   }
   __syncthreads();
-  T0_STAMP(3);
   if (*sFlag == 0) return;
 
   // ---- phase 2 (one workgroup per slide): the row chain of token 0.  All weight loads that do not depend on data go first.
@@ -244,7 +232,6 @@ token0_ws_kernel(T0Params p) {
     sZ[kq * DM + f] = num / den;
   }
   __syncthreads();
-  T0_STAMP(4);
   // o = Wv z_{head of row} + bv
   {
     const float* zc = sZ + (f >> 5) * DM + 32 * kq;
@@ -254,7 +241,6 @@ token0_ws_kernel(T0Params p) {
     sRed[kq * DM + f] = acc;
   }
   __syncthreads();
-  T0_STAMP(5);
   if (tid < DM) sO[tid] = ((sRed[tid] + sRed[DM + tid]) + (sRed[2 * DM + tid] + sRed[3 * DM + tid])) + p.bv[tid];
   __syncthreads();
   f32x4 w2[32];                                            // linear2: rows f, k quarter kq (128 k): first half issued while out_proj /
@@ -274,7 +260,6 @@ token0_ws_kernel(T0Params p) {
   if (tid < DM) sXa[tid] += p.cab[tid];
   __syncthreads();
   block_layernorm(sXa, p.ln2g, p.ln2b, p.eps, tid);
-  T0_STAMP(6);
   // h = relu(W1 x + b1): one hidden unit per thread
   {
     float acc = 0.f;
@@ -285,7 +270,6 @@ token0_ws_kernel(T0Params p) {
 #pragma unroll
   for (int i = 16; i < 32; ++i) w2[i] = ldg_f32x4(W + OFF_W2 + ((32 * kq + i) * DM + f) * 4);
   __syncthreads();
-  T0_STAMP(7);
   // y = W2 h + b2
   {
     float acc = 0.f;
@@ -296,7 +280,6 @@ token0_ws_kernel(T0Params p) {
   __syncthreads();
   if (tid < DM) sXa[tid] = sXa[tid] + (((sZ[tid] + sZ[DM + tid]) + (sZ[2 * DM + tid] + sZ[3 * DM + tid])) + p.b2[tid]);
   __syncthreads();
-  T0_STAMP(8);
   block_layernorm(sXa, p.ln3g, p.ln3b, p.eps, tid);
   // ---- decoder.norm, slide-context residual, classifier
   block_layernorm(sXa, p.lnfg, p.lnfb, p.eps_f, tid);
@@ -318,7 +301,6 @@ token0_ws_kernel(T0Params p) {
     acc = wave_sum64(acc);
     if (lane == 0) p.logits[(int64_t)b * p.num_logits + j] = acc + p.bcls[j];
   }
-  T0_STAMP(9);
 }
 
 
@@ -464,7 +446,6 @@ token0_dist_kernel(T0Params p) {
   };
   if (A_EARLY && k0 < k1) fetch(xa, k0);
 
-  T0_STAMP(0);
   // ---- phase 0: qt = A_head x0 + a0_head
   if (tid < DM) sX0[tid] = xb[(p.special_last ? (int64_t)min((int)p.num_ims[b], p.T - 1) * DM : 0) + tid];
   __syncthreads();
@@ -482,7 +463,6 @@ token0_dist_kernel(T0Params p) {
   if (tid < DM) sQ[tid] = ((sRed[tid] + sRed[DM + tid]) + (sRed[2 * DM + tid] + sRed[3 * DM + tid])) + W[OFF_A0 + head * DM + tid];
   __syncthreads();
 
-  T0_STAMP(1);
   // ---- phase 1: online softmax over this workgroup's tokens, z = sum p x; one token per half-wave and iteration, FPL features per lane
   float qv[FPL];
 #pragma unroll
@@ -528,7 +508,6 @@ token0_dist_kernel(T0Params p) {
   for (int e = 0; e < FPL; ++e) sZ[slot * DM + FPL * l5 + e] = z[e];
   if (l5 == 0) { sML[2 * slot] = m; sML[2 * slot + 1] = l; }
   __syncthreads();
-  T0_STAMP(2);
   float Mloc = -1e30f;
 #pragma unroll
   for (int sl = 0; sl < SLOTS; ++sl) Mloc = fmaxf(Mloc, sML[2 * sl]);
@@ -592,7 +571,6 @@ token0_dist_kernel(T0Params p) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   }
   __syncthreads();
-  T0_STAMP(3);
   {
     const int h = kq7;
     const float* hp = p.partials + (int64_t)b * G * REC;
@@ -623,7 +601,6 @@ token0_dist_kernel(T0Params p) {
   if (tid < DM) sXa[tid] += p.cab[tid];
   __syncthreads();
   block_layernorm_d<DM>(sXa, p.ln2g, p.ln2b, p.eps, tid);
-  T0_STAMP(4);
   // ---- feed-forward slice j: h = relu(W1[j HS .., :] x + b1), y_j = W2[:, j HS ..] h
   {
     float acc = 0.f;
@@ -657,7 +634,6 @@ token0_dist_kernel(T0Params p) {
   __syncthreads();
   if (tid == 0) *sFlag = (__hip_atomic_fetch_add(cnt + 2, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == G - 1) ? 1 : 0;
   __syncthreads();
-  T0_STAMP(5);
   if (*sFlag == 0) return;
   // ---- last arriver of ticket 2: x = norm3(x + sum_j y_j + b2), decoder.norm, slide-context residual, classifier
   if (tid == 0) {
@@ -695,7 +671,6 @@ token0_dist_kernel(T0Params p) {
     acc = wave_sum64(acc);
     if (lane == 0) p.logits[(int64_t)b * p.num_logits + jj] = acc + p.bcls[jj];
   }
-  T0_STAMP(9);
 }
 
 // ---- packing: A_h = c Wk_h^T Wq_h (fp32 FMA chains over the head dims), a0_h = c Wk_h^T bq_h, and the T4 transposes
@@ -742,11 +717,6 @@ token0_pack_kernel(const float* __restrict__ wqkv, const float* __restrict__ bqk
 
 }  // namespace
 
-#ifdef PATHS_T0_STAMPS
-static unsigned long long* g_t0_stamps = nullptr;
-extern "C" void paths_t0_stamp_buffer(unsigned long long* p) { g_t0_stamps = p; }     // development hook (tools/t0_time.py)
-#endif
-
 // token splits of the distributed form: the largest nts in {8, 4, 2, 1} (trans_dim 192: {4, 2} - a feed-forward slice must be a
 // multiple of 16 hidden units, and a thread holds at most 6 loads of it) with 128-token splits whose launch fits the chip with room
 // to spare - every workgroup of a slide spins on its siblings' arrival, so ALL of them must be resident at once: at most 3/4 of
@@ -762,13 +732,10 @@ static int dist_limit() {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(token0_dist_kernel<D_>), T0G<D_>::NT, 0) != hipSuccess || occ <= 0) return 0;
     cached[dev] = cus * (occ > 1 ? 1 : occ) * 3 / 4;      // (counted at ONE workgroup per CU: a second one there would share its memory queue)
-    if (getenv("PATHS_T0_DIST_LIMIT") != nullptr && atoi(getenv("PATHS_T0_DIST_LIMIT")) > 0) cached[dev] = atoi(getenv("PATHS_T0_DIST_LIMIT"));   // A/B runs
   }
   return cached[dev];
 }
 static int dist_splits(int B, int T, int d) {
-  static const bool off = getenv("PATHS_T0_DIST") != nullptr && atoi(getenv("PATHS_T0_DIST")) == 0;
-  if (off) return 0;
   const int limit = d == 192 ? dist_limit<192>() : dist_limit<128>();
   for (int nts = d == 192 ? 4 : 8; nts >= (d == 192 ? 2 : 1); nts >>= 1)
     if (NH * nts * B <= limit && (nts == 1 || (nts - 1) * TS_TOKENS < T)) return nts;
@@ -827,8 +794,7 @@ int paths_token0_pack_ws(const float* wqkv, const float* bqkv, const float* wo, 
 // counters: 3 B int32 words that are ZERO on entry (they are left zero: the last arrivers reset them); status (optional): an int32
 // word whose bit 4 is set if a bounded hand-off wait of the distributed form gave up (never observed; the result is then invalid).
 // Two forms, same results to fp32 rounding: up to 192 workgroups in the launch -> the DISTRIBUTED form (every workgroup of a slide
-// carries a slice of the row chain's weights); larger batches -> one row-chain workgroup per slide (PATHS_T0_DIST=0 forces it;
-// trans_dim 128 only: at 192 check paths_token0_ws_supported first).
+// carries a slice of the row chain's weights); larger batches -> one row-chain workgroup per slide (trans_dim 128 only: at 192 check paths_token0_ws_supported first).
 int paths_token0_tail_ws(const float* x1, const int64_t* num_ims, const void* img, const float* bv, const float* bo,
                          const float* ln1g, const float* ln1b, const float* cab, const float* ln2g, const float* ln2b,
                          const float* b1, const float* b2, const float* ln3g, const float* ln3b, const float* lnfg, const float* lnfb,
@@ -847,11 +813,7 @@ int paths_token0_tail_ws(const float* x1, const int64_t* num_ims, const void* im
     return paths_set_error(PATHS_EUNSUPPORTED, "token0_tail_ws: trans_dim %d has the distributed form only and %d slides do not fit it (paths_token0_ws_supported)", d, B);
   const int nts = nd ? nd : chain_splits(T);
   T0Params p{x1, num_ims, reinterpret_cast<const float*>(img), bv, bo, ln1g, ln1b, cab, ln2g, ln2b, b1, b2, ln3g, ln3b, lnfg, lnfb,
-             ctx_prev, ctx_stride, ctx_all, ctx_depth, wcls, bcls, num_logits, cls_in, ctx_out, logits, partials, counters, status, T, nts, eps, eps_final, special_last ? 1 : 0
-#ifdef PATHS_T0_STAMPS
-             , g_t0_stamps
-#endif
-  };
+             ctx_prev, ctx_stride, ctx_all, ctx_depth, wcls, bcls, num_logits, cls_in, ctx_out, logits, partials, counters, status, T, nts, eps, eps_final, special_last ? 1 : 0};
   if (nd && d == 192) hipLaunchKernelGGL(token0_dist_kernel<192>, dim3(NH * nts, B), dim3(T0G<192>::NT), 0, stream, p);
   else if (nd) hipLaunchKernelGGL(token0_dist_kernel<128>, dim3(NH * nts, B), dim3(NT), 0, stream, p);
   else hipLaunchKernelGGL(token0_ws_kernel, dim3(NH * nts, B), dim3(NT), 0, stream, p);

@@ -21,7 +21,7 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(paths_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_3():
     from paths_amd import _lib
     if not os.path.isfile(_lib.LIB_PATH):
         import __graft_entry__
@@ -38,7 +38,7 @@ def test_library_exports_every_declared_symbol():
         assert m, name
         assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
     lib.paths_abi_version.restype = ctypes.c_int
-    assert lib.paths_abi_version() == 2
+    assert lib.paths_abi_version() == 3
 
 
 def test_invalid_arguments_are_reported_not_launched():

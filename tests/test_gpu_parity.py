@@ -1577,7 +1577,7 @@ def test_fused_importance_qkv_finish_equals_the_separate_launches(dev, monkeypat
     np.testing.assert_allclose(outs[1]["importance"].numpy(), g["importance"], atol=STATE_TOL, rtol=0)
 
 
-def test_fused_importance_qkv_finish_in_the_recursion(dev, monkeypatch):
+def test_fused_importance_qkv_finish_modes_in_the_recursion(dev, monkeypatch):
     """The same equality through the device recursion (row-pointer GEMM operands, skipped padding tiles, the aggregator on its own
     stream, launch tape): 4 slides x 5 levels at K = 256, every level's importance / kept indices identical in the three modes,
     logits to rounding; eager == replayed bit for bit."""
@@ -1588,15 +1588,13 @@ def test_fused_importance_qkv_finish_in_the_recursion(dev, monkeypatch):
     cfg, model, _ = build_model(dev, 3, top_k_patches=[64] * 4)
     slides = [DeviceSlide.synthetic(14, s, (16, 16), device=dev) for s in range(4)]
     res = {}
-    for mode in (0, 1, 2, 3):
-        # (3 = mode 2 WITHOUT the top-K inside the importance finish: paths_importance_qkv_x6 phase 2 + paths_topk_rows instead of phase 8)
-        monkeypatch.setattr(ops, "FUSE_QKV", min(mode, 2))
-        monkeypatch.setattr(ops, "FUSE_TOPK", mode != 3)
+    for mode in (0, 1, 2):
+        monkeypatch.setattr(ops, "FUSE_QKV", mode)
         tr = []
         with torch.no_grad():
             with H.spy_calls() as calls:
                 out = putils.recurse(model, slides, cfg.top_k_patches, 5, trace=tr)
-            assert ("paths_topk_rows" in calls) == (mode != 2), (mode, sorted(set(calls)))
+            assert "paths_topk_rows" in calls, (mode, sorted(set(calls)))
             tape = putils.TapedRecursion(model, slides, cfg.top_k_patches, 5).record()
             rep = {k: v.clone() for k, v in tape.replay().items()}
             rep2 = {k: v.clone() for k, v in tape.replay().items()}
@@ -1604,7 +1602,7 @@ def test_fused_importance_qkv_finish_in_the_recursion(dev, monkeypatch):
         torch.cuda.synchronize()
         assert torch.equal(rep["logits"], out["logits"]) and torch.equal(rep2["logits"], out["logits"]), mode
         res[mode] = (out["logits"].clone(), [(lv["importance"].clone(), lv["logits"].clone(), lv.get("keep_idx")) for lv in tr])
-    for mode in (1, 2, 3):
+    for mode in (1, 2):
         assert float((res[mode][0] - res[0][0]).abs().max()) < 2e-6 and torch.equal(res[mode][0], res[1][0]), mode
         for l, ((ia, la, ka), (ib, lb, kb)) in enumerate(zip(res[mode][1], res[0][1])):
             # selection chain: bit-identical (the slide context it does NOT depend on differs in the last bits: special token last)

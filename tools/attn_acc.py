@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Accuracy of paths_attention_x6 (planes = 2) against an fp64 softmax(q k^T) v on uniform and on peaked score distributions.
-PATHS_HIP_LIB selects the library (attention variants: tools/mkvariant.sh)."""
+PATHS_HIP_LIB selects the library."""
 import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

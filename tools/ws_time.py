@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Time paths_token_layer_ws at the bench shape (qkv only / post only / post + qkv); with a PATHS_WS_STAMPS build also print the
-in-kernel phase stamps (median over workgroups).  PATHS_HIP_LIB selects the library."""
-import ctypes, math, os, sys
+"""Time paths_token_layer_ws at the bench shape (qkv only / post only / post + qkv).  PATHS_HIP_LIB selects the library."""
+import math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
@@ -21,12 +20,6 @@ aimg = (torch.randn(B * Tp * d * 2, device=dev, generator=g) * 0.5).half().view(
 ws = torch.empty(int(_lib.load().paths_attention_x6_workspace(B, T, H, hd, 2)), device=dev, dtype=torch.uint8)
 num_ims = torch.tensor(([1844, 1850, 1839, 1861, 1822, 1847, 1855, 1830] * 8)[:B], device=dev)
 p, st = _lib.ptr, _lib.stream()
-lib = _lib.load()
-stamps = None
-if hasattr(lib, "paths_ws_stamp_buffer"):
-    stamps = torch.zeros(((T + 63) // 64 * B, 16), device=dev, dtype=torch.int64)
-    lib.paths_ws_stamp_buffer.argtypes = [ctypes.c_void_p]
-    lib.paths_ws_stamp_buffer(stamps.data_ptr())
 def run(post, qkv):
     _lib.call("paths_token_layer_ws", p(x), None, p(aimg) if post else None, p(xo) if post else None, p(ip) if post else None, p(iq) if qkv else None,
               p(vec["bo"]), p(gam["ln1g"]), p(vec["ln1b"]), p(vec["cab"]), p(gam["ln2g"]), p(vec["ln2b"]), p(vec["b1"]), p(vec["b2"]),
@@ -39,20 +32,6 @@ for post, qkv in ((0, 1), (1, 0), (1, 1)):
     for _ in range(50): run(post, qkv)
     e1.record(); torch.cuda.synchronize()
     print(f"{os.environ.get('PATHS_HIP_LIB', 'default')}: post={post} qkv={qkv}: {e0.elapsed_time(e1) * 1e3 / 50:.1f} us", flush=True)
-    if stamps is not None:
-        stamps.zero_(); run(post, qkv); torch.cuda.synchronize()
-        s = stamps.cpu()
-        act = s[:, 0] > 0
-        s = s[act]
-        rel = (s - s[:, :1]).float()
-        names = ["start", "prologue", "out_proj", "ln1+ln2", "put x1", "ffn0", "ffn1", "ffn2", "ffn3", "ln3", "x_out/put", "q mm", "q st", "k mm", "k st", "end"]
-        med = rel.median(dim=0).values
-        print("   workgroups", int(act.sum()), "start spread (cycles)", int(s[:, 0].max() - s[:, 0].min()), "end spread", int(s[:, 15].max() - s[:, 15].min()))
-        prev = 0.0
-        for i, n in enumerate(names):
-            if s[:, i].max() > 0:
-                print(f"   {n:10s} at {med[i]:9.0f}  (+{med[i] - prev:7.0f})")
-                prev = float(med[i])
 
 # ---- kernel-level comparison against paths_token_layer_h3 on the same random layer
 if "--check" in sys.argv:
