@@ -292,6 +292,17 @@ int paths_attention_token0_fwd(const float* q, const float* k, const float* v, c
 int paths_attention_token0_bwd(const float* q, const float* k, const float* v, const float* a0, const float* da0, const float* lse0,
                                const int64_t* num_ims, float* dqkv, float* ws, int B, int T, int H, int head_dim, uint64_t drop_key,
                                float drop_p, paths_stream_t stream);
+/* Export of the special token's attention (interpretability side path, csrc/attn_token0.hip; what nn.MultiheadAttention returns
+ * with need_weights=True, row of the special token): for one decoder layer with input rows x [B, T, d] and its TRUE in_proj_weight
+ * [3d, d] / in_proj_bias [3d], per slide b and head h the softmax of q_h . k_t / sqrt(d/H) over the valid tokens t < num_ims[b] + 1
+ * (num_ims clamped to [0, T-1]; padding rows are never read).  attn_patch[b*patch_ld + h*(T-1) + j] = weight of patch j (exactly 0
+ * for j >= num_ims[b]), attn_self[b*self_ld + h] = weight of the special token on itself.  special_last = 0: special token at row 0,
+ * patch j at row j + 1 (the reference's order); 1: patch j at row j, special token at row num_ims[b] (paths_importance_qkv_x6's
+ * order).  Any d % H == 0 with d % 4 == 0, d <= 2048.  fp32, deterministic.  ws: paths_token0_attention_workspace(B, T, d, H) floats. */
+int64_t paths_token0_attention_workspace(int B, int T, int d, int H);
+int paths_token0_attention(const float* x, const int64_t* num_ims, const float* in_proj_weight, const float* in_proj_bias, float* attn_patch,
+                           int64_t patch_ld, float* attn_self, int64_t self_ld, float* ws, int B, int T, int d, int H, int special_last,
+                           paths_stream_t stream);
 
 /* Generic out = act(a W^T + b) on the fp32 matrix cores (W rows zero-padded to Npad, a multiple of 128). */
 int paths_linear_f32(const float* a, int64_t lda, const float* w, const float* b, float* out, int64_t ldo,

@@ -368,3 +368,206 @@ int paths_attention_token0_bwd(const float* q, const float* k, const float* v, c
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Export of the special token's attention probabilities (inference side path, not on the default launch sequence): for one decoder
+// layer, per (slide, head), the softmax row of the special token over the valid tokens, from the layer's INPUT rows x and its true
+// in_proj (the algebra of csrc/token0_ws.hip, fp32, no operand split):
+//   q_h = Wq_h x_s + bq_h,   qt_h = Wk_h^T q_h / sqrt(hd),   p_t = softmax_t(qt_h . x_t)   over t < num_ims[b] + 1
+// (q_h . bk_h is constant over t and cancels).  Valid rows are t in [0, n] in both token orders (n = num_ims[b] clamped to [0, T-1]);
+// rows beyond are never read.  Three launches, no wait between workgroups, fixed-order merges (bit-identical reruns):
+//   query   grid (H, B)       qt_h -> workspace
+//   scores  grid (S, H, B)    raw scores of the split's rows -> the output slots, split (m, l) -> workspace
+//   norm    grid (S2, H, B)   merge the S splits in a fixed order, rewrite exp(s - M) / L; padding patches get exactly 0
+namespace {
+
+constexpr int XA_THREADS = 256;
+constexpr int XA_WAVES = XA_THREADS / 64;
+constexpr int XA_SPLITS_MAX = 64;
+constexpr int XA_D_MAX = 2048;
+constexpr int XA_UNROLL = 4;          // row steps of a wave whose loads are issued together
+
+__device__ __forceinline__ void xa_merge(float& m, float& l, float m2, float l2) {
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;                     // both empty
+  l = (m == -INFINITY ? 0.f : l * expf(m - M)) + (m2 == -INFINITY ? 0.f : l2 * expf(m2 - M));
+  m = M;
+}
+
+__device__ __forceinline__ int xa_valid_last(const int64_t* num_ims, int b, int T) {
+  const int64_t n = num_ims[b];
+  return (int)(n < 0 ? 0 : (n > T - 1 ? T - 1 : n));
+}
+
+// qt [B][H][d]: workgroup (head, slide)
+__global__ void __launch_bounds__(XA_THREADS)
+token0_attention_query_kernel(const float* __restrict__ x, const int64_t* __restrict__ num_ims, const float* __restrict__ w_in,
+                              const float* __restrict__ b_in, float* __restrict__ qt, int T, int d, int H, int special_last, float scale) {
+  __shared__ f32x4 sx[XA_D_MAX / 4];
+  __shared__ float sq[XA_D_MAX];
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hd = d / H, d4 = d / 4;
+  const int n = xa_valid_last(num_ims, b, T);
+  const f32x4* xs = reinterpret_cast<const f32x4*>(x + ((int64_t)b * T + (special_last ? n : 0)) * d);
+  for (int i = tid; i < d4; i += XA_THREADS) sx[i] = xs[i];
+  __syncthreads();
+  for (int r = wave; r < hd; r += XA_WAVES) {           // q_h[r] = Wq[h hd + r] . x_s + bq[h hd + r]
+    const f32x4* w = reinterpret_cast<const f32x4*>(w_in + (int64_t)(h * hd + r) * d);
+    float a = 0.f;
+    for (int c4 = lane; c4 < d4; c4 += 64) {
+      const f32x4 wv = w[c4], xv = sx[c4];
+      a = fmaf(wv[0], xv[0], a); a = fmaf(wv[1], xv[1], a); a = fmaf(wv[2], xv[2], a); a = fmaf(wv[3], xv[3], a);
+    }
+    a = wave_sum(a);
+    if (lane == 0) sq[r] = a + b_in[h * hd + r];
+  }
+  __syncthreads();
+  const float* wk = w_in + (int64_t)(d + h * hd) * d;    // Wk_h rows: qt[c] = scale sum_r Wk_h[r][c] q_h[r] (coalesced over c)
+  float* dst = qt + ((int64_t)b * H + h) * d;
+  for (int c = tid; c < d; c += XA_THREADS) {
+    float a = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < hd; ++r) a = fmaf(wk[(int64_t)r * d + c], sq[r], a);
+    dst[c] = a * scale;
+  }
+}
+
+// raw scores + split statistics: workgroup (split, head, slide); a row is scored by `lpr` lanes (16-byte loads), 64 / lpr rows per
+// wave step, XA_UNROLL steps in flight
+__global__ void __launch_bounds__(XA_THREADS)
+token0_attention_score_kernel(const float* __restrict__ x, const int64_t* __restrict__ num_ims, const float* __restrict__ qt,
+                              float* __restrict__ attn_patch, int64_t patch_ld, float* __restrict__ attn_self, int64_t self_ld,
+                              float* __restrict__ stats, int T, int d, int H, int special_last, int S, int lpr) {
+  __shared__ f32x4 sqt[XA_D_MAX / 4];
+  __shared__ float sm[XA_WAVES], sl[XA_WAVES];
+  const int part = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d4 = d / 4, N = T - 1;
+  const int n = xa_valid_last(num_ims, b, T);
+  const int chunk = (T + S - 1) / S;
+  const int t0 = min(n + 1, part * chunk), t1 = min(n + 1, t0 + chunk);
+  const f32x4* q4 = reinterpret_cast<const f32x4*>(qt + ((int64_t)b * H + h) * d);
+  for (int i = tid; i < d4; i += XA_THREADS) sqt[i] = q4[i];
+  __syncthreads();
+  const int rpw = 64 / lpr, sub = lane / lpr, sll = lane % lpr;
+  const f32x4* xb = reinterpret_cast<const f32x4*>(x + (int64_t)b * T * d);
+  float* patch = attn_patch + (int64_t)b * patch_ld + (int64_t)h * N;
+  float m = -INFINITY, l = 0.f;
+  for (int base = t0 + wave * rpw; base < t1; base += XA_WAVES * rpw * XA_UNROLL) {
+    float a[XA_UNROLL];
+#pragma unroll
+    for (int u = 0; u < XA_UNROLL; ++u) a[u] = 0.f;
+    for (int c4 = sll; c4 < d4; c4 += lpr) {
+      const f32x4 qv = sqt[c4];
+#pragma unroll
+      for (int u = 0; u < XA_UNROLL; ++u) {
+        const int t = base + u * XA_WAVES * rpw + sub;
+        if (t < t1) {                                      // (rows >= n + 1 are padding: never read)
+          const f32x4 xv = xb[(int64_t)t * d4 + c4];
+          a[u] = fmaf(xv[0], qv[0], a[u]); a[u] = fmaf(xv[1], qv[1], a[u]); a[u] = fmaf(xv[2], qv[2], a[u]); a[u] = fmaf(xv[3], qv[3], a[u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < XA_UNROLL; ++u) {
+      float s = a[u];
+      for (int o = 1; o < lpr; o <<= 1) s += __shfl_xor(s, o);
+      const int t = base + u * XA_WAVES * rpw + sub;
+      if (t < t1 && sll == 0) {
+        const bool self = special_last ? t == n : t == 0;
+        if (self) attn_self[(int64_t)b * self_ld + h] = s;
+        else patch[special_last ? t : t - 1] = s;
+        xa_merge(m, l, s, 1.f);
+      }
+    }
+  }
+  for (int o = 1; o < 64; o <<= 1) {                     // (lanes without rows hold the neutral (-inf, 0))
+    const float m2 = __shfl_xor(m, o), l2 = __shfl_xor(l, o);
+    xa_merge(m, l, m2, l2);
+  }
+  if (lane == 0) { sm[wave] = m; sl[wave] = l; }
+  __syncthreads();
+  if (tid == 0) {
+    float M = sm[0], Lw = sl[0];
+    for (int w = 1; w < XA_WAVES; ++w) xa_merge(M, Lw, sm[w], sl[w]);
+    float* st = stats + (((int64_t)b * H + h) * S + part) * 2;
+    st[0] = M;
+    st[1] = Lw;
+  }
+}
+
+// probabilities: workgroup (part, head, slide), patches j = part * 256 + tid, stride S2 * 256
+__global__ void __launch_bounds__(XA_THREADS)
+token0_attention_norm_kernel(const int64_t* __restrict__ num_ims, float* __restrict__ attn_patch, int64_t patch_ld,
+                             float* __restrict__ attn_self, int64_t self_ld, const float* __restrict__ stats, int T, int H, int S) {
+  __shared__ float sml[2];
+  const int part = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int N = T - 1;
+  const int n = xa_valid_last(num_ims, b, T);
+  if (tid < 64) {                            // lane s holds split s (S <= 64); a fixed butterfly, lane 0's result is shared
+    const float* st = stats + ((int64_t)b * H + h) * S * 2;
+    float m = -INFINITY, l = 0.f;
+    if (tid < S) { m = st[2 * tid]; l = st[2 * tid + 1]; }
+    for (int o = 1; o < 64; o <<= 1) {
+      const float m2 = __shfl_xor(m, o), l2 = __shfl_xor(l, o);
+      xa_merge(m, l, m2, l2);
+    }
+    if (tid == 0) { sml[0] = m; sml[1] = l; }
+  }
+  __syncthreads();
+  const float M = sml[0], Lsum = sml[1];
+  float* patch = attn_patch + (int64_t)b * patch_ld + (int64_t)h * N;
+  for (int j = part * XA_THREADS + tid; j < N; j += gridDim.x * XA_THREADS) patch[j] = j < n ? expf(patch[j] - M) / Lsum : 0.f;
+  if (part == 0 && tid == 0) {
+    float* self = attn_self + (int64_t)b * self_ld + h;
+    *self = expf(*self - M) / Lsum;
+  }
+}
+
+int xa_splits(int B, int T, int H) {
+  int S = 1;
+  while (S < XA_SPLITS_MAX && (int64_t)B * H * S < 1024 && (T + 2 * S - 1) / (2 * S) >= 64) S *= 2;
+  return S;
+}
+
+}  // namespace
+
+extern "C" {
+
+// floats of scratch for paths_token0_attention: qt [B][H][d] + per-split (m, l)
+int64_t paths_token0_attention_workspace(int B, int T, int d, int H) {
+  (void)T;
+  if (B <= 0 || d <= 0 || H <= 0) return 0;
+  return (int64_t)B * H * (d + 2 * XA_SPLITS_MAX);
+}
+
+// attn_patch[b * patch_ld + h * (T-1) + j] (patch j, 0 for j >= num_ims[b]) and attn_self[b * self_ld + h] = the special token's
+// softmax row of one decoder layer with input rows x [B, T, d] and in_proj w_in [3d, d], b_in [3d] (unpadded, the module's own);
+// special_last: 0 = special token at row 0, patch j at row j + 1; 1 = patch j at row j, special token at row num_ims[b]
+int paths_token0_attention(const float* x, const int64_t* num_ims, const float* w_in, const float* b_in, float* attn_patch, int64_t patch_ld,
+                           float* attn_self, int64_t self_ld, float* ws, int B, int T, int d, int H, int special_last, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && T > 0, "token0_attention: B = %d and T = %d must be positive", B, T);
+  PATHS_REQUIRE(H > 0 && d > 0 && d % H == 0, "token0_attention: d %% H must be 0 (d = %d, H = %d)", d, H);
+  PATHS_REQUIRE(d <= XA_D_MAX && d % 4 == 0, "token0_attention: d = %d must be a multiple of 4 and d <= %d", d, XA_D_MAX);
+  PATHS_REQUIRE(special_last == 0 || special_last == 1, "token0_attention: special_last must be 0 or 1 (got %d)", special_last);
+  PATHS_REQUIRE(x && num_ims && w_in && b_in && attn_self && ws && (attn_patch || T == 1), "token0_attention: null pointer");
+  PATHS_REQUIRE(((uintptr_t)x | (uintptr_t)w_in | (uintptr_t)ws) % 16 == 0, "token0_attention: x, w_in and ws must be 16-byte aligned");
+  PATHS_REQUIRE(patch_ld >= (int64_t)H * (T - 1) && self_ld >= H, "token0_attention: output strides too small");
+  const int S = xa_splits(B, T, H);
+  int lpr = 1;
+  while (lpr < d / 4 && lpr < 64) lpr *= 2;
+  float* qt = ws;
+  float* stats = ws + (int64_t)B * H * d;
+  const float scale = (float)(1.0 / sqrt((double)(d / H)));
+  hipLaunchKernelGGL(token0_attention_query_kernel, dim3(H, B), dim3(XA_THREADS), 0, stream, x, num_ims, w_in, b_in, qt, T, d, H, special_last, scale);
+  PATHS_LAUNCH_CHECK("token0_attention(query)");
+  hipLaunchKernelGGL(token0_attention_score_kernel, dim3(S, H, B), dim3(XA_THREADS), 0, stream, x, num_ims, qt, attn_patch, patch_ld, attn_self,
+                     self_ld, stats, T, d, H, special_last, S, lpr);
+  PATHS_LAUNCH_CHECK("token0_attention(scores)");
+  const int S2 = std::min(16, std::max(1, (T - 1 + XA_THREADS - 1) / XA_THREADS));
+  hipLaunchKernelGGL(token0_attention_norm_kernel, dim3(S2, H, B), dim3(XA_THREADS), 0, stream, num_ims, attn_patch, patch_ld, attn_self, self_ld,
+                     stats, T, H, S);
+  PATHS_LAUNCH_CHECK("token0_attention(norm)");
+  return PATHS_OK;
+}
+
+}  // extern "C"

@@ -1,14 +1,17 @@
-"""Importance heat-map export (the data consumed by reference heatmap_visualise.py:113-175; drawing is out of scope).
+"""Heat-map export (the data consumed by reference heatmap_visualise.py:113-175; drawing is out of scope).
 
-``hierarchy_from_trace`` pulls one slide's per-level patch locations / importances / selected indices out of the trace
-of :func:`paths_amd.utils.recurse`; ``importance_map`` rasterises them exactly like the reference's overlay code:
-every patch of depth d paints ``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with
-weight 1/2 wherever they exist (heatmap_visualise.py:147-171).  The raster is in units of the FINEST level's patches
-(one cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
+``hierarchy_from_trace`` pulls one slide's per-level patch locations / importances / selected indices (and, from a
+``recurse(..., attention=True)`` trace, the special token's attention) out of the trace of :func:`paths_amd.utils.recurse`.
+
+``importance_map`` rasterises the importances exactly like the reference's overlay code: every patch of depth d paints
+``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with weight 1/2 wherever they exist
+(heatmap_visualise.py:147-171).  ``attention_map`` rasterises the special token's attention of one decoder layer (one head or
+the mean over heads), one raster per level and no fold across levels.  Rasters are in units of the FINEST level's patches (one
+cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -21,8 +24,18 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
              "parent_inds": lv["parent_inds"][slide, :n].cpu().numpy()}
         if "keep_idx" in lv:
             d["keep_inds"] = lv["keep_idx"][slide, : int(lv["keep_count"][slide])].cpu().numpy()
+        if "attention" in lv:
+            d["attention"] = lv["attention"][slide, :, :, :n].cpu().numpy()          # [L, H, n]
+            d["attention_self"] = lv["attention_self"][slide].cpu().numpy()          # [L, H]
         out.append(d)
     return out
+
+
+def _paint(dst: np.ndarray, locs: np.ndarray, values, size: int, patch_size: int, offset: float = 0.0):
+    """dst[footprint of patch i] = values[i] + offset; a footprint is size x size finest cells."""
+    cells = locs // patch_size
+    for (cx, cy), v in zip(cells, values):
+        dst[cx * size:(cx + 1) * size, cy * size:(cy + 1) * size] = v + offset
 
 
 def importance_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: int = 256, magnification_factor: int = 2) -> np.ndarray:
@@ -33,10 +46,28 @@ def importance_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: i
     overall = np.zeros((L,) + shape, dtype=np.float64)
     for depth, lv in enumerate(levels):
         size = magnification_factor ** (L - 1 - depth)                       # footprint of one patch, in finest cells
-        cells = lv["locs"] // patch_size
-        for (cx, cy), imp in zip(cells, lv["importance"]):
-            overall[depth, cx * size:(cx + 1) * size, cy * size:(cy + 1) * size] = imp + 1e-4
+        _paint(overall[depth], lv["locs"], lv["importance"], size, patch_size, 1e-4)
     for depth in range(L - 2, -1, -1):                                        # heatmap_visualise.py:167-169
         m = overall[depth + 1] != 0
         overall[depth][m] = overall[depth][m] + overall[depth + 1][m] * 0.5
     return overall[0]
+
+
+def attention_map(levels: List[Dict[str, np.ndarray]], base_grid, layer: int = -1, head: Optional[int] = None, patch_size: int = 256,
+                  magnification_factor: int = 2) -> List[np.ndarray]:
+    """One [X0 * f, Y0 * f] float map per level (f = magnification_factor**(L-1)): the special token's attention on each patch of
+    decoder layer ``layer``, head ``head`` (None: the mean over heads), painted over the patch's footprint; 0 where the level did
+    not visit.  ``levels`` from :func:`hierarchy_from_trace` of a ``recurse(..., attention=True)`` trace."""
+    L = len(levels)
+    f = magnification_factor ** (L - 1)
+    shape = (base_grid[0] * f, base_grid[1] * f)
+    maps = []
+    for depth, lv in enumerate(levels):
+        if "attention" not in lv:
+            raise KeyError("level %d carries no attention: run recurse(..., attention=True)" % depth)
+        a = lv["attention"][layer]                                            # [H, n]
+        w = a.mean(axis=0, dtype=np.float64) if head is None else a[head]
+        raster = np.zeros(shape, dtype=np.float64)
+        _paint(raster, lv["locs"], w, magnification_factor ** (L - 1 - depth), patch_size)
+        maps.append(raster)
+    return maps

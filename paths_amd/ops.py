@@ -396,6 +396,7 @@ def _pack_decoder_layers(agg) -> List[Dict[str, object]]:
             "w2": c(lyr.linear2.weight), "b2": c(lyr.linear2.bias),
             "eps": float(lyr.norm1.eps),
         })
+        layers[-1]["w_in"], layers[-1]["b_in"] = layers[-1]["wqkv"], layers[-1]["bqkv"]     # the true in_proj (attention export)
         if pad is not None:
             row, col, di = pad
             lay = layers[-1]
@@ -677,7 +678,8 @@ def fp8_supported(mc) -> bool:
     return d % 128 == 0 and d % H == 0 and (d // H) in FP8_HEAD_DIMS      # paths_gemm_nt_fp8 needs K % 128 == 0 (one 64-k instruction pair per stage)
 
 
-def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8: bool = False, status=None) -> Dict[str, torch.Tensor]:
+def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8: bool = False, status=None,
+                                attention=None) -> Dict[str, torch.Tensor]:
     """The aggregator for any (trans_dim, heads): generic GEMMs + csrc/generic.hip (reference model/aggregator.py:58-76 with torch's
     post-LN decoder layers, model/paths.py:130-139).  The last layer is evaluated at token 0 only (its other rows are never read).
     ``fp8`` (ops.AGG_FP8, the BASELINE configs[4] stress variant, NOT a parity path): the products over all tokens - in_proj, the full
@@ -723,6 +725,8 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
     for l in range(L):
         lay, gl = lvl_pack["layers"][l], gp["layers"][l]
         last = l == L - 1
+        if attention is not None:                 # (x: this layer's input rows [B*T, d], special token first)
+            _export_attention(attention, lvl_pack, l, x, num_ims, H, 0)
         big = fp8 and not last            # products over all tokens of a full layer
 
         def gemm(a, lda, key, bias, out, ldo, m, n, kdim, act=0, residual=None, ldr=0, low=False):
@@ -810,6 +814,8 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
     if tail192:
         # x: the last layer's input rows [B, T, d] (special token first: the reference's order)
         w = lvl_pack["layers"][L - 1]
+        if attention is not None:                 # (the loop left with `break` before the last layer's iteration)
+            _export_attention(attention, lvl_pack, L - 1, x, num_ims, H, 0)
         img = token0_ws_image(w, qscale)
         part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), **f32)
         cnt = token0_counters(dev, B)
@@ -833,18 +839,28 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
 # ---------------------------------------------------------------------------------------------
 def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor, num_ims: torch.Tensor,
                   state_prev: Optional[torch.Tensor], ctx_prev: Optional[torch.Tensor], ctx_all: Optional[torch.Tensor],
-                  skip_padding: bool) -> Dict[str, torch.Tensor]:
+                  skip_padding: bool, return_attention: bool = False) -> Dict[str, torch.Tensor]:
     """fts [B,N,D] fp32 contiguous; locs [B,N,2] int64; num_ims [B] int64;
     state_prev: [B,N,>=D+Hc] view whose last dim holds (h|c) of the previous level (row stride arbitrary) or None;
-    ctx_prev [B,d] (residual source) or None; ctx_all [B,depth,d] contiguous (concat mode) or None."""
+    ctx_prev [B,d] (residual source) or None; ctx_all [B,depth,d] contiguous (concat mode) or None.
+    ``return_attention``: the result also carries "attention" [B, L, H, N] and "attention_self" [B, L, H], the special token's attention
+    per decoder layer and head (see :func:`aggregator_forward`)."""
     sel = selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, skip_padding)
     status = torch.zeros((1,), device=fts.device, dtype=torch.int32)
-    agg = aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel)
+    attention = None
+    if return_attention:
+        B, N = locs.shape[:2]
+        f32 = dict(device=fts.device, dtype=torch.float32)
+        attention = (torch.empty((B, mc.trans_layers, mc.trans_heads, N), **f32), torch.empty((B, mc.trans_layers, mc.trans_heads), **f32))
+    agg = aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=attention)
     # the drop-in call is synchronous anyway (the range guard above it syncs): a token-0 tail whose bounded hand-off wait gave up
     # (status bit 2, csrc/token0_ws.hip) must not hand back its logits
     if int(status.item()) & 4:
         raise _lib.PathsHipError("a bounded in-launch hand-off wait of the token-0 tail gave up (csrc/token0_ws.hip): results invalid")
-    return {"logits": agg["logits"], "ctx_slide": agg["ctx_slide"], "ctx_patch": sel["ctx_patch"], "importance": sel["importance"]}
+    out = {"logits": agg["logits"], "ctx_slide": agg["ctx_slide"], "ctx_patch": sel["ctx_patch"], "importance": sel["importance"]}
+    if attention is not None:
+        out["attention"], out["attention_self"] = attention
+    return out
 
 
 def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, skip_padding: bool,
@@ -1066,22 +1082,50 @@ def parent_partials(lstm_pack, state_out: torch.Tensor, keep_idx: torch.Tensor, 
     return hp
 
 
-def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv=None) -> Dict[str, torch.Tensor]:
+def _export_attention(attention, lvl_pack, l: int, x, num_ims, H: int, special_last: int):
+    """Special token's attention of decoder layer ``l`` (input rows ``x`` [B, T, d], contiguous) into slot ``l`` of ``attention`` =
+    ([B, L, H, N], [B, L, H]) fp32 (csrc/attn_token0.hip: paths_token0_attention), on the current stream."""
+    patch, self_ = attention
+    B, L, _, N = patch.shape
+    T = N + 1
+    lay = lvl_pack["layers"][l]
+    d = lay["w_in"].shape[1]
+    ws = torch.empty((int(_lib.load().paths_token0_attention_workspace(B, T, d, H)),), device=x.device, dtype=torch.float32)
+    _lib.call("paths_token0_attention", _lib.ptr(x), _lib.ptr(num_ims), _lib.ptr(lay["w_in"]), _lib.ptr(lay["b_in"]),
+              patch.data_ptr() + 4 * l * H * N, L * H * N, self_.data_ptr() + 4 * l * H, L * H, _lib.ptr(ws), B, T, d, H, special_last,
+              _lib.stream())
+
+
+def _check_attention(attention, mc, tokens):
+    B, T, _ = tokens.shape
+    patch, self_ = attention
+    H, L = mc.trans_heads, mc.trans_layers
+    assert patch.shape == (B, L, H, T - 1) and self_.shape == (B, L, H), "attention: ([B, L, H, N], [B, L, H]) tensors"
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == tokens.device for t in attention)
+    assert tokens.is_contiguous()
+
+
+def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv=None, attention=None) -> Dict[str, torch.Tensor]:
     """The transformer aggregator + classifier of a level (reference model/aggregator.py:58-76, model/paths.py:126-139).
     Nothing here feeds the next level's patch selection, so the device recursion runs it on a second HIP stream.
     ``status`` (optional int32 [1] device tensor): bit 4 is set if a bounded in-launch hand-off wait gave up (csrc/token0_ws.hip).
     ``qkv`` (optional): the dict :func:`selection_forward` returned - when it carries "qkv_img" the first decoder layer's q | k | v
-    operand images were written by the importance / projection finish (FUSE_QKV) and the aggregator starts at the attention."""
+    operand images were written by the importance / projection finish (FUSE_QKV) and the aggregator starts at the attention.
+    ``attention`` (optional, inference): a pair of fp32 tensors [B, L, H, N] and [B, L, H] that receive the special token's attention
+    probabilities over the patches (in the order of ``importance`` / ``locs``, 0 on padding) and on itself, per decoder layer and head:
+    each layer's export is launched on this stream where the layer's input rows are final (:func:`_export_attention`)."""
     qkv_img, qkv_finish = (qkv.get("qkv_img"), qkv.get("qkv_finish")) if qkv is not None else (None, None)
+    if attention is not None:
+        _check_attention(attention, mc, tokens)
     if qkv_finish is not None:
         timed("agg_tokens_qkv", qkv_finish)            # FUSE_QKV = 2: tokens + images on THIS stream, outside the attention + FFN span
-    return timed("aggregator", lambda: _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status, qkv_img),
+    return timed("aggregator", lambda: _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status, qkv_img, attention),
                  {"T": tokens.shape[1], "d": tokens.shape[2], "L": mc.trans_layers, "planes": split_planes() if GEMM_MODE != "f32" else 0},
                  detail=False)
 
 
 def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer_old, status=None,
-                           qkv_ready: bool = False):
+                           qkv_ready: bool = False, attention=None):
     """Default-mode aggregator on the weight-stationary token-layer kernel (csrc/tlayer_ws.hip): in_proj writes the attention
     operand images, attention writes its output as the out_proj operand image, the chain kernel keeps weights in registers and
     shares only activations through LDS."""
@@ -1109,12 +1153,17 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     xa = tokens
     if not qkv_ready:                       # (FUSE_QKV: the importance / projection finish already wrote layer 0's operand images)
         timed("agg_in_proj", lambda: token_layer(xa, None, None, layers[0]))
+    order = 1 if qkv_ready else 0                # (the fused finish's token order: patch i = token i, the special token last)
     for l in range(L - 1):
+        if attention is not None:
+            _export_attention(attention, lvl_pack, l, xa, num_ims, H, order)
         timed("agg_attention", lambda: _lib.call("paths_attention_h3_img", p(o_img), p(num_ims), B, T, H, hd, p(qkv_img), st))
         last = l + 1 == L - 1
         timed("agg_token_chain", lambda: token_layer(xa, xb, layers[l], None if last else layers[l + 1]))
         xa, xb = xb, xa
     w = layers[L - 1]
+    if attention is not None:
+        _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, order)
 
     def tail_ws():
         img = token0_ws_image(w, qscale)
@@ -1147,12 +1196,12 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     return {"logits": logits, "ctx_slide": ctx_out}
 
 
-def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv_img=None) -> Dict[str, torch.Tensor]:
+def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv_img=None, attention=None) -> Dict[str, torch.Tensor]:
     _lib.require_cuda(tokens, num_ims, ctx_prev, ctx_all)
     if AGG_FP8:
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8=True)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8=True, attention=attention)
     if not fast_path(mc):
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=status)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=status, attention=attention)
     B, T, d = tokens.shape
     H, L = mc.trans_heads, mc.trans_layers
     st = _lib.stream()
@@ -1196,7 +1245,7 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     if qkv_img is not None:
         assert GEMM_MODE == "h3" and TLAYER_WS and QKV_IMAGES and L > 1 and not ATTN_FP8
         return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer, status,
-                                      qkv_ready=True)
+                                      qkv_ready=True, attention=attention)
     fp8 = ATTN_FP8 and L > 1          # opt-in e4m3 attention (csrc/attn_fp8.hip: outside the 1e-4 logit bar, stress-config measurement only)
     if fp8:
         attn_ws = torch.empty((int(_lib.load().paths_attention_fp8_workspace(B, T, H, hd)),), device=tokens.device, dtype=torch.uint8)
@@ -1207,9 +1256,12 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     # (no fp32 q, k, v round trip, no re-write launch); the last layer's q, k, v stay fp32 for the token-0 tail
     direct = GEMM_MODE == "h3" and attn_ws is not None and QKV_IMAGES and not fp8
     if direct and TLAYER_WS:
-        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, attn_ws, q, k, v, xb, ctx_out, logits, token_layer, status)
+        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, attn_ws, q, k, v, xb, ctx_out, logits, token_layer, status,
+                                      attention=attention)
     timed("agg_in_proj", lambda: token_layer(xa, None, None, layers[0], qkv_images=attn_ws if direct else None))
     for l in range(L - 1):
+        if attention is not None:
+            _export_attention(attention, lvl_pack, l, xa, num_ims, H, 0)
         if fp8:
             timed("agg_attention", lambda: _lib.call("paths_attention_fp8", p(q), p(k), p(v), p(attn), p(num_ims), B, T, H, hd, p(attn_ws), st))
         elif GEMM_MODE != "f32":
@@ -1222,6 +1274,8 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     # Last layer: only token 0 of its output is read (aggregator.py:75) -> one fused launch per level computes the
     # single-query attention, the row chain, decoder.norm, the slide-context residual and the classifier.
     w = layers[L - 1]
+    if attention is not None:
+        _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, 0)
     ws_part = torch.empty((B * H * 16 * 36,), **f32)
     timed("agg_token0_tail", lambda: _lib.call(
         "paths_token0_tail", p(xa), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
