@@ -303,6 +303,21 @@ int64_t paths_token0_attention_workspace(int B, int T, int d, int H);
 int paths_token0_attention(const float* x, const int64_t* num_ims, const float* in_proj_weight, const float* in_proj_bias, float* attn_patch,
                            int64_t patch_ld, float* attn_self, int64_t self_ld, float* ws, int B, int T, int d, int H, int special_last,
                            paths_stream_t stream);
+/* Attention rollout of the special token (Abnar & Zuidema 2020; interpretability side path, csrc/attn_rollout.hip): with A_l^h the
+ * softmax attention of layer l, head h over the valid tokens (T x T), r = e_s^T (0.5 mean_h A_{L-1}^h + 0.5 I) ... (0.5 mean_h A_0^h + 0.5 I).
+ * prepare: layer l's Q (scaled) / K rows and per-row softmax statistics from its input rows x [B, T, d] and TRUE in_proj [3d, d] / [3d]
+ * (token orders and num_ims clamping as paths_token0_attention) into ws (paths_attention_rollout_workspace floats per layer; rows in
+ * canonical order: 0 = special token, 1 + j = patch j).  seed: r [B][T] (canonical) = 0.5 e_s + 0.5 mean_h of the last layer's
+ * token-0 attention (paths_token0_attention's layout).  step: r_out = 0.5 r_in + 0.5 mean_h(r_in^T A^h) through a prepared layer.
+ * seed / step with r / r_out == NULL write the rollout itself: rollout[b * rollout_ld + j] (patch j, 0 for j >= num_ims[b]),
+ * rollout_self[b].  Any d % H == 0 with d % 4 == 0, d <= 2048.  fp32 (f32-input MFMA), deterministic, no T x T buffer. */
+int64_t paths_attention_rollout_workspace(int B, int T, int d, int H);
+int paths_attention_rollout_prepare(const float* x, const int64_t* num_ims, const float* in_proj_weight, const float* in_proj_bias, float* ws,
+                                    int B, int T, int d, int H, int special_last, paths_stream_t stream);
+int paths_attention_rollout_seed(const float* attn_patch, int64_t patch_ld, const float* attn_self, int64_t self_ld, const int64_t* num_ims,
+                                 float* r, float* rollout, int64_t rollout_ld, float* rollout_self, int B, int T, int H, paths_stream_t stream);
+int paths_attention_rollout_step(const float* ws, const int64_t* num_ims, const float* r_in, float* r_out, float* rollout, int64_t rollout_ld,
+                                 float* rollout_self, int B, int T, int d, int H, paths_stream_t stream);
 
 /* Generic out = act(a W^T + b) on the fp32 matrix cores (W rows zero-padded to Npad, a multiple of 128). */
 int paths_linear_f32(const float* a, int64_t lda, const float* w, const float* b, float* out, int64_t ldo,

@@ -1,12 +1,13 @@
 """Heat-map export (the data consumed by reference heatmap_visualise.py:113-175; drawing is out of scope).
 
 ``hierarchy_from_trace`` pulls one slide's per-level patch locations / importances / selected indices (and, from a
-``recurse(..., attention=True)`` trace, the special token's attention) out of the trace of :func:`paths_amd.utils.recurse`.
+``recurse(..., attention=True)`` trace, the special token's attention; from a ``recurse(..., rollout=True)`` trace, its attention
+rollout) out of the trace of :func:`paths_amd.utils.recurse`.
 
 ``importance_map`` rasterises the importances exactly like the reference's overlay code: every patch of depth d paints
 ``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with weight 1/2 wherever they exist
 (heatmap_visualise.py:147-171).  ``attention_map`` rasterises the special token's attention of one decoder layer (one head or
-the mean over heads), one raster per level and no fold across levels.  Rasters are in units of the FINEST level's patches (one
+the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout.  Rasters are in units of the FINEST level's patches (one
 cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
 """
 from __future__ import annotations
@@ -27,6 +28,9 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
         if "attention" in lv:
             d["attention"] = lv["attention"][slide, :, :, :n].cpu().numpy()          # [L, H, n]
             d["attention_self"] = lv["attention_self"][slide].cpu().numpy()          # [L, H]
+        if "rollout" in lv:
+            d["rollout"] = lv["rollout"][slide, :n].cpu().numpy()                      # [n]
+            d["rollout_self"] = float(lv["rollout_self"][slide])
         out.append(d)
     return out
 
@@ -69,5 +73,22 @@ def attention_map(levels: List[Dict[str, np.ndarray]], base_grid, layer: int = -
         w = a.mean(axis=0, dtype=np.float64) if head is None else a[head]
         raster = np.zeros(shape, dtype=np.float64)
         _paint(raster, lv["locs"], w, magnification_factor ** (L - 1 - depth), patch_size)
+        maps.append(raster)
+    return maps
+
+
+def rollout_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: int = 256, magnification_factor: int = 2) -> List[np.ndarray]:
+    """One [X0 * f, Y0 * f] float map per level (f = magnification_factor**(L-1)): the special token's attention rollout on each
+    patch, painted over the patch's footprint like :func:`attention_map`; 0 where the level did not visit, no fold across levels.
+    ``levels`` from :func:`hierarchy_from_trace` of a ``recurse(..., rollout=True)`` trace."""
+    L = len(levels)
+    f = magnification_factor ** (L - 1)
+    shape = (base_grid[0] * f, base_grid[1] * f)
+    maps = []
+    for depth, lv in enumerate(levels):
+        if "rollout" not in lv:
+            raise KeyError("level %d carries no rollout: run recurse(..., rollout=True)" % depth)
+        raster = np.zeros(shape, dtype=np.float64)
+        _paint(raster, lv["locs"], lv["rollout"], magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)
     return maps

@@ -49,14 +49,19 @@ class PATHSProcessor(nn.Module, Processor):
         self.global_agg = TransformerAggregator(input_dim=self.dim, model_dim=config.trans_dim, output_dim=self.dim,
                                                 nhead=config.trans_heads, layers=config.trans_layers, dropout=config.dropout)
 
-    def process(self, data, lstm=None, skip_padding: bool = False, return_attention: bool = False) -> Dict[str, torch.Tensor]:
+    def process(self, data, lstm=None, skip_padding: bool = False, return_attention: bool = False,
+                return_rollout: bool = False) -> Dict[str, torch.Tensor]:
         """The reference's four outputs; with ``return_attention`` (inference only) also "attention" [B, L, H, N] and
         "attention_self" [B, L, H]: the special token's attention over the patches (0 on padding) and on itself, per decoder layer
-        and head - what a hook on the reference's nn.MultiheadAttention with need_weights=True returns for row 0."""
+        and head - what a hook on the reference's nn.MultiheadAttention with need_weights=True returns for row 0.  With
+        ``return_rollout`` (inference only) also "rollout" [B, N] and "rollout_self" [B]: the special token's attention rollout over
+        the decoder stack (Abnar & Zuidema 2020; 0 on padding, patches + self sum to 1)."""
         mc = self.config
         ops.check_supported(mc)
         if return_attention and torch.is_grad_enabled():
             raise NotImplementedError("return_attention is an inference export: call it under torch.no_grad()")
+        if return_rollout and torch.is_grad_enabled():
+            raise NotImplementedError("return_rollout is an inference export: call it under torch.no_grad()")
         assert lstm is not None or not mc.lstm, "lstm=True needs the shared LSTMCell (RecursiveModel passes it)"
         if self.training and mc.dropout > 0 and not torch.is_grad_enabled():
             raise NotImplementedError("dropout > 0 in train mode is implemented on the differentiable path only: call model.eval() "
@@ -67,10 +72,11 @@ class PATHSProcessor(nn.Module, Processor):
             f32 = data.fts if (data.fts.dtype == torch.float32 and data.fts.is_contiguous()) else data.fts.float().contiguous()
             amax = _lib_absmax(f32, data.ctx_patch[:, :, -1] if self.depth > 0 else None)
             with ops.range_guard(amax):
-                return self._process(data, lstm, skip_padding, return_attention)
-        return self._process(data, lstm, skip_padding, return_attention)
+                return self._process(data, lstm, skip_padding, return_attention, return_rollout)
+        return self._process(data, lstm, skip_padding, return_attention, return_rollout)
 
-    def _process(self, data, lstm, skip_padding: bool, return_attention: bool = False) -> Dict[str, torch.Tensor]:
+    def _process(self, data, lstm, skip_padding: bool, return_attention: bool = False,
+                 return_rollout: bool = False) -> Dict[str, torch.Tensor]:
         mc = self.config
         if torch.is_grad_enabled():
             # differentiable path (training): same kernels + saved activations, backward in HIP (paths_amd/autograd.py)
@@ -105,7 +111,8 @@ class PATHSProcessor(nn.Module, Processor):
         ctx_all = data.ctx_slide.float().contiguous() if mc.slide_ctx_mode == "concat" else None
         with torch.no_grad():
             return ops.level_forward(mc, ops.pack_lstm(lstm) if mc.lstm else None, ops.pack_level(self), fts, data.locs, data.num_ims,
-                                     state_prev, ctx_prev, ctx_all, skip_padding, return_attention=return_attention)
+                                     state_prev, ctx_prev, ctx_all, skip_padding, return_attention=return_attention,
+                                     return_rollout=return_rollout)
 
     def ctx_dim(self) -> Tuple[int, int]:
         if self.config.lstm:

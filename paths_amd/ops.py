@@ -679,7 +679,7 @@ def fp8_supported(mc) -> bool:
 
 
 def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8: bool = False, status=None,
-                                attention=None) -> Dict[str, torch.Tensor]:
+                                attention=None, rollout=None) -> Dict[str, torch.Tensor]:
     """The aggregator for any (trans_dim, heads): generic GEMMs + csrc/generic.hip (reference model/aggregator.py:58-76 with torch's
     post-LN decoder layers, model/paths.py:130-139).  The last layer is evaluated at token 0 only (its other rows are never read).
     ``fp8`` (ops.AGG_FP8, the BASELINE configs[4] stress variant, NOT a parity path): the products over all tokens - in_proj, the full
@@ -727,6 +727,8 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
         last = l == L - 1
         if attention is not None:                 # (x: this layer's input rows [B*T, d], special token first)
             _export_attention(attention, lvl_pack, l, x, num_ims, H, 0)
+        if rollout is not None:
+            rollout.layer(l, x, 0)
         big = fp8 and not last            # products over all tokens of a full layer
 
         def gemm(a, lda, key, bias, out, ldo, m, n, kdim, act=0, residual=None, ldr=0, low=False):
@@ -816,6 +818,8 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
         w = lvl_pack["layers"][L - 1]
         if attention is not None:                 # (the loop left with `break` before the last layer's iteration)
             _export_attention(attention, lvl_pack, L - 1, x, num_ims, H, 0)
+        if rollout is not None:
+            rollout.layer(L - 1, x, 0)
         img = token0_ws_image(w, qscale)
         part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), **f32)
         cnt = token0_counters(dev, B)
@@ -839,12 +843,13 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
 # ---------------------------------------------------------------------------------------------
 def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor, num_ims: torch.Tensor,
                   state_prev: Optional[torch.Tensor], ctx_prev: Optional[torch.Tensor], ctx_all: Optional[torch.Tensor],
-                  skip_padding: bool, return_attention: bool = False) -> Dict[str, torch.Tensor]:
+                  skip_padding: bool, return_attention: bool = False, return_rollout: bool = False) -> Dict[str, torch.Tensor]:
     """fts [B,N,D] fp32 contiguous; locs [B,N,2] int64; num_ims [B] int64;
     state_prev: [B,N,>=D+Hc] view whose last dim holds (h|c) of the previous level (row stride arbitrary) or None;
     ctx_prev [B,d] (residual source) or None; ctx_all [B,depth,d] contiguous (concat mode) or None.
     ``return_attention``: the result also carries "attention" [B, L, H, N] and "attention_self" [B, L, H], the special token's attention
-    per decoder layer and head (see :func:`aggregator_forward`)."""
+    per decoder layer and head (see :func:`aggregator_forward`); ``return_rollout``: also "rollout" [B, N] and "rollout_self" [B],
+    the special token's attention rollout."""
     sel = selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, skip_padding)
     status = torch.zeros((1,), device=fts.device, dtype=torch.int32)
     attention = None
@@ -852,7 +857,13 @@ def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor
         B, N = locs.shape[:2]
         f32 = dict(device=fts.device, dtype=torch.float32)
         attention = (torch.empty((B, mc.trans_layers, mc.trans_heads, N), **f32), torch.empty((B, mc.trans_layers, mc.trans_heads), **f32))
-    agg = aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=attention)
+    rollout = None
+    if return_rollout:
+        B, N = locs.shape[:2]
+        f32 = dict(device=fts.device, dtype=torch.float32)
+        rollout = (torch.empty((B, N), **f32), torch.empty((B,), **f32))
+    agg = aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=attention,
+                             rollout=rollout)
     # the drop-in call is synchronous anyway (the range guard above it syncs): a token-0 tail whose bounded hand-off wait gave up
     # (status bit 2, csrc/token0_ws.hip) must not hand back its logits
     if int(status.item()) & 4:
@@ -860,6 +871,8 @@ def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor
     out = {"logits": agg["logits"], "ctx_slide": agg["ctx_slide"], "ctx_patch": sel["ctx_patch"], "importance": sel["importance"]}
     if attention is not None:
         out["attention"], out["attention_self"] = attention
+    if rollout is not None:
+        out["rollout"], out["rollout_self"] = rollout
     return out
 
 
@@ -1082,18 +1095,64 @@ def parent_partials(lstm_pack, state_out: torch.Tensor, keep_idx: torch.Tensor, 
     return hp
 
 
-def _export_attention(attention, lvl_pack, l: int, x, num_ims, H: int, special_last: int):
-    """Special token's attention of decoder layer ``l`` (input rows ``x`` [B, T, d], contiguous) into slot ``l`` of ``attention`` =
-    ([B, L, H, N], [B, L, H]) fp32 (csrc/attn_token0.hip: paths_token0_attention), on the current stream."""
+def _export_attention(attention, lvl_pack, l: int, x, num_ims, H: int, special_last: int, slot: Optional[int] = None):
+    """Special token's attention of decoder layer ``l`` (input rows ``x`` [B, T, d], contiguous) into slot ``l`` (or ``slot``) of
+    ``attention`` = ([B, L, H, N], [B, L, H]) fp32 (csrc/attn_token0.hip: paths_token0_attention), on the current stream."""
     patch, self_ = attention
     B, L, _, N = patch.shape
     T = N + 1
+    slot = l if slot is None else slot
     lay = lvl_pack["layers"][l]
     d = lay["w_in"].shape[1]
     ws = torch.empty((int(_lib.load().paths_token0_attention_workspace(B, T, d, H)),), device=x.device, dtype=torch.float32)
     _lib.call("paths_token0_attention", _lib.ptr(x), _lib.ptr(num_ims), _lib.ptr(lay["w_in"]), _lib.ptr(lay["b_in"]),
-              patch.data_ptr() + 4 * l * H * N, L * H * N, self_.data_ptr() + 4 * l * H, L * H, _lib.ptr(ws), B, T, d, H, special_last,
+              patch.data_ptr() + 4 * slot * H * N, L * H * N, self_.data_ptr() + 4 * slot * H, L * H, _lib.ptr(ws), B, T, d, H, special_last,
               _lib.stream())
+
+
+class _Rollout:
+    """One level's attention rollout of the special token (csrc/attn_rollout.hip), driven from the aggregator's layer loop on its
+    stream: :meth:`layer` is called where layer l's input rows are final.  Layers l <= L-2 are prepared (Q / K rows + softmax
+    statistics); at the last layer its token-0 attention is exported (into the caller's ``attention`` slot, or a private buffer)
+    and seed + steps run at once, the last step writing ``rollout`` = ([B, N], [B]) in the patch order of ``importance``."""
+
+    def __init__(self, rollout, attention, lvl_pack, tokens, num_ims, H: int, L: int):
+        self.out, self.out_self = rollout
+        self.attention, self.lvl_pack, self.num_ims, self.H, self.L = attention, lvl_pack, num_ims, H, L
+        self.B, self.T, self.d = tokens.shape
+        self.prepared: Dict[int, torch.Tensor] = {}
+
+    def layer(self, l: int, x, special_last: int):
+        B, T, d, H, L = self.B, self.T, self.d, self.H, self.L
+        p = _lib.ptr
+        f32 = dict(device=x.device, dtype=torch.float32)
+        if l < L - 1:
+            lay = self.lvl_pack["layers"][l]
+            ws = torch.empty((int(_lib.load().paths_attention_rollout_workspace(B, T, d, H)),), **f32)
+            _lib.call("paths_attention_rollout_prepare", p(x), p(self.num_ims), p(lay["w_in"]), p(lay["b_in"]), p(ws), B, T, d, H,
+                      special_last, _lib.stream())
+            self.prepared[l] = ws
+            return
+        att, slot = self.attention, L - 1
+        if att is None:                   # the last layer's token-0 attention, not requested by the caller
+            N = T - 1
+            att, slot = (torch.empty((B, 1, H, N), **f32), torch.empty((B, 1, H), **f32)), 0
+            _export_attention(att, self.lvl_pack, L - 1, x, self.num_ims, H, special_last, slot=0)
+        La = att[0].shape[1]
+        a_patch, a_self = att[0].data_ptr() + 4 * slot * H * (T - 1), att[1].data_ptr() + 4 * slot * H
+        out, out_self = p(self.out) if T > 1 else None, p(self.out_self)
+        if L == 1:
+            _lib.call("paths_attention_rollout_seed", a_patch, La * H * (T - 1), a_self, La * H, p(self.num_ims), None, out, T - 1, out_self,
+                      B, T, H, _lib.stream())
+            return
+        r = [torch.empty((B, T), **f32), torch.empty((B, T), **f32)]
+        _lib.call("paths_attention_rollout_seed", a_patch, La * H * (T - 1), a_self, La * H, p(self.num_ims), p(r[0]), None, 0, None,
+                  B, T, H, _lib.stream())
+        for i, l2 in enumerate(range(L - 2, -1, -1)):
+            last = l2 == 0
+            _lib.call("paths_attention_rollout_step", p(self.prepared.pop(l2)), p(self.num_ims), p(r[i % 2]),
+                      None if last else p(r[(i + 1) % 2]), out if last else None, T - 1, out_self if last else None, B, T, d, H,
+                      _lib.stream())
 
 
 def _check_attention(attention, mc, tokens):
@@ -1105,7 +1164,16 @@ def _check_attention(attention, mc, tokens):
     assert tokens.is_contiguous()
 
 
-def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv=None, attention=None) -> Dict[str, torch.Tensor]:
+def _check_rollout(rollout, tokens):
+    B, T, _ = tokens.shape
+    out, out_self = rollout
+    assert out.shape == (B, T - 1) and out_self.shape == (B,), "rollout: ([B, N], [B]) tensors"
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == tokens.device for t in rollout)
+    assert tokens.is_contiguous()
+
+
+def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv=None, attention=None,
+                       rollout=None) -> Dict[str, torch.Tensor]:
     """The transformer aggregator + classifier of a level (reference model/aggregator.py:58-76, model/paths.py:126-139).
     Nothing here feeds the next level's patch selection, so the device recursion runs it on a second HIP stream.
     ``status`` (optional int32 [1] device tensor): bit 4 is set if a bounded in-launch hand-off wait gave up (csrc/token0_ws.hip).
@@ -1113,19 +1181,26 @@ def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=
     operand images were written by the importance / projection finish (FUSE_QKV) and the aggregator starts at the attention.
     ``attention`` (optional, inference): a pair of fp32 tensors [B, L, H, N] and [B, L, H] that receive the special token's attention
     probabilities over the patches (in the order of ``importance`` / ``locs``, 0 on padding) and on itself, per decoder layer and head:
-    each layer's export is launched on this stream where the layer's input rows are final (:func:`_export_attention`)."""
+    each layer's export is launched on this stream where the layer's input rows are final (:func:`_export_attention`).
+    ``rollout`` (optional, inference): a pair of fp32 tensors [B, N] and [B] that receive the special token's attention rollout
+    (Abnar & Zuidema 2020) over the patches (same order, 0 on padding) and on itself; launched at the same points (:class:`_Rollout`).
+    Without it the launch sequence is unchanged; with it every other output is bit-identical."""
     qkv_img, qkv_finish = (qkv.get("qkv_img"), qkv.get("qkv_finish")) if qkv is not None else (None, None)
     if attention is not None:
         _check_attention(attention, mc, tokens)
+    ro = None
+    if rollout is not None:
+        _check_rollout(rollout, tokens)
+        ro = _Rollout(rollout, attention, lvl_pack, tokens, num_ims, mc.trans_heads, mc.trans_layers)
     if qkv_finish is not None:
         timed("agg_tokens_qkv", qkv_finish)            # FUSE_QKV = 2: tokens + images on THIS stream, outside the attention + FFN span
-    return timed("aggregator", lambda: _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status, qkv_img, attention),
+    return timed("aggregator", lambda: _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status, qkv_img, attention, ro),
                  {"T": tokens.shape[1], "d": tokens.shape[2], "L": mc.trans_layers, "planes": split_planes() if GEMM_MODE != "f32" else 0},
                  detail=False)
 
 
 def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer_old, status=None,
-                           qkv_ready: bool = False, attention=None):
+                           qkv_ready: bool = False, attention=None, rollout=None):
     """Default-mode aggregator on the weight-stationary token-layer kernel (csrc/tlayer_ws.hip): in_proj writes the attention
     operand images, attention writes its output as the out_proj operand image, the chain kernel keeps weights in registers and
     shares only activations through LDS."""
@@ -1157,6 +1232,8 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     for l in range(L - 1):
         if attention is not None:
             _export_attention(attention, lvl_pack, l, xa, num_ims, H, order)
+        if rollout is not None:
+            rollout.layer(l, xa, order)
         timed("agg_attention", lambda: _lib.call("paths_attention_h3_img", p(o_img), p(num_ims), B, T, H, hd, p(qkv_img), st))
         last = l + 1 == L - 1
         timed("agg_token_chain", lambda: token_layer(xa, xb, layers[l], None if last else layers[l + 1]))
@@ -1164,6 +1241,8 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     w = layers[L - 1]
     if attention is not None:
         _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, order)
+    if rollout is not None:
+        rollout.layer(L - 1, xa, order)
 
     def tail_ws():
         img = token0_ws_image(w, qscale)
@@ -1196,12 +1275,14 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     return {"logits": logits, "ctx_slide": ctx_out}
 
 
-def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv_img=None, attention=None) -> Dict[str, torch.Tensor]:
+def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv_img=None, attention=None,
+                        rollout=None) -> Dict[str, torch.Tensor]:
     _lib.require_cuda(tokens, num_ims, ctx_prev, ctx_all)
     if AGG_FP8:
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8=True, attention=attention)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8=True, attention=attention, rollout=rollout)
     if not fast_path(mc):
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=status, attention=attention)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=status, attention=attention,
+                                           rollout=rollout)
     B, T, d = tokens.shape
     H, L = mc.trans_heads, mc.trans_layers
     st = _lib.stream()
@@ -1245,7 +1326,7 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     if qkv_img is not None:
         assert GEMM_MODE == "h3" and TLAYER_WS and QKV_IMAGES and L > 1 and not ATTN_FP8
         return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer, status,
-                                      qkv_ready=True, attention=attention)
+                                      qkv_ready=True, attention=attention, rollout=rollout)
     fp8 = ATTN_FP8 and L > 1          # opt-in e4m3 attention (csrc/attn_fp8.hip: outside the 1e-4 logit bar, stress-config measurement only)
     if fp8:
         attn_ws = torch.empty((int(_lib.load().paths_attention_fp8_workspace(B, T, H, hd)),), device=tokens.device, dtype=torch.uint8)
@@ -1257,11 +1338,13 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     direct = GEMM_MODE == "h3" and attn_ws is not None and QKV_IMAGES and not fp8
     if direct and TLAYER_WS:
         return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, attn_ws, q, k, v, xb, ctx_out, logits, token_layer, status,
-                                      attention=attention)
+                                      attention=attention, rollout=rollout)
     timed("agg_in_proj", lambda: token_layer(xa, None, None, layers[0], qkv_images=attn_ws if direct else None))
     for l in range(L - 1):
         if attention is not None:
             _export_attention(attention, lvl_pack, l, xa, num_ims, H, 0)
+        if rollout is not None:
+            rollout.layer(l, xa, 0)
         if fp8:
             timed("agg_attention", lambda: _lib.call("paths_attention_fp8", p(q), p(k), p(v), p(attn), p(num_ims), B, T, H, hd, p(attn_ws), st))
         elif GEMM_MODE != "f32":
@@ -1276,6 +1359,8 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     w = layers[L - 1]
     if attention is not None:
         _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, 0)
+    if rollout is not None:
+        rollout.layer(L - 1, xa, 0)
     ws_part = torch.empty((B * H * 16 * 36,), **f32)
     timed("agg_token0_tail", lambda: _lib.call(
         "paths_token0_tail", p(xa), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),

@@ -36,23 +36,27 @@ class RecursionError_(RuntimeError):
 
 
 def recurse(model, slides, keep_patches: Sequence[int], num_levels: int,
-            trace: Optional[list] = None, check_status: bool = True, attention: bool = False) -> Dict[str, torch.Tensor]:
+            trace: Optional[list] = None, check_status: bool = True, attention: bool = False,
+            rollout: bool = False) -> Dict[str, torch.Tensor]:
     """Optimistic sync-free pass; if some slide produced zero children (status bit 0, checked once at the end) the
     batch is re-run level by level with the reference's rare fallback (data_utils/slide.py:336-352) handled on the
     device.  See :func:`_recurse` for the arguments.
 
     ``attention`` (needs ``trace``): every trace record also gets "attention" [B, L, H, N] and "attention_self" [B, L, H], the
     special token's attention over the level's patches (in the order of its locs / importance, 0 on padding) and on itself, per
-    decoder layer and head."""
+    decoder layer and head.  ``rollout`` (needs ``trace``, independent of ``attention``): every trace record also gets "rollout" [B, N]
+    and "rollout_self" [B], the special token's attention rollout over the decoder stack (same order, 0 on padding)."""
     if attention and trace is None:
         raise ValueError("recurse(attention=True) returns the attention in the trace records: pass trace=[]")
-    out = _recurse(model, slides, keep_patches, num_levels, trace, careful=False, attention=attention)
+    if rollout and trace is None:
+        raise ValueError("recurse(rollout=True) returns the rollout in the trace records: pass trace=[]")
+    out = _recurse(model, slides, keep_patches, num_levels, trace, careful=False, attention=attention, rollout=rollout)
     if not check_status:
         return out
     if check_status_word(out["status"]):        # the only host sync of the fast path, after the last level
         if trace is not None:
             trace.clear()
-        out = _recurse(model, slides, keep_patches, num_levels, trace, careful=True, attention=attention)
+        out = _recurse(model, slides, keep_patches, num_levels, trace, careful=True, attention=attention, rollout=rollout)
         check_status_word(out["status"], fallback_done=True)
     return out
 
@@ -355,15 +359,15 @@ def _streams(dev, lane: Optional[int] = None):
 
 
 def _recurse(model, slides, keep_patches: Sequence[int], num_levels: int,
-             trace: Optional[list] = None, careful: bool = False, attention: bool = False) -> Dict[str, torch.Tensor]:
+             trace: Optional[list] = None, careful: bool = False, attention: bool = False, rollout: bool = False) -> Dict[str, torch.Tensor]:
     batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
     with ops.range_guard(batch.feat_absmax):       # out-of-range features run on the exact bf16 split (no fp16 overflow)
-        return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention)
+        return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout)
 
 
-def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention=False):
+def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention=False, rollout=False):
     if not (OVERLAP_AGGREGATOR and batch.device.type == "cuda"):
-        return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, None, None, attention)
+        return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, None, None, attention, rollout)
     caller = torch.cuda.current_stream(batch.device)
     sel_stream, agg_stream, par_stream = _streams(batch.device)
     if torch.cuda.is_current_stream_capturing():
@@ -373,25 +377,27 @@ def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, att
         _lib.stream_wait(agg_stream, caller)
         if par_stream is not None:
             _lib.stream_wait(par_stream, caller)
-        return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention)
+        return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention, rollout)
     _lib.stream_wait(sel_stream, caller)
     _lib.stream_wait(agg_stream, caller)
     if par_stream is not None:
         _lib.stream_wait(par_stream, caller)
     with torch.cuda.stream(sel_stream):
-        out = _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention)
+        out = _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention, rollout)
     _lib.stream_wait(caller, sel_stream)     # (the body has already joined agg_stream into sel_stream)
     return out
 
 
 def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
-                  trace: Optional[list], careful: bool, agg_stream, par_stream=None, attention: bool = False) -> Dict[str, torch.Tensor]:
+                  trace: Optional[list], careful: bool, agg_stream, par_stream=None, attention: bool = False,
+                  rollout: bool = False) -> Dict[str, torch.Tensor]:
     """Run all levels for a batch of HBM-resident slides (a list of DeviceSlide, or a DeviceSlideBatch built once
     and re-used across calls).  Returns the last level's output dict (+ "status").
 
     ``trace`` (a list) receives one dict per level with device tensors num_ims / locs / parent_inds / importance /
     logits / ctx_slide / keep_idx / keep_count, for parity tests and heat-map export; with ``attention`` also attention /
-    attention_self (the special token's attention per decoder layer and head: ops.aggregator_forward).
+    attention_self (the special token's attention per decoder layer and head: ops.aggregator_forward); with ``rollout`` also
+    rollout / rollout_self (its attention rollout).
     """
     mc = model.procs[0].config
     ops.check_supported(mc)
@@ -470,9 +476,13 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
             if attention:                                 # (allocated on the aggregator's stream, like its logits)
                 Hh, Lt = mc.trans_heads, mc.trans_layers
                 att = (torch.empty((B, Lt, Hh, N), **f32), torch.empty((B, Lt, Hh), **f32))
-            agg = ops.aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=att)
+            ro = (torch.empty((B, N), **f32), torch.empty((B,), **f32)) if rollout else None
+            agg = ops.aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=att,
+                                         rollout=ro)
             if att is not None:
                 agg = dict(agg, attention=att[0], attention_self=att[1])
+            if ro is not None:
+                agg = dict(agg, rollout=ro[0], rollout_self=ro[1])
             return agg
 
         if overlap:                                       # (side_stream already waits for this level's tokens / num_ims: fork_behind above)
@@ -490,6 +500,8 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                    "logits": out["logits"], "ctx_slide": out["ctx_slide"]}
             if attention:
                 rec["attention"], rec["attention_self"] = agg["attention"], agg["attention_self"]
+            if rollout:
+                rec["rollout"], rec["rollout_self"] = agg["rollout"], agg["rollout_self"]
             trace.append(rec)
         if i == num_levels - 1:
             break
