@@ -5,7 +5,9 @@
  * point names the reference code it replaces (file:line relative to the reference repo root).
  *
  * Conventions
- *   - plain pointers + sizes; every pointer is a DEVICE pointer unless stated; no torch types;
+ *   - plain pointers + sizes; every pointer is a DEVICE pointer unless stated; no torch types.  Stated exceptions: the grid base
+ *     addresses in grid_ptrs of paths_level0_batch* / paths_gather_rows* and the row addresses paths_stage_rows follows may be
+ *     PINNED, device-mapped host addresses (hipHostMalloc / torch pin_memory; never pageable or managed memory);
  *   - returns 0 on success, a negative code on error (-1 invalid argument, -2 launch failure,
  *     -3 unsupported configuration); paths_last_error() returns a thread-local message;
  *   - never allocates, frees or synchronises; launches on the caller's stream (hipStream_t passed as
@@ -566,7 +568,9 @@ int paths_fallback_all_cells(const int* next_x, const int* next_y, const int64_t
  * (row stride ld_state_cur), Dp = number of columns copied into state_out [B, n_next, Dp].
  * fts_out may be NULL when row_ptrs [B, n_next] is given: the features are then not copied at all, row_ptrs receives the
  * ADDRESS of every child's feature row inside its resident grid (padding rows: zero_row, D zeros) and the split-operand
- * GEMMs read the rows in place (x_rows / y_rows of paths_lstm_cell_x6 / paths_importance_proj_x6). */
+ * GEMMs read the rows in place (x_rows / y_rows of paths_lstm_cell_x6 / paths_importance_proj_x6).
+ * grid_ptrs [B] may hold pinned, device-mapped HOST addresses (host-resident slides): with fts_out the rows are copied over the host
+ * link by this kernel; with row_ptrs alone nothing is read from the grids and paths_stage_rows fetches the rows afterwards. */
 int paths_gather_rows(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
                       int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
                       float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
@@ -596,7 +600,9 @@ int paths_sibling_sum(const int* keep_idx, int64_t ldk, const int* keep_count, c
 int paths_scatter_kept_rows(const float* src, int64_t ldk, int64_t ld_src, const int* keep_idx, const int* keep_count, float* dst,
                             int64_t n_dst, int64_t ld_dst, int width, int B, paths_stream_t stream);
 
-/* Level-0 batch: every grid cell in row-major order (reference data_utils/slide.py:257-269,362-381). */
+/* Level-0 batch: every grid cell in row-major order (reference data_utils/slide.py:257-269,362-381).  grid_ptrs [B]: base address of
+ * every slide's level-0 grid, device memory or pinned device-mapped host memory (with fts the rows are then copied over the host
+ * link; with row_ptrs only their addresses are written, for paths_stage_rows). */
 int paths_level0_batch(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
                        float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                        const float* zero_row, paths_stream_t stream);
@@ -604,6 +610,14 @@ int paths_level0_batch(const int64_t* grid_ptrs, const int* gx, const int* gy, i
 int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
                            float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                            const float* zero_row, paths_stream_t stream);
+
+/* Row staging for host-resident slides (paths_amd/data_utils/slide.py:HostSlide; the reference gathers rows on the CPU from grids in
+ * host RAM, data_utils/slide.py:320-331).  row_ptrs [rows] is an address table written by paths_level0_batch* / paths_gather_rows*
+ * whose grid_ptrs were pinned, device-mapped HOST addresses: for every m with row_ptrs[m] != zero_row the row_bytes bytes at
+ * row_ptrs[m] (16-byte aligned) are copied over the host link to stage + m * row_bytes and row_ptrs[m] is rewritten to that address;
+ * entries equal to zero_row (padding) are neither followed nor changed.  stage: DEVICE buffer of rows * row_bytes bytes, 16-byte
+ * aligned.  A byte copy: one entry point for fp32 and fp16 rows.  Each source row is read once; row_bytes % 16 == 0. */
+int paths_stage_rows(int64_t* row_ptrs, int64_t rows, int row_bytes, void* stage, const void* zero_row, paths_stream_t stream);
 
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */

@@ -10,6 +10,9 @@ At K=2048 one slide is 2.9 GB (level-4 grid alone 2.1 GB); 288 GB of HBM holds ~
 Grids may also be kept in fp16 (``dtype=torch.float16``, opt-in): half the HBM per slide (~180 K=2048 slides per MI355X).  The
 device kernels read fp16 rows where they live and widen them exactly; the host conversion goes through :func:`to_float16`, which
 refuses values an fp16 grid cannot hold.  bf16 is not supported.
+
+:class:`HostSlide` is the sibling for cohorts that do not fit in HBM: its grids stay in PINNED host memory, only the tissue masks
+live on the device, and the recursion fetches just the rows it selects over the host link (paths_stage_rows).
 """
 from __future__ import annotations
 
@@ -62,6 +65,8 @@ def to_float16(grid, chunk_rows: int = 1 << 16) -> Tuple[torch.Tensor, float]:
 
 
 class DeviceSlide:
+    host_resident = False           # the grids live in HBM (HostSlide: in pinned host memory)
+
     def __init__(self, grids: Sequence[torch.Tensor], patch_size: int = 256, slide_id: str = "", subtype=None):
         """``grids``: device tensors [X, Y, D], all torch.float32 or all torch.float16 (kept as they are: no fp32 copy is made)."""
         assert len(grids) >= 1
@@ -152,17 +157,177 @@ class DeviceSlide:
         return s
 
 
+def plan_mask_chunks(cells: int, D: int, itemsize: int, budget_bytes: int) -> List[Tuple[int, int]]:
+    """Row chunks ``[(row0, rows), ...]`` in which a host grid of ``cells`` rows of ``D`` elements is streamed through a device bounce
+    buffer of ``budget_bytes``: every row exactly once, in order, no chunk larger than the budget (the last one may be partial).
+    Raises ValueError when the budget does not hold one row."""
+    row_bytes = int(D) * int(itemsize)
+    if cells <= 0 or row_bytes <= 0:
+        raise ValueError(f"plan_mask_chunks: empty grid (cells {cells}, row of {row_bytes} bytes)")
+    per = int(budget_bytes) // row_bytes
+    if per < 1:
+        raise ValueError(f"plan_mask_chunks: a bounce buffer of {budget_bytes} bytes does not hold one row of {row_bytes} bytes")
+    return [(r0, min(per, cells - r0)) for r0 in range(0, cells, per)]
+
+
+def _pinned(g: torch.Tensor) -> torch.Tensor:
+    """``g`` (CPU, contiguous) in pinned memory: itself when it already is, else a pinned copy."""
+    return g if g.is_pinned() else g.pin_memory()
+
+
+class HostSlide:
+    """A slide whose feature grids stay in PINNED host memory (the reference keeps them in host RAM too and gathers on the CPU,
+    data_utils/slide.py:320-331).  The read surface is :class:`DeviceSlide`'s; ``grids[l]`` are CPU tensors [X, Y, D] that the
+    device can address (pinned = device-mapped), ``masks[l]`` are the usual uint8 [X, Y] DEVICE tensors.  Device memory per slide is
+    the masks alone (0.7 MB at K = 2048 x 5 levels against 2.86 GB of grids).
+
+    The masks and max|x| come from ONE pass of the resident slides' kernel (paths_tissue_mask_absmax[_h16]) over the grid, streamed
+    in row chunks through a bounded device bounce buffer (``bounce_bytes``, or a caller-owned uint8 device tensor ``bounce`` shared by
+    many slides); ``masks=`` + ``absmax=`` skip the pass for callers who cached them.  Grids that are not pinned yet are copied into
+    pinned memory here: a kernel must never be handed pageable memory."""
+
+    host_resident = True
+
+    def __init__(self, grids: Sequence[torch.Tensor], device="cuda", patch_size: int = 256, slide_id: str = "", subtype=None,
+                 masks: Optional[Sequence[torch.Tensor]] = None, absmax: Optional[float] = None, bounce_bytes: int = 64 << 20,
+                 bounce: Optional[torch.Tensor] = None):
+        assert len(grids) >= 1
+        self.dtype = check_grid_dtype(grids[0].dtype)
+        if any(g.dtype != self.dtype for g in grids):
+            raise ValueError("HostSlide: all levels of a slide must have the same dtype")
+        if any(g.device.type != "cpu" or g.dim() != 3 for g in grids):
+            raise ValueError("HostSlide: grids are CPU tensors [X, Y, D] (DeviceSlide holds device grids)")
+        if (masks is None) != (absmax is None):
+            raise ValueError("HostSlide: cached masks= and absmax= come together")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PathsHipError("paths_amd runs on the GPU only: a HostSlide needs a GPU device for its masks (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.patch_size = patch_size
+        self.slide_id = slide_id
+        self.subtype = subtype
+        self.grids: List[torch.Tensor] = [_pinned(g.contiguous()) for g in grids]
+        self.masks: List[torch.Tensor] = []
+        self._absmax_bits = None
+        self._absmax: Optional[float] = None
+        if masks is not None:
+            for g, m in zip(self.grids, masks):
+                _lib.require_cuda(m)
+                if m.dtype != torch.uint8 or tuple(m.shape) != tuple(g.shape[:2]) or not m.is_contiguous():
+                    raise ValueError("HostSlide: masks are contiguous uint8 [X, Y] device tensors, one per grid")
+            self.masks = list(masks)
+            self._absmax = float(absmax)
+            return
+        with torch.cuda.device(self.device):
+            self._mask_pass(int(bounce_bytes), bounce)
+
+    def _mask_pass(self, bounce_bytes: int, bounce: Optional[torch.Tensor]):
+        dev, es = self.device, self.grids[0].element_size()
+        if bounce is None:
+            # (no larger than the largest grid; whole rows)
+            largest = max(g.numel() * es for g in self.grids)
+            plan_mask_chunks(1, self.dim, es, bounce_bytes)                       # raises if the budget holds no row
+            bounce = torch.empty((min(int(bounce_bytes), largest),), dtype=torch.uint8, device=dev)
+        else:
+            _lib.require_cuda(bounce)
+            assert bounce.dtype == torch.uint8 and bounce.is_contiguous() and bounce.data_ptr() % 16 == 0
+        self._absmax_bits = torch.zeros((1,), dtype=torch.int32, device=dev)
+        name = "paths_tissue_mask_absmax_h16" if self.dtype == torch.float16 else "paths_tissue_mask_absmax"
+        for g in self.grids:
+            X, Y, D = g.shape
+            m = torch.empty((X, Y), dtype=torch.uint8, device=dev)
+            flat = g.view(X * Y, D)
+            for r0, rows in plan_mask_chunks(X * Y, D, es, bounce.numel()):
+                assert flat.is_pinned()
+                chunk = bounce[:rows * D * es].view(self.dtype).view(rows, D)
+                chunk.copy_(flat[r0:r0 + rows], non_blocking=True)               # same stream as the kernel: chunks follow each other
+                _lib.call(name, chunk.data_ptr(), rows, D, m.data_ptr() + r0, self._absmax_bits.data_ptr(), _lib.stream())
+            self.masks.append(m)
+        # the host must not re-use or free the bounce buffer's view of the last chunk early; the pass is once per slide
+        torch.cuda.current_stream(dev).synchronize()
+
+    feature_absmax = DeviceSlide.feature_absmax
+    num_levels = DeviceSlide.num_levels
+    shape = DeviceSlide.shape
+    dim = DeviceSlide.dim
+
+    def host_bytes(self) -> int:
+        """Pinned host memory held by the grids."""
+        return sum(g.numel() * g.element_size() for g in self.grids)
+
+    def to_device(self) -> DeviceSlide:
+        """The equivalent resident slide (a full upload of every grid)."""
+        s = DeviceSlide([g.to(self.device, non_blocking=True) for g in self.grids], patch_size=self.patch_size, slide_id=self.slide_id,
+                        subtype=self.subtype)
+        if hasattr(self, "synthetic_spec"):
+            s.synthetic_spec = self.synthetic_spec
+        return s
+
+    @staticmethod
+    def from_host(grids: Sequence, device="cuda", dtype=torch.float32, **kw) -> "HostSlide":
+        """Host grids (numpy or CPU tensors) as pinned ``dtype`` grids (torch.float16: converted by :func:`to_float16`, which raises on
+        values fp16 cannot hold).  Grids that already are pinned tensors of ``dtype`` are used where they are."""
+        if check_grid_dtype(dtype) == torch.float16:
+            conv = [g if (torch.is_tensor(g) and g.dtype == torch.float16) else to_float16(g)[0] for g in grids]
+        else:
+            conv = [torch.as_tensor(g, dtype=torch.float32) for g in grids]
+        return HostSlide(conv, device=device, **kw)
+
+    @staticmethod
+    def from_preprocessed(root: str, slide_id: str, powers: Sequence[float], device="cuda", patch_size: int = 256,
+                          subtype=None, dtype=torch.float32, **kw) -> "HostSlide":
+        """The file contract of :meth:`DeviceSlide.from_preprocessed` (``<root>/<slide_id>_<power:.3f>.pt``, one [X, Y, D] float tensor
+        per magnification), kept in pinned host memory.  The dtype and every path are checked before the device is touched."""
+        import os
+        check_grid_dtype(dtype)
+        paths = [os.path.join(root, slide_id + f"_{power:.3f}.pt") for power in powers]
+        for path in paths:
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"Pre-process load: path '{path}' not found!")
+        grids = []
+        for path in paths:
+            g = torch.load(path, map_location="cpu")
+            assert g.dim() == 3, f"{path}: expected a [X, Y, D] grid, got {tuple(g.shape)}"
+            grids.append(g.float() if dtype == torch.float32 else g)
+        return HostSlide.from_host(grids, device, dtype=dtype, patch_size=patch_size, slide_id=slide_id, subtype=subtype, **kw)
+
+    @staticmethod
+    def synthetic(seed: int, slide: int, base_shape: Tuple[int, int], dim: int = 1024, num_levels: int = 5, p_bg: float = 0.1,
+                  device="cuda", patch_size: int = 256, dtype=torch.float32, **kw) -> "HostSlide":
+        """The counter-based synthetic pyramid of :meth:`DeviceSlide.synthetic`, generated on the host (synthetic.SyntheticSlide.grid:
+        the same bytes) straight into pinned memory."""
+        h16 = check_grid_dtype(dtype) == torch.float16
+        spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg, feature_dtype="float16" if h16 else "float32")
+        grids = []
+        for l in range(num_levels):
+            X, Y = spec.shape(l)
+            g = torch.empty((X, Y, dim), dtype=dtype, pin_memory=True)
+            g.copy_(torch.from_numpy(spec.grid(l)))             # (fp16: the values are fp16-representable already, the cast is exact)
+            grids.append(g)
+        s = HostSlide(grids, device=device, patch_size=patch_size, slide_id=f"synthetic-{seed}-{slide}", **kw)
+        s.synthetic_spec = spec
+        return s
+
+
 class DeviceSlideBatch:
     """Per-batch device tables (grid / mask base pointers and grid dims per level) built ONCE.
 
     ``torch.tensor(list, device=...)`` is a blocking host->device copy that also waits for everything queued on
     the stream; building these tables inside every recursion call cost ~1.5 ms of idle GPU per step.
+
+    The slides are all :class:`DeviceSlide` or all :class:`HostSlide` (``host_resident``: ``grid_ptrs`` then hold pinned host
+    addresses, which the device can dereference; the recursion stages the selected rows into HBM, paths_stage_rows).
     """
 
     def __init__(self, slides):
         assert len(slides) > 0
         self.slides = list(slides)
-        dev = self.slides[0].grids[0].device
+        kinds = {bool(getattr(s, "host_resident", False)) for s in self.slides}
+        if len(kinds) != 1:
+            raise ValueError("DeviceSlideBatch: slides of one batch are all resident (DeviceSlide) or all host-resident (HostSlide)")
+        self.host_resident = kinds.pop()
+        dev = (self.slides[0].masks if self.host_resident else self.slides[0].grids)[0].device
         L = min(s.num_levels for s in self.slides)
         self.device, self.num_levels = dev, L
         self.dim = self.slides[0].dim
@@ -175,7 +340,13 @@ class DeviceSlideBatch:
         def table(fn, dtype):
             return [torch.tensor([fn(s, l) for s in self.slides], device=dev, dtype=dtype) for l in range(L)]
 
-        self.grid_ptrs = table(lambda s, l: s.grids[l].data_ptr(), torch.int64)
+        def grid_ptr(s, l):
+            g = s.grids[l]
+            if self.host_resident:          # a kernel that touches pageable host memory faults: only pinned grids get into the table
+                assert (not g.is_cuda) and g.is_pinned() and g.is_contiguous(), "HostSlide grids must be pinned host memory"
+            return g.data_ptr()
+
+        self.grid_ptrs = table(grid_ptr, torch.int64)
         self.mask_ptrs = table(lambda s, l: s.masks[l].data_ptr(), torch.int64)
         self.gx = table(lambda s, l: s.shape(l)[0], torch.int32)
         self.gy = table(lambda s, l: s.shape(l)[1], torch.int32)

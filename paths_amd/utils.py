@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .data_utils.slide import DeviceSlide, DeviceSlideBatch
+from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide
 
 
 def nll_loss(hazards, y, c, alpha=0.4, eps=1e-7):
@@ -93,6 +93,9 @@ class GraphedRecursion:
     def __init__(self, model, slides, keep_patches: Sequence[int], num_levels: int):
         self.model, self.keep, self.levels = model, list(keep_patches), int(num_levels)
         self.batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+        if self.batch.host_resident:
+            raise NotImplementedError("GraphedRecursion: host-resident slides (HostSlide) are not captured into a HIP graph; use "
+                                      "TapedRecursion / PipelinedRecursion or recurse()")
         self.graph, self.out, self.versions = None, None, None
 
     def _param_versions(self):
@@ -206,7 +209,8 @@ class TapedRecursion:
         return self
 
     def rebind(self, slides) -> "TapedRecursion":
-        """Point the recorded tape at ANOTHER batch of resident slides without recording again (a stream of distinct slides would
+        """Point the recorded tape at ANOTHER batch of slides of the same kind (resident, or host-resident: one recorded launch sequence
+        then serves a whole cohort streamed from pinned host memory) without recording again (a stream of distinct slides would
         otherwise pay record() per batch or run eager).  The tape addresses the recorded batch's per-level TABLE tensors (grid / mask
         base pointers, grid dims: a private copy made by record()), never the slides themselves, and every capacity in it is static - so a batch
         with the same slide count, feature width and level count whose level-0 cell count, grid extents and operand range fit the
@@ -216,6 +220,9 @@ class TapedRecursion:
         rec = self._rec_batch
         if new.dtype != self.batch.dtype:           # (the launches differ by grid dtype: a tape never serves both)
             raise ValueError(f"rebind: the tape serves {self.batch.dtype} grids, the new batch holds {new.dtype} grids")
+        if new.host_resident != self.batch.host_resident:      # (a host batch's tape stages its rows, a resident batch's does not)
+            kind = lambda h: "host-resident" if h else "resident"
+            raise ValueError(f"rebind: the tape serves {kind(self.batch.host_resident)} slides, the new batch is {kind(new.host_resident)}")
         fits = (self.tape is not None and rec is not None and len(new) == len(rec) and new.dim == rec.dim and new.device == rec.device
                 and new.num_levels >= self.levels and new.n0 <= rec.n0
                 and all(new.max_dim[l] <= rec.max_dim[l] for l in range(self.levels))
@@ -392,7 +399,8 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                   trace: Optional[list], careful: bool, agg_stream, par_stream=None, attention: bool = False,
                   rollout: bool = False) -> Dict[str, torch.Tensor]:
     """Run all levels for a batch of HBM-resident slides (a list of DeviceSlide, or a DeviceSlideBatch built once
-    and re-used across calls).  Returns the last level's output dict (+ "status").
+    and re-used across calls) or of host-resident ones (HostSlide: the rows a level selected are staged into HBM over the host link
+    right after their addresses are known, paths_stage_rows).  Returns the last level's output dict (+ "status").
 
     ``trace`` (a list) receives one dict per level with device tensors num_ims / locs / parent_inds / importance /
     logits / ctx_slide / keep_idx / keep_count, for parity tests and heat-map export; with ``attention`` also attention /
@@ -427,11 +435,21 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
     zero_row = torch.zeros((D,), **f32) if rows_in_place else None
     fts = None if rows_in_place else torch.empty((B, N, D), **f32)
     x_rows = torch.empty((B, N), **i64) if rows_in_place else None
+    # Host-resident slides: the grid addresses are pinned host memory.  Where rows are copied (fts) the copying kernel reads them over
+    # the host link once and nothing else does; where they are read in place, the address table is staged: the selected rows are
+    # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
+    stage_host = batch.host_resident and rows_in_place
+
+    def stage_rows(rows, n, stream):
+        buf = torch.empty((B, n, D), device=dev, dtype=batch.dtype)
+        ops.timed("stage", lambda: _lib.call("paths_stage_rows", p(rows), B * n, D * buf.element_size(), p(buf), p(zero_row), stream))
+        return buf
     locs = torch.empty((B, N, 2), **i64)
     parent_inds = torch.empty((B, N), **i64)
     num_ims = torch.empty((B,), **i64)
     _lib.call("paths_level0_batch" + sfx, p(grid_ptrs[0]), p(gx[0]), p(gy[0]), B, D, mc.patch_size, N,
               p(fts), p(locs), p(parent_inds), p(num_ims), 0, p(x_rows), p(zero_row), st)
+    staged = stage_rows(x_rows, N, st) if stage_host else None          # (what x_rows addresses now; alive while the level reads it)
     state_prev, ctx_hist, parent = None, [], None
     out = None
     # The aggregator of level i (attention, token chain, classifier) feeds nothing of level i+1 except the slide context, so
@@ -549,7 +567,7 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                     _lib.call("paths_fallback_all_cells", p(gx[i + 1]), p(gy[i + 1]), p(mask_ptrs[i + 1]), mc.patch_size, B, Nn,
                               p(num_next), p(locs_next), p(parent_next), p(src_row), p(src_cell), p(status),
                               p(hp_row) if share_parent else None, st2)
-            x_rows_next = None
+            x_rows_next, staged_next = None, None
             if share_parent:
                 # children only need their parent's c row (h enters through the per-parent partials below)
                 Hc = Dp - D
@@ -561,6 +579,8 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                     ops.timed("gather", lambda: _lib.call(
                         "paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
                         p(src_row), Hc, p(num_next), B, Nn, None, p(state_next), 0, p(x_rows_next), p(zero_row), st2))
+                    if stage_host:
+                        staged_next = stage_rows(x_rows_next, Nn, st2)
                 else:
                     fts_next = torch.empty((B, Nn, D), **f32)
                     _lib.call("paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
@@ -574,10 +594,11 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
                           p(num_next), B, Nn, p(fts_next), p(state_next), 0, None, None, st2)
             if forked:
                 fork_pending = True
-                keepalive.append((num_next, locs_next, parent_next, src_row, src_cell, hp_row, parent, fts_next, x_rows_next))
+                keepalive.append((num_next, locs_next, parent_next, src_row, src_cell, hp_row, parent, fts_next, x_rows_next, staged_next))
         if rec is not None:
             rec["keep_idx"], rec["keep_count"] = keep_idx, keep_count
         fts, x_rows, locs, parent_inds, num_ims, state_prev, N = fts_next, x_rows_next, locs_next, parent_next, num_next, state_next, Nn
+        staged = staged_next
     if overlap:
         _lib.stream_wait(main_stream, side_stream)
         if par_stream is not None:
@@ -774,10 +795,10 @@ def train_step(model, optimizer, batch, num_levels, keep_patches, task: str = "s
 
 
 def inference_end2end(num_levels, keep_patches, model, base_power, batch, task: str):
-    """reference utils.py:228-279.  ``batch["slide"]`` is a list of :class:`DeviceSlide`; labels as in the reference
+    """reference utils.py:228-279.  ``batch["slide"]`` is a list of :class:`DeviceSlide` (or of :class:`HostSlide`); labels as in the reference
     (``survival_bin`` / ``censored`` or ``subtype``).  Returns (hazards or logits, loss)."""
     slides = batch["slide"]
-    dev = slides.device if isinstance(slides, DeviceSlideBatch) else slides[0].grids[0].device
+    dev = slides.device if isinstance(slides, DeviceSlideBatch) else slides[0].masks[0].device
     out = recurse(model, slides, keep_patches, num_levels)
     logits = out["logits"]
     if task == "survival":
