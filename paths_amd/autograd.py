@@ -3,9 +3,12 @@
 torch's autograd ENGINE only orders the calls and accumulates ``.grad``; every derivative is computed by the HIP
 launch sequences of paths_amd/backward.py:
 
-  * :class:`LevelFn`  — one magnification level (``PATHSProcessor.process``): forward = the training forward that keeps
-    the tensors the backward needs, backward = transformer_backward + selection_backward;
-  * :class:`GatherFn` — the child gather between levels (``PreprocessedSlide.iter``): backward = paths_gather_rows_bwd.
+  * :class:`LevelFn`  - one magnification level (``PATHSProcessor.process``), entered through :func:`level_apply`: forward = the
+    training forward that keeps the tensors the backward needs, backward = transformer_backward + selection_backward.  One Function
+    serves the LSTM level per child, the LSTM level in the once-per-parent form and the lstm = false level;
+  * :class:`GatherFn` / :class:`GatherParentFn` - the child gather between levels (``PreprocessedSlide.iter``) per child / once per
+    parent: backward = paths_gather_rows_bwd / paths_sibling_sum + paths_scatter_kept_rows;
+  * :class:`AggregatorFn` - a ``TransformerAggregator`` on its own.
 
 Training covers lstm = true / false and slide_ctx_mode residual / concat / none.  Dropout > 0 in train mode runs the
 transformer's row chain on the generic kernels with regenerated masks (paths_amd/backward.py:Drop).
@@ -169,17 +172,6 @@ def next_dropout_seed(device) -> int:
     return z ^ (z >> 29)
 
 
-def check_dropout_supported(proc):
-    """Every entry to the differentiable path passes here (LevelFn.forward): a config with dropout > 0 in train mode is
-    never silently run with its five dropout sites per layer as identity (reference model/aggregator.py:25-33)."""
-    if proc.training and proc.config.dropout > 0 and not DROPOUT_IMPLEMENTED:
-        raise NotImplementedError("dropout > 0 in train mode is not implemented on the HIP path: set model_config.dropout = 0 "
-                                  "or call model.eval()")
-
-
-DROPOUT_IMPLEMENTED = True
-
-
 def _detached_saves(sel: dict, tr: dict):
     """The dicts kept on ctx for the backward, with the tensors that forward() RETURNS replaced by detached aliases.  A returned
     tensor gets grad_fn = this node, the node owns ctx, and ctx -> dict -> that tensor would close a reference cycle through C++
@@ -194,14 +186,28 @@ def _detached_saves(sel: dict, tr: dict):
 
 
 class LevelFn(torch.autograd.Function):
+    """One magnification level.  ``lstm`` given (config.lstm = true): the LSTM selection chain, either per child (``state_prev`` [B,N,Dp]
+    or None at level 0) or in the device recursion's once-per-parent form: instead of a per-child copy of the parent state the level
+    takes the children's inherited memory cell ``c0`` [B,N,Hc], the kept parents' h rows ``h_kept`` [B*cap, D] and ``parent`` = {"hp_row":
+    child -> kept-slot map, "child_pos", "keep_count", "cap"} (paths_amd/backward.py:selection_forward_train ``parent=``); gradients come
+    back for ``c0`` and ``h_kept``.  config.lstm = false (reference model/paths.py:95-109): same transformer, the selection chain is
+    alpha * X + hctx_mlp(previous Z) (paths_amd/backward.py:selection_forward_train_nolstm)."""
+
     @staticmethod
-    def forward(ctx, proc, lstm, fts, locs, num_ims, state_prev, ctx_prev, *params):
+    def forward(ctx, proc, lstm, fts, locs, num_ims, state_prev, c0, h_kept, parent, ctx_prev, *params):
         """ctx_prev: [B,d] (slide_ctx_mode "residual": the previous level's slide context) or [B,depth,d] (mode "concat": all
         previous levels' slide contexts, reference model/paths.py:134-137) or None."""
         mc = proc.config
-        check_dropout_supported(proc)
-        lp, vp = ops.pack_lstm(lstm), ops.pack_level(proc)
-        sel = bw.selection_forward_train(mc, lp, vp, fts, locs.contiguous(), num_ims.contiguous(), state_prev)
+        if mc.lstm:
+            lp, vp = ops.pack_lstm(lstm), ops.pack_level(proc)
+            if parent is not None:
+                parent = dict(parent, c0=c0, h_kept=h_kept, cap=int(parent["cap"]))
+            sel = bw.selection_forward_train(mc, lp, vp, fts, locs.contiguous(), num_ims.contiguous(), state_prev, parent=parent)
+        else:
+            vp = ops.pack_level(proc)
+            if state_prev is not None:
+                state_prev = state_prev.contiguous()
+            sel = bw.selection_forward_train_nolstm(mc, vp, fts, locs.contiguous(), num_ims.contiguous(), state_prev)
         res = ctx_prev if (mc.slide_ctx_mode == "residual" and ctx_prev is not None) else None
         cat = ctx_prev.contiguous() if (mc.slide_ctx_mode == "concat" and ctx_prev is not None and ctx_prev.shape[1] > 0) else None
         assert res is None or res.dim() == 2
@@ -222,86 +228,60 @@ class LevelFn(torch.autograd.Function):
         proc, lstm, sel, tr = ctx.proc, ctx.lstm, ctx.sel, ctx.tr
         ctx.sel = ctx.tr = None                     # the saved activations die with this call (see _detached_saves)
         mc = proc.config
-        lp, vp = ops.pack_lstm(lstm), ops.pack_level(proc)
+        lp = ops.pack_lstm(lstm) if mc.lstm else None
+        vp = ops.pack_level(proc)
         cont = lambda t: t.contiguous() if t is not None else None
-        # Parameters without a path to the loss get NO gradient (None, as in the reference: AdamW then leaves them alone, weight
-        # decay included).  no_agg: neither this level's logits nor its slide context are used downstream (non-final levels
-        # under slide_ctx_mode "none"): the whole aggregator, proj_in and - its only consumer being the tokens - the
-        # importance MLP are cut off; importance_mode != "mul": the importance only drives the (non-differentiable) top-K.
-        no_agg = d_logits is None and d_ctx_out is None
+        no_agg = d_logits is None and d_ctx_out is None      # (see _aggregator_grads)
         with bw.deferred_reductions():               # the ~35 slab reductions of this level's parameter gradients: one launch
             if no_agg:
                 tg, d_ctx_prev = None, None
                 d_tok = torch.zeros_like(tr["tokens"])
             else:
                 tg, d_tok, d_ctx_prev = bw.transformer_backward(mc, vp, tr, cont(d_logits), cont(d_ctx_out))
-            sg, d_state_prev = bw.selection_backward(mc, lp, vp, sel, d_tok, cont(d_state_out))
-        grads = _level_grads(mc, lstm, sg, tg, no_agg, d_logits is not None)
-        return (None, None, None, None, None, d_state_prev if ctx.has_state else None,
-                d_ctx_prev if ctx.has_ctx else None, *grads)
-
-
-class LevelParentFn(torch.autograd.Function):
-    """:class:`LevelFn` in the device recursion's once-per-parent form: instead of a per-child copy of the parent state the level takes
-    the children's inherited memory cell ``c0`` [B,N,Hc], the kept parents' h rows ``h_kept`` [B*cap, D] and the child -> kept-slot map
-    (paths_amd/backward.py:selection_forward_train ``parent=``); gradients come back for ``c0`` and ``h_kept``."""
-
-    @staticmethod
-    def forward(ctx, proc, lstm, fts, locs, num_ims, c0, h_kept, hp_row, child_pos, keep_count, cap, ctx_prev, *params):
-        mc = proc.config
-        check_dropout_supported(proc)
-        lp, vp = ops.pack_lstm(lstm), ops.pack_level(proc)
-        sel = bw.selection_forward_train(mc, lp, vp, fts, locs.contiguous(), num_ims.contiguous(), None,
-                                         parent={"c0": c0, "h_kept": h_kept, "hp_row": hp_row, "child_pos": child_pos,
-                                                 "keep_count": keep_count, "cap": int(cap)})
-        res = ctx_prev if (mc.slide_ctx_mode == "residual" and ctx_prev is not None) else None
-        cat = ctx_prev.contiguous() if (mc.slide_ctx_mode == "concat" and ctx_prev is not None and ctx_prev.shape[1] > 0) else None
-        drop = None
-        if proc.training and mc.dropout > 0:
-            drop = bw.Drop(mc.dropout, next_dropout_seed(fts.device), proc.depth)
-        tr = bw.transformer_forward_train(mc, vp, sel["tokens"], sel["num_ims"], res, drop, cat)
-        ctx.proc, ctx.lstm = proc, lstm
-        ctx.sel, ctx.tr = _detached_saves(sel, tr)
-        ctx.has_ctx = res is not None or cat is not None
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(sel["importance"])
-        return tr["logits"], tr["ctx_out"], sel["state_out"], sel["importance"]
-
-    @staticmethod
-    def backward(ctx, d_logits, d_ctx_out, d_state_out, _d_imp):
-        proc, lstm, sel, tr = ctx.proc, ctx.lstm, ctx.sel, ctx.tr
-        ctx.sel = ctx.tr = None
-        mc = proc.config
-        lp, vp = ops.pack_lstm(lstm), ops.pack_level(proc)
-        cont = lambda t: t.contiguous() if t is not None else None
-        no_agg = d_logits is None and d_ctx_out is None
-        with bw.deferred_reductions():
-            if no_agg:
-                tg, d_ctx_prev = None, None
-                d_tok = torch.zeros_like(tr["tokens"])
+            if mc.lstm:
+                sg, d_prev = bw.selection_backward(mc, lp, vp, sel, d_tok, cont(d_state_out))
             else:
-                tg, d_tok, d_ctx_prev = bw.transformer_backward(mc, vp, tr, cont(d_logits), cont(d_ctx_out))
-            sg, (d_c0, d_hk) = bw.selection_backward(mc, lp, vp, sel, d_tok, cont(d_state_out))
-        grads = _level_grads(mc, lstm, sg, tg, no_agg, d_logits is not None)
-        return (None, None, None, None, None, d_c0, d_hk, None, None, None, None, d_ctx_prev if ctx.has_ctx else None, *grads)
+                sg, d_prev = bw.selection_backward_nolstm(mc, vp, sel, d_tok, cont(d_state_out))
+        # the selection backward's second result: (d_c0, d_h_kept) in the once-per-parent form, else d_state_prev
+        d_state_prev, (d_c0, d_hk) = (None, d_prev) if sel.get("parent") is not None else (d_prev if ctx.has_state else None, (None, None))
+        grads = _level_grads(mc, lstm, sg, tg, d_logits is not None)
+        return (None, None, None, None, None, d_state_prev, d_c0, d_hk, None, d_ctx_prev if ctx.has_ctx else None, *grads)
 
 
-def _level_grads(mc, lstm, sg, tg, no_agg: bool, has_logits: bool):
-    """Parameter gradients of one level in the order of lstm_params + level_params (None where there is no path to the loss)."""
+def _aggregator_grads(mc, tg, proj_in=None, has_logits: bool = False):
+    """The aggregator part of a gradient list from transformer_backward's ``tg``: [``proj_in`` = (proj_in.weight, proj_in.bias, special
+    token) of a level,] LAYER_ORDER per decoder layer, the final norm [, a level's classifier].  ``proj_in`` None = a standalone
+    aggregator (AggregatorFn).
+
+    Parameters without a path to the loss get NO gradient (None, as in the reference: AdamW then leaves them alone, weight decay
+    included).  ``tg`` None (no_agg): neither this level's logits nor its slide context are used downstream (non-final levels under
+    slide_ctx_mode "none"): the whole aggregator, proj_in and - its only consumer being the tokens - the LSTM level's importance MLP
+    are cut off (lstm = false: Z = alpha X + hctx still reaches the next level); no logits gradient: the classifier is cut off."""
+    if tg is None:
+        return [None] * (3 + len(LAYER_ORDER) * mc.trans_layers + 4)
+    grads = list(proj_in) if proj_in is not None else []
+    for g in tg["layers"]:
+        grads += [g[key] for _, key in LAYER_ORDER]
+    grads += [tg["lnfg"], tg["lnfb"]]
+    if proj_in is not None:
+        grads += [tg["wcls"], tg["bcls"]] if has_logits else [None, None]
+    return grads
+
+
+def _level_grads(mc, lstm, sg, tg, has_logits: bool):
+    """Parameter gradients of one level in the order of lstm_params + level_params, or of level_params_nolstm (None where there is
+    no path to the loss: _aggregator_grads)."""
+    if not mc.lstm:
+        v = lambda t, shape: t.view(shape) if t is not None else None
+        grads = [sg["w1"], sg["b1"], v(sg["w2"], (1, -1)), sg["b2"], sg["wh1"], sg["bh1"], sg["wh2"], sg["bh2"]]
+        return grads + _aggregator_grads(mc, tg, (sg["wp"], sg["bp"], sg["special"]), has_logits)
     lg = bw.unpack_lstm_grads(lstm, sg)
     grads = [lg[k] for k in LSTM_ORDER]
     Hi = mc.importance_mlp_hidden_dim
-    imp_live = mc.importance_mode == "mul" and not no_agg
+    # importance_mode != "mul": the importance only drives the (non-differentiable) top-K
+    imp_live = mc.importance_mode == "mul" and tg is not None
     grads += [sg["w_ip"][:Hi], sg["b1"], sg["w2"].view(1, -1), sg["b2"]] if imp_live else [None] * 4
-    if no_agg:
-        grads += [None] * (3 + len(LAYER_ORDER) * mc.trans_layers + 4)
-    else:
-        grads += [sg["w_ip"][Hi:], sg["bp"], sg["special"]]
-        for l, g in enumerate(tg["layers"]):
-            grads += [g[key] for _, key in LAYER_ORDER]
-        grads += [tg["lnfg"], tg["lnfb"]]
-        grads += [tg["wcls"], tg["bcls"]] if has_logits else [None, None]
-    return grads
+    return grads + _aggregator_grads(mc, tg, (sg["w_ip"][Hi:], sg["bp"], sg["special"]), has_logits)
 
 
 def aggregator_params(agg) -> List[torch.nn.Parameter]:
@@ -340,11 +320,7 @@ class AggregatorFn(torch.autograd.Function):
         mc, vp = agg._geometry(), ops.pack_aggregator(agg)
         with bw.deferred_reductions():
             tg, d_tok, _ = bw.transformer_backward(mc, vp, tr, None, d_out.contiguous())
-        grads = []
-        for g in tg["layers"]:
-            grads += [g[key] for _, key in LAYER_ORDER]
-        grads += [tg["lnfg"], tg["lnfb"]]
-        return (None, d_tok, None, *grads)
+        return (None, d_tok, None, *_aggregator_grads(mc, tg))
 
 
 class GatherParentFn(torch.autograd.Function):
@@ -386,70 +362,17 @@ class GatherParentFn(torch.autograd.Function):
 
 
 def level_params_nolstm(proc) -> List[torch.nn.Parameter]:
-    """lstm = false: the level's live parameters incl. its hctx_mlp, in the order LevelFnNoLstm returns their gradients."""
+    """lstm = false: the level's live parameters incl. its hctx_mlp, in the order LevelFn returns their gradients."""
     return [proc.importance_mlp[0].weight, proc.importance_mlp[0].bias, proc.importance_mlp[2].weight, proc.importance_mlp[2].bias,
             proc.hctx_mlp[0].weight, proc.hctx_mlp[0].bias, proc.hctx_mlp[2].weight, proc.hctx_mlp[2].bias] + level_params(proc)[4:]
 
 
-class LevelFnNoLstm(torch.autograd.Function):
-    """One level of the lstm = false variant (reference model/paths.py:95-109): same transformer as LevelFn, the selection chain
-    is alpha * X + hctx_mlp(previous Z) (paths_amd/backward.py:selection_forward_train_nolstm)."""
-
-    @staticmethod
-    def forward(ctx, proc, fts, locs, num_ims, state_prev, ctx_prev, *params):
-        mc = proc.config
-        check_dropout_supported(proc)
-        vp = ops.pack_level(proc)
-        if state_prev is not None:
-            state_prev = state_prev.contiguous()
-        sel = bw.selection_forward_train_nolstm(mc, vp, fts, locs.contiguous(), num_ims.contiguous(), state_prev)
-        res = ctx_prev if (mc.slide_ctx_mode == "residual" and ctx_prev is not None) else None
-        cat = ctx_prev.contiguous() if (mc.slide_ctx_mode == "concat" and ctx_prev is not None and ctx_prev.shape[1] > 0) else None
-        drop = None
-        if proc.training and mc.dropout > 0:
-            drop = bw.Drop(mc.dropout, next_dropout_seed(fts.device), proc.depth)
-        tr = bw.transformer_forward_train(mc, vp, sel["tokens"], sel["num_ims"], res, drop, cat)
-        ctx.proc = proc
-        ctx.sel, ctx.tr = _detached_saves(sel, tr)
-        ctx.has_state, ctx.has_ctx = state_prev is not None, (res is not None or cat is not None)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(sel["importance"])
-        return tr["logits"], tr["ctx_out"], sel["state_out"], sel["importance"]
-
-    @staticmethod
-    def backward(ctx, d_logits, d_ctx_out, d_state_out, _d_imp):
-        proc, sel, tr = ctx.proc, ctx.sel, ctx.tr
-        ctx.sel = ctx.tr = None
-        mc = proc.config
-        vp = ops.pack_level(proc)
-        cont = lambda t: t.contiguous() if t is not None else None
-        no_agg = d_logits is None and d_ctx_out is None          # (see LevelFn.backward; here Z = alpha X + hctx still reaches the next level)
-        with bw.deferred_reductions():
-            if no_agg:
-                tg, d_ctx_prev = None, None
-                d_tok = torch.zeros_like(tr["tokens"])
-            else:
-                tg, d_tok, d_ctx_prev = bw.transformer_backward(mc, vp, tr, cont(d_logits), cont(d_ctx_out))
-            sg, d_state_prev = bw.selection_backward_nolstm(mc, vp, sel, d_tok, cont(d_state_out))
-        v = lambda t, shape: t.view(shape) if t is not None else None
-        grads = [sg["w1"], sg["b1"], v(sg["w2"], (1, -1)), sg["b2"], sg["wh1"], sg["bh1"], sg["wh2"], sg["bh2"]]
-        if no_agg:
-            grads += [None] * (3 + len(LAYER_ORDER) * mc.trans_layers + 4)
-        else:
-            grads += [sg["wp"], sg["bp"], sg["special"]]
-            for l, g in enumerate(tg["layers"]):
-                grads += [g[key] for _, key in LAYER_ORDER]
-            grads += [tg["lnfg"], tg["lnfb"]]
-            grads += [tg["wcls"], tg["bcls"]] if d_logits is not None else [None, None]
-        return (None, None, None, None, d_state_prev if (ctx.has_state and d_state_prev is not None) else None,
-                d_ctx_prev if ctx.has_ctx else None, *grads)
-
-
-def level_apply(proc, lstm, fts, locs, num_ims, state_prev, ctx_prev):
-    """Differentiable ``process``: returns (logits, ctx_slide, ctx_patch, importance)."""
-    if not proc.config.lstm:
-        return LevelFnNoLstm.apply(proc, fts, locs, num_ims, state_prev, ctx_prev, *level_params_nolstm(proc))
-    return LevelFn.apply(proc, lstm, fts, locs, num_ims, state_prev, ctx_prev, *lstm_params(lstm), *level_params(proc))
+def level_apply(proc, lstm, fts, locs, num_ims, state_prev, ctx_prev, parent=None):
+    """Differentiable ``process``: returns (logits, ctx_slide, ctx_patch, importance).  ``parent`` (LSTM only, ``state_prev`` None then):
+    the once-per-parent inputs {"c0", "h_kept", "hp_row", "child_pos", "keep_count", "cap"} of :class:`LevelFn`."""
+    params = lstm_params(lstm) + level_params(proc) if proc.config.lstm else level_params_nolstm(proc)
+    c0, h_kept = (parent["c0"], parent["h_kept"]) if parent is not None else (None, None)
+    return LevelFn.apply(proc, lstm, fts, locs, num_ims, state_prev, c0, h_kept, parent, ctx_prev, *params)
 
 
 class GatherFn(torch.autograd.Function):

@@ -343,37 +343,44 @@ def selection_forward_train(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_p
                   P(sv["y"]), D, P(sv["o"]), P(sv["frm"]), P(sv["tc"]), hp, hp_row, M, D, Hc, None, N, 7, st)
     sv["importance"] = torch.empty((B, N), **f32)
     sv["tokens"] = torch.empty((B, T, d), **f32)
-    Hi = mc.importance_mlp_hidden_dim
-    sv["hid"] = torch.empty((B, N, Hi), **f32)
+    sv["hid"] = torch.empty((B, N, mc.importance_mlp_hidden_dim), **f32)
     sv["pproj"] = torch.empty((B, N, d), **f32)
+    _importance_tokens(mc, lvl_pack, sv["y"], locs, num_ims, sv["importance"], sv["hid"], sv["pproj"], sv["tokens"],
+                       1 if mc.importance_mode == "mul" else 0, x6)
+    return sv
+
+
+def _importance_tokens(mc, lvl_pack, src, locs, num_ims, imp_out, hid_out, pproj_out, tokens_out, scale: int, x6: bool = False):
+    """Importance MLP + proj_in + positional encoding over the rows ``src`` [B,N,D], keeping hid = relu(src W1^T + b1) and
+    P = src Wp^T for the backward (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65).  ``scale`` 1: tokens =
+    importance * P + bp + PE; 0: tokens = P + bp + PE (importance_mode != "mul", or ``src`` is already scaled)."""
+    B, N, D = src.shape
+    d, Hi, M = mc.trans_dim, mc.importance_mlp_hidden_dim, B * N
+    st = _lib.stream()
     pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    div = P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"])
     if not ops.fast_path(mc):
-        # any (trans_dim, hidden) widths: two generic GEMMs + the row kernels of csrc/generic.hip, keeping hid = relu(Y W1^T + b1)
-        # and P = Y Wp^T for the backward (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65)
+        # any (trans_dim, hidden) widths: two generic GEMMs + the row kernels of csrc/generic.hip
         gp = ops.generic_pack(lvl_pack, mc)
-        ops.gemm_f32(sv["y"], D, gp["w1"], lvl_pack["b1"], sv["hid"], Hi, M, Hi, D, act=1)
-        _lib.call("paths_importance_rows", P(sv["hid"]), Hi, P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(num_ims), N, M, Hi, P(sv["importance"]), 0, st)
-        ops.gemm_f32(sv["y"], D, gp["wp"], None, sv["pproj"], d, M, d, D)
-        _lib.call("paths_tokens_assemble", P(sv["pproj"]), d, P(sv["importance"]), 1 if mc.importance_mode == "mul" else 0, P(lvl_pack["bp"]),
-                  P(lvl_pack["special"]), P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), P(locs), N, mc.patch_size, pe_mode, d, B,
-                  P(sv["tokens"]), st)
-        return sv
-    tail = (P(lvl_pack["b1"]), P(lvl_pack["w2"]), P(lvl_pack["b2"]),
-            P(lvl_pack["bp"]), P(lvl_pack["special"]), P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), None, 0, P(locs),
-            P(num_ims), N, mc.patch_size, pe_mode, 1 if mc.importance_mode == "mul" else 0, P(sv["importance"]),
-            P(sv["tokens"]), P(sv["hid"]), P(sv["pproj"]), M, D, mc.importance_mlp_hidden_dim, d, 0, st)
+        ops.gemm_f32(src, D, gp["w1"], lvl_pack["b1"], hid_out, Hi, M, Hi, D, act=1)
+        _lib.call("paths_importance_rows", P(hid_out), Hi, P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(num_ims), N, M, Hi, P(imp_out), 0, st)
+        ops.gemm_f32(src, D, gp["wp"], None, pproj_out, d, M, d, D)
+        _lib.call("paths_tokens_assemble", P(pproj_out), d, P(imp_out), scale, P(lvl_pack["bp"]), P(lvl_pack["special"]), div, P(locs), N,
+                  mc.patch_size, pe_mode, d, B, P(tokens_out), st)
+        return
+    tail = (P(lvl_pack["b1"]), P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(lvl_pack["bp"]), P(lvl_pack["special"]), div, None, 0, P(locs),
+            P(num_ims), N, mc.patch_size, pe_mode, scale, P(imp_out), P(tokens_out), P(hid_out), P(pproj_out), M, D, Hi, d, 0, st)
     if x6:
         TP = ops.TRAIN_FWD_PLANES
         wip, wip_s = ops._x6_of(lvl_pack, "w_ip_fwd", TP, lagged=True)
         # M / 128 blocks fill half the chip: two k halves on twice the blocks + the epilogue launch, as in inference (round 5)
         splitk_ws = None
         if TRAIN_SPLITK_IMPORTANCE and TP == 2 and (M + 127) // 128 <= 160:
-            splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=fts.device, dtype=torch.uint8)
-        _lib.call("paths_importance_proj_x6", P(sv["y"]), D, None, None, 0, P(wip), *tail[:-1], TP, wip_s, ops.A_SCALE if TP == 2 else 1.0,
+            splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=src.device, dtype=torch.uint8)
+        _lib.call("paths_importance_proj_x6", P(src), D, None, None, 0, P(wip), *tail[:-1], TP, wip_s, ops.A_SCALE if TP == 2 else 1.0,
                   P(splitk_ws), tail[-1])
     else:
-        _lib.call("paths_importance_proj", P(sv["y"]), D, P(lvl_pack["w_ip_fwd"]), *tail)
-    return sv
+        _lib.call("paths_importance_proj", P(src), D, P(lvl_pack["w_ip_fwd"]), *tail)
 
 
 def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_state_out: Optional[torch.Tensor]):
@@ -489,20 +496,9 @@ def selection_forward_train_nolstm(mc, lvl_pack, fts, locs, num_ims, state_prev)
     sv["tokens"] = torch.empty((B, T, d), **f32)
     sv["hid"] = torch.empty((B, N, Hi), **f32)
     scratch_p = torch.empty((B, N, d), **f32)
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
 
-    def imp_proj(src, imp_out, hid_out, pproj_out):
-        if not ops.fast_path(mc):      # any widths: generic GEMMs + row kernels (tokens = P + bp + PE: src is already scaled)
-            gp = ops.generic_pack(lvl_pack, mc)
-            ops.gemm_f32(src, D, gp["w1"], lvl_pack["b1"], hid_out, Hi, M, Hi, D, act=1)
-            _lib.call("paths_importance_rows", P(hid_out), Hi, P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(num_ims), N, M, Hi, P(imp_out), 0, st)
-            ops.gemm_f32(src, D, gp["wp"], None, pproj_out, d, M, d, D)
-            _lib.call("paths_tokens_assemble", P(pproj_out), d, P(imp_out), 0, P(lvl_pack["bp"]), P(lvl_pack["special"]),
-                      P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), P(locs), N, mc.patch_size, pe_mode, d, B, P(sv["tokens"]), st)
-            return
-        _lib.call("paths_importance_proj", P(src), D, P(lvl_pack["w_ip_fwd"]), P(lvl_pack["b1"]), P(lvl_pack["w2"]), P(lvl_pack["b2"]),
-                  P(lvl_pack["bp"]), P(lvl_pack["special"]), P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), None, 0, P(locs),
-                  P(num_ims), N, mc.patch_size, pe_mode, 0, P(imp_out), P(sv["tokens"]), P(hid_out), P(pproj_out), M, D, Hi, d, 0, st)
+    def imp_proj(src, imp_out, hid_out, pproj_out):      # (scale 0: pass 2's src is already scaled, pass 1's tokens are overwritten)
+        _importance_tokens(mc, lvl_pack, src, locs, num_ims, imp_out, hid_out, pproj_out, sv["tokens"], 0)
 
     imp_proj(fts, sv["importance"], sv["hid"], scratch_p)                    # pass 1: alpha and the importance MLP's hidden layer
     hctx = None

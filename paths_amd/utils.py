@@ -10,6 +10,7 @@ synchronisation inside the level loop: padded length per level is the static cap
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import contextlib
@@ -18,6 +19,15 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide
+
+OVERLAP_AGGREGATOR = os.environ.get("PATHS_OVERLAP_AGGREGATOR", "1") != "0"
+ZERO_GRAD_ALL = os.environ.get("PATHS_ZERO_GRAD_ALL", "0") != "0"     # train_step: optimizer.zero_grad(set_to_none=True) over ALL parameters (A/B)
+ROCTX_RANGES = os.environ.get("PATHS_ROCTX", "0") != "0"     # roctx ranges "level i: selection / aggregator / expansion" around the launches
+                                                             # of each level (rocprofv3 --marker-trace; torch.cuda.nvtx = roctx on ROCm)
+ROWS_IN_PLACE = os.environ.get("PATHS_ROWS_IN_PLACE", "1") != "0"
+TRAIN_PARENT = os.environ.get("PATHS_TRAIN_PARENT", "1") != "0"      # training: h half of the LSTM gates once per kept parent
+STREAM_LANE = 0      # which stream triple _recurse uses (TapedRecursion(lane=k) records each lane on its own streams)
+_STREAMS: Dict[int, tuple] = {}
 
 
 def nll_loss(hazards, y, c, alpha=0.4, eps=1e-7):
@@ -75,6 +85,20 @@ def check_status_word(status, fallback_done: bool = False) -> bool:
     return bool(code & 1) and not fallback_done
 
 
+def _param_versions(model):
+    """What a captured graph / recorded tape of ``model`` was built from: it is stale once any parameter's version counter has moved."""
+    return tuple((p.data_ptr(), p._version) for p in model.parameters())
+
+
+def _checked(rec, out) -> Dict[str, torch.Tensor]:
+    """The status check of :func:`recurse` behind a replay of ``rec`` (a Graphed / TapedRecursion): one host sync after the last level;
+    a batch with a slide without tissue children is handed to ``recurse()`` (eager, careful path)."""
+    if check_status_word(out["status"]):
+        with torch.no_grad():
+            return recurse(rec.model, rec.batch, rec.keep, rec.levels)
+    return out
+
+
 class GraphedRecursion:
     """One batch's whole recursion (all levels, all three streams) captured ONCE into a HIP graph and replayed per step.
 
@@ -98,9 +122,6 @@ class GraphedRecursion:
                                       "TapedRecursion / PipelinedRecursion or recurse()")
         self.graph, self.out, self.versions = None, None, None
 
-    def _param_versions(self):
-        return tuple((p.data_ptr(), p._version) for p in self.model.parameters())
-
     def capture(self):
         dev = self.batch.device
         with torch.no_grad():
@@ -110,22 +131,18 @@ class GraphedRecursion:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out = _recurse(self.model, self.batch, self.keep, self.levels, None, careful=False)
-        self.graph, self.out, self.versions = g, out, self._param_versions()
+        self.graph, self.out, self.versions = g, out, _param_versions(self.model)
         return self
 
     def replay(self) -> Dict[str, torch.Tensor]:
-        if self.graph is None or self.versions != self._param_versions():
+        if self.graph is None or self.versions != _param_versions(self.model):
             self.capture()
         self.graph.replay()
         return self.out
 
     def run(self) -> Dict[str, torch.Tensor]:
         """replay + the status check of :func:`recurse` (one host sync after the last level)."""
-        out = self.replay()
-        if check_status_word(out["status"]):
-            with torch.no_grad():
-                return recurse(self.model, self.batch, self.keep, self.levels)
-        return out
+        return _checked(self, self.replay())
 
 
 class TapedRecursion:
@@ -158,9 +175,6 @@ class TapedRecursion:
         self._pool = torch.cuda.MemPool()
         if model.procs[0].config.slide_ctx_mode == "concat":
             raise NotImplementedError("TapedRecursion: slide_ctx_mode='concat' is not taped; use recurse()")
-
-    def _param_versions(self):
-        return tuple((p.data_ptr(), p._version) for p in self.model.parameters())
 
     def close(self):
         """Drop the tape and destroy the HIP events of its stream joins (a service that records one tape per batch would otherwise
@@ -203,7 +217,7 @@ class TapedRecursion:
             STREAM_LANE = saved_lane
         # arguments pre-converted to their ctypes types once: a replayed call then skips ctypes' per-argument conversion
         tape = [(fn, tuple(a if a is None else t(a) for t, a in zip(fn.argtypes, args)), name) for fn, args, name in tape]
-        self.tape, self.out, self.versions = tape, out, self._param_versions()
+        self.tape, self.out, self.versions = tape, out, _param_versions(self.model)
         self.stream_handle = torch.cuda.current_stream(self.batch.device).cuda_stream
         self._rec_batch = tab
         return self
@@ -260,7 +274,7 @@ class TapedRecursion:
         """join=False leaves out the tape's last entry (the caller stream waiting for this lane's streams): several lanes
         (sub-batches recorded on different stream triples) are then enqueued back to back and run CONCURRENTLY; call
         :meth:`join` on each afterwards."""
-        if self.tape is None or self.versions != self._param_versions():
+        if self.tape is None or self.versions != _param_versions(self.model):
             self.record()
         assert torch.cuda.current_stream(self.batch.device).cuda_stream == self.stream_handle, "replay on the stream the tape was recorded on"
         assert self.tape[-1][2] == "paths_stream_wait"
@@ -274,11 +288,7 @@ class TapedRecursion:
 
     def run(self) -> Dict[str, torch.Tensor]:
         """replay + the status check of :func:`recurse` (one host sync after the last level)."""
-        out = self.replay()
-        if check_status_word(out["status"]):
-            with torch.no_grad():
-                return recurse(self.model, self.batch, self.keep, self.levels)
-        return out
+        return _checked(self, self.replay())
 
 
 class PipelinedRecursion:
@@ -298,21 +308,12 @@ class PipelinedRecursion:
     def result(self, k: int, check: bool = True) -> Dict[str, torch.Tensor]:
         t = self.tapes[k]
         t.join()
-        if check and check_status_word(t.out["status"]):
-            with torch.no_grad():
-                return recurse(t.model, t.batch, t.keep, t.levels)
-        return t.out
+        return _checked(t, t.out) if check else t.out
 
     def close(self):
         for t in self.tapes:
             t.close()
         self.tapes = []
-
-
-OVERLAP_AGGREGATOR = os.environ.get("PATHS_OVERLAP_AGGREGATOR", "1") != "0"
-ZERO_GRAD_ALL = os.environ.get("PATHS_ZERO_GRAD_ALL", "0") != "0"     # train_step: optimizer.zero_grad(set_to_none=True) over ALL parameters (A/B)
-ROCTX_RANGES = os.environ.get("PATHS_ROCTX", "0") != "0"     # roctx ranges "level i: selection / aggregator / expansion" around the launches
-                                                             # of each level (rocprofv3 --marker-trace; torch.cuda.nvtx = roctx on ROCm)
 
 
 class _Range:
@@ -329,12 +330,6 @@ class _Range:
         if ROCTX_RANGES:
             torch.cuda.nvtx.range_pop()
         return False
-ROWS_IN_PLACE = os.environ.get("PATHS_ROWS_IN_PLACE", "1") != "0"
-TRAIN_PARENT = os.environ.get("PATHS_TRAIN_PARENT", "1") != "0"      # training: h half of the LSTM gates once per kept parent
-_STREAMS: Dict[int, tuple] = {}
-
-
-STREAM_LANE = 0      # which stream triple _recurse uses (TapedRecursion(lane=k) records each lane on its own streams)
 
 
 def _streams(dev, lane: Optional[int] = None):
@@ -382,25 +377,177 @@ def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, att
         # hipStreamEndCapture, so every side stream forks from the capture's origin stream: the selection chain runs on the origin
         # stream itself, the aggregator and expansion streams fork from / join into it (the body joins them at its end)
         _lib.stream_wait(agg_stream, caller)
-        if par_stream is not None:
-            _lib.stream_wait(par_stream, caller)
+        _lib.stream_wait(par_stream, caller)
         return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention, rollout)
     _lib.stream_wait(sel_stream, caller)
     _lib.stream_wait(agg_stream, caller)
-    if par_stream is not None:
-        _lib.stream_wait(par_stream, caller)
+    _lib.stream_wait(par_stream, caller)
     with torch.cuda.stream(sel_stream):
         out = _recurse_body(model, batch, keep_patches, num_levels, trace, careful, agg_stream, par_stream, attention, rollout)
     _lib.stream_wait(caller, sel_stream)     # (the body has already joined agg_stream into sel_stream)
     return out
 
 
-def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
-                  trace: Optional[list], careful: bool, agg_stream, par_stream=None, attention: bool = False,
-                  rollout: bool = False) -> Dict[str, torch.Tensor]:
-    """Run all levels for a batch of HBM-resident slides (a list of DeviceSlide, or a DeviceSlideBatch built once
-    and re-used across calls) or of host-resident ones (HostSlide: the rows a level selected are staged into HBM over the host link
-    right after their addresses are known, paths_stage_rows).  Returns the last level's output dict (+ "status").
+def _child_capacity(n: int, keep: int):
+    """The static capacities of the step from a level of ``n`` (padded) patches to its children: (cap_keep = the most parents the
+    top-K keeps (``keep`` < 0: all), Nn = 4 * cap_keep = the children's padded length; padding is masked by ``num_ims``)."""
+    cap_keep = n if keep < 0 else min(n, keep)
+    return cap_keep, 4 * cap_keep
+
+
+def _level_sizes(n0: int, keep_patches, num_levels: int) -> List[int]:
+    """Padded patch count of every level of the optimistic pass (the careful path may grow a level: _expand_children)."""
+    sizes = [n0]
+    for i in range(num_levels - 1):
+        sizes.append(_child_capacity(sizes[-1], int(keep_patches[i]))[1])
+    return sizes
+
+
+def _expand_children(batch, nxt: int, patch_size: int, keep_idx, keep_count, locs, N: int, Nn: int, status, stream: int, careful: bool,
+                     want_child_pos: bool, want_hp_row: bool):
+    """The children (level ``nxt``) of the kept patches: paths_expand_children into buffers of capacity ``Nn`` on ``stream``.  Returns
+    (Nn, num_next [B], locs_next [B,Nn,2], parent_next [B,Nn], src_row [B,Nn], src_cell [B,Nn], child_pos [B, 4 cap_keep] or None,
+    hp_row [B,Nn] (child -> kept slot) or None).
+
+    ``careful``: one host sync; a slide whose kept patches have no tissue children falls back to all tissue cells of the next grid
+    with zero parent state (reference data_utils/slide.py:336-352, paths_fallback_all_cells: src_row = -1, no gradient to any parent -
+    child_pos of that slide is all -1), in buffers regrown to hold them (the returned Nn)."""
+    B, cap_keep, p = len(batch), keep_idx.shape[1], _lib.ptr
+    i32 = dict(device=batch.device, dtype=torch.int32)
+    i64 = dict(device=batch.device, dtype=torch.int64)
+    gx, gy, masks = p(batch.gx[nxt]), p(batch.gy[nxt]), p(batch.mask_ptrs[nxt])
+    child_pos = torch.empty((B, 4 * cap_keep), **i32) if want_child_pos else None
+
+    def expand(cap):
+        bufs = (torch.empty((B,), **i64), torch.empty((B, cap, 2), **i64), torch.empty((B, cap), **i64),
+                torch.empty((B, cap), **i32), torch.empty((B, cap), **i32), torch.empty((B, cap), **i32) if want_hp_row else None)
+        _lib.call("paths_expand_children", p(keep_idx), cap_keep, p(keep_count), p(locs), N, patch_size, gx, gy, masks, B, cap,
+                  *(p(t) for t in bufs[:5]), p(status), p(child_pos), p(bufs[5]), stream)
+        return bufs
+
+    bufs = ops.timed("expand", lambda: expand(Nn))
+    if careful:
+        empty = (bufs[0] == 0).cpu()                      # per-level sync: slow path only
+        if bool(empty.any()):
+            need = Nn
+            for b in torch.nonzero(empty).flatten().tolist():
+                tissue = int(batch.slides[b].masks[nxt].sum().item())
+                X, Y = batch.slides[b].shape(nxt)
+                need = max(need, tissue if tissue > 0 else X * Y)
+            if need > Nn:
+                Nn = need
+                bufs = expand(Nn)
+            _lib.call("paths_fallback_all_cells", gx, gy, masks, patch_size, B, Nn, *(p(t) for t in bufs[:5]), p(status), p(bufs[5]), stream)
+    return (Nn, *bufs[:5], child_pos, bufs[5])
+
+
+def _stage_rows(batch, rows, n: int, zero_row, stream: int):
+    """Host-resident slides whose rows are read in place: pull the rows the address table ``rows`` [B,n] names over the host link into a
+    compact HBM buffer and point the table at the copies.  Returns the buffer (alive for as long as a level reads through the table)."""
+    buf = torch.empty((len(batch), n, batch.dim), device=batch.device, dtype=batch.dtype)
+    p = _lib.ptr
+    ops.timed("stage", lambda: _lib.call("paths_stage_rows", p(rows), len(batch) * n, batch.dim * buf.element_size(), p(buf), p(zero_row), stream))
+    return buf
+
+
+def _level0(r) -> SimpleNamespace:
+    """Level 0's rows: every cell of the base grids (paths_level0_batch)."""
+    B, N, D, p = r.B, r.batch.n0, r.D, _lib.ptr
+    lv = SimpleNamespace(N=N, state_prev=None, parent=None, staged=None)
+    lv.fts = None if r.rows_in_place else torch.empty((B, N, D), **r.f32)
+    lv.x_rows = torch.empty((B, N), **r.i64) if r.rows_in_place else None
+    lv.locs = torch.empty((B, N, 2), **r.i64)
+    lv.parent_inds = torch.empty((B, N), **r.i64)
+    lv.num_ims = torch.empty((B,), **r.i64)
+    _lib.call("paths_level0_batch" + r.sfx, p(r.batch.grid_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, r.mc.patch_size, N,
+              p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), r.st)
+    if r.stage_host:
+        lv.staged = _stage_rows(r.batch, lv.x_rows, N, r.zero_row, r.st)
+    return lv
+
+
+def _aggregate(r, lvl_pack, sel, ctx_hist, N: int):
+    """The aggregator launches of one level (attention, token chain, classifier) on the current stream, with the optional attention /
+    rollout exports."""
+    mc, B, f32 = r.mc, r.B, r.f32
+    ctx_prev = ctx_hist[-1] if (ctx_hist and mc.slide_ctx_mode == "residual") else None
+    ctx_all = torch.stack(ctx_hist, dim=1) if (ctx_hist and mc.slide_ctx_mode == "concat") else None
+    att = None
+    if r.attention:                                 # (allocated on the aggregator's stream, like its logits)
+        Hh, Lt = mc.trans_heads, mc.trans_layers
+        att = (torch.empty((B, Lt, Hh, N), **f32), torch.empty((B, Lt, Hh), **f32))
+    ro = (torch.empty((B, N), **f32), torch.empty((B,), **f32)) if r.rollout else None
+    agg = ops.aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=r.status, qkv=sel, attention=att,
+                                 rollout=ro)
+    if att is not None:
+        agg = dict(agg, attention=att[0], attention_self=att[1])
+    if ro is not None:
+        agg = dict(agg, rollout=ro[0], rollout_self=ro[1])
+    return agg
+
+
+def _child_step(r, i: int, lv, out, keep: int):
+    """From level ``i`` (``lv``, outputs ``out``) to level i + 1: top-K, the kept parents' h-partials, child expansion, row gathers.
+    Returns (the next level's rows, keep_idx, keep_count)."""
+    B, D, Dp, N, p, st = r.B, r.D, r.Dp, lv.N, _lib.ptr, r.st
+    batch, share_parent, rows_in_place = r.batch, r.share_parent, r.rows_in_place
+    cap_keep, Nn = _child_capacity(N, keep)
+    # After the top-K the chain forks: the kept parents' h-partials (gather + GEMM, the longer branch) stay on this stream,
+    # the child expansion and the row gathers (tiny latency-bound kernels) run beside them on a third stream and are joined
+    # before the next level's gate GEMMs.  (The fork travels as the top-K kernel's stop event: _lib.fork_behind.)
+    forked = r.overlap and share_parent
+    keep_idx = torch.empty((B, cap_keep), **r.i32)
+    keep_count = torch.empty((B,), **r.i32)
+    kept_rows = None
+    with (_lib.fork_behind([r.par_stream], r.main_stream) if forked else contextlib.nullcontext()):
+        if rows_in_place:
+            # ... with the addresses of the kept parents' h rows (row b, i -> ctx_patch[b, keep_idx[b, i], :D]) for the parent GEMM
+            kept_rows = torch.empty((B, cap_keep), **r.i64)
+            ops.timed("topk", lambda: _lib.call("paths_topk_rows", p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep,
+                                                p(keep_count), p(out["ctx_patch"]), Dp, N, p(kept_rows), p(r.zero_row), st))
+        else:
+            _lib.call("paths_topk", p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
+    hp = ops.parent_partials(r.lstm_pack, out["ctx_patch"], keep_idx, keep_count, kept_rows) if share_parent else None
+    st2 = r.par_stream.cuda_stream if forked else st
+    nx = SimpleNamespace(fts=None, x_rows=None, staged=None, state_prev=None, parent=None)
+    with (torch.cuda.stream(r.par_stream) if forked else contextlib.nullcontext()):
+        Nn, num_next, locs_next, parent_next, src_row, src_cell, _, hp_row = _expand_children(
+            batch, i + 1, r.mc.patch_size, keep_idx, keep_count, lv.locs, N, Nn, r.status, st2, r.careful, False, share_parent)
+        nx.N, nx.num_ims, nx.locs, nx.parent_inds = Nn, num_next, locs_next, parent_next
+        grid = p(batch.grid_ptrs[i + 1])
+        if share_parent:
+            # children only need their parent's c row (h enters through the per-parent partials)
+            Hc = Dp - D
+            c0 = torch.empty((B, Nn, Hc), **r.f32)
+            if rows_in_place:
+                # ... and their feature rows are not copied either: the GEMMs of the next level read them in the resident grids
+                nx.x_rows = torch.empty((B, Nn), **r.i64)
+                ops.timed("gather", lambda: _lib.call(
+                    "paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                    p(src_row), Hc, p(num_next), B, Nn, None, p(c0), 0, p(nx.x_rows), p(r.zero_row), st2))
+                if r.stage_host:
+                    nx.staged = _stage_rows(batch, nx.x_rows, Nn, r.zero_row, st2)
+            else:
+                nx.fts = torch.empty((B, Nn, D), **r.f32)
+                _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                          p(src_row), Hc, p(num_next), B, Nn, p(nx.fts), p(c0), 0, None, None, st2)
+            nx.parent = {"hp": hp, "hp_row": hp_row, "c0": c0}
+        else:
+            nx.fts = torch.empty((B, Nn, D), **r.f32)
+            nx.state_prev = torch.empty((B, Nn, Dp), **r.f32)
+            _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
+                      p(num_next), B, Nn, p(nx.fts), p(nx.state_prev), 0, None, None, st2)
+        if forked:            # allocated on the expansion stream, read by the next level on the selection stream
+            r.keepalive.append((nx, src_row, src_cell))
+    return nx, keep_idx, keep_count
+
+
+def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, trace: Optional[list], careful: bool, agg_stream,
+                  par_stream, attention: bool = False, rollout: bool = False) -> Dict[str, torch.Tensor]:
+    """Run all levels for a DeviceSlideBatch of HBM-resident slides or of host-resident ones (HostSlide: the rows a level selected are
+    staged into HBM over the host link right after their addresses are known, paths_stage_rows).  ``agg_stream`` / ``par_stream``:
+    both None = everything on the current stream; else the aggregator and the child expansion overlap the selection chain on them.
+    Returns the last level's output dict (+ "status").
 
     ``trace`` (a list) receives one dict per level with device tensors num_ims / locs / parent_inds / importance /
     logits / ctx_slide / keep_idx / keep_count, for parity tests and heat-map export; with ``attention`` also attention /
@@ -409,200 +556,81 @@ def _recurse_body(model, slides, keep_patches: Sequence[int], num_levels: int,
     """
     mc = model.procs[0].config
     ops.check_supported(mc)
-    batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
     assert batch.num_levels >= num_levels
-    B = len(batch)
-    dev = batch.device
-    D = batch.dim
+    B, dev, D = len(batch), batch.device, batch.dim
     Dp = model.procs[0].ctx_dim()[1]
-    st = _lib.stream()
-    p = _lib.ptr
-    i32 = dict(device=dev, dtype=torch.int32)
-    i64 = dict(device=dev, dtype=torch.int64)
     f32 = dict(device=dev, dtype=torch.float32)
-
-    grid_ptrs, mask_ptrs, gx, gy = batch.grid_ptrs, batch.mask_ptrs, batch.gx, batch.gy
-    N = batch.n0
     # fp16 grids: the selection-chain kernels and the row-addressed GEMMs take their _h16 forms; every gathered copy is fp32
     h16 = batch.dtype == torch.float16
-    sfx = "_h16" if h16 else ""
     lstm_pack = ops.pack_lstm(model.lstm) if model.use_lstm else None
     share_parent = model.use_lstm          # siblings share the parent's h: h-half of the gate GEMM once per kept parent
     # default split mode: feature rows are read in place in the resident grids (row-pointer GEMM operands) instead of being
     # copied (level 0) or gathered (children)
     rows_in_place = (share_parent and ops.use_x6(D, Dp - D) and ops.split_planes() == 2 and ROWS_IN_PLACE
                      and (ops.fast_path(mc) or (ops.GENERIC_ADD and ops.GENERIC_SPLIT and D % 128 == 0)))
-    zero_row = torch.zeros((D,), **f32) if rows_in_place else None
-    fts = None if rows_in_place else torch.empty((B, N, D), **f32)
-    x_rows = torch.empty((B, N), **i64) if rows_in_place else None
-    # Host-resident slides: the grid addresses are pinned host memory.  Where rows are copied (fts) the copying kernel reads them over
-    # the host link once and nothing else does; where they are read in place, the address table is staged: the selected rows are
-    # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
-    stage_host = batch.host_resident and rows_in_place
-
-    def stage_rows(rows, n, stream):
-        buf = torch.empty((B, n, D), device=dev, dtype=batch.dtype)
-        ops.timed("stage", lambda: _lib.call("paths_stage_rows", p(rows), B * n, D * buf.element_size(), p(buf), p(zero_row), stream))
-        return buf
-    locs = torch.empty((B, N, 2), **i64)
-    parent_inds = torch.empty((B, N), **i64)
-    num_ims = torch.empty((B,), **i64)
-    _lib.call("paths_level0_batch" + sfx, p(grid_ptrs[0]), p(gx[0]), p(gy[0]), B, D, mc.patch_size, N,
-              p(fts), p(locs), p(parent_inds), p(num_ims), 0, p(x_rows), p(zero_row), st)
-    staged = stage_rows(x_rows, N, st) if stage_host else None          # (what x_rows addresses now; alive while the level reads it)
-    state_prev, ctx_hist, parent = None, [], None
-    out = None
     # The aggregator of level i (attention, token chain, classifier) feeds nothing of level i+1 except the slide context, so
     # it runs on a second HIP stream beside the selection chain of level i+1 (top-K, expansion, gathers, gate GEMMs).  Several
     # of those kernels cannot fill 256 CUs alone (116-232 workgroups, one per CU); the other chain's waves take the idle CUs.
     overlap = agg_stream is not None
     main_stream = torch.cuda.current_stream(dev) if overlap else None
-    side_stream = agg_stream
     keepalive = []                         # tensors read on a stream other than the one that allocated them: kept until the streams join
+    # Host-resident slides: the grid addresses are pinned host memory.  Where rows are copied (fts) the copying kernel reads them over
+    # the host link once and nothing else does; where they are read in place, the address table is staged: the selected rows are
+    # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
+    r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(), sfx="_h16" if h16 else "", f32=f32,
+                        i32=dict(device=dev, dtype=torch.int32), i64=dict(device=dev, dtype=torch.int64),
+                        lstm_pack=lstm_pack, share_parent=share_parent, rows_in_place=rows_in_place,
+                        zero_row=torch.zeros((D,), **f32) if rows_in_place else None, stage_host=batch.host_resident and rows_in_place,
+                        careful=careful, attention=attention, rollout=rollout, overlap=overlap, main_stream=main_stream,
+                        par_stream=par_stream, keepalive=keepalive, status=None)
+    lv = _level0(r)
     # importance of padded rows is 0 (reference utils.py:106-115): ONE zero fill for all levels (sizes are known up front
     # unless the careful path has to grow a level)
-    sizes, n_l = [], N
-    for i in range(num_levels):
-        sizes.append(n_l)
-        if i < num_levels - 1:
-            keep = int(keep_patches[i])
-            n_l = 4 * (n_l if keep < 0 else min(n_l, keep))
+    sizes = _level_sizes(lv.N, keep_patches, num_levels)
     # (the status word rides on the same zero fill as the importance rows: one fill launch per step instead of two at its head)
     zbuf = _lib.zeros((B * sum(sizes) + 64,), **f32)
     imp_all = zbuf[:B * sum(sizes)]
-    status = zbuf[B * sum(sizes) + 32:B * sum(sizes) + 33].view(torch.int32)
+    r.status = status = zbuf[B * sum(sizes) + 32:B * sum(sizes) + 33].view(torch.int32)
     imp_off = [B * sum(sizes[:i]) for i in range(num_levels)]
-    fork_pending = False
+    out, ctx_hist, fork_pending = None, [], False
     for i in range(num_levels):
-        proc = model.procs[i]
-        lvl_pack = ops.pack_level(proc)
+        lvl_pack = ops.pack_level(model.procs[i])
         if fork_pending:
             _lib.stream_wait(main_stream, par_stream)     # this level's rows / bookkeeping from the expansion branch are ready
-            fork_pending = False
+        N = lv.N
         imp_buf = imp_all[imp_off[i]:imp_off[i] + B * N].view(B, N) if N == sizes[i] else None
         # (the aggregator's fork travels as the stop event of the chain's last kernel where that kernel can carry one: _lib.fork_behind)
         last = i == num_levels - 1
         with _Range(f"level {i}: selection chain (LSTM gates, importance, projection)"), \
-                (_lib.fork_behind([side_stream], main_stream) if overlap else contextlib.nullcontext()):
-            sel = ops.selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, True, parent=parent,
-                                        max_pos=batch.max_dim[i], x_rows=x_rows, feat_dim=D, importance_out=imp_buf,
+                (_lib.fork_behind([agg_stream], main_stream) if overlap else contextlib.nullcontext()):
+            sel = ops.selection_forward(mc, lstm_pack, lvl_pack, lv.fts, lv.locs, lv.num_ims, lv.state_prev, True, parent=lv.parent,
+                                        max_pos=batch.max_dim[i], x_rows=lv.x_rows, feat_dim=D, importance_out=imp_buf,
                                         last_level=last, x_rows_h16=h16 and rows_in_place)
-        def aggregate():
-            ctx_prev = ctx_hist[-1] if (ctx_hist and mc.slide_ctx_mode == "residual") else None
-            ctx_all = torch.stack(ctx_hist, dim=1) if (ctx_hist and mc.slide_ctx_mode == "concat") else None
-            att = None
-            if attention:                                 # (allocated on the aggregator's stream, like its logits)
-                Hh, Lt = mc.trans_heads, mc.trans_layers
-                att = (torch.empty((B, Lt, Hh, N), **f32), torch.empty((B, Lt, Hh), **f32))
-            ro = (torch.empty((B, N), **f32), torch.empty((B,), **f32)) if rollout else None
-            agg = ops.aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=att,
-                                         rollout=ro)
-            if att is not None:
-                agg = dict(agg, attention=att[0], attention_self=att[1])
-            if ro is not None:
-                agg = dict(agg, rollout=ro[0], rollout_self=ro[1])
-            return agg
-
-        if overlap:                                       # (side_stream already waits for this level's tokens / num_ims: fork_behind above)
+        if overlap:                                       # (agg_stream already waits for this level's tokens / num_ims: fork_behind above)
             keepalive.append((sel["tokens"], sel["num_ims"], sel.get("qkv_img"), sel.get("_qkv_ws")))
-            with torch.cuda.stream(side_stream), _Range(f"level {i}: aggregator (second stream)"):
-                agg = aggregate()
-        else:
-            with _Range(f"level {i}: aggregator"):
-                agg = aggregate()
+        with (torch.cuda.stream(agg_stream) if overlap else contextlib.nullcontext()), \
+                _Range(f"level {i}: aggregator (second stream)" if overlap else f"level {i}: aggregator"):
+            agg = _aggregate(r, lvl_pack, sel, ctx_hist, N)
         out = {"logits": agg["logits"], "ctx_slide": agg["ctx_slide"], "ctx_patch": sel["ctx_patch"], "importance": sel["importance"]}
         ctx_hist.append(out["ctx_slide"])
         rec = None
         if trace is not None:
-            rec = {"num_ims": num_ims, "locs": locs, "parent_inds": parent_inds, "importance": out["importance"],
+            rec = {"num_ims": lv.num_ims, "locs": lv.locs, "parent_inds": lv.parent_inds, "importance": out["importance"],
                    "logits": out["logits"], "ctx_slide": out["ctx_slide"]}
             if attention:
                 rec["attention"], rec["attention_self"] = agg["attention"], agg["attention_self"]
             if rollout:
                 rec["rollout"], rec["rollout_self"] = agg["rollout"], agg["rollout_self"]
             trace.append(rec)
-        if i == num_levels - 1:
+        if last:
             break
-        keep = int(keep_patches[i])
-        cap_keep = N if keep < 0 else min(N, keep)
-        # After the top-K the chain forks: the kept parents' h-partials (gather + GEMM, the longer branch) stay on this stream,
-        # the child expansion and the row gathers (tiny latency-bound kernels) run beside them on a third stream and are joined
-        # before the next level's gate GEMMs.  (The fork travels as the top-K kernel's stop event: _lib.fork_behind.)
-        forked = overlap and par_stream is not None and share_parent
-        keep_idx = torch.empty((B, cap_keep), **i32)
-        keep_count = torch.empty((B,), **i32)
-        kept_rows = None
-        with (_lib.fork_behind([par_stream], main_stream) if forked else contextlib.nullcontext()):
-            if rows_in_place:
-                # ... with the addresses of the kept parents' h rows (row b, i -> ctx_patch[b, keep_idx[b, i], :D]) for the parent GEMM
-                kept_rows = torch.empty((B, cap_keep), **i64)
-                ops.timed("topk", lambda: _lib.call("paths_topk_rows", p(out["importance"]), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep,
-                                                    p(keep_count), p(out["ctx_patch"]), Dp, N, p(kept_rows), p(zero_row), st))
-            else:
-                _lib.call("paths_topk", p(out["importance"]), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
-        Nn = 4 * cap_keep
-        hp = ops.parent_partials(lstm_pack, out["ctx_patch"], keep_idx, keep_count, kept_rows) if share_parent else None
-        st2 = par_stream.cuda_stream if forked else st
-        with (torch.cuda.stream(par_stream) if forked else contextlib.nullcontext()):
-            def expand(cap):
-                bufs = (torch.empty((B,), **i64), torch.empty((B, cap, 2), **i64), torch.empty((B, cap), **i64),
-                        torch.empty((B, cap), **i32), torch.empty((B, cap), **i32), torch.empty((B, cap), **i32))
-                _lib.call("paths_expand_children", p(keep_idx), cap_keep, p(keep_count), p(locs), N, mc.patch_size,
-                          p(gx[i + 1]), p(gy[i + 1]), p(mask_ptrs[i + 1]), B, cap, p(bufs[0]), p(bufs[1]), p(bufs[2]),
-                          p(bufs[3]), p(bufs[4]), p(status), None, p(bufs[5]) if share_parent else None, st2)
-                return bufs
-
-            num_next, locs_next, parent_next, src_row, src_cell, hp_row = ops.timed("expand", lambda: expand(Nn))
-            if careful:
-                empty = (num_next == 0).cpu()                      # per-level sync: slow path only
-                if bool(empty.any()):
-                    need = Nn
-                    for b in torch.nonzero(empty).flatten().tolist():
-                        tissue = int(batch.slides[b].masks[i + 1].sum().item())
-                        X, Y = batch.slides[b].shape(i + 1)
-                        need = max(need, tissue if tissue > 0 else X * Y)
-                    if need > Nn:
-                        Nn = need
-                        num_next, locs_next, parent_next, src_row, src_cell, hp_row = expand(Nn)
-                    _lib.call("paths_fallback_all_cells", p(gx[i + 1]), p(gy[i + 1]), p(mask_ptrs[i + 1]), mc.patch_size, B, Nn,
-                              p(num_next), p(locs_next), p(parent_next), p(src_row), p(src_cell), p(status),
-                              p(hp_row) if share_parent else None, st2)
-            x_rows_next, staged_next = None, None
-            if share_parent:
-                # children only need their parent's c row (h enters through the per-parent partials below)
-                Hc = Dp - D
-                state_next = torch.empty((B, Nn, Hc), **f32)
-                if rows_in_place:
-                    # ... and their feature rows are not copied either: the GEMMs of the next level read them in the resident grids
-                    fts_next = None
-                    x_rows_next = torch.empty((B, Nn), **i64)
-                    ops.timed("gather", lambda: _lib.call(
-                        "paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
-                        p(src_row), Hc, p(num_next), B, Nn, None, p(state_next), 0, p(x_rows_next), p(zero_row), st2))
-                    if stage_host:
-                        staged_next = stage_rows(x_rows_next, Nn, st2)
-                else:
-                    fts_next = torch.empty((B, Nn, D), **f32)
-                    _lib.call("paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
-                              p(src_row), Hc, p(num_next), B, Nn, p(fts_next), p(state_next), 0, None, None, st2)
-                parent = {"hp": hp, "hp_row": hp_row, "c0": state_next}
-                state_next = None
-            else:
-                fts_next = torch.empty((B, Nn, D), **f32)
-                state_next = torch.empty((B, Nn, Dp), **f32)
-                _lib.call("paths_gather_rows" + sfx, p(grid_ptrs[i + 1]), p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
-                          p(num_next), B, Nn, p(fts_next), p(state_next), 0, None, None, st2)
-            if forked:
-                fork_pending = True
-                keepalive.append((num_next, locs_next, parent_next, src_row, src_cell, hp_row, parent, fts_next, x_rows_next, staged_next))
+        lv, keep_idx, keep_count = _child_step(r, i, lv, out, int(keep_patches[i]))
+        fork_pending = overlap and share_parent
         if rec is not None:
             rec["keep_idx"], rec["keep_count"] = keep_idx, keep_count
-        fts, x_rows, locs, parent_inds, num_ims, state_prev, N = fts_next, x_rows_next, locs_next, parent_next, num_next, state_next, Nn
-        staged = staged_next
     if overlap:
-        _lib.stream_wait(main_stream, side_stream)
-        if par_stream is not None:
-            _lib.stream_wait(main_stream, par_stream)
+        _lib.stream_wait(main_stream, agg_stream)
+        _lib.stream_wait(main_stream, par_stream)
         keepalive.clear()
     out = dict(out)
     out["status"] = status
@@ -645,7 +673,7 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
     state_prev, ctx_prev, ctx_hist = None, None, []
     logits = None
     # Once-per-parent form (LSTM, optimistic pass): siblings share their parent's h, so the h half of the gate pre-activations is one
-    # product over the kept parents and its gradients are products over a quarter of the rows (autograd.LevelParentFn /
+    # product over the kept parents and its gradients are products over a quarter of the rows (autograd.LevelFn ``parent`` /
     # GatherParentFn).  The careful re-run (rare: a slide whose kept patches have no tissue children) keeps the per-child form,
     # whose fallback rows carry no parent.  PATHS_TRAIN_PARENT=0 keeps the per-child form everywhere.
     parent_form = TRAIN_PARENT and model.use_lstm and not careful
@@ -653,55 +681,19 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
     for i in range(num_levels):
         if mc.slide_ctx_mode == "concat":          # the classifier reads every previous level's slide context (model/paths.py:134-137)
             ctx_prev = torch.stack(ctx_hist, dim=1) if ctx_hist else None
-        if par is not None:
-            logits, ctx_slide, state_out, importance = pag.LevelParentFn.apply(
-                model.procs[i], model.lstm, fts, locs, num_ims, par["c0"], par["h_kept"], par["hp_row"], par["child_pos"], par["keep_count"],
-                par["cap"], ctx_prev, *pag.lstm_params(model.lstm), *pag.level_params(model.procs[i]))
-        else:
-            logits, ctx_slide, state_out, importance = pag.level_apply(model.procs[i], model.lstm if model.use_lstm else None, fts, locs,
-                                                                       num_ims, state_prev, ctx_prev)
+        logits, ctx_slide, state_out, importance = pag.level_apply(model.procs[i], model.lstm if model.use_lstm else None, fts, locs,
+                                                                   num_ims, state_prev, ctx_prev, parent=par)
         ctx_prev = ctx_slide
         ctx_hist.append(ctx_slide)
         if i == num_levels - 1:
             break
         keep = int(keep_patches[i])
-        cap_keep = N if keep < 0 else min(N, keep)
+        cap_keep, Nn = _child_capacity(N, keep)
         keep_idx = torch.empty((B, cap_keep), **i32)
         keep_count = torch.empty((B,), **i32)
         _lib.call("paths_topk", p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
-        Nn = 4 * cap_keep
-        num_next = torch.empty((B,), **i64)
-        locs_next = torch.empty((B, Nn, 2), **i64)
-        parent_next = torch.empty((B, Nn), **i64)
-        src_row = torch.empty((B, Nn), **i32)
-        src_cell = torch.empty((B, Nn), **i32)
-        child_pos = torch.empty((B, 4 * cap_keep), **i32)
-        hp_row = torch.empty((B, Nn), **i32) if parent_form else None
-
-        def expand():
-            _lib.call("paths_expand_children", p(keep_idx), cap_keep, p(keep_count), p(locs), N, mc.patch_size,
-                      p(batch.gx[i + 1]), p(batch.gy[i + 1]), p(batch.mask_ptrs[i + 1]), B, Nn, p(num_next), p(locs_next),
-                      p(parent_next), p(src_row), p(src_cell), p(status), p(child_pos), p(hp_row), st)
-
-        expand()
-        if careful:
-            empty = (num_next == 0).cpu()                      # per-level sync: slow path only
-            if bool(empty.any()):
-                need = Nn
-                for b in torch.nonzero(empty).flatten().tolist():
-                    tissue = int(batch.slides[b].masks[i + 1].sum().item())
-                    X, Y = batch.slides[b].shape(i + 1)
-                    need = max(need, tissue if tissue > 0 else X * Y)
-                if need > Nn:
-                    Nn = need
-                    locs_next = torch.empty((B, Nn, 2), **i64)
-                    parent_next = torch.empty((B, Nn), **i64)
-                    src_row = torch.empty((B, Nn), **i32)
-                    src_cell = torch.empty((B, Nn), **i32)
-                    expand()
-                # fallback rows: src_row = -1 (zero parent state, no gradient to any parent: child_pos of that slide is all -1)
-                _lib.call("paths_fallback_all_cells", p(batch.gx[i + 1]), p(batch.gy[i + 1]), p(batch.mask_ptrs[i + 1]), mc.patch_size,
-                          B, Nn, p(num_next), p(locs_next), p(parent_next), p(src_row), p(src_cell), p(status), None, st)
+        Nn, num_next, locs_next, parent_next, src_row, src_cell, child_pos, hp_row = _expand_children(
+            batch, i + 1, mc.patch_size, keep_idx, keep_count, locs, N, Nn, status, st, careful, True, parent_form)
         if parent_form:
             fts, c0, h_kept = pag.GatherParentFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx, keep_count,
                                                        child_pos, D, Nn, h16)
