@@ -619,6 +619,14 @@ int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* g
  * aligned.  A byte copy: one entry point for fp32 and fp16 rows.  Each source row is read once; row_bytes % 16 == 0. */
 int paths_stage_rows(int64_t* row_ptrs, int64_t rows, int row_bytes, void* stage, const void* zero_row, paths_stream_t stream);
 
+/* Per-patch reductions of the feature gradient (paths_amd/saliency.py:input_gradients; interpretability side path,
+ * csrc/saliency_rows.hip).  For every row r of [B * rows_per_slide]: gxi[r] = sum_d dx[r,d] x[r,d] (gradient x input) and
+ * gnorm[r] = sqrt(sum_d dx[r,d]^2); rows at or beyond num_ims[b] are not read and get exact zeros in both.  dx / x: fp32 rows with
+ * element strides ldd / ldx (multiples of 4, >= D; 16-byte aligned bases); D % 128 == 0.  Fixed summation order per row
+ * (bit-reproducible), no workspace, no atomics. */
+int paths_saliency_rows(const float* dx, int64_t ldd, const float* x, int64_t ldx, const int64_t* num_ims, int rows_per_slide, int D,
+                        int B, float* gxi, float* gnorm, paths_stream_t stream);
+
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */
 int paths_scale_add_rows(const float* x, const float* alpha, const float* h, const int64_t* num_ims, int rows_per_slide,

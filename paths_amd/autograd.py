@@ -232,20 +232,30 @@ class LevelFn(torch.autograd.Function):
         vp = ops.pack_level(proc)
         cont = lambda t: t.contiguous() if t is not None else None
         no_agg = d_logits is None and d_ctx_out is None      # (see _aggregator_grads)
-        with bw.deferred_reductions():               # the ~35 slab reductions of this level's parameter gradients: one launch
+        # the gradient of the feature rows (input 2) is one more product of the selection backward, formed only when somebody asked
+        # for it (paths_amd/saliency.py); with no parameter gradient wanted either, every weight-gradient launch is left out
+        want_dx = ctx.needs_input_grad[2]
+        want_w = any(ctx.needs_input_grad[10:])
+        if want_dx and not mc.lstm:
+            raise NotImplementedError("feature gradients are not implemented for the lstm=false variant (selection_backward_nolstm)")
+        # (weight gradients on: the ~35 slab reductions of this level's parameter gradients run as one launch)
+        with (bw.deferred_reductions() if want_w else bw.no_weight_grads()):
             if no_agg:
                 tg, d_ctx_prev = None, None
                 d_tok = torch.zeros_like(tr["tokens"])
             else:
                 tg, d_tok, d_ctx_prev = bw.transformer_backward(mc, vp, tr, cont(d_logits), cont(d_ctx_out))
-            if mc.lstm:
+            d_fts = None
+            if mc.lstm and want_dx:
+                sg, d_prev, d_fts = bw.selection_backward(mc, lp, vp, sel, d_tok, cont(d_state_out), want_dx=True)
+            elif mc.lstm:
                 sg, d_prev = bw.selection_backward(mc, lp, vp, sel, d_tok, cont(d_state_out))
             else:
                 sg, d_prev = bw.selection_backward_nolstm(mc, vp, sel, d_tok, cont(d_state_out))
         # the selection backward's second result: (d_c0, d_h_kept) in the once-per-parent form, else d_state_prev
         d_state_prev, (d_c0, d_hk) = (None, d_prev) if sel.get("parent") is not None else (d_prev if ctx.has_state else None, (None, None))
-        grads = _level_grads(mc, lstm, sg, tg, d_logits is not None)
-        return (None, None, None, None, None, d_state_prev, d_c0, d_hk, None, d_ctx_prev if ctx.has_ctx else None, *grads)
+        grads = _level_grads(mc, lstm, sg, tg, d_logits is not None) if want_w else [None] * (len(ctx.needs_input_grad) - 10)
+        return (None, None, d_fts, None, None, d_state_prev, d_c0, d_hk, None, d_ctx_prev if ctx.has_ctx else None, *grads)
 
 
 def _aggregator_grads(mc, tg, proj_in=None, has_logits: bool = False):
@@ -367,10 +377,13 @@ def level_params_nolstm(proc) -> List[torch.nn.Parameter]:
             proc.hctx_mlp[0].weight, proc.hctx_mlp[0].bias, proc.hctx_mlp[2].weight, proc.hctx_mlp[2].bias] + level_params(proc)[4:]
 
 
-def level_apply(proc, lstm, fts, locs, num_ims, state_prev, ctx_prev, parent=None):
+def level_apply(proc, lstm, fts, locs, num_ims, state_prev, ctx_prev, parent=None, detach_params: bool = False):
     """Differentiable ``process``: returns (logits, ctx_slide, ctx_patch, importance).  ``parent`` (LSTM only, ``state_prev`` None then):
-    the once-per-parent inputs {"c0", "h_kept", "hp_row", "child_pos", "keep_count", "cap"} of :class:`LevelFn`."""
+    the once-per-parent inputs {"c0", "h_kept", "hp_row", "child_pos", "keep_count", "cap"} of :class:`LevelFn`.  ``detach_params``: the
+    parameters enter detached - no parameter gradient is computed or accumulated (``fts`` with requires_grad still gets its own)."""
     params = lstm_params(lstm) + level_params(proc) if proc.config.lstm else level_params_nolstm(proc)
+    if detach_params:
+        params = [p.detach() for p in params]
     c0, h_kept = (parent["c0"], parent["h_kept"]) if parent is not None else (None, None)
     return LevelFn.apply(proc, lstm, fts, locs, num_ims, state_prev, c0, h_kept, parent, ctx_prev, *params)
 

@@ -201,6 +201,25 @@ DEFER_REDUCTIONS = os.environ.get("PATHS_DEFER_REDUCTIONS", "1") != "0"
 _DEFER = {"depth": 0, "keep": [], "post": []}
 
 
+# Weight gradients on / off.  A backward pass that only wants the gradient of a level's INPUTS (paths_amd/saliency.py: no parameter
+# requires a gradient) runs inside ``with no_weight_grads():``: gemm_tn / colsum launch nothing (their outputs stay unwritten and
+# nothing reads them), the touch-ups of after_reductions are dropped and the LayerNorm backward skips the reduction of its affine
+# sums.  The dX chain is untouched.
+WEIGHT_GRADS = True
+
+
+class no_weight_grads:
+    def __enter__(self):
+        global WEIGHT_GRADS
+        self.prev, WEIGHT_GRADS = WEIGHT_GRADS, False
+        return self
+
+    def __exit__(self, *exc):
+        global WEIGHT_GRADS
+        WEIGHT_GRADS = self.prev
+        return False
+
+
 def flush_reductions():
     if _DEFER["depth"] > 0:
         _lib.call("paths_flush_reductions", None, _lib.stream())
@@ -212,6 +231,8 @@ def flush_reductions():
 
 def after_reductions(fn):
     """Run ``fn()`` (a torch op on gradients still waiting for their reduction) once they have been reduced: now when nothing is deferred."""
+    if not WEIGHT_GRADS:
+        return
     if _DEFER["depth"] > 0:
         _DEFER["post"].append(fn)
     else:
@@ -248,6 +269,8 @@ class deferred_reductions:
 
 def gemm_tn(a, lda, b0, ldb0, out, M, N1, N2, b1=None, ldb1=0, nb0=0, ldo=None, accumulate=False):
     """out[N1,N2] (+)= a[M,N1]^T [b0 | b1][M,N2]."""
+    if not WEIGHT_GRADS:
+        return
     dev = out.device
     if TN_MODE == "x6" and M >= TN_X6_MIN_M and N1 % 128 == 0 and N2 % 128 == 0 and M * 4 * max(lda, ldb0, ldb1) < (1 << 31):
         splits = _splits_x6(M, N1, N2, nb0 if b1 is not None else 0)
@@ -273,6 +296,8 @@ def colsum(a, lda, M, N, out=None, accumulate=False):
     dev = a.device if not isinstance(a, int) else out.device
     if out is None:
         out = torch.empty((N,), **_f32(dev))
+    if not WEIGHT_GRADS:
+        return out
     splits = max(1, min(256, M // 64))
     ws = torch.empty((splits * N,), **_f32(dev))
     ap = a if isinstance(a, int) else a.data_ptr()
@@ -383,10 +408,11 @@ def _importance_tokens(mc, lvl_pack, src, locs, num_ims, imp_out, hid_out, pproj
         _lib.call("paths_importance_proj", P(src), D, P(lvl_pack["w_ip_fwd"]), *tail)
 
 
-def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_state_out: Optional[torch.Tensor]):
+def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_state_out: Optional[torch.Tensor], want_dx: bool = False):
     """d_tokens [B,T,128]: gradient of the token sequence (row 0 = special token);
     d_state_out [B,N,D+Hc] or None: gradient flowing into (h1|c1) from the next level's gather.
-    Returns (grads dict in PACKED layouts, d_state_prev [B,N,D+Hc] or None)."""
+    Returns (grads dict in PACKED layouts, d_state_prev [B,N,D+Hc] or None); with ``want_dx`` also the gradient of the feature rows,
+    dX [B,N,D] = dG W_gates[:, :D] + dY (X enters the gates' x panel and Y = X + h1; padded rows are not meaningful)."""
     fts, state_prev, num_ims = sv["fts"], sv["state_prev"], sv["num_ims"]
     B, N, D = fts.shape
     Hc = lstm_pack["Hc"]
@@ -440,6 +466,7 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
     w_mem_t = Transposed(lstm_pack["w_mem"], D, Hc)                      # [Hc, D]
     gemm_nt(dpre_h, D, w_mem_t, dc1_h, Hc, M, Hc, D)
     par = sv.get("parent")
+    dx = torch.empty((B, N, D), **f32) if want_dx else None
     d_state_prev = torch.empty((B, N, Dp), **f32) if state_prev is not None else None
     ext_c = d_state_out.data_ptr() + 4 * D if d_state_out is not None else None
     if par is not None:                 # once-per-parent form: the children inherited c0 [B,N,Hc]; its gradient goes back as such
@@ -449,6 +476,9 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
         c0_ptr = state_prev.data_ptr() + 4 * D if state_prev is not None else None
         _lib.call("paths_lstm_bwd_b", P(dc1_h), ext_c, Dp, P(sv["frm"]), c0_ptr, state_prev.stride(1) if state_prev is not None else 0,
                   P(num_ims), N, M, Hc, P(dG), G, d_state_prev.data_ptr() + 4 * D if d_state_prev is not None else None, Dp, st)
+    if want_dx:
+        # the x panel of the gates runs over the children in every form (level 0, per child, once per parent): one product
+        gemm_nt(dG, G, Transposed(lstm_pack["w_gates"], G, D, ld=2 * D, offset=0), dx, D, M, D, G, residual=dy, ldr=D)
     if par is not None:
         # dHP[b, i] = sum of dG over the surviving children of kept parent i (the pre-activations got HP[parent] added): then the h
         # half of the weight gradient and the parents' h gradient are products over the kept parents - a quarter of the rows
@@ -464,7 +494,7 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
         d_hk = torch.empty((M4, D), **f32)
         gemm_nt(dhp, G, wh_t, d_hk, D, M4, D, G)
         side_join(dev)
-        return grads, (d_c0, d_hk)
+        return (grads, (d_c0, d_hk), dx) if want_dx else (grads, (d_c0, d_hk))
     with side_stream(dev, dG, fts):
         grads["b_gates"] = colsum(dG, G, M, G)
         grads["w_gates"] = torch.empty((G, 2 * D), **f32)
@@ -477,7 +507,7 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
         wh_t = Transposed(lstm_pack["w_gates"], G, D, ld=2 * D, offset=D)   # [D, G] = (W_gates[:, D:2D])^T
         gemm_nt(dG, G, wh_t, d_state_prev.data_ptr(), Dp, M, D, G)
     side_join(dev)                     # (before the saved activations behind the raw pointers above can be freed)
-    return grads, d_state_prev
+    return (grads, d_state_prev, dx) if want_dx else (grads, d_state_prev)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -649,6 +679,8 @@ def _ln_bwd_sums(dy, xh, rs, g, rows, d=128):
     slabs = torch.empty((nblk, 3 * d), **f32)
     _lib.call("paths_layernorm_bwd_sums" if d == 128 else "paths_layernorm_bwd_sums_any", P(dy), P(xh), P(rs), P(g), P(dx), P(slabs), rows, d, rpb,
               _lib.stream())
+    if not WEIGHT_GRADS:
+        return dx, None, None, None
     gb = torch.empty((3 * d,), **f32)
     _lib.call("paths_reduce_slabs_f32", P(slabs), nblk, 3 * d, P(gb), 0, _lib.stream())
     _keep_slabs(slabs)

@@ -2,12 +2,13 @@
 
 ``hierarchy_from_trace`` pulls one slide's per-level patch locations / importances / selected indices (and, from a
 ``recurse(..., attention=True)`` trace, the special token's attention; from a ``recurse(..., rollout=True)`` trace, its attention
-rollout) out of the trace of :func:`paths_amd.utils.recurse`.
+rollout; from the trace of :func:`paths_amd.saliency.input_gradients`, every patch's gradient x input and gradient norm) out of the
+trace of :func:`paths_amd.utils.recurse`.
 
 ``importance_map`` rasterises the importances exactly like the reference's overlay code: every patch of depth d paints
 ``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with weight 1/2 wherever they exist
 (heatmap_visualise.py:147-171).  ``attention_map`` rasterises the special token's attention of one decoder layer (one head or
-the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout.  Rasters are in units of the FINEST level's patches (one
+the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout and ``saliency_map`` for the gradient attributions.  Rasters are in units of the FINEST level's patches (one
 cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
 """
 from __future__ import annotations
@@ -31,6 +32,9 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
         if "rollout" in lv:
             d["rollout"] = lv["rollout"][slide, :n].cpu().numpy()                      # [n]
             d["rollout_self"] = float(lv["rollout_self"][slide])
+        for key in ("grad_x_input", "grad_norm"):                                      # (saliency.input_gradients)
+            if key in lv:
+                d[key] = lv[key][slide, :n].cpu().numpy()                              # [n]
         out.append(d)
     return out
 
@@ -90,5 +94,26 @@ def rollout_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: int 
             raise KeyError("level %d carries no rollout: run recurse(..., rollout=True)" % depth)
         raster = np.zeros(shape, dtype=np.float64)
         _paint(raster, lv["locs"], lv["rollout"], magnification_factor ** (L - 1 - depth), patch_size)
+        maps.append(raster)
+    return maps
+
+
+def saliency_map(levels: List[Dict[str, np.ndarray]], base_grid, kind: str = "grad_x_input", patch_size: int = 256,
+                 magnification_factor: int = 2) -> List[np.ndarray]:
+    """One [X0 * f, Y0 * f] float map per level (f = magnification_factor**(L-1)): every patch's gradient x input (``kind``
+    "grad_x_input", signed) or gradient norm ("grad_norm"), painted over the patch's footprint like :func:`rollout_map`; 0 where the
+    level did not visit, no fold across levels.  ``levels`` from :func:`hierarchy_from_trace` of a
+    :func:`paths_amd.saliency.input_gradients` trace."""
+    if kind not in ("grad_x_input", "grad_norm"):
+        raise ValueError("kind must be 'grad_x_input' or 'grad_norm', got %r" % (kind,))
+    L = len(levels)
+    f = magnification_factor ** (L - 1)
+    shape = (base_grid[0] * f, base_grid[1] * f)
+    maps = []
+    for depth, lv in enumerate(levels):
+        if kind not in lv:
+            raise KeyError("level %d carries no %s: take the trace from saliency.input_gradients" % (depth, kind))
+        raster = np.zeros(shape, dtype=np.float64)
+        _paint(raster, lv["locs"], lv[kind], magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)
     return maps

@@ -637,7 +637,8 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
     return out
 
 
-def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, careful: bool = False) -> Dict[str, torch.Tensor]:
+def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, careful: bool = False,
+                  trace: Optional[list] = None) -> Dict[str, torch.Tensor]:
     """Differentiable recursion for training: same kernels as :func:`recurse`, but every level goes through
     paths_amd.autograd.LevelFn / GatherFn so that ``loss.backward()`` runs the hand-written backward kernels.
     Padded rows are zero-filled and computed (no tile skipping) so that every saved activation is finite.
@@ -645,13 +646,18 @@ def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, c
     Like :func:`recurse` the default pass is optimistic and sync-free; the returned ``status`` word has bit 0 set when some
     slide's kept patches had no tissue children.  The caller (:func:`forward_backward`) then repeats the step with
     ``careful=True``: one host sync per level and the reference's fallback to all tissue cells of the next grid with zero
-    parent state (data_utils/slide.py:336-352), handled on the device (paths_fallback_all_cells)."""
+    parent state (data_utils/slide.py:336-352), handled on the device (paths_fallback_all_cells).
+
+    ``trace`` (a list) turns the pass into the one feature gradients are taken from (paths_amd/saliency.py:input_gradients): every
+    level's feature rows become a detached leaf that requires a gradient, the parameters enter detached (no parameter gradient is
+    computed or accumulated) and the list receives one dict per level in the format of :func:`recurse`'s trace - num_ims / locs /
+    parent_inds / importance / logits, keep_idx / keep_count below the last level - plus ``fts``, the leaf [B,N,D]."""
     batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
     with ops.range_guard(batch.feat_absmax):
-        return _recurse_train_body(model, batch, keep_patches, num_levels, careful)
+        return _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace)
 
 
-def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
+def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=None):
     from . import autograd as pag
     mc = model.procs[0].config
     ops.check_supported(mc, training=True)
@@ -681,10 +687,18 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
     for i in range(num_levels):
         if mc.slide_ctx_mode == "concat":          # the classifier reads every previous level's slide context (model/paths.py:134-137)
             ctx_prev = torch.stack(ctx_hist, dim=1) if ctx_hist else None
+        if trace is not None:                      # (the gathers mark their feature rows non-differentiable: a fresh leaf per level)
+            fts = fts.detach().requires_grad_(True)
         logits, ctx_slide, state_out, importance = pag.level_apply(model.procs[i], model.lstm if model.use_lstm else None, fts, locs,
-                                                                   num_ims, state_prev, ctx_prev, parent=par)
+                                                                   num_ims, state_prev, ctx_prev, parent=par,
+                                                                   detach_params=trace is not None)
         ctx_prev = ctx_slide
         ctx_hist.append(ctx_slide)
+        rec = None
+        if trace is not None:
+            rec = {"num_ims": num_ims, "locs": locs, "parent_inds": parent, "importance": importance, "logits": logits.detach(),
+                   "fts": fts}
+            trace.append(rec)
         if i == num_levels - 1:
             break
         keep = int(keep_patches[i])
@@ -694,6 +708,8 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful):
         _lib.call("paths_topk", p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
         Nn, num_next, locs_next, parent_next, src_row, src_cell, child_pos, hp_row = _expand_children(
             batch, i + 1, mc.patch_size, keep_idx, keep_count, locs, N, Nn, status, st, careful, True, parent_form)
+        if rec is not None:
+            rec["keep_idx"], rec["keep_count"] = keep_idx, keep_count
         if parent_form:
             fts, c0, h_kept = pag.GatherParentFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx, keep_count,
                                                        child_pos, D, Nn, h16)
