@@ -167,22 +167,22 @@ def load() -> C.CDLL:
     return _lib
 
 
-def ptr(t: Optional[torch.Tensor]):
-    if t is None:
-        return None
+def ptr(t):
+    """Device address of a tensor; ``None`` and an ``int`` that already is an address pass through."""
+    if t is None or type(t) is int:
+        return t
     return t.data_ptr()
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _GET_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
-_FAST_STREAM = os.environ.get("PATHS_FAST_STREAM", "1") != "0"
 
 
 def stream() -> int:
     """Handle of torch's current stream on the current device.  Called once per launch (~600 times per training step): the public
     ``torch.cuda.current_stream()`` builds a Stream object through four Python layers (5 ms per step measured under cProfile); the
     two C bindings below return the same handle directly."""
-    if _RAW_STREAM is not None and _GET_DEVICE is not None and _FAST_STREAM:
+    if _RAW_STREAM is not None and _GET_DEVICE is not None:
         return _RAW_STREAM(_GET_DEVICE())
     return torch.cuda.current_stream().cuda_stream
 

@@ -25,16 +25,12 @@ TN_SPLIT2 = int(os.environ.get("PATHS_TN_SPLIT2", "2"))
 TN_MODE = os.environ.get("PATHS_TN_MODE", "x6")
 # dX / recompute GEMMs go to the split-operand kernel when the output width is a multiple of this (128: the d = 128 products too)
 NT_X6_MIN_N = int(os.environ.get("PATHS_NT_X6_MIN_N", "128"))
-PACK_T = os.environ.get("PATHS_PACK_T", "1") != "0"        # dX products image W^T straight from W (one launch instead of transpose + pack)
 # Row counts from which the gradient GEMMs run on the split-bf16 kernels (below: the f32-input MFMA kernels, which are as fast there).
 # Module constants so that tests can force the split kernels onto the small shapes of the reference's trajectory fixtures.
 NT_X6_MIN_M = int(os.environ.get("PATHS_NT_X6_MIN_M", "1024"))
 TN_X6_MIN_M = int(os.environ.get("PATHS_TN_X6_MIN_M", "512"))
 # attention backward: "x6q" = the split-bf16 kernels (csrc/attn_bwd_x6.hip: dQ, dK and dV), "f32" = all of it on the f32 MFMA (csrc/attn_bwd.hip)
 ATTN_BWD_MODE = os.environ.get("PATHS_ATTN_BWD_MODE", "x6q")
-
-
-TRAIN_SPLITK_IMPORTANCE = os.environ.get("PATHS_TRAIN_SPLITK_IMPORTANCE", "1") != "0"     # training: importance / proj GEMM as two k halves + finish
 
 
 def _f32(dev):
@@ -93,29 +89,21 @@ def gemm_nt(a, lda, wt, out, ldo, M, N, K, bias=None, act=0, residual=None, ldr=
     if isinstance(wt, Transposed):
         kfull = wt.pad_to if (wt.pad_to is not None and wt.pad_to > wt.rows) else wt.rows
         if (ops.GEMM_MODE != "f32" and N % NT_X6_MIN_N == 0 and K >= 128 and K % 128 == 0 and M >= NT_X6_MIN_M and ldw is None and N == wt.cols and K == kfull
-                and ops.TRAIN_PLANES in (3, 4) and PACK_T):
+                and ops.TRAIN_PLANES in (3, 4)):
             pl = ops.TRAIN_PLANES
             wx = torch.empty((N * K * 2 * (2 if pl == 4 else pl),), device=wt.w.device, dtype=torch.uint8)
             _lib.call("paths_x6_pack_weights_t", wt.w.data_ptr() + 4 * wt.offset, wt.ld if wt.ld is not None else wt.w.stride(0), P(wx), N, N, K, wt.rows,
                       pl, _lib.stream())
-            ap = a if isinstance(a, int) else a.data_ptr()
-            op = out if isinstance(out, int) else out.data_ptr()
-            rp = None if residual is None else (residual if isinstance(residual, int) else residual.data_ptr())
-            mp = None if mask is None else (mask if isinstance(mask, int) else mask.data_ptr())
-            _lib.call("paths_gemm_nt_x6", ap, lda, P(wx), K, 0, P(bias), op, ldo, M, N, N, K, act, rp, ldr, mp, ldm,
+            _lib.call("paths_gemm_nt_x6", P(a), lda, P(wx), K, 0, P(bias), P(out), ldo, M, N, N, K, act, P(residual), ldr, P(mask), ldm,
                       1 if accumulate else 0, pl, 1.0, 1.0, _lib.stream())
             return
         wt = wt.tensor()
-    ap = a if isinstance(a, int) else a.data_ptr()
-    op = out if isinstance(out, int) else out.data_ptr()
-    rp = None if residual is None else (residual if isinstance(residual, int) else residual.data_ptr())
-    mp = None if mask is None else (mask if isinstance(mask, int) else mask.data_ptr())
     ldw = ldw if ldw is not None else K
     if ops.GEMM_MODE != "f32" and N % NT_X6_MIN_N == 0 and K >= 128 and K % 128 == 0 and M >= NT_X6_MIN_M and isinstance(wt, torch.Tensor) and wt.dim() == 2 \
             and wt.shape[0] >= N and wt.stride(0) == ldw and wt.stride(1) == 1:
         # split-bf16 GEMM: the (transposed) weight is re-imaged per call - 6 N K bytes, microseconds next to an M >= 1024 product
         wx, wx_s = ops.x6_pack(wt[:N, :K], planes=ops.TRAIN_PLANES)
-        _lib.call("paths_gemm_nt_x6", ap, lda, P(wx), K, 0, P(bias), op, ldo, M, N, N, K, act, rp, ldr, mp, ldm,
+        _lib.call("paths_gemm_nt_x6", P(a), lda, P(wx), K, 0, P(bias), P(out), ldo, M, N, N, K, act, P(residual), ldr, P(mask), ldm,
                   1 if accumulate else 0, ops.TRAIN_PLANES, wx_s, 1.0, _lib.stream())
         return
     n_pad = N
@@ -124,11 +112,11 @@ def gemm_nt(a, lda, wt, out, ldo, M, N, K, bias=None, act=0, residual=None, ldr=
         n_pad = (N + 127) // 128 * 128
         if wt.shape[0] < n_pad:
             wt = ops._pad_rows(wt[:N])
-    _lib.call("paths_gemm_nt_f32", ap, lda, P(wt), ldw, P(bias), op, ldo, M, N, n_pad, K, act, rp, ldr,
-              mp, ldm, 1 if accumulate else 0, _lib.stream())
+    _lib.call("paths_gemm_nt_f32", P(a), lda, P(wt), ldw, P(bias), P(out), ldo, M, N, n_pad, K, act, P(residual), ldr,
+              P(mask), ldm, 1 if accumulate else 0, _lib.stream())
 
 
-_TN_WGS = int(os.environ.get("PATHS_TN_WGS", "256"))      # workgroups of 256 x 256 tiles a weight-gradient launch aims at: ONE round of the 256 CUs
+_TN_WGS = 256                                              # workgroups of 256 x 256 tiles a weight-gradient launch aims at: ONE round of the 256 CUs
                                                            # (two rounds = twice the split-M slabs to write and to sum: 13.83 / 14.68 ms per step against 13.65 / 14.45)
 
 
@@ -138,58 +126,6 @@ def _splits_x6(M: int, N1: int, N2: int, nb0: int) -> int:
     big = N1 % 256 == 0 and N2 % 256 == 0 and nb0 % 256 == 0
     tiles = (N1 // 256) * (N2 // 256) if big else (N1 // 128) * (N2 // 128)
     return max(1, min(64, (_TN_WGS if big else 2 * _TN_WGS) // tiles, M // 128))
-
-
-# ---- the gradient side stream.  In a level's backward the dX chain is the critical path (each product feeds the next); the weight
-# / bias gradients (dW = dY^T X, column sums) only CONSUME what it produces.  They run on a second HIP stream: the many short
-# launches of the chain (LayerNorm, dropout masks, column sums: 3-10 us each, a few workgroups) then share the chip with the large
-# weight-gradient GEMMs instead of queueing behind them.  Same kernels, same arguments, same order within each stream: results are
-# bit-identical to the single-stream schedule.  MEASURED (round 4, K = 2048, 8 slides) and therefore OFF by default
-# (PATHS_BWD_SIDE=1 enables it): the device side of a step gets shorter (the host no longer waits for it: drain 2.7 -> 0.06 ms), but
-# the ~35 fork points per step (event record + stream wait + record_stream + torch's stream context) cost 3.2 ms of HOST time
-# (backward enqueue 8.2 -> 11.4 ms) and the step becomes host-bound: 15.9 -> 17.0-17.9 ms.  It pays once the backward is replayed
-# from a launch tape (no Python per launch).
-BWD_SIDE = os.environ.get("PATHS_BWD_SIDE", "0") != "0"
-_SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
-
-
-class side_stream:
-    """``with side_stream(dev, t1, t2, ...):`` - the launches inside go to the device's gradient side stream, ordered after
-    everything enqueued on the current stream so far; the tensors named are read there (their blocks are not re-used before that
-    work is done: ``record_stream``).  :func:`side_join` orders the current stream behind the side stream again - the backward
-    functions call it before they return, i.e. before their raw-pointer operands (saved activations) can be freed."""
-
-    def __init__(self, dev, *reads):
-        self.on = BWD_SIDE and dev.type == "cuda" and _lib.TAPE is None
-        self.dev, self.reads = dev, reads
-
-    def __enter__(self):
-        if not self.on:
-            return self
-        idx = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-        side = _SIDE_STREAMS.get(idx)
-        if side is None:
-            side = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=idx)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        for t in self.reads:
-            if isinstance(t, torch.Tensor):
-                t.record_stream(side)
-        self.ctx = torch.cuda.stream(side)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.ctx.__exit__(*exc)
-        return False
-
-
-def side_join(dev):
-    if BWD_SIDE and dev.type == "cuda":
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        side = _SIDE_STREAMS.get(idx)
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
 
 
 # Deferred slab reductions (csrc/reduce_multi.hip): inside ``with deferred_reductions():`` the "out (+)= sum of slabs" pass that ends
@@ -246,7 +182,7 @@ def _keep_slabs(ws):
 
 class deferred_reductions:
     def __enter__(self):
-        self.on = DEFER_REDUCTIONS and not BWD_SIDE and _lib.TAPE is None
+        self.on = DEFER_REDUCTIONS and _lib.TAPE is None
         if self.on:
             if _DEFER["depth"] == 0:
                 _lib.load().paths_defer_reductions(1)
@@ -275,33 +211,26 @@ def gemm_tn(a, lda, b0, ldb0, out, M, N1, N2, b1=None, ldb1=0, nb0=0, ldo=None, 
     if TN_MODE == "x6" and M >= TN_X6_MIN_M and N1 % 128 == 0 and N2 % 128 == 0 and M * 4 * max(lda, ldb0, ldb1) < (1 << 31):
         splits = _splits_x6(M, N1, N2, nb0 if b1 is not None else 0)
         ws = torch.empty((splits * N1 * N2,), **_f32(dev))
-        ap = a if isinstance(a, int) else a.data_ptr()
-        b0p = b0 if isinstance(b0, int) else b0.data_ptr()
-        b1p = None if b1 is None else (b1 if isinstance(b1, int) else b1.data_ptr())
-        _lib.call("paths_gemm_tn_x6", ap, lda, b0p, ldb0, nb0, b1p, ldb1, P(out), ldo if ldo is not None else N2, M, N1, N2,
+        _lib.call("paths_gemm_tn_x6", P(a), lda, P(b0), ldb0, nb0, P(b1), ldb1, P(out), ldo if ldo is not None else N2, M, N1, N2,
                   splits, 1 if accumulate else 0, P(ws), 2 if ops.TRAIN_PLANES == 4 else 3, _lib.stream())
         _keep_slabs(ws)
         return
     splits = _splits(M, ((N1 + 127) // 128) * ((N2 + 127) // 128))
     ws = torch.empty((splits * N1 * N2,), **_f32(dev))
-    ap = a if isinstance(a, int) else a.data_ptr()
-    b0p = b0 if isinstance(b0, int) else b0.data_ptr()
-    b1p = None if b1 is None else (b1 if isinstance(b1, int) else b1.data_ptr())
-    _lib.call("paths_gemm_tn_f32", ap, lda, b0p, ldb0, nb0, b1p, ldb1, P(out), ldo if ldo is not None else N2, M, N1, N2,
+    _lib.call("paths_gemm_tn_f32", P(a), lda, P(b0), ldb0, nb0, P(b1), ldb1, P(out), ldo if ldo is not None else N2, M, N1, N2,
               splits, 1 if accumulate else 0, P(ws), _lib.stream())
     _keep_slabs(ws)
 
 
 def colsum(a, lda, M, N, out=None, accumulate=False):
-    dev = a.device if not isinstance(a, int) else out.device
+    dev = (out if type(a) is int else a).device
     if out is None:
         out = torch.empty((N,), **_f32(dev))
     if not WEIGHT_GRADS:
         return out
     splits = max(1, min(256, M // 64))
     ws = torch.empty((splits * N,), **_f32(dev))
-    ap = a if isinstance(a, int) else a.data_ptr()
-    _lib.call("paths_colsum_f32", ap, lda, M, N, P(out), splits, 1 if accumulate else 0, P(ws), _lib.stream())
+    _lib.call("paths_colsum_f32", P(a), lda, M, N, P(out), splits, 1 if accumulate else 0, P(ws), _lib.stream())
     _keep_slabs(ws)
     return out
 
@@ -320,9 +249,8 @@ def selection_forward_train(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_p
     d = mc.trans_dim
     Hc = lstm_pack["Hc"]
     Dp = D + Hc
-    M, T = B * N, N + 1
+    T = N + 1
     f32 = _f32(fts.device)
-    st = _lib.stream()
     sv = {"fts": fts, "state_prev": state_prev, "num_ims": num_ims, "locs": locs}
     sv["state_out"] = torch.empty((B, N, Dp), **f32)
     sv["y"] = torch.empty((B, N, D), **f32)
@@ -331,81 +259,39 @@ def selection_forward_train(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_p
     sv["tc"] = torch.empty((B, N, D), **f32)
     G = 3 * Hc + D
     x6 = ops.use_x6(D, Hc)        # forward GEMMs on the split-bf16 path (weight images are re-packed when the optimizer steps)
-    hp, hp_row = None, None
+    planes = ops.TRAIN_FWD_PLANES if x6 else 0
+    hpt = None
     if parent is not None:
-        assert state_prev is None
-        c0t, hk = parent["c0"], parent["h_kept"]
-        assert c0t.shape == (B, N, Hc) and c0t.is_contiguous() and hk.shape[1] == D and hk.is_contiguous()
-        ld, h0, c0 = Hc, None, c0t.data_ptr()
-        M4 = hk.shape[0]
-        sv["parent"] = {"c0": c0t, "h_kept": hk, "hp_row": parent["hp_row"], "child_pos": parent["child_pos"],
+        hk = parent["h_kept"]
+        assert hk.shape[1] == D and hk.is_contiguous()
+        sv["parent"] = {"c0": parent["c0"], "h_kept": hk, "hp_row": parent["hp_row"], "child_pos": parent["child_pos"],
                         "keep_count": parent["keep_count"], "cap": parent["cap"]}
-        hpt = torch.empty((M4, G), **f32)              # HP = h_kept W_gates[:, D:2D]^T (no bias), packed gate-column order
-        if x6 and G % 256 == 0:
-            TP = ops.TRAIN_FWD_PLANES
-            wg, wg_s = ops._x6_of(lstm_pack, "w_gates", TP, lagged=True)
-            _lib.call("paths_gemm_nt_x6", P(hk), D, P(wg), 2 * D, D, None, P(hpt), G, M4, G, G, D, 0, None, 0, None, 0, 0, TP, wg_s,
-                      ops.A_SCALE if TP == 2 else 1.0, st)
-        else:
-            _lib.call("paths_gemm_nt_f32", P(hk), D, lstm_pack["w_gates"].data_ptr() + 4 * D, 2 * D, None, P(hpt), G, M4, G, G, D, 0,
-                      None, 0, None, 0, 0, st)
-        hp, hp_row = P(hpt), P(parent["hp_row"])
-    elif state_prev is not None:
-        assert state_prev.shape == (B, N, Dp) and state_prev.stride(2) == 1 and state_prev.stride(0) == N * state_prev.stride(1)
-        ld, h0, c0 = state_prev.stride(1), state_prev.data_ptr(), state_prev.data_ptr() + 4 * D
-    else:
-        ld, h0, c0 = 0, None, None
-    if x6:
-        TP = ops.TRAIN_FWD_PLANES
-        asc = ops.A_SCALE if TP == 2 else 1.0
-        (wg, wg_s), (wm, wm_s) = ops._x6_of(lstm_pack, "w_gates", TP, lagged=True), ops._x6_of(lstm_pack, "w_mem", TP, lagged=True)
-        _lib.call("paths_lstm_cell_x6", P(fts), D, None, h0, ld, c0, ld, P(wg), P(lstm_pack["b_gates"]), P(wm), P(lstm_pack["b_mem"]),
-                  P(sv["state_out"]), Dp, P(sv["y"]), D, P(sv["o"]), P(sv["frm"]), P(sv["tc"]), hp, hp_row, M, D, Hc, None, N, 7,
-                  TP, wg_s, wm_s, asc, st)
-    else:
-        _lib.call("paths_lstm_cell", P(fts), D, h0, ld, c0, ld, P(lstm_pack["w_gates"]), P(lstm_pack["b_gates"]),
-                  P(lstm_pack["w_mem"]), P(lstm_pack["b_mem"]), P(sv["state_out"]), Dp,
-                  P(sv["y"]), D, P(sv["o"]), P(sv["frm"]), P(sv["tc"]), hp, hp_row, M, D, Hc, None, N, 7, st)
+        hpt = torch.empty((hk.shape[0], G), **f32)              # HP = h_kept W_gates[:, D:2D]^T (no bias), packed gate-column order
+        ops.parent_gate_product(lstm_pack, hk, hpt, planes, lagged=True)
+    prev = ops.prev_state_operands(parent, state_prev, B, N, D, Hc, hpt)
+    ops.lstm_cell(lstm_pack, fts, None, prev, sv["state_out"], sv["y"], sv["o"], sv["frm"], sv["tc"], N, None, 7, planes, lagged=True)
     sv["importance"] = torch.empty((B, N), **f32)
     sv["tokens"] = torch.empty((B, T, d), **f32)
     sv["hid"] = torch.empty((B, N, mc.importance_mlp_hidden_dim), **f32)
     sv["pproj"] = torch.empty((B, N, d), **f32)
     _importance_tokens(mc, lvl_pack, sv["y"], locs, num_ims, sv["importance"], sv["hid"], sv["pproj"], sv["tokens"],
-                       1 if mc.importance_mode == "mul" else 0, x6)
+                       1 if mc.importance_mode == "mul" else 0, planes)
     return sv
 
 
-def _importance_tokens(mc, lvl_pack, src, locs, num_ims, imp_out, hid_out, pproj_out, tokens_out, scale: int, x6: bool = False):
+def _importance_tokens(mc, lvl_pack, src, locs, num_ims, imp_out, hid_out, pproj_out, tokens_out, scale: int, planes: int = 0):
     """Importance MLP + proj_in + positional encoding over the rows ``src`` [B,N,D], keeping hid = relu(src W1^T + b1) and
     P = src Wp^T for the backward (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65).  ``scale`` 1: tokens =
-    importance * P + bp + PE; 0: tokens = P + bp + PE (importance_mode != "mul", or ``src`` is already scaled)."""
+    importance * P + bp + PE; 0: tokens = P + bp + PE (importance_mode != "mul", or ``src`` is already scaled).  ``planes``: the
+    operand split of the shipped geometry's GEMM (0: f32 inputs)."""
     B, N, D = src.shape
-    d, Hi, M = mc.trans_dim, mc.importance_mlp_hidden_dim, B * N
-    st = _lib.stream()
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
-    div = P(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"])
     if not ops.fast_path(mc):
         # any (trans_dim, hidden) widths: two generic GEMMs + the row kernels of csrc/generic.hip
-        gp = ops.generic_pack(lvl_pack, mc)
-        ops.gemm_f32(src, D, gp["w1"], lvl_pack["b1"], hid_out, Hi, M, Hi, D, act=1)
-        _lib.call("paths_importance_rows", P(hid_out), Hi, P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(num_ims), N, M, Hi, P(imp_out), 0, st)
-        ops.gemm_f32(src, D, gp["wp"], None, pproj_out, d, M, d, D)
-        _lib.call("paths_tokens_assemble", P(pproj_out), d, P(imp_out), scale, P(lvl_pack["bp"]), P(lvl_pack["special"]), div, P(locs), N,
-                  mc.patch_size, pe_mode, d, B, P(tokens_out), st)
+        ops.importance_proj_generic(mc, lvl_pack, src, D, locs, num_ims, B, N, D, scale, imp_out, tokens_out, hid=hid_out, pproj=pproj_out)
         return
-    tail = (P(lvl_pack["b1"]), P(lvl_pack["w2"]), P(lvl_pack["b2"]), P(lvl_pack["bp"]), P(lvl_pack["special"]), div, None, 0, P(locs),
-            P(num_ims), N, mc.patch_size, pe_mode, scale, P(imp_out), P(tokens_out), P(hid_out), P(pproj_out), M, D, Hi, d, 0, st)
-    if x6:
-        TP = ops.TRAIN_FWD_PLANES
-        wip, wip_s = ops._x6_of(lvl_pack, "w_ip_fwd", TP, lagged=True)
-        # M / 128 blocks fill half the chip: two k halves on twice the blocks + the epilogue launch, as in inference (round 5)
-        splitk_ws = None
-        if TRAIN_SPLITK_IMPORTANCE and TP == 2 and (M + 127) // 128 <= 160:
-            splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=src.device, dtype=torch.uint8)
-        _lib.call("paths_importance_proj_x6", P(src), D, None, None, 0, P(wip), *tail[:-1], TP, wip_s, ops.A_SCALE if TP == 2 else 1.0,
-                  P(splitk_ws), tail[-1])
-    else:
-        _lib.call("paths_importance_proj", P(src), D, P(lvl_pack["w_ip_fwd"]), *tail)
+    # M / 128 blocks fill half the chip: two k halves on twice the blocks + the epilogue launch, as in inference
+    ops.importance_proj(mc, lvl_pack, src, None, None, locs, num_ims, None, scale, imp_out, tokens_out, hid_out, pproj_out, B, N, D, False,
+                        planes=planes, lagged=True, splitk=planes == 2 and (B * N + 127) // 128 <= 160)
 
 
 def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_state_out: Optional[torch.Tensor], want_dx: bool = False):
@@ -435,18 +321,17 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
     else:
         _lib.call("paths_importance_bwd_any", P(d_tokens), P(sv["pproj"]), P(sv["hid"]), P(sv["importance"]), P(lvl_pack["w2"]),
                   P(num_ims), N, M, 1 if mc.importance_mode == "mul" else 0, Hi, d, U, P(du), P(da), P(dah), st)
-    with side_stream(dev, dah, da, du, d_tokens):
-        grads["w2"] = colsum(dah, Hi, M, Hi)
-        grads["b2"] = colsum(da, 1, M, 1)
-        grads["b1"] = colsum(du, U, M, Hi)
-        grads["special"] = colsum(d_tokens, T * d, B, d)
-        # proj_in.bias: sum of token gradients over the valid patch rows = colsum of dP / alpha is not usable (alpha may
-        # be 0), so sum d_tokens rows 1..N directly; padded token rows carry exact zeros (masked keys, unused queries)
-        # = (sum over all B*T token rows) - (sum over the B special-token rows): two launches instead of 2 B
-        grads["bp"] = bp_all = colsum(d_tokens, d, B * T, d)
-        after_reductions(lambda a=bp_all, b=grads["special"]: a.sub_(b))
-        grads["w_ip"] = torch.empty((Hi + d, D), **f32)
-        gemm_tn(du, U, sv["y"], D, grads["w_ip"], M, Hi + d, D)
+    grads["w2"] = colsum(dah, Hi, M, Hi)
+    grads["b2"] = colsum(da, 1, M, 1)
+    grads["b1"] = colsum(du, U, M, Hi)
+    grads["special"] = colsum(d_tokens, T * d, B, d)
+    # proj_in.bias: sum of token gradients over the valid patch rows = colsum of dP / alpha is not usable (alpha may
+    # be 0), so sum d_tokens rows 1..N directly; padded token rows carry exact zeros (masked keys, unused queries)
+    # = (sum over all B*T token rows) - (sum over the B special-token rows): two launches instead of 2 B
+    grads["bp"] = bp_all = colsum(d_tokens, d, B * T, d)
+    after_reductions(lambda a=bp_all, b=grads["special"]: a.sub_(b))
+    grads["w_ip"] = torch.empty((Hi + d, D), **f32)
+    gemm_tn(du, U, sv["y"], D, grads["w_ip"], M, Hi + d, D)
     dy = torch.empty((M, D), **f32)
     w_ip_t = Transposed(lvl_pack["w_ip"], Hi + d, D, pad_to=U)          # [D, U]
     gemm_nt(du, U, w_ip_t, dy, D, M, D, U)
@@ -458,10 +343,9 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
     _lib.call("paths_lstm_bwd_a", P(dy), D, ext_h, Dp, P(sv["o"]), P(sv["tc"]), P(num_ims), N, M, D,
               dG.data_ptr() + 4 * 3 * Hc, G, P(dpre_h), st)
     c1_ptr = sv["state_out"].data_ptr() + 4 * D
-    with side_stream(dev, dpre_h):
-        grads["b_mem"] = colsum(dpre_h, D, M, D)
-        grads["w_mem"] = torch.empty((D, Hc), **f32)
-        gemm_tn(dpre_h, D, c1_ptr, Dp, grads["w_mem"], M, D, Hc)
+    grads["b_mem"] = colsum(dpre_h, D, M, D)
+    grads["w_mem"] = torch.empty((D, Hc), **f32)
+    gemm_tn(dpre_h, D, c1_ptr, Dp, grads["w_mem"], M, D, Hc)
     dc1_h = torch.empty((M, Hc), **f32)
     w_mem_t = Transposed(lstm_pack["w_mem"], D, Hc)                      # [Hc, D]
     gemm_nt(dpre_h, D, w_mem_t, dc1_h, Hc, M, Hc, D)
@@ -493,20 +377,17 @@ def selection_backward(mc, lstm_pack, lvl_pack, sv, d_tokens: torch.Tensor, d_st
         wh_t = Transposed(lstm_pack["w_gates"], G, D, ld=2 * D, offset=D)                  # [D, G] = (W_gates[:, D:2D])^T
         d_hk = torch.empty((M4, D), **f32)
         gemm_nt(dhp, G, wh_t, d_hk, D, M4, D, G)
-        side_join(dev)
         return (grads, (d_c0, d_hk), dx) if want_dx else (grads, (d_c0, d_hk))
-    with side_stream(dev, dG, fts):
-        grads["b_gates"] = colsum(dG, G, M, G)
-        grads["w_gates"] = torch.empty((G, 2 * D), **f32)
-        if state_prev is None:
-            grads["w_gates"][:, D:].zero_()                                      # the h panel is dead at depth 0
-            gemm_tn(dG, G, fts, D, grads["w_gates"], M, G, D, ldo=2 * D)        # only the x panel is live at depth 0
-        else:
-            gemm_tn(dG, G, fts, D, grads["w_gates"], M, G, 2 * D, b1=state_prev.data_ptr(), ldb1=state_prev.stride(1), nb0=D)
+    grads["b_gates"] = colsum(dG, G, M, G)
+    grads["w_gates"] = torch.empty((G, 2 * D), **f32)
+    if state_prev is None:
+        grads["w_gates"][:, D:].zero_()                                      # the h panel is dead at depth 0
+        gemm_tn(dG, G, fts, D, grads["w_gates"], M, G, D, ldo=2 * D)        # only the x panel is live at depth 0
+    else:
+        gemm_tn(dG, G, fts, D, grads["w_gates"], M, G, 2 * D, b1=state_prev.data_ptr(), ldb1=state_prev.stride(1), nb0=D)
     if state_prev is not None:
         wh_t = Transposed(lstm_pack["w_gates"], G, D, ld=2 * D, offset=D)   # [D, G] = (W_gates[:, D:2D])^T
         gemm_nt(dG, G, wh_t, d_state_prev.data_ptr(), Dp, M, D, G)
-    side_join(dev)                     # (before the saved activations behind the raw pointers above can be freed)
     return (grads, d_state_prev, dx) if want_dx else (grads, d_state_prev)
 
 
@@ -619,9 +500,6 @@ def unpack_lstm_grads(lstm, g: Dict[str, torch.Tensor]) -> Dict[str, torch.Tenso
 # ---------------------------------------------------------------------------------------------------------------
 # transformer aggregator (post-LN decoder stack over an empty memory; last layer evaluated at token 0 only)
 # ---------------------------------------------------------------------------------------------------------------
-LOG2E = 1.4426950408889634
-
-
 class Drop:
     """Dropout of one level's transformer in one training step (reference nn.Transformer(..., dropout=p): five sites per decoder
     layer).  ``seed`` is drawn once per level forward from the device's default generator (paths_amd/autograd.py:next_dropout_seed:
@@ -642,12 +520,11 @@ class Drop:
 
 def dropout_rows(x, ldx, M, N, key, p, out=None, ldo=None, resid=None, ldr=0, vec=None):
     """out = (resid) + (vec broadcast | x) * mask / (1 - p)   (paths_dropout_rows); x / resid / out may be raw pointers."""
-    ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
     dev = next(t for t in (out, x, resid, vec) if t is not None and not isinstance(t, int)).device
     if out is None:
         out = torch.empty((M, N), **_f32(dev))
         ldo = N
-    _lib.call("paths_dropout_rows", ptr(x) if vec is None else None, ldx, ptr(vec), ptr(resid), ldr, ptr(out), ldo if ldo is not None else N,
+    _lib.call("paths_dropout_rows", P(x) if vec is None else None, ldx, P(vec), P(resid), ldr, P(out), ldo if ldo is not None else N,
               M, N, key, p, _lib.stream())
     return out
 
@@ -754,12 +631,11 @@ def chain_backward(w, x_in_ptr: int, ldx: int, attn_ptr: int, lda: int, M: int, 
     gemm_nt(dffo, d, Transposed(w["w2"], d, F), dhid, F, M, F, d, mask=hid, ldm=F)
     if drop is not None:
         dropout_rows(dhid, F, M, F, drop.key(layer, Drop.FF_INNER), p, out=dhid, ldo=F)
-    with side_stream(dev, dffo, hd, dhid, n2):
-        g["w2"] = torch.empty((d, F), **f32)
-        gemm_tn(dffo, d, hd, F, g["w2"], M, d, F)
-        g["w1"] = torch.empty((F, d), **f32)
-        gemm_tn(dhid, F, n2, d, g["w1"], M, F, d)
-        g["b1"] = colsum(dhid, F, M, F)
+    g["w2"] = torch.empty((d, F), **f32)
+    gemm_tn(dffo, d, hd, F, g["w2"], M, d, F)
+    g["w1"] = torch.empty((F, d), **f32)
+    gemm_tn(dhid, F, n2, d, g["w1"], M, F, d)
+    g["b1"] = colsum(dhid, F, M, F)
     dn2 = torch.empty((M, d), **f32)
     gemm_nt(dhid, F, Transposed(w["w1"], F, d), dn2, d, M, d, F, residual=du3, ldr=d)
     du2, g["ln2g"], g["ln2b"], cs2 = _ln_bwd_sums(dn2, c["xh2"], c["rs2"], w["ln2g"], M, d)
@@ -772,9 +648,8 @@ def chain_backward(w, x_in_ptr: int, ldx: int, attn_ptr: int, lda: int, M: int, 
         g["bo"] = colsum(dsa, d, M, d)
     dattn = torch.empty((M, di), **f32)
     gemm_nt(dsa, d, Transposed(w["wo"], d, di), dattn, di, M, di, d)
-    with side_stream(dev, dsa):
-        g["wo"] = torch.empty((d, di), **f32)
-        gemm_tn(dsa, d, attn_ptr, lda, g["wo"], M, d, di)
+    g["wo"] = torch.empty((d, di), **f32)
+    gemm_tn(dsa, d, attn_ptr, lda, g["wo"], M, d, di)
     return g, du1, dattn
 
 
@@ -789,12 +664,11 @@ def qkv_backward(w, x_in: torch.Tensor, dqkv: torch.Tensor, M: int, qscale: floa
     if fold_qscale:
         wt[:, :di] *= qscale
     gemm_nt(dqkv, 3 * di, wt, dx_accum, d, M, d, 3 * di, accumulate=True)
-    with side_stream(x_in.device, dqkv, x_in):
-        g["wqkv"] = torch.empty((3 * di, d), **f32)
-        gemm_tn(dqkv, 3 * di, x_in, d, g["wqkv"], M, 3 * di, d)
-        g["bqkv"] = colsum(dqkv, 3 * di, M, 3 * di)
-        if fold_qscale:
-            after_reductions(lambda w_=g["wqkv"], b_=g["bqkv"]: (w_[:d].mul_(qscale), b_[:d].mul_(qscale)))
+    g["wqkv"] = torch.empty((3 * di, d), **f32)
+    gemm_tn(dqkv, 3 * di, x_in, d, g["wqkv"], M, 3 * di, d)
+    g["bqkv"] = colsum(dqkv, 3 * di, M, 3 * di)
+    if fold_qscale:
+        after_reductions(lambda w_=g["wqkv"], b_=g["bqkv"]: (w_[:d].mul_(qscale), b_[:d].mul_(qscale)))
     return g
 
 
@@ -836,24 +710,14 @@ def transformer_forward_train(mc, lvl_pack, tokens, num_ims, ctx_prev, drop: Opt
     H, L = mc.trans_heads, mc.trans_layers
     hd = d // H
     f32 = _f32(tokens.device)
-    st = _lib.stream()
-    qscale = LOG2E / math.sqrt(hd)
+    qscale = ops.LOG2E / math.sqrt(hd)
     layers = lvl_pack["layers"]
     # ctx_prev [B,128]: slide_ctx_mode "residual" (added to the slide feature); ctx_all [B,depth,128] contiguous: "concat" (the
     # classifier reads cat(flatten(ctx_all), slide feature), reference model/paths.py:134-137); at most one of the two is given
-    assert ctx_prev is None or ctx_all is None
-    cdepth = ctx_all.shape[1] if ctx_all is not None else 0
-    cat_ptr = P(ctx_all) if cdepth > 0 else None
-    sv = {"layers": [], "num_ims": num_ims, "tokens": tokens, "ctx_prev": ctx_prev, "ctx_all": ctx_all if cdepth > 0 else None}
+    sv = {"layers": [], "num_ims": num_ims, "tokens": tokens, "ctx_prev": ctx_prev}
 
-    def token_layer(x_in, x_out, post, nxt, attn, q, k, v):
-        w = post or nxt
-        gg = lambda dct, key: P(dct[key]) if dct is not None else None
-        _lib.call("paths_token_layer_f32", P(x_in), P(attn) if post else None, P(x_out) if post else None,
-                  gg(post, "wo"), gg(post, "bo"), gg(post, "ln1g"), gg(post, "ln1b"), gg(post, "cab"), gg(post, "ln2g"), gg(post, "ln2b"),
-                  gg(post, "w1"), gg(post, "b1"), gg(post, "w2"), gg(post, "b2"), gg(post, "ln3g"), gg(post, "ln3b"),
-                  gg(nxt, "wqkv"), gg(nxt, "bqkv"), P(q), P(k), P(v), P(num_ims), B, T, d, H,
-                  1 if post else 0, 1 if nxt else 0, 0, qscale, w["eps"], 0, st)
+    def token_layer(x_in, x_out, post, nxt, attn, q, k, v):        # (skip 0: padded token rows are computed too)
+        ops.token_layer_f32(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B, T, d, H, qscale, 0)
 
     x = tokens
     q, k, v = (torch.empty((B, H, T, hd), **f32) for _ in range(3))
@@ -875,29 +739,18 @@ def transformer_forward_train(mc, lvl_pack, tokens, num_ims, ctx_prev, drop: Opt
         x, q, k, v = x_out, q2, k2, v2
     # last layer at token 0 (+ decoder.norm, residual, classifier): one fused launch
     w = layers[L - 1]
-    nlog = lvl_pack["wcls"].shape[0]
-    ctx_out = torch.empty((B, d), **f32)
-    logits = torch.empty((B, nlog), **f32)
+    head = ops.slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B, d, tokens.device)
+    sv["ctx_all"], sv["ctx_out"], sv["logits"] = head[1], head[3], head[4]
     if drop is not None:
         # the fused token-0 tail has no dropout sites either: single-query attention (rows > 0 of the output are not needed), the
         # row chain on the B token-0 rows, decoder.norm, slide-context residual and classifier with the generic kernels
         a0, lse0 = attention_token0(q, k, v, num_ims, B, T, H, hd, drop.key(L - 1, Drop.ATTN), drop.p)
         chain0 = chain_forward(w, x.data_ptr(), T * d, a0.data_ptr(), d, B, tokens.device, drop, L - 1)
-        x3 = chain0["x3"]
-        _lib.call("paths_final_head", P(x3), d, P(lvl_pack["lnfg"]), P(lvl_pack["lnfb"]), P(ctx_prev),
-                  ctx_prev.stride(0) if ctx_prev is not None else 0, cat_ptr, cdepth, P(lvl_pack["wcls"]), P(lvl_pack["bcls"]), nlog,
-                  lvl_pack["wcls"].shape[1], P(ctx_out), P(logits), B, d, lvl_pack["lnf_eps"], st)
+        ops.final_head(lvl_pack, chain0["x3"], d, head, B, d, any_width=False)
         sv["last"] = {"x_in": x, "q": q, "k": k, "v": v, "a0": a0, "lse0": lse0, "chain": chain0}
-        sv["ctx_out"], sv["logits"] = ctx_out, logits
         return sv
-    ws = torch.empty((B * H * 16 * 36,), **f32)
-    _lib.call("paths_token0_tail", P(x), P(q), P(k), P(v), P(num_ims), P(w["wo"]), P(w["bo"]), P(w["ln1g"]), P(w["ln1b"]),
-              P(w["cab"]), P(w["ln2g"]), P(w["ln2b"]), P(w["w1"]), P(w["b1"]), P(w["w2"]), P(w["b2"]), P(w["ln3g"]), P(w["ln3b"]),
-              P(lvl_pack["lnfg"]), P(lvl_pack["lnfb"]), P(ctx_prev), ctx_prev.stride(0) if ctx_prev is not None else 0, cat_ptr, cdepth,
-              P(lvl_pack["wcls"]), P(lvl_pack["bcls"]), nlog, lvl_pack["wcls"].shape[1], P(ctx_out), P(logits), P(ws),
-              B, T, d, H, w["eps"], lvl_pack["lnf_eps"], st)
+    ops.token0_tail(lvl_pack, x, q, k, v, num_ims, head, B, T, d, H)
     sv["last"] = {"x_in": x, "q": q, "k": k, "v": v}
-    sv["ctx_out"], sv["logits"] = ctx_out, logits
     return sv
 
 
@@ -934,13 +787,10 @@ def _transformer_forward_train_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, 
     di = H * hd
     dev = tokens.device
     f32 = _f32(dev)
-    qscale = LOG2E / math.sqrt(d // H)
+    qscale = ops.LOG2E / math.sqrt(d // H)
     layers = lvl_pack["layers"]
     M = B * T
-    assert ctx_prev is None or ctx_all is None
-    cdepth = ctx_all.shape[1] if ctx_all is not None else 0
-    sv = {"layers": [], "num_ims": num_ims, "tokens": tokens, "ctx_prev": ctx_prev, "ctx_all": ctx_all if cdepth > 0 else None,
-          "drop": drop}
+    sv = {"layers": [], "num_ims": num_ims, "tokens": tokens, "ctx_prev": ctx_prev, "drop": drop}
 
     spare = 128 if ops.wide_head(hd) else 0          # wide heads: the score products read whole 128-row tiles of k / v
 
@@ -965,15 +815,10 @@ def _transformer_forward_train_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, 
     attn0, lse0 = zeros_group(dev, (B, T, di), (B, H, T))
     _attention_generic(qkv, attn0, lse0, num_ims, B, T, H, hd, qscale, 1, drop, L - 1)
     chain0 = chain_forward(w, x.data_ptr(), T * d, attn0.data_ptr(), T * di, B, dev, drop, L - 1)
-    x3 = chain0["x3"]
-    nlog = lvl_pack["wcls"].shape[0]
-    ctx_out = torch.empty((B, d), **f32)
-    logits = torch.empty((B, nlog), **f32)
-    _lib.call("paths_final_head_any", P(x3), d, P(lvl_pack["lnfg"]), P(lvl_pack["lnfb"]), P(ctx_prev),
-              ctx_prev.stride(0) if ctx_prev is not None else 0, P(ctx_all) if cdepth > 0 else None, cdepth, P(lvl_pack["wcls"]),
-              P(lvl_pack["bcls"]), nlog, lvl_pack["wcls"].shape[1], P(ctx_out), P(logits), B, d, lvl_pack["lnf_eps"], _lib.stream())
+    head = ops.slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B, d, dev)
+    ops.final_head(lvl_pack, chain0["x3"], d, head, B, d, any_width=True)
     sv["last"] = {"x_in": x, "qkv": qkv, "attn0": attn0, "lse0": lse0, "chain": chain0}
-    sv["ctx_out"], sv["logits"] = ctx_out, logits
+    sv["ctx_all"], sv["ctx_out"], sv["logits"] = head[1], head[3], head[4]
     return sv
 
 
@@ -990,7 +835,7 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
     dev = tokens.device
     f32 = _f32(dev)
     st = _lib.stream()
-    qscale = LOG2E / math.sqrt(d // H)
+    qscale = ops.LOG2E / math.sqrt(d // H)
     layers = lvl_pack["layers"]
     grads = {"layers": [None] * L}
     nlog = lvl_pack["wcls"].shape[0]
@@ -1089,7 +934,6 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
         g.update(qkv_backward(w, lv["x_in"], dqkv, M, qscale, dx_in, fold_qscale=fast))
         grads["layers"][l] = g
         dx = dx_in.view(B, T, d)
-    side_join(dev)                     # the weight / bias gradients issued on the side stream (chain_backward, qkv_backward)
     # zero-padded heads (ops.padded_head_dim): gradients of the padded in_proj / out_proj images back to the parameters' own rows /
     # columns (once the deferred slab reductions that produce them have run)
     for l in range(L):

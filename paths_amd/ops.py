@@ -180,36 +180,30 @@ def reset_lagged_scales():
     _LAGGED_EPOCH[0] += 1
 
 
-def tlayer_h3_images(layer: Dict[str, object], part: int):
-    """(image, scales) of a decoder layer's weights for paths_token_layer_h3: part 0 = (wo, w1, w2), part 1 = wqkv.
-    Built on first use and cached in the layer's pack dict (rebuilt when weights change)."""
-    key = f"h3_image_{part}"
+def _tlayer_images(layer: Dict[str, object], part: int, kind: str):
+    """(image, scales) of a decoder layer's weights for paths_token_layer_<kind> (kind "h3" or "ws"): part 0 = (wo, w1, w2), part 1 =
+    wqkv.  Built on first use and cached in the layer's pack dict (rebuilt when weights change)."""
+    key = f"{kind}_image_{part}"
     if key not in layer:
         ws = [layer["wo"], layer["w1"], layer["w2"]] if part == 0 else [layer["wqkv"]]
         scales = tuple(_pow2_scale(w) for w in ws)
-        nbytes = int(_lib.load().paths_tlayer_h3_image_bytes(part))
-        img = torch.empty((nbytes,), device=ws[0].device, dtype=torch.uint8)
+        dims = (layer["wo"].shape[0],) if kind == "ws" else ()           # (the ws kernels are instantiated per trans_dim)
+        img = torch.empty((int(getattr(_lib.load(), f"paths_tlayer_{kind}_image_bytes")(part, *dims)),), device=ws[0].device, dtype=torch.uint8)
         pw = [_lib.ptr(w) for w in ws] + [None] * (3 - len(ws))
         sc = list(scales) + [1.0] * (3 - len(scales))
-        _lib.call("paths_tlayer_pack_h3", part, pw[0], pw[1], pw[2], sc[0], sc[1], sc[2], _lib.ptr(img), _lib.stream())
+        _lib.call(f"paths_tlayer_pack_{kind}", part, pw[0], pw[1], pw[2], sc[0], sc[1], sc[2], _lib.ptr(img), *dims, _lib.stream())
         layer[key] = (img, scales)
     return layer[key]
+
+
+def tlayer_h3_images(layer: Dict[str, object], part: int):
+    """:func:`_tlayer_images` for paths_token_layer_h3."""
+    return _tlayer_images(layer, part, "h3")
 
 
 def tlayer_ws_images(layer: Dict[str, object], part: int):
-    """(image, scales) of a decoder layer's weights for paths_token_layer_ws: part 0 = (wo, w1, w2), part 1 = wqkv; cached in the
-    layer's pack dict like :func:`tlayer_h3_images`."""
-    key = f"ws_image_{part}"
-    if key not in layer:
-        ws = [layer["wo"], layer["w1"], layer["w2"]] if part == 0 else [layer["wqkv"]]
-        scales = tuple(_pow2_scale(w) for w in ws)
-        d = layer["wo"].shape[0]
-        img = torch.empty((int(_lib.load().paths_tlayer_ws_image_bytes(part, d)),), device=ws[0].device, dtype=torch.uint8)
-        pw = [_lib.ptr(w) for w in ws] + [None] * (3 - len(ws))
-        sc = list(scales) + [1.0] * (3 - len(scales))
-        _lib.call("paths_tlayer_pack_ws", part, pw[0], pw[1], pw[2], sc[0], sc[1], sc[2], _lib.ptr(img), d, _lib.stream())
-        layer[key] = (img, scales)
-    return layer[key]
+    """:func:`_tlayer_images` for paths_token_layer_ws / paths_token_layer_ws_rows."""
+    return _tlayer_images(layer, part, "ws")
 
 
 def token0_ws_image(layer: Dict[str, object], qscale: float) -> torch.Tensor:
@@ -295,17 +289,25 @@ def _versions(params):
     return tuple((p.data_ptr(), p._version) for p in params)
 
 
+def _cached_pack(owner, list_params):
+    """(version key of ``owner``'s parameters, the pack dict cached on it under that key or None).  ``list_params()`` runs once per
+    module (walking the module tree on every call was 1.5 ms of host time per training step); the caller stores a fresh pack as
+    ``owner._paths_pack = (key, packed)``."""
+    params = getattr(owner, "_paths_param_list", None)
+    if params is None:
+        params = list_params()
+        object.__setattr__(owner, "_paths_param_list", params)
+    key = _versions(params)
+    cache = getattr(owner, "_paths_pack", None)
+    return key, (cache[1] if cache is not None and cache[0] == key else None)
+
+
 def pack_lstm(lstm) -> Dict[str, torch.Tensor]:
     """Gate rows regrouped so that one 96-column wave tile holds forget|remember|map of 32 memory units."""
     srcs = [lstm.forget_gate[0], lstm.remember_gate[0], lstm.remember_map[0], lstm.out_select_gate[0], lstm.mem_to_out[0]]
-    params = getattr(lstm, "_paths_param_list", None)
-    if params is None:
-        params = [t for m in srcs for t in (m.weight, m.bias)]
-        object.__setattr__(lstm, "_paths_param_list", params)
-    key = _versions(params)
-    cache = getattr(lstm, "_paths_pack", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
+    key, packed = _cached_pack(lstm, lambda: [t for m in srcs for t in (m.weight, m.bias)])
+    if packed is not None:
+        return packed
     with torch.no_grad():
         f, r, m, o, mo = srcs
         Hc = f.weight.shape[0]
@@ -328,17 +330,12 @@ def pack_level(proc) -> Dict[str, object]:
     """Per-level tensors in the layout the kernels read.  Dead encoder / cross-attention matrices are
     never touched (only ``multihead_attn.out_proj.bias`` is live)."""
     agg = proc.global_agg
-    params = getattr(proc, "_paths_param_list", None)        # (walking the module tree here was 1.5 ms of host time per training step)
-    if params is None:
-        params = list(proc.importance_mlp.parameters()) + [agg.proj_in.weight, agg.proj_in.bias, agg.special_token]
-        params += list(agg.transformer.decoder.parameters()) + list(proc.classification_layer.parameters())
-        if hasattr(proc, "hctx_mlp"):
-            params += list(proc.hctx_mlp.parameters())
-        object.__setattr__(proc, "_paths_param_list", params)
-    key = _versions(params)
-    cache = getattr(proc, "_paths_pack", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
+    key, packed = _cached_pack(proc, lambda: (
+        list(proc.importance_mlp.parameters()) + [agg.proj_in.weight, agg.proj_in.bias, agg.special_token]
+        + list(agg.transformer.decoder.parameters()) + list(proc.classification_layer.parameters())
+        + (list(proc.hctx_mlp.parameters()) if hasattr(proc, "hctx_mlp") else [])))
+    if packed is not None:
+        return packed
     with torch.no_grad():
         c = lambda t: t.detach().float().contiguous()
         d = agg.dim
@@ -414,14 +411,9 @@ def pack_aggregator(agg) -> Dict[str, object]:
     """The aggregator's own tensors for a STANDALONE ``TransformerAggregator.forward`` (reference model/aggregator.py:58-76): the
     decoder layers, the final norm, the special token and proj_in; the classifier slot of the token-0 tail is a zero [1, d] row
     (its logit is discarded).  Cached on the module, invalidated by parameter version counters like :func:`pack_level`."""
-    params = getattr(agg, "_paths_param_list", None)
-    if params is None:
-        params = [agg.proj_in.weight, agg.proj_in.bias, agg.special_token] + list(agg.transformer.decoder.parameters())
-        object.__setattr__(agg, "_paths_param_list", params)
-    key = _versions(params)
-    cache = getattr(agg, "_paths_pack", None)
-    if cache is not None and cache[0] == key:
-        return cache[1]
+    key, packed = _cached_pack(agg, lambda: [agg.proj_in.weight, agg.proj_in.bias, agg.special_token] + list(agg.transformer.decoder.parameters()))
+    if packed is not None:
+        return packed
     with torch.no_grad():
         c = lambda t: t.detach().float().contiguous()
         d = agg.dim
@@ -524,7 +516,7 @@ def gemm_f32(a, lda: int, w_pad: torch.Tensor, bias, out, ldo: int, M: int, N: i
     ``split`` = (cache dict, key) (inference only: the image costs one host sync per weight version): products with M >= 1024 rows run
     on the split-operand kernel of the tuned path instead (csrc/gemm_x6.hip: two fp16 planes per operand in the default mode, 22-bit
     products, fp32 accumulate - the arithmetic of every big product of the shipped geometry), 3x the f32-MFMA rate."""
-    ptr = lambda t: t if isinstance(t, int) or t is None else t.data_ptr()
+    ptr = _lib.ptr
     if split is not None and GENERIC_SPLIT and GEMM_MODE != "f32" and M >= 1024 and K >= 128 and K % 32 == 0:
         cache, key = split
         k6 = f"{key}_x6_{split_planes()}"
@@ -538,22 +530,57 @@ def gemm_f32(a, lda: int, w_pad: torch.Tensor, bias, out, ldo: int, M: int, N: i
               ptr(residual), ldr, None, 0, 0, _lib.stream())
 
 
-def importance_proj_generic(mc, lvl_pack, src, ld_src: int, locs, num_ims, B: int, N: int, D: int, imp_mul: int, imp_out, tokens):
+def importance_proj_generic(mc, lvl_pack, src, ld_src: int, locs, num_ims, B: int, N: int, D: int, imp_mul: int, imp_out, tokens,
+                            hid=None, pproj=None):
     """importance MLP + masked sigmoid + alpha * proj_in + positional encoding + special token for any (trans_dim, hidden) widths
-    (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65): two GEMMs and two row kernels."""
+    (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65): two GEMMs and two row kernels.  ``hid`` / ``pproj``
+    (training): the buffers that keep hid = relu(src W1^T + b1) and P = src Wp^T for the backward - both products then stay on the
+    f32-input kernel (a split weight image costs a host sync per weight version); inference allocates scratch."""
     gp = generic_pack(lvl_pack, mc)
     d, Hi, M = mc.trans_dim, mc.importance_mlp_hidden_dim, B * N
     dev = locs.device
     st = _lib.stream()
     p = _lib.ptr
-    hid = torch.empty((M, Hi), device=dev, dtype=torch.float32)
-    gemm_f32(src, ld_src, gp["w1"], lvl_pack["b1"], hid, Hi, M, Hi, D, act=1, split=(gp, "w1"))
+    train = hid is not None
+    if not train:
+        hid = torch.empty((M, Hi), device=dev, dtype=torch.float32)
+    gemm_f32(src, ld_src, gp["w1"], lvl_pack["b1"], hid, Hi, M, Hi, D, act=1, split=None if train else (gp, "w1"))
     _lib.call("paths_importance_rows", p(hid), Hi, p(lvl_pack["w2"]), p(lvl_pack["b2"]), p(num_ims), N, M, Hi, p(imp_out), 0, st)
-    proj = torch.empty((M, d), device=dev, dtype=torch.float32)
-    gemm_f32(src, ld_src, gp["wp"], None, proj, d, M, d, D, split=(gp, "wp"))
+    if not train:
+        pproj = torch.empty((M, d), device=dev, dtype=torch.float32)
+    gemm_f32(src, ld_src, gp["wp"], None, pproj, d, M, d, D, split=None if train else (gp, "wp"))
     pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
-    _lib.call("paths_tokens_assemble", p(proj), d, p(imp_out), imp_mul, p(lvl_pack["bp"]), p(lvl_pack["special"]),
+    _lib.call("paths_tokens_assemble", p(pproj), d, p(imp_out), imp_mul, p(lvl_pack["bp"]), p(lvl_pack["special"]),
               p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), p(locs), N, mc.patch_size, pe_mode, d, B, p(tokens), st)
+
+
+def importance_proj(mc, lvl_pack, src, x_rows, add, locs, num_ims, pe_tab, imp_mul: int, imp_out, tokens, hid, pproj, B: int, N: int, D: int,
+                    skip_padding: bool, planes: int = 0, lagged: bool = False, splitk: bool = False, h16: str = ""):
+    """importance MLP + masked sigmoid + alpha * proj_in + positional encoding + special token of the shipped geometry in one GEMM
+    with a fused epilogue (reference model/paths.py:95-98,119-124; model/aggregator.py:37-65).  ``planes`` 0: the f32-input kernel
+    (paths_importance_proj); 2 / 3: the split-operand kernel (paths_importance_proj_x6) whose input is ``src`` - or the rows at the
+    addresses ``x_rows`` when ``src`` is None (``h16``: fp16 rows) - plus ``add`` (row stride arbitrary) summed while it is staged;
+    ``splitk``: two k halves on twice the blocks + an epilogue launch (M / 128 blocks fill half the chip at K = 2048 x 8 slides).
+    ``hid`` / ``pproj`` (training): keep relu(src W1^T + b1) and src Wp^T for the backward; ``lagged``: see :func:`_x6_of`."""
+    p = _lib.ptr
+    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    M = B * N
+    common = (p(lvl_pack["b1"]), p(lvl_pack["w2"]), p(lvl_pack["b2"]),
+              p(lvl_pack["bp"]), p(lvl_pack["special"]), p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]),
+              p(pe_tab), pe_tab.shape[0] if pe_tab is not None else 0, p(locs),
+              p(num_ims), N, mc.patch_size, pe_mode, imp_mul, p(imp_out), p(tokens), p(hid), p(pproj),
+              M, D, mc.importance_mlp_hidden_dim, mc.trans_dim, 1 if skip_padding else 0)
+    if not planes:
+        assert add is None and x_rows is None
+        _lib.call("paths_importance_proj", p(src), D, p(lvl_pack["w_ip_fwd"]), *common, _lib.stream())
+        return
+    wip, wip_s = _x6_of(lvl_pack, "w_ip_fwd", planes, lagged=lagged)
+    splitk_ws = None
+    if splitk:
+        splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=locs.device, dtype=torch.uint8)
+    _lib.call("paths_importance_proj_x6" + (h16 if src is None else ""), p(src), D, p(x_rows) if src is None else None, p(add),
+              add.stride(1) if add is not None else 0, p(wip), *common, planes, wip_s, A_SCALE if planes == 2 else 1.0,
+              p(splitk_ws), _lib.stream())
 
 
 def importance_proj_generic_add(mc, lvl_pack, src, x_rows, add, locs, num_ims, B: int, N: int, D: int, imp_mul: int, imp_out, tokens, skip_padding: bool,
@@ -628,7 +655,7 @@ def _fp8_image(fp, key: str, nbytes: int, dev, zero: bool = False) -> torch.Tens
 def gemm_fp8(fp, a, lda: int, w8sc, bias, out, ldo: int, M: int, N: int, K: int, act: int = 0, residual=None, ldr: int = 0, tok=None):
     """out[M, N] = act(a[M, K] w^T + bias) (+ residual) with e4m3 operands (csrc/gemm_fp8.hip): per-tensor activation scale from a
     device-side max|a| (no host sync), the activation image from one quantisation pass, the weight image and its scale from :func:`fp8_pack`."""
-    ptr = lambda t: t if isinstance(t, int) or t is None else t.data_ptr()
+    ptr = _lib.ptr
     st = _lib.stream()
     # tok = (num_ims, T): the rows are tokens of slides - only valid ones count for the scale (padded rows may hold anything)
     _lib.call("paths_fp8_scale", ptr(a), lda, M, K, fp["a_scale"].data_ptr(), fp["scratch"].data_ptr(), tok[0].data_ptr() if tok else None,
@@ -678,8 +705,120 @@ def fp8_supported(mc) -> bool:
     return d % 128 == 0 and d % H == 0 and (d // H) in FP8_HEAD_DIMS      # paths_gemm_nt_fp8 needs K % 128 == 0 (one 64-k instruction pair per stage)
 
 
-def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8: bool = False, status=None,
-                                attention=None, rollout=None) -> Dict[str, torch.Tensor]:
+# ---------------------------------------------------------------------------------------------
+# launches shared by the inference forms here and the training forward (paths_amd/backward.py): one function per C entry point
+# ---------------------------------------------------------------------------------------------
+def slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B: int, d: int, dev, mode: Optional[str] = None):
+    """(res, cat, depth, ctx_out, logits): what the head of a level reads and writes (reference model/paths.py:130-139).  ``res`` [B, d]
+    is added to the slide feature (slide_ctx_mode "residual"), ``cat`` [B, depth, d] contiguous is what the classifier reads in front
+    of it ("concat"), ``ctx_out`` [B, d] / ``logits`` [B, classes] are fresh.  ``mode`` = mc.slide_ctx_mode picks from (ctx_prev,
+    ctx_all); None (training): the caller hands in only what its mode reads, at most one of the two."""
+    assert mode is not None or ctx_prev is None or ctx_all is None
+    ctx_out = torch.empty((B, d), device=dev, dtype=torch.float32)
+    logits = torch.empty((B, lvl_pack["wcls"].shape[0]), device=dev, dtype=torch.float32)
+    res = ctx_prev if mode in (None, "residual") else None
+    cat = ctx_all.contiguous() if (mode in (None, "concat") and ctx_all is not None and ctx_all.shape[1] > 0) else None
+    return res, cat, cat.shape[1] if cat is not None else 0, ctx_out, logits
+
+
+def final_head(lvl_pack, x, ldx: int, head, B: int, d: int, any_width: bool):
+    """decoder.norm of the rows ``x`` (row stride ldx) + slide-context residual / concat + classifier (reference model/aggregator.py:75,
+    model/paths.py:130-139); ``head`` = :func:`slide_ctx_operands`.  ``any_width``: the shape-generic kernel (csrc/generic.hip)."""
+    p = _lib.ptr
+    res, cat, depth, ctx_out, logits = head
+    _lib.call("paths_final_head_any" if any_width else "paths_final_head", p(x), ldx, p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res),
+              res.stride(0) if res is not None else 0, p(cat), depth, p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1],
+              lvl_pack["wcls"].shape[1], p(ctx_out), p(logits), B, d, lvl_pack["lnf_eps"], _lib.stream())
+
+
+def token0_tail_ws(lvl_pack, x, num_ims, head, status, B: int, T: int, d: int, H: int, qscale: float, special_last: int):
+    """The LAST decoder layer at token 0 (K / V projections folded into the query) + decoder.norm + slide context + classifier in one
+    launch (csrc/token0_ws.hip; reference model/aggregator.py:75, model/paths.py:130-139).  ``x``: the layer's input rows [B, T, d];
+    ``special_last``: the special token sits at index num_ims[b] instead of 0 (token order of the fused finish)."""
+    p = _lib.ptr
+    w = lvl_pack["layers"][-1]
+    res, cat, depth, ctx_out, logits = head
+    img = token0_ws_image(w, qscale)
+    part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), device=x.device, dtype=torch.float32)
+    cnt = token0_counters(x.device, B)
+    _lib.call(
+        "paths_token0_tail_ws", p(x), p(num_ims), p(img), w["bqkv"].data_ptr() + 4 * 2 * d, p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
+        p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["b1"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
+        p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res), res.stride(0) if res is not None else 0, p(cat), depth,
+        p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
+        p(part), p(cnt), p(status), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], special_last, _lib.stream())
+
+
+def token0_tail(lvl_pack, x, q, k, v, num_ims, head, B: int, T: int, d: int, H: int):
+    """Last layer: only token 0 of its output is read (reference model/aggregator.py:75) -> one fused launch per level computes the
+    single-query attention from fp32 q, k, v, the row chain, decoder.norm, the slide-context residual and the classifier."""
+    p = _lib.ptr
+    w = lvl_pack["layers"][-1]
+    res, cat, depth, ctx_out, logits = head
+    ws_part = torch.empty((B * H * 16 * 36,), device=x.device, dtype=torch.float32)
+    _lib.call(
+        "paths_token0_tail", p(x), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
+        p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["w1"]), p(w["b1"]), p(w["w2"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
+        p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res), res.stride(0) if res is not None else 0, p(cat), depth,
+        p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
+        p(ws_part), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], _lib.stream())
+
+
+def token_layer_f32(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B: int, T: int, d: int, H: int, qscale: float, skip: int,
+                    max_tokens: int = 0):
+    """Row chain of decoder layer ``post`` (out_proj .. norm3 on ``attn``, ``x_in`` -> ``x_out``) and / or the in_proj of layer ``nxt``
+    into fp32 q, k, v [B, H, T, hd] (q pre-scaled) on the f32-input kernel (csrc/tlayer_f32.hip); either may be None.  ``skip`` 1:
+    padded token rows are skipped (inference); 0: computed (training: finite values everywhere)."""
+    p = _lib.ptr
+    w = post or nxt
+    g = lambda dct, key: p(dct[key]) if dct is not None else None
+    _lib.call("paths_token_layer_f32", p(x_in), p(attn) if post else None, p(x_out) if post else None,
+              g(post, "wo"), g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
+              g(post, "w1"), g(post, "b1"), g(post, "w2"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"),
+              g(nxt, "wqkv"), g(nxt, "bqkv"), p(q), p(k), p(v), p(num_ims), B, T, d, H,
+              1 if post else 0, 1 if nxt else 0, skip, qscale, w["eps"], max_tokens, _lib.stream())
+
+
+def _tlayer_ws_biases(post, nxt):
+    """The eleven bias / LayerNorm vectors of the weight-stationary token-layer kernels: ten of the chain of ``post``, in_proj's of ``nxt``."""
+    p = _lib.ptr
+    g = lambda dct, key: p(dct[key]) if dct is not None else None
+    return (g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
+            g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"))
+
+
+def token_layer_ws(x_in, x_out, o_img, post, nxt, qkv_img, num_ims, B: int, T: int, d: int, H: int, qscale: float):
+    """Weight-stationary token layer (csrc/tlayer_ws.hip): the row chain of ``post`` reads the attention's output image ``o_img`` and
+    writes ``x_out``; the in_proj of ``nxt`` writes q | k | v straight into the attention's operand images ``qkv_img``.  Either of
+    ``post`` / ``nxt`` may be None."""
+    p = _lib.ptr
+    ip, sp = tlayer_ws_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
+    iq, sq = tlayer_ws_images(nxt, 1) if nxt is not None else (None, (1.0,))
+    _lib.call("paths_token_layer_ws", p(x_in), None, p(o_img) if post is not None else None, p(x_out) if post is not None else None,
+              p(ip), p(iq), *_tlayer_ws_biases(post, nxt), sp[0], sp[1], sp[2], sq[0], p(qkv_img) if nxt is not None else None,
+              p(num_ims), B, T, d, H, 1 if post is not None else 0, 1 if nxt is not None else 0, 1, qscale, (post or nxt)["eps"], None, 0,
+              _lib.stream())
+
+
+def token_layer_ws_rows(x_in, attn, post, nxt, num_ims, B: int, T: int, d: int, qkv=None):
+    """:func:`token_layer_ws` with fp32 rows on both sides (trans_dim 192): the chain of ``post`` reads the attention output ``attn``
+    [B*T, d] and writes fresh rows, the in_proj of ``nxt`` writes q | k | v as rows [B*T, 3d] (into ``qkv`` if given).  Returns
+    (the chain's output rows or None, the q | k | v rows or None)."""
+    p = _lib.ptr
+    f32 = dict(device=x_in.device, dtype=torch.float32)
+    ip, sp = tlayer_ws_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
+    x_out = torch.empty((B * T, d), **f32) if post is not None else None
+    iq, sq = tlayer_ws_images(nxt, 1) if nxt is not None else (None, (1.0,))
+    if nxt is not None and qkv is None:
+        qkv = torch.empty((B * T, 3 * d), **f32)
+    _lib.call("paths_token_layer_ws_rows", p(x_in), p(attn) if post is not None else None, p(x_out), p(ip), p(iq), *_tlayer_ws_biases(post, nxt),
+              sp[0], sp[1], sp[2], sq[0], p(qkv), 3 * d if nxt is not None else 0, p(num_ims), B, T, d,
+              1 if post is not None else 0, 1 if nxt is not None else 0, 1, (post or nxt)["eps"], _lib.stream())
+    return x_out, qkv
+
+
+def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, export, fp8: bool = False,
+                                status=None) -> Dict[str, torch.Tensor]:
     """The aggregator for any (trans_dim, heads): generic GEMMs + csrc/generic.hip (reference model/aggregator.py:58-76 with torch's
     post-LN decoder layers, model/paths.py:130-139).  The last layer is evaluated at token 0 only (its other rows are never read).
     ``fp8`` (ops.AGG_FP8, the BASELINE configs[4] stress variant, NOT a parity path): the products over all tokens - in_proj, the full
@@ -725,10 +864,13 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
     for l in range(L):
         lay, gl = lvl_pack["layers"][l], gp["layers"][l]
         last = l == L - 1
-        if attention is not None:                 # (x: this layer's input rows [B*T, d], special token first)
-            _export_attention(attention, lvl_pack, l, x, num_ims, H, 0)
-        if rollout is not None:
-            rollout.layer(l, x, 0)
+        if last and tail192:                      # (the head's buffers before the export's scratch, as in every other form)
+            head = slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B, d, dev, mc.slide_ctx_mode)
+        export.layer(l, x, 0)                     # (x: this layer's input rows [B*T, d], special token first)
+        if last and tail192:
+            # the chain launch in front stopped at these rows: the layer at token 0 + decoder.norm + context + classifier in one launch
+            token0_tail_ws(lvl_pack, x, num_ims, head, status, B, T, d, H, qscale, 0)
+            return {"logits": head[4], "ctx_slide": head[3]}
         big = fp8 and not last            # products over all tokens of a full layer
 
         def gemm(a, lda, key, bias, out, ldo, m, n, kdim, act=0, residual=None, ldr=0, low=False):
@@ -741,14 +883,10 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
             qkv_ready = False
         elif ws192 and WS_IMAGES_192 and h3 and not last and H == 4:
             # q | k | v straight into the head_dim-48 operand images of the attention (no fp32 rows, no prep launch)
-            iq, sq = tlayer_ws_images(lay, 1)
-            _lib.call("paths_token_layer_ws", p(x), None, None, None, None, p(iq), None, None, None, None, None, None, None, None, None, None,
-                      p(lay["bqkv"]), 1.0, 1.0, 1.0, sq[0], p(wsh), p(num_ims), B, T, d, H, 0, 1, 1, qscale, lay["eps"], None, 0, st)
+            token_layer_ws(x, None, None, None, lay, wsh, num_ims, B, T, d, H, qscale)
             img_ready = True
         elif ws192:
-            iq, sq = tlayer_ws_images(lay, 1)
-            _lib.call("paths_token_layer_ws_rows", p(x), None, None, None, p(iq), None, None, None, None, None, None, None, None, None, None,
-                      p(lay["bqkv"]), 1.0, 1.0, 1.0, sq[0], p(qkv), 3 * d, p(num_ims), B, T, d, 0, 1, 1, lay["eps"], st)
+            token_layer_ws_rows(x, None, None, lay, num_ims, B, T, d, qkv=qkv)
         else:
             gemm(x, d, "wqkv", lay["bqkv"], qkv, 3 * di, M, 3 * di, d, low=fp8)        # (the last layer's K / V cover all tokens too)
         if big:
@@ -771,21 +909,11 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
             # the reference's dataclass-default width (config.py:30): out_proj + norm1 + cross-attention bias + norm2 + feed-forward +
             # norm3 of a full layer AND the next layer's in_proj in ONE launch of the weight-stationary chain kernel (csrc/tlayer_ws.hip
             # instantiated at 192; attention output in, q | k | v out as fp32 rows) instead of four GEMMs and two LayerNorm launches
-            nxt = lvl_pack["layers"][l + 1]
-            ip, sp = tlayer_ws_images(lay, 0)
-            x3 = torch.empty((M, d), **f32)
-            if tail192 and l + 1 == L - 1:
-                _lib.call("paths_token_layer_ws_rows", p(x), p(attn), p(x3), p(ip), None, p(lay["bo"]), p(lay["ln1g"]), p(lay["ln1b"]), p(lay["cab"]),
-                          p(lay["ln2g"]), p(lay["ln2b"]), p(lay["b1"]), p(lay["b2"]), p(lay["ln3g"]), p(lay["ln3b"]), None, sp[0], sp[1], sp[2],
-                          1.0, None, 0, p(num_ims), B, T, d, 1, 0, 1, lay["eps"], st)
-                x = x3
-                break
-            iq, sq = tlayer_ws_images(nxt, 1)
-            qkv_next = torch.empty((M, 3 * d), **f32)
-            _lib.call("paths_token_layer_ws_rows", p(x), p(attn), p(x3), p(ip), p(iq), p(lay["bo"]), p(lay["ln1g"]), p(lay["ln1b"]), p(lay["cab"]),
-                      p(lay["ln2g"]), p(lay["ln2b"]), p(lay["b1"]), p(lay["b2"]), p(lay["ln3g"]), p(lay["ln3b"]), p(nxt["bqkv"]), sp[0], sp[1], sp[2],
-                      sq[0], p(qkv_next), 3 * d, p(num_ims), B, T, d, 1, 1, 1, lay["eps"], st)
-            x, ldx, qkv, qkv_ready = x3, d, qkv_next, True
+            # (before the token-0 tail the chain stops at the last layer's input rows: no in_proj)
+            nxt = None if (tail192 and l + 1 == L - 1) else lvl_pack["layers"][l + 1]
+            x, qkv_next = token_layer_ws_rows(x, attn, lay, nxt, num_ims, B, T, d)
+            if nxt is not None:
+                ldx, qkv, qkv_ready = d, qkv_next, True
             continue
         if last:
             rows, ldx, lda_attn = B, T * d, T * di    # rows = token 0 of every slide: row stride T * d (T * di) into the [B, T, .] tensors
@@ -808,34 +936,10 @@ def _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all
         x3 = torch.empty((rows, d), **f32)
         _lib.call("paths_layernorm_rows", p(y2), d, None, p(lay["ln3g"]), p(lay["ln3b"]), p(x3), d, rows, d, lay["eps"], st)
         x, ldx = x3, d
-    nlog = lvl_pack["wcls"].shape[0]
-    ctx_out = torch.empty((B, d), **f32)
-    logits = torch.empty((B, nlog), **f32)
-    res = ctx_prev if mc.slide_ctx_mode == "residual" else None
-    cat = ctx_all.contiguous() if (mc.slide_ctx_mode == "concat" and ctx_all is not None and ctx_all.shape[1] > 0) else None
-    if tail192:
-        # x: the last layer's input rows [B, T, d] (special token first: the reference's order)
-        w = lvl_pack["layers"][L - 1]
-        if attention is not None:                 # (the loop left with `break` before the last layer's iteration)
-            _export_attention(attention, lvl_pack, L - 1, x, num_ims, H, 0)
-        if rollout is not None:
-            rollout.layer(L - 1, x, 0)
-        img = token0_ws_image(w, qscale)
-        part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), **f32)
-        cnt = token0_counters(dev, B)
-        _lib.call(
-            "paths_token0_tail_ws", p(x), p(num_ims), p(img), w["bqkv"].data_ptr() + 4 * 2 * d, p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
-            p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["b1"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-            p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res) if res is not None else None,
-            res.stride(0) if res is not None else 0, p(cat) if cat is not None else None, cat.shape[1] if cat is not None else 0,
-            p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), nlog, lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
-            p(part), p(cnt), p(status) if status is not None else None, B, T, d, H, w["eps"], lvl_pack["lnf_eps"], 0, st)
-        return {"logits": logits, "ctx_slide": ctx_out}
+    head = slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B, d, dev, mc.slide_ctx_mode)
     # x: [B, d] if the loop ended on the last layer's token-0 rows (L >= 1), row stride d
-    _lib.call("paths_final_head_any", p(x), d if L >= 1 else T * d, p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res) if res is not None else None,
-              res.stride(0) if res is not None else 0, p(cat) if cat is not None else None, cat.shape[1] if cat is not None else 0,
-              p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), nlog, lvl_pack["wcls"].shape[1], p(ctx_out), p(logits), B, d, lvl_pack["lnf_eps"], st)
-    return {"logits": logits, "ctx_slide": ctx_out}
+    final_head(lvl_pack, x, d if L >= 1 else T * d, head, B, d, any_width=True)
+    return {"logits": head[4], "ctx_slide": head[3]}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -852,16 +956,10 @@ def level_forward(mc, lstm_pack, lvl_pack, fts: torch.Tensor, locs: torch.Tensor
     the special token's attention rollout."""
     sel = selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, skip_padding)
     status = torch.zeros((1,), device=fts.device, dtype=torch.int32)
-    attention = None
-    if return_attention:
-        B, N = locs.shape[:2]
-        f32 = dict(device=fts.device, dtype=torch.float32)
-        attention = (torch.empty((B, mc.trans_layers, mc.trans_heads, N), **f32), torch.empty((B, mc.trans_layers, mc.trans_heads), **f32))
-    rollout = None
-    if return_rollout:
-        B, N = locs.shape[:2]
-        f32 = dict(device=fts.device, dtype=torch.float32)
-        rollout = (torch.empty((B, N), **f32), torch.empty((B,), **f32))
+    (B, N), LH = locs.shape[:2], (mc.trans_layers, mc.trans_heads)
+    pair = lambda *lead: (torch.empty((B, *lead, N), device=fts.device, dtype=torch.float32), torch.empty((B, *lead), device=fts.device, dtype=torch.float32))
+    attention = pair(*LH) if return_attention else None          # ([B, L, H, N], [B, L, H])
+    rollout = pair() if return_rollout else None                 # ([B, N], [B])
     agg = aggregator_forward(mc, lvl_pack, sel["tokens"], sel["num_ims"], ctx_prev, ctx_all, status=status, qkv=sel, attention=attention,
                              rollout=rollout)
     # the drop-in call is synchronous anyway (the range guard above it syncs): a token-0 tail whose bounded hand-off wait gave up
@@ -914,7 +1012,6 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
     locs = locs.contiguous()
     num_ims = num_ims.contiguous()
     assert locs.dtype == torch.int64 and num_ims.dtype == torch.int64
-    nim = p(num_ims) if skip_padding else None
     pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
     tokens = torch.empty((B, T, d), **f32)
 
@@ -938,50 +1035,37 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
     # any aggregator geometry on the tuned LSTM kernels: the importance / projection products take x + h1 summed while staged
     generic_add = generic and x6 and split_planes() == 2 and mc.lstm and GENERIC_ADD and GENERIC_SPLIT and D % 128 == 0
 
-    def importance_proj(src, imp_mul, imp_out, add=None):
+    def imp_proj(src, imp_mul, imp_out, add=None):
         """tokens / importance from ``src`` (+ ``add``: x6 only, the GEMM input is src + add, row stride of add arbitrary)."""
         if generic:
             assert add is None and src is not None
             return importance_proj_generic(mc, lvl_pack, src, D, locs, num_ims, B, N, D, imp_mul, imp_out, tokens)
-        common = (p(lvl_pack["b1"]), p(lvl_pack["w2"]), p(lvl_pack["b2"]),
-                  p(lvl_pack["bp"]), p(lvl_pack["special"]), p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]),
-                  p(pe_tab), pe_tab.shape[0] if pe_tab is not None else 0, p(locs),
-                  p(num_ims), N, mc.patch_size, pe_mode, imp_mul, p(imp_out), p(tokens), None, None,
-                  M, D, mc.importance_mlp_hidden_dim, d, 1 if skip_padding else 0, st)
-        if x6:
+        splitk = x6 and SPLITK_IMPORTANCE and add is not None and split_planes() == 2 and (M + 127) // 128 <= 160
+        splitk = splitk or (x6 and x_rows_h16 and src is None)          # (the fp16-row form has the split-K kernel only)
+        if splitk and fuse_qkv and imp_out is importance:
+            # GEMM rows in token order + a finish that also projects q | k | v of decoder layer 0 into the attention's operand images
             wip, wip_s = _x6_of(lvl_pack, "w_ip_fwd")
-            splitk = SPLITK_IMPORTANCE and add is not None and split_planes() == 2 and (M + 127) // 128 <= 160
-            splitk = splitk or (x_rows_h16 and src is None)          # (the fp16-row form has the split-K kernel only)
-            if splitk and fuse_qkv and imp_out is importance:
-                # GEMM rows in token order + a finish that also projects q | k | v of decoder layer 0 into the attention's operand images
-                lay0 = lvl_pack["layers"][0]
-                iq, sq = tlayer_ws_images(lay0, 1)
-                hd = d // H
-                ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=dev, dtype=torch.uint8)
-                qkv_img = torch.empty((int(_lib.load().paths_attention_x6_workspace(B, T, H, hd, 2)),), device=dev, dtype=torch.uint8)
-                args = (p(src), D, p(x_rows) if src is None else None, p(add), add.stride(1), p(wip), p(lvl_pack["b1"]), p(lvl_pack["w2"]),
-                        p(lvl_pack["b2"]), p(lvl_pack["bp"]), p(lvl_pack["special"]), p(pe_tab), pe_tab.shape[0], p(locs), p(num_ims), B, N,
-                        mc.patch_size, pe_mode, imp_mul, p(imp_out), p(tokens), D, 1 if skip_padding else 0, wip_s, a_scale(), p(ws),
-                        p(iq), p(lay0["bqkv"]), sq[0], LOG2E / math.sqrt(hd), p(qkv_img))
-                # (token order of this form: patch i = token i, the special token at index num_ims[b]; the tail is told: special_last)
-                if FUSE_QKV == 2 and not last_level:
-                    _lib.call("paths_importance_qkv_x6" + h16, *args, 3, 0, st)
-                    # (the aggregator stream finishes the tokens: ws / qkv_img travel with the closure)
-                    fused["finish"] = lambda: _lib.call("paths_importance_qkv_x6", *args, 4, 1, _lib.stream())
-                else:
-                    _lib.call("paths_importance_qkv_x6" + h16, *args, 5, 0, st)
-                fused["qkv_img"], fused["ws"] = qkv_img, ws
-                return
-            # M/128 blocks fill half the chip at K = 2048 x 8 slides: two k halves on twice the blocks + an epilogue launch
-            splitk_ws = None
-            if splitk:
-                splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=dev, dtype=torch.uint8)
-            _lib.call("paths_importance_proj_x6" + (h16 if src is None else ""), p(src), D, p(x_rows) if src is None else None, p(add),
-                      add.stride(1) if add is not None else 0,
-                      p(wip), *common[:-1], split_planes(), wip_s, a_scale(), p(splitk_ws), common[-1])
-        else:
-            assert add is None
-            _lib.call("paths_importance_proj", p(src), D, p(lvl_pack["w_ip_fwd"]), *common)
+            lay0 = lvl_pack["layers"][0]
+            iq, sq = tlayer_ws_images(lay0, 1)
+            hd = d // H
+            ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=dev, dtype=torch.uint8)
+            qkv_img = torch.empty((int(_lib.load().paths_attention_x6_workspace(B, T, H, hd, 2)),), device=dev, dtype=torch.uint8)
+            args = (p(src), D, p(x_rows) if src is None else None, p(add), add.stride(1), p(wip), p(lvl_pack["b1"]), p(lvl_pack["w2"]),
+                    p(lvl_pack["b2"]), p(lvl_pack["bp"]), p(lvl_pack["special"]), p(pe_tab), pe_tab.shape[0], p(locs), p(num_ims), B, N,
+                    mc.patch_size, pe_mode, imp_mul, p(imp_out), p(tokens), D, 1 if skip_padding else 0, wip_s, a_scale(), p(ws),
+                    p(iq), p(lay0["bqkv"]), sq[0], LOG2E / math.sqrt(hd), p(qkv_img))
+            # (token order of this form: patch i = token i, the special token at index num_ims[b]; the tail is told: special_last)
+            if FUSE_QKV == 2 and not last_level:
+                _lib.call("paths_importance_qkv_x6" + h16, *args, 3, 0, st)
+                # (the aggregator stream finishes the tokens: ws / qkv_img travel with the closure)
+                fused["finish"] = lambda: _lib.call("paths_importance_qkv_x6", *args, 4, 1, _lib.stream())
+            else:
+                _lib.call("paths_importance_qkv_x6" + h16, *args, 5, 0, st)
+            fused["qkv_img"], fused["ws"] = qkv_img, ws
+            return
+        assert x6 or add is None
+        importance_proj(mc, lvl_pack, src, x_rows, add, locs, num_ims, pe_tab, imp_mul, imp_out, tokens, None, None, B, N, D, skip_padding,
+                        planes=split_planes() if x6 else 0, splitk=splitk, h16=h16)
 
     if importance_out is not None:          # caller's buffer, already zero where padding rows must read 0
         assert importance_out.shape == (B, N) and importance_out.is_contiguous() and importance_out.dtype == torch.float32
@@ -995,37 +1079,17 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
         # x6: Y = X + h1 is summed inside the importance/proj GEMM's staging (the generic importance / projection GEMMs read a stored Y)
         y = None if (x6 and (not generic or generic_add)) else torch.empty((B, N, D), **f32)
         ws_o = torch.empty(((M + 255) // 256 * 256, D), **f32)       # gate scratch: whole 256-row tiles (raw accumulator layout)
-        hp, hp_row = None, None
-        if parent is not None:
-            assert state_prev is None
-            c0t = parent["c0"]
-            assert c0t.shape == (B, N, Hc) and c0t.is_contiguous()
-            ld, h0, c0 = Hc, None, c0t.data_ptr()
-            hp, hp_row = p(parent["hp"]), p(parent["hp_row"])
-        elif state_prev is not None:
-            assert state_prev.shape[:2] == (B, N) and state_prev.shape[2] == Dp and state_prev.stride(2) == 1
-            assert state_prev.stride(0) == N * state_prev.stride(1), "state rows must be uniformly strided"
-            ld = state_prev.stride(1)
-            h0, c0 = state_prev.data_ptr(), state_prev.data_ptr() + 4 * D
-        else:
-            ld, h0, c0 = 0, None, None
+        prev = prev_state_operands(parent, state_prev, B, N, D, Hc, parent["hp"] if parent is not None else None)
 
         def lstm(phases):
-            if x6:
-                (wg, wg_s), (wm, wm_s) = _x6_of(lstm_pack, "w_gates"), _x6_of(lstm_pack, "w_mem")
-                _lib.call("paths_lstm_cell_x6" + h16, p(fts), D, p(x_rows), h0, ld, c0, ld, p(wg), p(lstm_pack["b_gates"]), p(wm), p(lstm_pack["b_mem"]),
-                          p(state_out), Dp, p(y), D, p(ws_o), None, None, hp, hp_row, M, D, Hc, nim, N, phases,
-                          split_planes(), wg_s, wm_s, a_scale(), st)
-            else:
-                _lib.call("paths_lstm_cell", p(fts), D, h0, ld, c0, ld, p(lstm_pack["w_gates"]), p(lstm_pack["b_gates"]),
-                          p(lstm_pack["w_mem"]), p(lstm_pack["b_mem"]), p(state_out), Dp, p(y), D,
-                          p(ws_o), None, None, hp, hp_row, M, D, Hc, nim, N, phases, st)
+            lstm_cell(lstm_pack, fts, x_rows, prev, state_out, y, ws_o, None, None, N, num_ims if skip_padding else None, phases,
+                      planes=split_planes() if x6 else 0, h16=h16)
 
         if KERNEL_TIMER is None:
             lstm(7)
         else:                   # bench.py: bracket the dominant kernel (output-gate GEMM) with events on this stream
             timed("lstm_gate_c", lambda: lstm(1))
-            timed("lstm_gate_o", lambda: lstm(2), {"rows": N, "B": B, "K": D if h0 is None else 2 * D, "Ncols": D, "parent_partials": parent is not None,
+            timed("lstm_gate_o", lambda: lstm(2), {"rows": N, "B": B, "K": D if prev[1] is None else 2 * D, "Ncols": D, "parent_partials": parent is not None,
                                                    "x6": x6, "planes": split_planes() if x6 else 0}, detail=False)
             timed("lstm_mem_to_out", lambda: lstm(4))
         if generic_add:
@@ -1033,14 +1097,14 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
                                                                          1 if mc.importance_mode == "mul" else 0, importance, tokens, skip_padding, pe_tab=pe_tab,
                                                                          x_rows_h16=x_rows_h16))
         elif x6 and not generic:
-            timed("importance_proj", lambda: importance_proj(fts, 1 if mc.importance_mode == "mul" else 0, importance, add=state_out))
+            timed("importance_proj", lambda: imp_proj(fts, 1 if mc.importance_mode == "mul" else 0, importance, add=state_out))
         else:
-            timed("importance_proj", lambda: importance_proj(y, 1 if mc.importance_mode == "mul" else 0, importance))
+            timed("importance_proj", lambda: imp_proj(y, 1 if mc.importance_mode == "mul" else 0, importance))
         del ws_o
     else:
         # lstm=false (reference model/paths.py:95-109): alpha from X; Z = alpha*X (+ hctx_mlp(previous Z) on valid rows);
         # patch ctx = Z; tokens = proj_in(Z) + PE.  Re-uses the GEMM kernels; not a tuned path.
-        importance_proj(fts, 0, importance)                      # pass 1: importance only (tokens overwritten below)
+        imp_proj(fts, 0, importance)                             # pass 1: importance only (tokens overwritten below)
         hctx = None
         if state_prev is not None and mc.hierarchical_ctx:
             assert state_prev.shape == (B, N, D) and state_prev.stride(2) == 1 and state_prev.stride(0) == N * state_prev.stride(1)
@@ -1055,13 +1119,71 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
         _lib.call("paths_scale_add_rows", p(fts), p(importance), p(hctx) if hctx is not None else None, p(num_ims), N, D, M,
                   1 if mc.importance_mode == "mul" else 0, p(state_out), st)
         scratch_imp = torch.empty((B, N), **f32)
-        importance_proj(state_out, 0, scratch_imp)               # pass 2: tokens = proj_in(Z) + PE
+        imp_proj(state_out, 0, scratch_imp)                      # pass 2: tokens = proj_in(Z) + PE
 
     out = {"ctx_patch": state_out, "importance": importance, "tokens": tokens, "num_ims": num_ims}
     if "qkv_img" in fused:
         # the attention's operand images are ready (or, FUSE_QKV = 2, one call away: "qkv_finish" runs on the aggregator's stream)
         out["qkv_img"], out["qkv_finish"], out["_qkv_ws"] = fused["qkv_img"], fused.get("finish"), fused["ws"]
     return out
+
+
+def prev_state_operands(parent, state_prev, B: int, N: int, D: int, Hc: int, hp=None):
+    """(ld, h0, c0, hp, hp_row): where the LSTM cell finds the previous level's state (reference model/interface.py:49-56).
+    ``state_prev`` [B, N, >= D + Hc] holds (h | c) per row, row stride ld; ``parent`` (once-per-parent form, ``state_prev`` None
+    then) carries the children's inherited memory cell "c0" [B, N, Hc] and "hp_row" [B, N] int32, the child -> kept-parent rows of
+    ``hp`` [rows, 3Hc + D] (the h half of the gate pre-activations, :func:`parent_gate_product`); neither: depth 0, zero state."""
+    if parent is not None:
+        assert state_prev is None
+        c0t = parent["c0"]
+        assert c0t.shape == (B, N, Hc) and c0t.is_contiguous()
+        return Hc, None, c0t.data_ptr(), _lib.ptr(hp), _lib.ptr(parent["hp_row"])
+    if state_prev is not None:
+        assert state_prev.shape[:2] == (B, N) and state_prev.shape[2] == D + Hc and state_prev.stride(2) == 1
+        assert state_prev.stride(0) == N * state_prev.stride(1), "state rows must be uniformly strided"
+        return state_prev.stride(1), state_prev.data_ptr(), state_prev.data_ptr() + 4 * D, None, None
+    return 0, None, None, None, None
+
+
+def lstm_cell(lstm_pack, fts, x_rows, prev, state_out, y, o, frm, tc, N: int, num_ims, phases: int, planes: int = 0, lagged: bool = False,
+              h16: str = ""):
+    """The LSTM state update of a level's rows (reference model/interface.py:49-56): gates GEMM (c part, o part) + mem_to_out GEMM
+    with fused epilogues; ``phases`` is the bit mask of the three (7 = all).  ``fts`` [B, N, D] or, when None, the rows at the
+    addresses ``x_rows`` (``h16``: fp16 rows); ``prev`` = :func:`prev_state_operands`; ``state_out`` [B, N, D + Hc] receives (h1 | c1),
+    ``y`` = x + h1 (or None); ``o`` is the output gate (inference: raw scratch of whole 256-row tiles), ``frm`` / ``tc`` the gate
+    values training keeps.  ``num_ims``: rows of padding are skipped (None: computed).  ``planes`` 0: the f32-input kernel; 2 / 3:
+    the split-operand kernel (``lagged``: see :func:`_x6_of`)."""
+    p = _lib.ptr
+    ld, h0, c0, hp, hp_row = prev
+    Dp = state_out.shape[2]
+    Hc = lstm_pack["Hc"]
+    D = Dp - Hc
+    M = state_out.shape[0] * N
+    if planes:
+        (wg, wg_s), (wm, wm_s) = _x6_of(lstm_pack, "w_gates", planes, lagged=lagged), _x6_of(lstm_pack, "w_mem", planes, lagged=lagged)
+        _lib.call("paths_lstm_cell_x6" + h16, p(fts), D, p(x_rows), h0, ld, c0, ld, p(wg), p(lstm_pack["b_gates"]), p(wm), p(lstm_pack["b_mem"]),
+                  p(state_out), Dp, p(y), D, p(o), p(frm), p(tc), hp, hp_row, M, D, Hc, p(num_ims), N, phases,
+                  planes, wg_s, wm_s, A_SCALE if planes == 2 else 1.0, _lib.stream())
+    else:
+        _lib.call("paths_lstm_cell", p(fts), D, h0, ld, c0, ld, p(lstm_pack["w_gates"]), p(lstm_pack["b_gates"]),
+                  p(lstm_pack["w_mem"]), p(lstm_pack["b_mem"]), p(state_out), Dp, p(y), D,
+                  p(o), p(frm), p(tc), hp, hp_row, M, D, Hc, p(num_ims), N, phases, _lib.stream())
+
+
+def parent_gate_product(lstm_pack, hk, hp, planes: int = 0, lagged: bool = False):
+    """hp [rows, 3Hc + D] = hk [rows, D] W_gates[:, D:2D]^T (no bias), packed gate-column order: the h half of the gate
+    pre-activations, once per kept PARENT (siblings share their parent's h).  ``planes`` 2 / 3: the split-operand kernel (needs
+    3Hc + D a multiple of 256; ``lagged``: see :func:`_x6_of`); otherwise the f32-input kernel."""
+    p = _lib.ptr
+    rows, D = hk.shape
+    G = hp.shape[1]
+    if planes and G % 256 == 0:
+        wg, wg_s = _x6_of(lstm_pack, "w_gates", planes, lagged=lagged)
+        _lib.call("paths_gemm_nt_x6", p(hk), D, p(wg), 2 * D, D, None, p(hp), G, rows, G, G, D, 0, None, 0, None, 0, 0, planes, wg_s,
+                  A_SCALE if planes == 2 else 1.0, _lib.stream())
+    else:
+        _lib.call("paths_gemm_nt_f32", p(hk), D, lstm_pack["w_gates"].data_ptr() + 4 * D, 2 * D, None, p(hp), G, rows, G, G, D, 0,
+                  None, 0, None, 0, 0, _lib.stream())
 
 
 def parent_partials(lstm_pack, state_out: torch.Tensor, keep_idx: torch.Tensor, keep_count: torch.Tensor,
@@ -1085,13 +1207,7 @@ def parent_partials(lstm_pack, state_out: torch.Tensor, keep_idx: torch.Tensor, 
         return hp
     hk = torch.empty((B * cap, D), **f32)
     _lib.call("paths_gather_kept_rows", p(state_out), N, Dp, p(keep_idx), cap, p(keep_count), D, B, p(hk), st)
-    if use_x6(D, Hc) and G % 256 == 0:
-        wg, wg_s = _x6_of(lstm_pack, "w_gates")
-        _lib.call("paths_gemm_nt_x6", p(hk), D, p(wg), 2 * D, D, None, p(hp), G, B * cap, G, G, D, 0,
-                  None, 0, None, 0, 0, split_planes(), wg_s, a_scale(), st)
-    else:
-        _lib.call("paths_gemm_nt_f32", p(hk), D, lstm_pack["w_gates"].data_ptr() + 4 * D, 2 * D, None, p(hp), G, B * cap, G, G, D, 0,
-                  None, 0, None, 0, 0, st)
+    parent_gate_product(lstm_pack, hk, hp, planes=split_planes() if use_x6(D, Hc) else 0)
     return hp
 
 
@@ -1155,6 +1271,21 @@ class _Rollout:
                       _lib.stream())
 
 
+class _Export:
+    """The optional per-layer exports of an aggregator run: :meth:`layer` is called by every aggregator form where decoder layer l's
+    input rows ``x`` [B, T, d] are final, and launches the special token's attention export (:func:`_export_attention`), the
+    rollout step (:class:`_Rollout`), both or neither on the current stream."""
+
+    def __init__(self, attention, rollout, lvl_pack, num_ims, H: int):
+        self.attention, self.rollout, self.lvl_pack, self.num_ims, self.H = attention, rollout, lvl_pack, num_ims, H
+
+    def layer(self, l: int, x, special_last: int):
+        if self.attention is not None:
+            _export_attention(self.attention, self.lvl_pack, l, x, self.num_ims, self.H, special_last)
+        if self.rollout is not None:
+            self.rollout.layer(l, x, special_last)
+
+
 def _check_attention(attention, mc, tokens):
     B, T, _ = tokens.shape
     patch, self_ = attention
@@ -1199,11 +1330,11 @@ def aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=
                  detail=False)
 
 
-def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer_old, status=None,
-                           qkv_ready: bool = False, attention=None, rollout=None):
+def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, head, qkv_img, xb, tail_f32, export, status=None, qkv_ready: bool = False):
     """Default-mode aggregator on the weight-stationary token-layer kernel (csrc/tlayer_ws.hip): in_proj writes the attention
     operand images, attention writes its output as the out_proj operand image, the chain kernel keeps weights in registers and
-    shares only activations through LDS."""
+    shares only activations through LDS.  ``head`` = :func:`slide_ctx_operands`; ``xb``: the second [B, T, d] row buffer;
+    ``tail_f32(x, True)``: the last layer + head from fp32 q, k, v (TAIL_WS = False)."""
     B, T, d = tokens.shape
     H, L = mc.trans_heads, mc.trans_layers
     hd = d // H
@@ -1213,76 +1344,36 @@ def _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_i
     qscale = LOG2E / math.sqrt(hd)
     Tp = (T + 63) // 64 * 64
     o_img = torch.empty((B * Tp * d * 4,), device=tokens.device, dtype=torch.uint8)
-    g = lambda dct, key: p(dct[key]) if dct is not None else None
 
-    def token_layer(x_in, x_out, post, nxt, use_img=True):
-        w = post or nxt
-        ip, sp = tlayer_ws_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
-        iq, sq = tlayer_ws_images(nxt, 1) if nxt is not None else (None, (1.0,))
-        _lib.call("paths_token_layer_ws", p(x_in), None, p(o_img) if post is not None else None, p(x_out) if post is not None else None,
-                  p(ip), p(iq), g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
-                  g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"),
-                  sp[0], sp[1], sp[2], sq[0], p(qkv_img) if nxt is not None else None, p(num_ims), B, T, d, H,
-                  1 if post is not None else 0, 1 if nxt is not None else 0, 1, qscale, w["eps"], None, 0, st)
+    def token_layer(x_in, x_out, post, nxt):
+        token_layer_ws(x_in, x_out, o_img, post, nxt, qkv_img, num_ims, B, T, d, H, qscale)
 
     xa = tokens
     if not qkv_ready:                       # (FUSE_QKV: the importance / projection finish already wrote layer 0's operand images)
         timed("agg_in_proj", lambda: token_layer(xa, None, None, layers[0]))
     order = 1 if qkv_ready else 0                # (the fused finish's token order: patch i = token i, the special token last)
     for l in range(L - 1):
-        if attention is not None:
-            _export_attention(attention, lvl_pack, l, xa, num_ims, H, order)
-        if rollout is not None:
-            rollout.layer(l, xa, order)
+        export.layer(l, xa, order)
         timed("agg_attention", lambda: _lib.call("paths_attention_h3_img", p(o_img), p(num_ims), B, T, H, hd, p(qkv_img), st))
         last = l + 1 == L - 1
         timed("agg_token_chain", lambda: token_layer(xa, xb, layers[l], None if last else layers[l + 1]))
         xa, xb = xb, xa
-    w = layers[L - 1]
-    if attention is not None:
-        _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, order)
-    if rollout is not None:
-        rollout.layer(L - 1, xa, order)
-
-    def tail_ws():
-        img = token0_ws_image(w, qscale)
-        part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), device=tokens.device, dtype=torch.float32)
-        cnt = token0_counters(tokens.device, B)
-        _lib.call(
-            "paths_token0_tail_ws", p(xa), p(num_ims), p(img), w["bqkv"].data_ptr() + 4 * 2 * d, p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
-            p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["b1"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-            p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res) if res is not None else None,
-            res.stride(0) if res is not None else 0, p(cat) if cat is not None else None, depth,
-            p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
-            p(part), p(cnt), p(status) if status is not None else None, B, T, d, H, w["eps"], lvl_pack["lnf_eps"], 1 if qkv_ready else 0, st)
-
+    export.layer(L - 1, xa, order)
     if TAIL_WS:
-        timed("agg_token0_tail", tail_ws)
-        return {"logits": logits, "ctx_slide": ctx_out}
-
-    def tail():
-        token_layer_old(xa, None, None, w)          # fp32 q, k, v of the last layer for the token-0 tail
-        ws_part = torch.empty((B * H * 16 * 36,), device=tokens.device, dtype=torch.float32)
-        _lib.call(
-            "paths_token0_tail", p(xa), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
-            p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["w1"]), p(w["b1"]), p(w["w2"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-            p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res) if res is not None else None,
-            res.stride(0) if res is not None else 0, p(cat) if cat is not None else None, depth,
-            p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
-            p(ws_part), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], st)
-
-    timed("agg_token0_tail", tail)
-    return {"logits": logits, "ctx_slide": ctx_out}
+        timed("agg_token0_tail", lambda: token0_tail_ws(lvl_pack, xa, num_ims, head, status, B, T, d, H, qscale, order))
+    else:
+        timed("agg_token0_tail", lambda: tail_f32(xa, True))
+    return {"logits": head[4], "ctx_slide": head[3]}
 
 
 def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=None, qkv_img=None, attention=None,
                         rollout=None) -> Dict[str, torch.Tensor]:
     _lib.require_cuda(tokens, num_ims, ctx_prev, ctx_all)
+    export = _Export(attention, rollout, lvl_pack, num_ims, mc.trans_heads)
     if AGG_FP8:
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, fp8=True, attention=attention, rollout=rollout)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, export, fp8=True)
     if not fast_path(mc):
-        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status=status, attention=attention,
-                                           rollout=rollout)
+        return _aggregator_forward_generic(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, export, status=status)
     B, T, d = tokens.shape
     H, L = mc.trans_heads, mc.trans_layers
     st = _lib.stream()
@@ -1298,35 +1389,30 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     layers = lvl_pack["layers"]
 
     def token_layer(x_in, x_out, post, nxt, max_tokens=0, qkv_images=None):
-        w = post or nxt
+        if GEMM_MODE != "h3":
+            return token_layer_f32(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B, T, d, H, qscale, 1, max_tokens)
         g = lambda dct, key: p(dct[key]) if dct is not None else None
-        if GEMM_MODE == "h3":
-            ip, sp = tlayer_h3_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
-            iq, sq = tlayer_h3_images(nxt, 1) if nxt is not None else (None, (1.0,))
-            _lib.call("paths_token_layer_h3", p(x_in), p(attn) if post else None, p(x_out) if post else None, p(ip), p(iq),
-                      g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
-                      g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"),
-                      sp[0], sp[1], sp[2], sq[0], p(q), p(k), p(v), p(num_ims), B, T, d, H,
-                      1 if post else 0, 1 if nxt else 0, 1, qscale, w["eps"], max_tokens, p(qkv_images), st)
-            return
-        _lib.call("paths_token_layer_f32", p(x_in), p(attn) if post else None, p(x_out) if post else None,
-                  g(post, "wo"), g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
-                  g(post, "w1"), g(post, "b1"), g(post, "w2"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"),
-                  g(nxt, "wqkv"), g(nxt, "bqkv"), p(q), p(k), p(v), p(num_ims), B, T, d, H,
-                  1 if post else 0, 1 if nxt else 0, 1, qscale, w["eps"], max_tokens, st)
+        ip, sp = tlayer_h3_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
+        iq, sq = tlayer_h3_images(nxt, 1) if nxt is not None else (None, (1.0,))
+        _lib.call("paths_token_layer_h3", p(x_in), p(attn) if post else None, p(x_out) if post else None, p(ip), p(iq),
+                  g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
+                  g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"),
+                  sp[0], sp[1], sp[2], sq[0], p(q), p(k), p(v), p(num_ims), B, T, d, H,
+                  1 if post else 0, 1 if nxt else 0, 1, qscale, (post or nxt)["eps"], max_tokens, p(qkv_images), st)
 
-    nlog = lvl_pack["wcls"].shape[0]
-    ctx_out = torch.empty((B, d), **f32)
-    logits = torch.empty((B, nlog), **f32)
-    res = ctx_prev if mc.slide_ctx_mode == "residual" else None
-    cat = ctx_all.contiguous() if (mc.slide_ctx_mode == "concat" and ctx_all is not None and ctx_all.shape[1] > 0) else None
-    depth = cat.shape[1] if cat is not None else 0
+    def tail_f32(x, in_proj: bool):
+        """The last layer at token 0 + head from that layer's fp32 q, k, v; ``in_proj``: project them first (the weight-stationary
+        loop leaves operand images only)."""
+        if in_proj:
+            token_layer(x, None, None, layers[L - 1])
+        token0_tail(lvl_pack, x, q, k, v, num_ims, head, B, T, d, H)
+
+    head = slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B, d, tokens.device, mc.slide_ctx_mode)
 
     attn_ws = None
     if qkv_img is not None:
         assert GEMM_MODE == "h3" and TLAYER_WS and QKV_IMAGES and L > 1 and not ATTN_FP8
-        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, qkv_img, q, k, v, xb, ctx_out, logits, token_layer, status,
-                                      qkv_ready=True, attention=attention, rollout=rollout)
+        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, head, qkv_img, xb, tail_f32, export, status, qkv_ready=True)
     fp8 = ATTN_FP8 and L > 1          # opt-in e4m3 attention (csrc/attn_fp8.hip: outside the 1e-4 logit bar, stress-config measurement only)
     if fp8:
         attn_ws = torch.empty((int(_lib.load().paths_attention_fp8_workspace(B, T, H, hd)),), device=tokens.device, dtype=torch.uint8)
@@ -1337,14 +1423,10 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     # (no fp32 q, k, v round trip, no re-write launch); the last layer's q, k, v stay fp32 for the token-0 tail
     direct = GEMM_MODE == "h3" and attn_ws is not None and QKV_IMAGES and not fp8
     if direct and TLAYER_WS:
-        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, res, cat, depth, attn_ws, q, k, v, xb, ctx_out, logits, token_layer, status,
-                                      attention=attention, rollout=rollout)
+        return _aggregator_forward_ws(mc, lvl_pack, tokens, num_ims, head, attn_ws, xb, tail_f32, export, status)
     timed("agg_in_proj", lambda: token_layer(xa, None, None, layers[0], qkv_images=attn_ws if direct else None))
     for l in range(L - 1):
-        if attention is not None:
-            _export_attention(attention, lvl_pack, l, xa, num_ims, H, 0)
-        if rollout is not None:
-            rollout.layer(l, xa, 0)
+        export.layer(l, xa, 0)
         if fp8:
             timed("agg_attention", lambda: _lib.call("paths_attention_fp8", p(q), p(k), p(v), p(attn), p(num_ims), B, T, H, hd, p(attn_ws), st))
         elif GEMM_MODE != "f32":
@@ -1354,19 +1436,6 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
             timed("agg_attention", lambda: _lib.call("paths_attention_f32", p(q), p(k), p(v), p(attn), None, p(num_ims), B, T, H, hd, 0, st))
         timed("agg_token_chain", lambda: token_layer(xa, xb, layers[l], layers[l + 1], qkv_images=attn_ws if (direct and l + 1 < L - 1) else None))
         xa, xb = xb, xa
-    # Last layer: only token 0 of its output is read (aggregator.py:75) -> one fused launch per level computes the
-    # single-query attention, the row chain, decoder.norm, the slide-context residual and the classifier.
-    w = layers[L - 1]
-    if attention is not None:
-        _export_attention(attention, lvl_pack, L - 1, xa, num_ims, H, 0)
-    if rollout is not None:
-        rollout.layer(L - 1, xa, 0)
-    ws_part = torch.empty((B * H * 16 * 36,), **f32)
-    timed("agg_token0_tail", lambda: _lib.call(
-        "paths_token0_tail", p(xa), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
-        p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["w1"]), p(w["b1"]), p(w["w2"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-        p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res) if res is not None else None,
-        res.stride(0) if res is not None else 0, p(cat) if cat is not None else None, depth,
-        p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), nlog, lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
-        p(ws_part), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], st))
-    return {"logits": logits, "ctx_slide": ctx_out}
+    export.layer(L - 1, xa, 0)
+    timed("agg_token0_tail", lambda: tail_f32(xa, False))
+    return {"logits": head[4], "ctx_slide": head[3]}

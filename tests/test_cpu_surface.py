@@ -21,6 +21,34 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(paths_[a-z0-9_]+)\s*\(", text)))
 
 
+_C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t}
+
+
+def _ctype(decl: str, ret: bool = False):
+    """ctypes type of one C parameter (``const float* x``) or return type: pointers and paths_stream_t are c_void_p."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return ctypes.c_char_p if (ret and "char" in words) else ctypes.c_void_p
+    words = [w for w in words if w != "const"]
+    if not ret:
+        assert len(words) == 2, decl          # type and name
+    return ctypes.c_void_p if words[0] == "paths_stream_t" else _C_TYPES[words[0]]
+
+
+def header_declarations():
+    """name -> (return ctype, [parameter ctypes]) of every function declared in include/paths_hip.h."""
+    text = open(os.path.join(ROOT, "include", "paths_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t]*[\w*][ \t*]*)\b(paths_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text):
+        params = [a.strip() for a in params.split(",") if a.strip() and a.strip() != "void"]
+        assert name not in out, name
+        out[name] = (_ctype(ret, ret=True), [_ctype(a) for a in params])
+    return out
+
+
 def test_library_exports_every_declared_symbol_at_abi_3():
     from paths_amd import _lib
     if not os.path.isfile(_lib.LIB_PATH):
@@ -31,12 +59,15 @@ def test_library_exports_every_declared_symbol_at_abi_3():
     assert len(syms) >= 16
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/paths_hip.h but not exported"
-    # every ctypes signature corresponds to a declared symbol, with the same number of parameters
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "paths_hip.h")).read(), flags=re.S)
-    for name, args in _lib.SIGNATURES.items():
-        m = re.search(r"\b%s\s*\((.*?)\);" % name, text, flags=re.S)
-        assert m, name
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(args), name
+    # every declared function is bound with exactly the declared parameter and return types, and nothing is bound that is not declared
+    decls = header_declarations()
+    assert sorted(decls) == syms
+    bound = {name: (ctypes.c_int, list(args)) for name, args in _lib.SIGNATURES.items()}
+    assert not set(bound) & set(_lib._PLAIN), "a function is bound twice"
+    bound.update({name: (res, list(args)) for name, (res, args) in _lib._PLAIN.items()})
+    assert sorted(bound) == syms, sorted(set(bound) ^ set(syms))
+    for name, (res, args) in bound.items():
+        assert (res, args) == decls[name], f"{name}: bound as {(res, args)}, declared as {decls[name]}"
     lib.paths_abi_version.restype = ctypes.c_int
     assert lib.paths_abi_version() == 3
 
