@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "dropout.h"
+#include "lanes.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
 int paths_attention_bwd_x6_launch(const float* q, const float* k, const float* v, const float* d_o, const float* lse, const float* dsum,
@@ -30,12 +31,6 @@ constexpr int HD = 32;
 constexpr int LD40 = 40;     // row stride for 16-byte row reads of the 16x16x4 A operand (conflict-free)
 constexpr int LD36 = 36;     // row stride for 4-byte "column" reads
 constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // D[b,h,q] = sum_dv dO[b,q,h*32+dv] * O[b,q,h*32+dv]; one wave per token row, 16 lanes per head
 __global__ void __launch_bounds__(256)

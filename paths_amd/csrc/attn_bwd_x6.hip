@@ -18,13 +18,9 @@
 //                             72 v_mfma_f32_16x16x32_bf16 (16 cycles) per 32 x 32 block against 96 v_mfma_f32_16x16x4_f32 (32 cycles).
 #include "common.h"
 #include "dropout.h"
+#include "split.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 32;
 constexpr int FRAG = 1024;
@@ -32,48 +28,8 @@ constexpr int KSTEP = 64;
 constexpr int QT = 2;
 constexpr float LN2 = 0.6931471805599453f;
 
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// 8 fp32 -> PL planes of 8 bf16: PL = 3 hi, mid, lo (exact: 3 x 8 = the 24 bits of fp32); PL = 2 hi, mid only (16 significant bits at
-// fp32's exponent range - the setting of the training step's gradient GEMMs, PATHS_TRAIN_PLANES=4: no scales, nothing overflows)
-template <int PL>
-__device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[PL]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_bf16(a, b);
-    const float ra = a - bf_lo(h), rb = b - bf_hi(h);
-    const uint32_t m = pk_bf16(ra, rb);
-    pl[0][i] = h; pl[1][i] = m;
-    if constexpr (PL == 3) {
-      const float sa = ra - bf_lo(m), sb = rb - bf_hi(m);
-      pl[2][i] = pk_bf16(sa, sb);
-    }
-  }
-}
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4 c) {   // hi, mid, lo: six largest of nine
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
-  return c;
-}
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4 c) {   // hi, mid: all but mid*mid
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
-  return c;
-}
-
+// PL = bf16 planes per operand (split.h): 3 hi, mid, lo, exact; 2 hi, mid only - the setting of the training step's gradient GEMMs,
+// PATHS_TRAIN_PLANES=4: no scales, nothing overflows
 template <int PL>
 __global__ void __launch_bounds__(256)
 attn_bwd_x6_prep_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
@@ -226,8 +182,8 @@ attn_bwd_q_x6_kernel(const char* __restrict__ qr, const char* __restrict__ kr, c
         }
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-          s[qt][t] = mfma_split(kf, qf[qt], f32x4{0.f, 0.f, 0.f, 0.f});
-          dp[qt][t] = mfma_split(vf, gf[qt], f32x4{0.f, 0.f, 0.f, 0.f});
+          s[qt][t] = mfma_split_bf16<PL>(kf, qf[qt], f32x4{0.f, 0.f, 0.f, 0.f});
+          dp[qt][t] = mfma_split_bf16<PL>(vf, gf[qt], f32x4{0.f, 0.f, 0.f, 0.f});
         }
       }
       u32x4 dsf[QT][PL];
@@ -256,7 +212,7 @@ attn_bwd_q_x6_kernel(const char* __restrict__ qr, const char* __restrict__ kr, c
 #pragma unroll
         for (int p = 0; p < PL; ++p) tf[p] = *reinterpret_cast<const u32x4*>(sT + ((kg * 2 + dt) * PL + p) * FRAG);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) dq[dt][qt] = mfma_split(tf, dsf[qt], dq[dt][qt]);
+        for (int qt = 0; qt < QT; ++qt) dq[dt][qt] = mfma_split_bf16<PL>(tf, dsf[qt], dq[dt][qt]);
       }
     }
     if (kt_ + 1 < nkt) swrite(kt_ + 1);                 // the other buffer: read one step ago, everyone passed the barrier since
@@ -373,8 +329,8 @@ attn_bwd_kv_x6_kernel(const char* __restrict__ qr, const char* __restrict__ kr, 
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          s[qt_][t] = mfma_split(qf, kf[t], f32x4{0.f, 0.f, 0.f, 0.f});
-          dp[qt_][t] = mfma_split(gf, vf[t], f32x4{0.f, 0.f, 0.f, 0.f});
+          s[qt_][t] = mfma_split_bf16<PL>(qf, kf[t], f32x4{0.f, 0.f, 0.f, 0.f});
+          dp[qt_][t] = mfma_split_bf16<PL>(gf, vf[t], f32x4{0.f, 0.f, 0.f, 0.f});
         }
       }
       u32x4 pf[2][PL], dsf[2][PL];
@@ -425,8 +381,8 @@ attn_bwd_kv_x6_kernel(const char* __restrict__ qr, const char* __restrict__ kr, 
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          dv[t][dt] = mfma_split(gtf, pf[t], dv[t][dt]);
-          dk[t][dt] = mfma_split(qtf, dsf[t], dk[t][dt]);
+          dv[t][dt] = mfma_split_bf16<PL>(gtf, pf[t], dv[t][dt]);
+          dk[t][dt] = mfma_split_bf16<PL>(qtf, dsf[t], dk[t][dt]);
         }
       }
     }

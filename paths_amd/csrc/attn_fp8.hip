@@ -12,12 +12,9 @@
 // by 256 before the conversion (e4m3's normal range starts at 2^-6) and the 1/256 is folded into the final normalisation; the row
 // sum l is accumulated in fp32 from the unquantised probabilities.
 #include "common.h"
+#include "lanes.h"
 
 namespace {
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int F8 = 512;                    // bytes of one 16-row x 32-k fp8 fragment (64 lanes x 8 bytes)
 constexpr int KSTEP = 64;                  // keys per LDS buffer
@@ -37,8 +34,6 @@ __device__ __forceinline__ u32x2 fp8x8(const float (&x)[8], float scale) {
 }
 __device__ __forceinline__ long as_long(u32x2 v) { return __builtin_bit_cast(long, v); }
 __device__ __forceinline__ f32x4 mfma8(long a, long b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float rows_max(float x) { x = fmaxf(x, __shfl_xor(x, 16)); return fmaxf(x, __shfl_xor(x, 32)); }
-__device__ __forceinline__ float rows_sum(float x) { x += __shfl_xor(x, 16); return x + __shfl_xor(x, 32); }
 
 // Fragment images per (slide, head), Tp = T rounded up to 64 (the lane maps of attn_x6.hip, 8 bytes per lane), NK = HD / 32 k-steps,
 // NDV = HD / 16 output-dim tiles:

@@ -8,44 +8,14 @@
 // padded to a multiple of 32 on the score side (16 -> 32, 48 -> 64: zero dims) - correctness first, not tuned like attn_x6.hip.
 // q, k, v are read from the token-major in_proj output [B*T, 3d] (q unscaled: log2(e)/sqrt(hd) is applied while the images are written).
 #include "common.h"
+#include "lanes.h"
+#include "split.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int FB = 1024;                   // bytes of one 16-row x 32-k fp16 fragment plane (64 lanes x 16 bytes)
 constexpr int KSTEP = 64;                  // keys per LDS buffer
 constexpr int QT = 2;                      // 16-query tiles per wave
-
-__device__ __forceinline__ uint32_t pk_f16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-// 8 fp32 -> two planes of 8 fp16 (hi, lo): 22 significant bits
-__device__ __forceinline__ void split8h(const float (&x)[8], u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_f16(a, b);
-    float ra, rb;
-    f16_pair_residuals(h, a, b, ra, rb);
-    hi[i] = h; lo[i] = pk_f16(ra, rb);
-  }
-}
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// acc += A * B from (hi, lo) planes, smallest partial products first: all but lo * lo
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4 c) {
-  c = mfma_f16(a[1], b[0], c);
-  c = mfma_f16(a[0], b[1], c);
-  return mfma_f16(a[0], b[0], c);
-}
-__device__ __forceinline__ float rows_max(float x) { x = fmaxf(x, __shfl_xor(x, 16)); return fmaxf(x, __shfl_xor(x, 32)); }
-__device__ __forceinline__ float rows_sum(float x) { x += __shfl_xor(x, 16); return x + __shfl_xor(x, 32); }
 
 // Fragment images per (slide, head), Tp = T rounded up to 64, NK = ceil(HD / 32) k-steps on the score side, NDV = HD / 16 output tiles:
 //   Q / K : [Tp/16 tiles][NK][2 planes][64 lanes][16 B]    lane (r = l&15, g = l>>4): token 16 tile + r, dims 32 kk + 8g .. + 7 (0 past HD)
@@ -182,7 +152,7 @@ attn_h3_any_kernel(const char* __restrict__ qi, const char* __restrict__ ki, con
           kf[0] = *reinterpret_cast<const u32x4*>(gK + (t * NK + kk) * (2 * FB));
           kf[1] = *reinterpret_cast<const u32x4*>(gK + (t * NK + kk) * (2 * FB) + FB);
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split(kf, qf[qt][kk], s[qt][t]);
+          for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split_f16(kf, qf[qt][kk], s[qt][t]);
         }
       }
       if (kt == nkt - 1) {
@@ -232,7 +202,7 @@ attn_h3_any_kernel(const char* __restrict__ qi, const char* __restrict__ ki, con
           vf[0] = *reinterpret_cast<const u32x4*>(gV + (kg * NDV + dvt) * (2 * FB));
           vf[1] = *reinterpret_cast<const u32x4*>(gV + (kg * NDV + dvt) * (2 * FB) + FB);
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pf[qt][kg], oacc[dvt][qt]);
+          for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split_f16(vf, pf[qt][kg], oacc[dvt][qt]);
         }
     }
     // per-lane states -> LDS [4 waves][2 QT + 4 NDV QT][64]  (a wave without a key step: m = -inf, l = 0, O = 0: weight 0 in the merge)
@@ -304,7 +274,7 @@ attn_h3_any_kernel(const char* __restrict__ qi, const char* __restrict__ ki, con
         kf[0] = *reinterpret_cast<const u32x4*>(sK + (t * NK + kk) * (2 * FB));
         kf[1] = *reinterpret_cast<const u32x4*>(sK + (t * NK + kk) * (2 * FB) + FB);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split(kf, qf[qt][kk], s[qt][t]);
+        for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split_f16(kf, qf[qt][kk], s[qt][t]);
       }
     }
   };
@@ -365,7 +335,7 @@ attn_h3_any_kernel(const char* __restrict__ qi, const char* __restrict__ ki, con
         vf[0] = *reinterpret_cast<const u32x4*>(sV + (kg * NDV + dvt) * (2 * FB));
         vf[1] = *reinterpret_cast<const u32x4*>(sV + (kg * NDV + dvt) * (2 * FB) + FB);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pf[qt][kg], oacc[dvt][qt]);
+        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split_f16(vf, pf[qt][kg], oacc[dvt][qt]);
       }
     swrite(kt + 2, kt + 1, morek, morev);               // K over K(kt) (read one step ago), V over V(kt-1)
     __syncthreads();

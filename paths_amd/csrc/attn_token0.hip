@@ -9,6 +9,7 @@
 // domain, dropout mask element ((slide*H + head)*T + 0)*T + key of the site (csrc/dropout.h).
 #include "common.h"
 #include "dropout.h"
+#include "lanes.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
 
@@ -18,17 +19,6 @@ constexpr int HD = 32;
 constexpr int S_MAX = 16;
 constexpr int PSTRIDE = 36;       // floats per partial record: m, l, -, -, o[32]
 constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 __device__ __forceinline__ void split_range(int len, int S, int part, int& k0, int& k1) {
   const int chunk = ((len + S - 1) / S + 63) & ~63;

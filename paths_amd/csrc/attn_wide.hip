@@ -27,12 +27,13 @@ namespace {
 
 constexpr float LN2 = 0.6931471805599453f;
 
-__device__ __forceinline__ float wave_max(float v) {
+// 64-lane butterflies walking the offsets 32 DOWN to 1: another summation order than lanes.h wave_sum (1 up to 32), and other bits with it
+__device__ __forceinline__ float wave_max_desc(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
+__device__ __forceinline__ float wave_sum_desc(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
@@ -60,10 +61,10 @@ wide_softmax_kernel(float* __restrict__ S, int Tp, int nq, const int64_t* __rest
   } else {
     float m = -INFINITY;
     for (int c = lane; c < len; c += 64) m = fmaxf(m, row[c] * qscale);
-    m = wave_max(m);                                   // finite: key 0 (the special token) is always valid
+    m = wave_max_desc(m);                              // finite: key 0 (the special token) is always valid
     float l = 0.f;
     for (int c = lane; c < len; c += 64) l += __builtin_amdgcn_exp2f(row[c] * qscale - m);
-    l = wave_sum(l);
+    l = wave_sum_desc(l);
     L = m + __builtin_amdgcn_logf(l);                  // v_log_f32 = log2
     if (lse_out != nullptr && lane == 0) lse_out[r] = L;
   }
@@ -94,7 +95,7 @@ wide_ds_kernel(float* __restrict__ P, float* __restrict__ dP, int Tp, int nq, co
   }
   float D = 0.f;
   for (int c = lane; c < hd; c += 64) D = fmaf(d_o[(int64_t)r * ldo + c], o[(int64_t)r * ldo + c], D);
-  D = wave_sum(D);
+  D = wave_sum_desc(D);
   const uint64_t mrow = (site_base + (uint64_t)r) * drop_attn_stride(T);
   float* prow = P + (int64_t)r * Tp;
   float* drow = dP + (int64_t)r * Tp;

@@ -20,18 +20,12 @@
 // The six kept partial products per operand pair are accumulated smallest first, exactly as in gemm_x6.hip.
 #include "common.h"
 #include "dropout.h"
+#include "lanes.h"
+#include "split.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 32;
 constexpr int FRAG = 1024;                 // bytes of one fragment (64 lanes x 8 bf16)
@@ -40,49 +34,12 @@ constexpr int KSTEP = 64;                  // keys staged per LDS buffer
 // NP = 3: bf16 hi|mid|lo, 6 MFMAs per product (x6);  NP = 2: fp16 hi|lo, 3 MFMAs (h3; q, k, v and P are O(1): no scaling)
 template <int NP> constexpr int step_bytes() { return 8 * NP * FRAG; }
 
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-__device__ __forceinline__ uint32_t pk_f16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-// 8 fp32 -> two planes of 8 fp16 (hi, lo): 22 significant bits
-__device__ __forceinline__ void split8h(const float (&x)[8], u32x4& hi, u32x4& lo) {
-  // residual + rounding of the lo plane: one v_fma_mixlo_f16 / v_fma_mixhi_f16 per value (common.h: f16_pair_residuals_pk), the four
-  // low halves first: a half-register write directly in front of the other half's costs a wait state each (16 s_nop per key step)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) hi[i] = pk_f16(x[2 * i], x[2 * i + 1]);
-  uint32_t r[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r[i]) : "v"(hi[i]), "v"(x[2 * i]));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r[i]) : "v"(hi[i]), "v"(x[2 * i + 1]));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) lo[i] = r[i];
-}
-// planes[0..NP) of 8 values
+// planes[0..NP) of 8 values: NP = 3 bf16 hi, mid, lo; NP = 2 fp16 hi, lo in this kernel's own instruction order (split.h)
 template <int NP>
-__device__ __forceinline__ void split_planes(const float (&x)[8], u32x4 (&pl)[NP]);
-// 8 fp32 -> three planes of 8 bf16 (hi, mid, lo), exact
-__device__ __forceinline__ void split8(const float (&x)[8], u32x4& hi, u32x4& mid, u32x4& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_bf16(a, b);
-    const float ra = a - bf_lo(h), rb = b - bf_hi(h);
-    const uint32_t m = pk_bf16(ra, rb);
-    const float sa = ra - bf_lo(m), sb = rb - bf_hi(m);
-    hi[i] = h; mid[i] = m; lo[i] = pk_bf16(sa, sb);
-  }
+__device__ __forceinline__ void split_planes(const float (&x)[8], u32x4 (&pl)[NP]) {
+  if constexpr (NP == 3) split8<3>(x, pl);
+  else split8h_lows_first(x, pl[0], pl[1]);
 }
-
-template <> __device__ __forceinline__ void split_planes<3>(const float (&x)[8], u32x4 (&pl)[3]) { split8(x, pl[0], pl[1], pl[2]); }
-template <> __device__ __forceinline__ void split_planes<2>(const float (&x)[8], u32x4 (&pl)[2]) { split8h(x, pl[0], pl[1]); }
 
 // Fragment images (per (slide, head), Tp = T rounded up to 64):
 //   Q6 / K6 : [Tp/16 tiles][3 planes][64 lanes][8 bf16]        lane (r = l&15, g = l>>4): token 16 tile + r, dims 8g .. 8g+7
@@ -137,31 +94,12 @@ attn_x6_prep_kernel(const float* __restrict__ q, const float* __restrict__ k, co
   }
 }
 
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+// acc += A * B from split operands of NP planes (split.h: smallest partial products first)
+template <int NP>
+__device__ __forceinline__ f32x4 mfma_planes(const u32x4 (&a)[NP], const u32x4 (&b)[NP], f32x4 c) {
+  if constexpr (NP == 3) return mfma_split_bf16<3>(a, b, c);
+  else return mfma_split_f16(a, b, c);
 }
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// acc += A * B from split operands, smallest partial products first
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4 c) {   // hi, mid, lo: six largest of nine
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
-  return c;
-}
-__device__ __forceinline__ f32x4 mfma_split(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x4 c) {   // hi, lo: all but lo*lo
-  c = mfma_f16(a[1], b[0], c);
-  c = mfma_f16(a[0], b[1], c);
-  c = mfma_f16(a[0], b[0], c);
-  return c;
-}
-
-__device__ __forceinline__ float rows_max(float x) { x = fmaxf(x, __shfl_xor(x, 16)); return fmaxf(x, __shfl_xor(x, 32)); }
-__device__ __forceinline__ float rows_sum(float x) { x += __shfl_xor(x, 16); return x + __shfl_xor(x, 32); }
 
 // DROP (training with dropout > 0, reference nn.MultiheadAttention(dropout=p)): the softmax probabilities that enter the PV product
 // are multiplied by the regenerated mask / (1 - p) (element ((slide*H + head)*T + query)*T + key of the site, csrc/dropout.h); the
@@ -252,7 +190,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
 #pragma unroll
       for (int p = 0; p < NP; ++p) kf[p] = *reinterpret_cast<const u32x4*>(sK + (t * NP + p) * FRAG);
 #pragma unroll
-      for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_split(kf, qf[qt], negm[qt]);      // (zero outside FAST)
+      for (int qt = 0; qt < QT; ++qt) s[qt][t] = mfma_planes<NP>(kf, qf[qt], negm[qt]);      // (zero outside FAST)
     }
   };
   gload_k(0); gload_v(0);
@@ -342,7 +280,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
 #pragma unroll
         for (int p = 0; p < NP; ++p) vf[p] = *reinterpret_cast<const u32x4*>(sV + ((kg * 2 + dvt) * NP + p) * FRAG);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pf[qt][kg], oacc[dvt][qt]);
+        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_planes<NP>(vf, pf[qt][kg], oacc[dvt][qt]);
       }
     if (kt + 2 < nkt) swrite_k(kt + 2);                 // over K(kt): read one step ago
     if (kt + 1 < nkt) swrite_v(kt + 1);                 // over V(kt-1)
@@ -362,7 +300,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
 #pragma unroll
         for (int p = 0; p < 2; ++p) vf[p] = *reinterpret_cast<const u32x4*>(sV + ((kg * 2 + dvt) * NP + p) * FRAG);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split(vf, pfr[qt][kg], oacc[dvt][qt]);
+        for (int qt = 0; qt < QT; ++qt) oacc[dvt][qt] = mfma_split_f16(vf, pfr[qt][kg], oacc[dvt][qt]);
       }
   };
   auto step_fast = [&](int kt, f32x4 (&s)[QT][4], f32x4 (&sn)[QT][4], auto lastc) __attribute__((always_inline)) {
@@ -479,7 +417,7 @@ attn_x6_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const c
           const float v[8] = {oacc[0][qt][0] * inv, oacc[0][qt][1] * inv, oacc[0][qt][2] * inv, oacc[0][qt][3] * inv,
                               oacc[1][qt][0] * inv, oacc[1][qt][1] * inv, oacc[1][qt][2] * inv, oacc[1][qt][3] * inv};
           u32x4 hi, lo;
-          split8h(v, hi, lo);
+          split8h_lows_first(v, hi, lo);
           char* dst = o_img + ((((int64_t)b * (Tp >> 6) + (tq >> 6)) * H + head) * 4 + ((tq >> 4) & 3)) * (2 * FRAG) + lane * 16;
           *reinterpret_cast<u32x4*>(dst) = hi;
           *reinterpret_cast<u32x4*>(dst + FRAG) = lo;
@@ -628,7 +566,7 @@ attn_m32_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const 
             ps[j & 3] += pv[j];
             asm("" : "+v"(ps[j & 3]));
           }
-          split8h(pv, pf[t][u][0], pf[t][u][1]);
+          split8h_lows_first(pv, pf[t][u][0], pf[t][u][1]);
         }
       psum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
     };
@@ -690,7 +628,7 @@ attn_m32_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const 
         const float v[8] = {oacc[i0] * inv, oacc[i0 + 1] * inv, oacc[i0 + 2] * inv, oacc[i0 + 3] * inv,
                             oacc[i1] * inv, oacc[i1 + 1] * inv, oacc[i1 + 2] * inv, oacc[i1 + 3] * inv};
         u32x4 hi, lo;
-        split8h(v, hi, lo);
+        split8h_lows_first(v, hi, lo);
         char* dst = o_img + ((((int64_t)b * (Tp >> 6) + (tq >> 6)) * H + head) * 4 + ((tq >> 4) & 3)) * (2 * FRAG) + (l15 + 16 * (h + 2 * gg)) * 16;
         *reinterpret_cast<u32x4*>(dst) = hi;
         *reinterpret_cast<u32x4*>(dst + FRAG) = lo;
@@ -801,7 +739,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
           const float v[8] = {oacc[i0] * inv, oacc[i0 + 1] * inv, oacc[i0 + 2] * inv, oacc[i0 + 3] * inv,
                               oacc[i1] * inv, oacc[i1 + 1] * inv, oacc[i1 + 2] * inv, oacc[i1 + 3] * inv};
           u32x4 hi, lo;
-          split8h(v, hi, lo);
+          split8h_lows_first(v, hi, lo);
           char* dst = o_img + ((((int64_t)b * (Tp >> 6) + (tq >> 6)) * H + head) * 4 + ((tq >> 4) & 3)) * (2 * FRAG) + (l15 + 16 * (h + 2 * gg)) * 16;
           *reinterpret_cast<u32x4*>(dst) = hi;
           *reinterpret_cast<u32x4*>(dst + FRAG) = lo;
@@ -861,7 +799,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
               pv[j] = __builtin_amdgcn_exp2f(s[t][4 * u + (j & 3) + 8 * (j >> 2)]);
               ps[j & 3] += pv[j];
             }
-            split8h(pv, pf[t][u][0], pf[t][u][1]);
+            split8h_lows_first(pv, pf[t][u][0], pf[t][u][1]);
           }
         psum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
       };
@@ -1034,7 +972,7 @@ attn_m32p_kernel(const char* __restrict__ q6, const char* __restrict__ k6, const
               ps[j & 3] += pv[j];
               asm("" : "+v"(ps[j & 3]));
             }
-            split8h(pv, pf[t][u][0], pf[t][u][1]);
+            split8h_lows_first(pv, pf[t][u][0], pf[t][u][1]);
           }
         psum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
       };

@@ -5,6 +5,7 @@
 //   nn.LayerNorm               (post-LN decoder layers + decoder.norm of the nn.Transformer at model/aggregator.py:25-33)
 // as applied by autograd in the reference train step (train.py:65).
 #include "common.h"
+#include "lanes.h"
 
 namespace {
 
@@ -64,12 +65,6 @@ lstm_bwd_b_kernel(const float* __restrict__ dc1_h, const float* __restrict__ dc1
     dg[row * ldg + blk * 96 + 64 + jj] = dm;
     if (dc0) dc0[row * lddc0 + j] = d0;
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // ---- importance + projection backward, one wave per patch row (width d = Hi = 128 -> 2 values per lane)

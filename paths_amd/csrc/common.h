@@ -7,8 +7,11 @@
 #include <stdio.h>
 #include <type_traits>
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- error convention (include/paths_hip.h): 0 = ok, negative = error, message in thread-local buffer
 #define PATHS_OK 0
@@ -57,24 +60,6 @@ hipEvent_t paths_take_stop_event(void);      // runtime.hip: returns and clears 
   } while (0)
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [I0, N) - indices stay constants without relying on the unroller
-// Residuals of a packed fp16 pair: ra = a - (float)h.lo, rb = b - (float)h.hi, one v_fma_mix_f32 each (the mixed-precision FMA reads
-// the half straight out of the packed register; written as a - (float)h hipcc emits v_cvt_f32_f16 + v_sub_f32, and turns an
-// fmaf(h, -1, a) back into that).  Exact either way: the same fp32 subtraction.
-__device__ __forceinline__ void f16_pair_residuals(uint32_t h, float a, float b, float& ra, float& rb) {
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(ra) : "v"(h), "v"(a));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(h), "v"(b));
-}
-
-// The same residuals ROUNDED to fp16 and packed (the lo plane of the pair): v_fma_mixlo_f16 / v_fma_mixhi_f16 compute the fp32
-// FMA and write its fp16 rounding (nearest even, as v_cvt_pk_f16_f32) into one half of the destination - two instructions where
-// residuals + pack took three.
-__device__ __forceinline__ uint32_t f16_pair_residuals_pk(uint32_t h, float a, float b) {
-  uint32_t r;
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(a));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(h), "v"(b));
-  return r;
-}
-
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) {
@@ -122,6 +107,14 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 __device__ __forceinline__ f32x4 ldg_f32x4(const float* p) {
   typedef const f32x4 __attribute__((address_space(1))) * gptr;
   return *reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p));
+}
+
+// XCD-aware workgroup order (speed only): the hardware places workgroup `lin` of a launch on XCD lin % 8, each with a private L2.
+// Returns the position workgroup `lin` takes in the kernel's own tile sequence such that XCD x owns one contiguous run of it
+// (the first nblk % 8 XCDs get one tile more); bijective for any nblk.
+__device__ __forceinline__ int xcd_tile_order(int lin, int nblk) {
+  const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, j = lin >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
 }
 
 __device__ __forceinline__ int c32_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }

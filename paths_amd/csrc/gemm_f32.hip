@@ -49,11 +49,7 @@ gemm_f32_kernel(GemmOperands g, Epi epi) {
   // column-block fastest within groups of GM row-blocks, so the ~64 workgroups resident on one XCD cover a
   // GM x (N/BN) patch and re-use each A and W k-tile from that XCD's private L2.
   const int nbx = gridDim.x, nby = gridDim.y, nblk = nbx * nby;
-  int lin = blockIdx.y * nbx + blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, j = lin >> 3;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;   // bijective for any nblk
-  }
+  const int lin = xcd_tile_order(blockIdx.y * nbx + blockIdx.x, nblk);
   constexpr int GM = 8;
   const int per_group = GM * nbx;
   const int grp = lin / per_group, in_grp = lin - grp * per_group;

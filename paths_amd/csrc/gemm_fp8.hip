@@ -19,11 +19,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lanes.h"
 
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 256, BN = 256;
 // k bytes per stage BK = 64 (any K % 128 == 0; a 128-byte stage needs more staging registers than the pipelined k-steps leave: it
@@ -54,8 +54,7 @@ absmax_kernel(const float* __restrict__ x, int64_t ld, int64_t M, int K, unsigne
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + r * ld + 4 * c);
     m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
   }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(bits, __float_as_uint(m));
 }
 __global__ void scale_from_bits_kernel(unsigned int* __restrict__ bits, float* __restrict__ scale) {
@@ -306,8 +305,7 @@ gemm_fp8_kernel(Fp8Gemm g) {
     }
   }
   if (g.out_absmax) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    amax = wave_max(amax);
     if (lane == 0) atomicMax(g.out_absmax, __float_as_uint(amax));
   }
 }

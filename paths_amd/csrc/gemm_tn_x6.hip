@@ -22,22 +22,11 @@
 
 #include "common.h"
 #include "reduce.h"
+#include "split.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // v_cvt_pk_bf16_f32: round to nearest even
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
 
 constexpr int TK = 16;                 // rows of the reduction dimension per stage
 constexpr int IMG = TK * 256;          // bytes of one [16 m][128 n] 16-bit image
@@ -73,11 +62,7 @@ gemm_tn_x6_kernel(TnX6Operands g) {
   // XCD-aware order (speed only): XCD x (= linear id % 8) owns a contiguous run of the (split, tile) sequence, tile fastest: the
   // workgroups that share one split's rows of A and B run on one XCD and re-use them from its private L2.
   const int nt2 = g.N2 / B2, ntiles = (g.N1 / B1) * nt2, nblk = ntiles * g.splits;
-  int lin = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, j = lin >> 3;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int lin = xcd_tile_order(blockIdx.x, nblk);
   const int split = lin / ntiles, tile = lin - split * ntiles;
   const int n1_0 = (tile / nt2) * B1, n2_0 = (tile % nt2) * B2;
   const int m_begin = split * g.rows_per_split;

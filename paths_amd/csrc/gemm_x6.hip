@@ -29,6 +29,7 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "finish_qkv.h"
+#include "split.h"
 
 // PATHS_X6_PART = 1 / 2 / 3: this translation unit defines one third of the C entry points (LSTM cell + weight packing, importance /
 // projection, the gemm_nt family) - the file takes 4.5 minutes to compile whole, __graft_entry__.build() compiles the parts in
@@ -39,29 +40,6 @@
 
 namespace {
 using namespace paths_epi;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // v_cvt_pk_bf16_f32: round to nearest even
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// fp16 twin of the bf16 helpers (NP == 2 split, see below)
-__device__ __forceinline__ uint32_t pk_f16(float a, float b) {       // v_cvt_pk_f16_f32 / 2 x v_cvt_f16_f32: round to nearest even
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float h_lo(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-__device__ __forceinline__ float h_hi(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
 
 constexpr int FRAG = 1024;         // bytes of one 32-row x 16-k fragment of one plane (16-bit elements either way)
 // NP = operand split: 3 = three bf16 planes hi|mid|lo, 6 MFMAs per product block ("x6", exact fp32 products); 2 = two fp16 planes
@@ -118,11 +96,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
   // XCD-aware tile order (speed only): XCD x (= linear id % 8) owns a contiguous run of the tile sequence, column-block
   // fastest within groups of GM row-blocks, so the workgroups of one XCD re-use A and W stages from its private L2.
   const int nbx = gridDim.x, nby = gridDim.y, nblk = nbx * nby;
-  int lin = blockIdx.y * nbx + blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, j = lin >> 3;
-    lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;   // bijective for any nblk
-  }
+  const int lin = xcd_tile_order(blockIdx.y * nbx + blockIdx.x, nblk);
   constexpr int GM = 8;
   const int per_group = GM * nbx;
   const int grp = lin / per_group, in_grp = lin - grp * per_group;

@@ -7,16 +7,11 @@
 // not tuned like the 128-wide path.
 #include "common.h"
 #include "dropout.h"
+#include "lanes.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---- fused masked self-attention, fp32 MFMA (the scheme of attn_f32.hip), templated on the head dim; q, k, v are read in place
 // from the token-major in_proj output [B*T, 3d] (q | k | v blocks of d columns, head h at columns h*HD), q scaled here.

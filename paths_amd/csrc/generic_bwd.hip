@@ -9,18 +9,13 @@
 // reasonable speed (VALU dot products over LDS-staged tiles), not tuned like the 128-wide path.
 #include "common.h"
 #include "dropout.h"
+#include "lanes.h"
 
 DropSite paths_make_drop_site(uint64_t key, float p);      // dropout.hip
 
 namespace {
 
 constexpr float LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // LayerNorm, any width d <= 2048 (d % 4 == 0): one wave per row, lane l owns columns 4 l + 256 i, i < NI

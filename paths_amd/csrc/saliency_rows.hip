@@ -5,14 +5,9 @@
 // Rows at or beyond num_ims[b] are not read (the training path computes padded rows: their dX means nothing) and get exact zeros.
 // HBM-bound: 2 M D 4 bytes in, 8 M bytes out.
 #include "common.h"
+#include "lanes.h"
 
 constexpr int SAL_WAVES = 4;        // rows per workgroup
-
-__device__ __forceinline__ float sal_wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __global__ void __launch_bounds__(SAL_WAVES * 64)
 saliency_rows_kernel(const float* __restrict__ dx, int64_t ldd, const float* __restrict__ x, int64_t ldx,
@@ -33,8 +28,8 @@ saliency_rows_kernel(const float* __restrict__ dx, int64_t ldd, const float* __r
       dot += (a[0] * c[0] + a[1] * c[1]) + (a[2] * c[2] + a[3] * c[3]);
       sq += (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
     }
-    dot = sal_wave_sum(dot);
-    sq = sal_wave_sum(sq);
+    dot = wave_sum(dot);
+    sq = wave_sum(sq);
   }
   if (lane == 0) {
     gxi[row] = dot;

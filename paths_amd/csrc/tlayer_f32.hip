@@ -16,6 +16,7 @@
 // and LayerNorm's feature reduction is 31 in-lane adds + 2 cross-lane swaps.  16-token waves (rather
 // than 32) keep >= 1000 waves in flight at 8 slides x 2049 tokens, enough for all 1024 SIMDs.
 #include "common.h"
+#include "lanes.h"
 
 namespace {
 
@@ -273,12 +274,6 @@ struct Token0Params {
   const float *wcls, *bcls; int num_logits, cls_in;
   float *ctx_out, *logits; int T, H; float eps, eps_f;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // y[f] = dot(W[f][0:K], xin[0:K]) for f in [f0, f0+nf), nf a multiple of R: R rows in flight per wave so the
 // row loads and the cross-lane reductions of different rows overlap (this kernel is latency-, not bandwidth-bound)

@@ -18,13 +18,9 @@
 //   * LayerNorm'd activations and relu outputs are O(1): no activation scaling (|activation| < 65504; below 0.125 the lo
 //     plane is subnormal: absolute error 2^-25 per element).
 #include "common.h"
+#include "split.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DM = 128;            // trans_dim
 constexpr int DFF = 512;           // dim_feedforward = 4 * trans_dim
@@ -37,28 +33,6 @@ constexpr int N_QKV = 6;           // chunks of in_proj: rows 64 c
 // first one's LDS / barrier waits, the global -> LDS chunk traffic per token halves, and the launch needs half the CUs.
 constexpr int NWAVES = 8;
 constexpr int NTHREADS = 64 * NWAVES, TOK_WG = 16 * NWAVES, NSTAGE = 2048 / NTHREADS;   // 16-byte pieces per thread and chunk
-
-__device__ __forceinline__ uint32_t pk_f16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float h_lo(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[0]; }
-__device__ __forceinline__ float h_hi(uint32_t p) { return (float)__builtin_bit_cast(f16x2, p)[1]; }
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-// 8 fp32 -> hi | lo planes of 8 fp16 (22 significant bits)
-__device__ __forceinline__ void split8h(const float (&x)[8], u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_f16(a, b);
-    float ra, rb;
-    f16_pair_residuals(h, a, b, ra, rb);
-    hi[i] = h; lo[i] = pk_f16(ra, rb);
-  }
-}
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 struct TLayerH3Params {
   const float* x_in; const float* attn; float* x_out;

@@ -21,14 +21,10 @@
 #include "common.h"
 #include "finish_qkv.h"
 #include "gemm_epi.h"
+#include "lanes.h"
+#include "split.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FRAG = 1024;         // bytes of one 16-row x 32-k fragment of one plane
 constexpr int NW = 4;              // waves per workgroup
@@ -49,53 +45,9 @@ template <int DM> struct Geo {
   static constexpr int N_POST = 1 + 2 * NFF, N_QKV = 3;   // units: Wo | (W1 rows c DM.., W2[:, c DM..]) x 4   and   Wq | Wk | Wv
 };
 
-__device__ __forceinline__ uint32_t pk_f16(float a, float b) {
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
-// 8 fp32 -> hi | lo planes of 8 fp16 (22 significant bits)
-__device__ __forceinline__ void split8h(const float (&x)[8], u32x4& hi, u32x4& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_f16(a, b);
-    float ra, rb;
-    f16_pair_residuals(h, a, b, ra, rb);
-    hi[i] = h; lo[i] = pk_f16(ra, rb);
-  }
-}
-__device__ __forceinline__ void split4h(const float (&x)[4], u32x2& hi, u32x2& lo) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float a = x[2 * i], b = x[2 * i + 1];
-    const uint32_t h = pk_f16(a, b);
-    float ra, rb;
-    f16_pair_residuals(h, a, b, ra, rb);
-    hi[i] = h; lo[i] = pk_f16(ra, rb);
-  }
-}
-__device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ u32x4 ldg_u32x4(const char* p) {
   typedef const u32x4 __attribute__((address_space(1))) * gptr;
   return *reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p));
-}
-
-// x + (x of lane ^ 16) and x + (x of lane ^ 32) by v_permlane16/32_swap (VALU latency instead of the LDS round trip of
-// ds_bpermute).  v_permlane16_swap exchanges the odd 16-lane rows of its first operand with the even rows of the second,
-// v_permlane32_swap the upper half of the first with the lower half of the second: given the same value in both, the two results
-// add up to the pair sum in every lane.  Inline asm: through __builtin_amdgcn_permlane16_swap hipcc (ROCm 7.2) added result 0 to
-// itself here (v_add v, r0, r0: wrong sums).  s_nop 1 = the two wait states between a VALU write of an operand and the swap.
-__device__ __forceinline__ float sum_xor16(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float sum_xor32(float x) {
-  float a = x, b = x;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
 }
 
 struct WsParams {

@@ -16,6 +16,7 @@
 //            coalesced loads, no cross-lane reductions), all weight loads of the chain issued before the first dependent stage.
 // Exact fp32 FMA chains throughout (no operand split).
 #include "common.h"
+#include "lanes.h"
 
 namespace {
 
@@ -52,25 +53,6 @@ struct T0Params {
   int special_last;                // 0: the special token is row 0 (the reference's order); 1: it is row num_ims[b] (paths_importance_qkv_x6's order)
 };
 
-// sum over the 16 lanes of a row (DPP: two quad permutes, two mirrors), over 32 (+ v_permlane16_swap) and over 64 lanes
-// (+ v_permlane32_swap); every lane ends up with the total.  No LDS round trips (ds_bpermute) in the dependent chains.
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));  // row_mirror
-  return v;
-}
-__device__ __forceinline__ float half_sum32(float v) {
-  float a = row_sum16(v), b = a;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));      // (inline asm: see tlayer_ws.hip sum_xor16)
-  return a + b;
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-  float a = half_sum32(v), b = a;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
 // partial records are written by OTHER workgroups of this launch: read them on the vector path with agent-scope (sc1) loads - a
 // wave-uniform address would otherwise become an s_load through the scalar cache, which the acquire fence does not invalidate
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -343,7 +325,6 @@ struct T0G {
 };
 static_assert(T0G<128>::OFF_OB == OFF_OB && T0G<128>::IMG_FLOATS == IMG_FLOATS && T0G<128>::REC == REC && T0G<128>::NT == NT, "one image layout at 128");
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // FPL consecutive floats of a row (FPL = 4: one 16-byte load; 6: three 8-byte loads) through a GLOBAL address-space pointer
 template <int FPL>
 __device__ __forceinline__ void ld_feats(const float* p, float (&x)[FPL]) {
