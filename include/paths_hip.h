@@ -556,6 +556,29 @@ int paths_expand_children(const int* keep_idx, int64_t ldk, const int* keep_coun
                           int64_t n_next, int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row,
                           int* src_cell, int* status, int* child_pos, int* hp_row, paths_stream_t stream);
 
+/* paths_expand_children split around the caller, for slides whose next-level features are encoded on demand (no tissue mask of the next
+ * grid exists: whether a cell is tissue is known only once the caller has supplied its row; reference RawSlide.recurse,
+ * data_utils/slide.py:173-198).  One workgroup per slide each.
+ *
+ * paths_candidate_children - the first half: the four children of every kept patch in the block order of slide.py:305-315
+ *   ((2x,2y) | (2x,2y+1) | (2x+1,2y) | (2x+1,2y+1), each block in top-K order), those inside the next grid (next_x / next_y [B]),
+ *   compacted stably.  cand_count [B]; cand_cells [B, 4*ldk, 2]: int64 CELL coordinates (the cells to encode); cand_slot [B, 4*ldk]:
+ *   the kept slot i of the parent.  Entries at and beyond cand_count[b] are -1 in both tables.
+ * paths_admit_children - the second half: cand_mask [B, 4*ldk] (1 = the row supplied for that candidate has fp32 sum != 0, i.e.
+ *   paths_tissue_mask_absmax[_h16] over the candidate rows as a grid of B * 4*ldk cells) selects the admitted candidates, compacted
+ *   stably; num_out, locs_out (pixel coordinates), parent_out, src_row (= keep_idx[b, slot]), hp_row (= b*ldk + slot, optional),
+ *   child_pos (optional, indexed like paths_expand_children's) and the zeroed padding tail are what paths_expand_children writes;
+ *   src_cell is the candidate's index in the slide's candidate rows (grid_ptrs[b] of paths_gather_rows* = the address of slide b's
+ *   first candidate row).  A candidate whose slot is not in [0, keep_count[b]) is never admitted.  status bit0: a slide without an
+ *   admitted child, bit1: n_next exceeded (that slide then writes num_out[b] only). */
+int paths_candidate_children(const int* keep_idx, int64_t ldk, const int* keep_count, const int64_t* locs, int64_t n_cur,
+                             int patch_size, const int* next_x, const int* next_y, int B, int* cand_count, int64_t* cand_cells,
+                             int* cand_slot, paths_stream_t stream);
+int paths_admit_children(const int* cand_count, const int64_t* cand_cells, const int* cand_slot, const uint8_t* cand_mask,
+                         const int* keep_idx, int64_t ldk, const int* keep_count, int patch_size, int B, int64_t n_next,
+                         int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row, int* src_cell, int* status,
+                         int* child_pos, int* hp_row, paths_stream_t stream);
+
 /* Rare fallback of reference data_utils/slide.py:336-352 for slides with num_out[b] == 0 after paths_expand_children:
  * continue with every tissue cell of the next grid (every cell if it has no tissue), zero patch context (src_row = -1),
  * parent_inds = cell index.  Other slides are untouched.  status bit1 set if n_next is too small. */

@@ -252,6 +252,178 @@ expand_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The expansion split around the caller (on-demand slides, paths_amd/data_utils/slide.py:OnDemandSlide; reference RawSlide.recurse,
+// data_utils/slide.py:173-198): such a slide has no tissue mask of the next grid - whether a cell is tissue is known only once the
+// caller has encoded it.  candidate_kernel is expand_kernel's first half (children, bounds, stable compaction: the cells the caller
+// is asked for), admit_kernel its second half (tissue filter over the rows the caller supplied, stable compaction, the bookkeeping
+// expand_kernel writes).  Both: one workgroup per slide and expand_kernel's scan (shuffles inside a wave, wave totals through LDS).
+// ------------------------------------------------------------------------------------------------
+// exclusive prefix of `mine` over the workgroup's threads; total = the sum over all of them.  part: 2 * EXP_NW ints of LDS
+__device__ __forceinline__ int exp_scan(int mine, int* part, int tid, int& total) {
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if ((tid & 63) >= off) incl += v;
+  }
+  if ((tid & 63) == 63) part[tid >> 6] = incl;
+  __syncthreads();
+  if (tid < EXP_NW) {
+    int t = part[tid];
+#pragma unroll
+    for (int off = 1; off < EXP_NW; off <<= 1) {
+      const int v = __shfl_up(t, off);
+      if (tid >= off) t += v;
+    }
+    part[EXP_NW + tid] = t;                             // inclusive totals of waves 0 .. tid
+  }
+  __syncthreads();
+  total = part[2 * EXP_NW - 1];
+  return incl - mine + ((tid >> 6) ? part[EXP_NW + (tid >> 6) - 1] : 0);
+}
+
+__global__ void __launch_bounds__(EXP_NT)
+candidate_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restrict__ keep_count,
+                 const int64_t* __restrict__ locs, int64_t n_cur, int patch_size,
+                 const int* __restrict__ next_x, const int* __restrict__ next_y,
+                 int* __restrict__ cand_count, int64_t* __restrict__ cand_cells /*[B, 4*ldk, 2]*/, int* __restrict__ cand_slot /*[B, 4*ldk]*/) {
+  __shared__ int part[2 * EXP_NW];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int count = max(0, min(keep_count[b], (int)ldk));      // (the tables hold 4 * ldk entries per slide)
+  const int total = 4 * count;
+  const int X = next_x[b], Y = next_y[b];
+  const int per = (total + EXP_NT - 1) / EXP_NT;
+  const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
+
+  // cell of candidate c = blk * count + i (block order of slide.py:305-315) and whether it lies inside the next grid
+  auto cell = [&](int64_t lx, int64_t ly, int blk, int64_t& x, int64_t& y) -> bool {
+    const bool small = (uint64_t)(lx | ly) < 0x80000000ull;       // (the 32-bit division is only the fast path)
+    const int64_t px = small ? (int64_t)((int)lx / patch_size) : lx / patch_size;
+    const int64_t py = small ? (int64_t)((int)ly / patch_size) : ly / patch_size;
+    x = 2 * px + (blk >> 1); y = 2 * py + (blk & 1);
+    return x >= 0 && y >= 0 && x < X && y < Y;
+  };
+  auto child = [&](int c, int64_t& x, int64_t& y, int& i) -> bool {
+    const int blk = c / count;
+    i = c - blk * count;
+    const int prow = keep_idx[(int64_t)b * ldk + i];
+    return cell(locs[((int64_t)b * n_cur + prow) * 2], locs[((int64_t)b * n_cur + prow) * 2 + 1], blk, x, y);
+  };
+
+  // as in expand_kernel: the first candidates of a thread are evaluated once, their load chains side by side, and kept for the write pass
+  constexpr int CACHE = 4;
+  int64_t ccx[CACHE], ccy[CACHE];
+  int cci[CACHE];
+  bool ckeep[CACHE];
+  int mine = 0;
+  {
+    int blk[CACHE], prow[CACHE];
+    bool on[CACHE];
+    int64_t lx[CACHE], ly[CACHE];
+#pragma unroll
+    for (int u = 0; u < CACHE; ++u) {
+      on[u] = c0 + u < c1;
+      const int c = on[u] ? c0 + u : 0;
+      blk[u] = count > 0 ? c / count : 0;
+      cci[u] = c - blk[u] * count;
+      prow[u] = on[u] ? keep_idx[(int64_t)b * ldk + cci[u]] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < CACHE; ++u) {
+      lx[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2] : 0;
+      ly[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2 + 1] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < CACHE; ++u) {
+      ckeep[u] = cell(lx[u], ly[u], blk[u], ccx[u], ccy[u]) && on[u];
+      mine += ckeep[u] ? 1 : 0;
+    }
+  }
+  for (int c = c0 + CACHE; c < c1; ++c) { int64_t x, y; int i; mine += child(c, x, y, i) ? 1 : 0; }
+  int n_cand;
+  int pos = exp_scan(mine, part, tid, n_cand);
+  if (tid == 0) cand_count[b] = n_cand;
+  const int64_t row = (int64_t)b * 4 * ldk;
+  for (int c = c0; c < c1; ++c) {
+    int64_t x = 0, y = 0;
+    int i = 0;
+    bool keepc;
+    const int u = c - c0;
+    if (u < CACHE) {
+      keepc = false;
+#pragma unroll
+      for (int v = 0; v < CACHE; ++v)
+        if (v == u) { keepc = ckeep[v]; x = ccx[v]; y = ccy[v]; i = cci[v]; }
+    } else {
+      keepc = child(c, x, y, i);
+    }
+    if (keepc) {
+      cand_cells[2 * (row + pos)] = x;
+      cand_cells[2 * (row + pos) + 1] = y;
+      cand_slot[row + pos] = i;
+      ++pos;
+    }
+  }
+  // padding: no cell, no slot
+  for (int64_t j = n_cand + tid; j < 4 * ldk; j += EXP_NT) {
+    cand_cells[2 * (row + j)] = -1; cand_cells[2 * (row + j) + 1] = -1; cand_slot[row + j] = -1;
+  }
+}
+
+__global__ void __launch_bounds__(EXP_NT)
+admit_kernel(const int* __restrict__ cand_count, const int64_t* __restrict__ cand_cells, const int* __restrict__ cand_slot,
+             const uint8_t* __restrict__ cand_mask /*[B, 4*ldk]: 1 = the supplied row is tissue*/,
+             const int* __restrict__ keep_idx, int64_t ldk, const int* __restrict__ keep_count, int patch_size, int64_t n_next,
+             int64_t* __restrict__ num_out, int64_t* __restrict__ locs_out, int64_t* __restrict__ parent_out,
+             int* __restrict__ src_row, int* __restrict__ src_cell, int* __restrict__ status,
+             int* __restrict__ child_pos /*[B, 4*ldk] or null*/, int* __restrict__ hp_row /*[B, n_next] or null*/) {
+  __shared__ int part[2 * EXP_NW];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int64_t row = (int64_t)b * 4 * ldk;
+  const int n_cand = (int)max((int64_t)0, min((int64_t)cand_count[b], 4 * ldk));
+  const int per = (n_cand + EXP_NT - 1) / EXP_NT;
+  const int j0 = min(tid * per, n_cand), j1 = min(j0 + per, n_cand);
+  const int count = max(0, min(keep_count[b], (int)ldk));
+  // admitted: tissue, and the slot names a kept parent (a table that does not can make nothing below write out of bounds)
+  auto admitted = [&](int j) { return cand_mask[row + j] != 0 && (unsigned)cand_slot[row + j] < (unsigned)count; };
+  int mine = 0;
+  for (int j = j0; j < j1; ++j) mine += admitted(j) ? 1 : 0;
+  int n_out;
+  int pos = exp_scan(mine, part, tid, n_out);
+  if (tid == 0) {
+    num_out[b] = n_out;
+    if (n_out == 0) atomicOr(status, 1);               // no tissue among the children (the reference would take every cell, slide.py:336-352)
+    if (n_out > n_next) atomicOr(status, 2);
+  }
+  if (n_out > n_next) return;
+  if (child_pos) {
+    // expand_kernel's table is indexed by the candidate BEFORE the bounds filter, c = blk * count + slot: every entry starts as
+    // "dropped", the admitted ones are written behind the barrier (blk is the parity of the cell)
+    for (int c = tid; c < 4 * count; c += EXP_NT) child_pos[row + c] = -1;
+    __syncthreads();
+  }
+  for (int j = j0; j < j1; ++j) {
+    if (!admitted(j)) continue;
+    const int64_t cx = cand_cells[2 * (row + j)], cy = cand_cells[2 * (row + j) + 1];
+    const int i = cand_slot[row + j];
+    const int64_t o = (int64_t)b * n_next + pos;
+    locs_out[2 * o] = cx * patch_size;
+    locs_out[2 * o + 1] = cy * patch_size;
+    parent_out[o] = i;
+    src_row[o] = keep_idx[(int64_t)b * ldk + i];
+    src_cell[o] = j;                                    // the row's index in the slide's candidate buffer
+    if (hp_row) hp_row[o] = (int)((int64_t)b * ldk + i);
+    if (child_pos) child_pos[row + (int)(((cx & 1) << 1) | (cy & 1)) * count + i] = pos;
+    ++pos;
+  }
+  for (int j = n_out + tid; j < n_next; j += EXP_NT) {   // padding tail, as expand_kernel
+    const int64_t o = (int64_t)b * n_next + j;
+    locs_out[2 * o] = 0; locs_out[2 * o + 1] = 0; parent_out[o] = 0; src_row[o] = -1; src_cell[o] = -1;
+    if (hp_row) hp_row[o] = -1;
+  }
+}
+
 
 // Rare fallback (reference data_utils/slide.py:336-352): a slide whose kept patches have NO tissue children
 // continues with every tissue cell of the next grid (or every cell if the grid has no tissue at all), zero patch
@@ -583,6 +755,32 @@ int paths_expand_children(const int* keep_idx, int64_t ldk, const int* keep_coun
   hipLaunchKernelGGL(expand_kernel, dim3(B), dim3(EXP_NT), 0, stream, keep_idx, ldk, keep_count, locs, n_cur, patch_size,
                      next_x, next_y, mask_ptrs, n_next, num_out, locs_out, parent_out, src_row, src_cell, status, child_pos, hp_row);
   PATHS_LAUNCH_CHECK("expand_children");
+  return PATHS_OK;
+}
+
+int paths_candidate_children(const int* keep_idx, int64_t ldk, const int* keep_count, const int64_t* locs, int64_t n_cur,
+                             int patch_size, const int* next_x, const int* next_y, int B, int* cand_count, int64_t* cand_cells,
+                             int* cand_slot, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n_cur > 0 && patch_size > 0 && ldk > 0, "candidate_children: bad shape");
+  PATHS_REQUIRE(4 * ldk <= (int64_t)1 << 30, "candidate_children: too many candidates");
+  PATHS_REQUIRE(keep_idx && keep_count && locs && next_x && next_y && cand_count && cand_cells && cand_slot, "candidate_children: null pointer");
+  hipLaunchKernelGGL(candidate_kernel, dim3(B), dim3(EXP_NT), 0, stream, keep_idx, ldk, keep_count, locs, n_cur, patch_size, next_x,
+                     next_y, cand_count, cand_cells, cand_slot);
+  PATHS_LAUNCH_CHECK("candidate_children");
+  return PATHS_OK;
+}
+
+int paths_admit_children(const int* cand_count, const int64_t* cand_cells, const int* cand_slot, const uint8_t* cand_mask,
+                         const int* keep_idx, int64_t ldk, const int* keep_count, int patch_size, int B, int64_t n_next,
+                         int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row, int* src_cell, int* status,
+                         int* child_pos, int* hp_row, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n_next > 0 && patch_size > 0 && ldk > 0, "admit_children: bad shape");
+  PATHS_REQUIRE(4 * ldk <= (int64_t)1 << 30, "admit_children: too many candidates");
+  PATHS_REQUIRE(cand_count && cand_cells && cand_slot && cand_mask && keep_idx && keep_count && num_out && locs_out && parent_out &&
+                src_row && src_cell && status, "admit_children: null pointer");
+  hipLaunchKernelGGL(admit_kernel, dim3(B), dim3(EXP_NT), 0, stream, cand_count, cand_cells, cand_slot, cand_mask, keep_idx, ldk,
+                     keep_count, patch_size, n_next, num_out, locs_out, parent_out, src_row, src_cell, status, child_pos, hp_row);
+  PATHS_LAUNCH_CHECK("admit_children");
   return PATHS_OK;
 }
 

@@ -13,10 +13,13 @@ refuses values an fp16 grid cannot hold.  bf16 is not supported.
 
 :class:`HostSlide` is the sibling for cohorts that do not fit in HBM: its grids stay in PINNED host memory, only the tissue masks
 live on the device, and the recursion fetches just the rows it selects over the host link (paths_stage_rows).
+
+:class:`OnDemandSlide` holds no grid at all: the recursion asks the caller's ``encode`` for the features of exactly the cells it is
+about to visit (reference ``RawSlide.recurse``, data_utils/slide.py:173-198).
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -320,9 +323,14 @@ class DeviceSlideBatch:
     addresses, which the device can dereference; the recursion stages the selected rows into HBM, paths_stage_rows).
     """
 
+    on_demand = False               # (OnDemandSlideBatch: the rows of a level are supplied by the caller's encoder during the pass)
+
     def __init__(self, slides):
         assert len(slides) > 0
         self.slides = list(slides)
+        if any(getattr(s, "on_demand", False) for s in self.slides):
+            raise ValueError("DeviceSlideBatch: on-demand slides (OnDemandSlide) form batches of their own (slide_batch / OnDemandSlideBatch), "
+                             "not mixed with resident or host-resident slides")
         kinds = {bool(getattr(s, "host_resident", False)) for s in self.slides}
         if len(kinds) != 1:
             raise ValueError("DeviceSlideBatch: slides of one batch are all resident (DeviceSlide) or all host-resident (HostSlide)")
@@ -386,3 +394,186 @@ class DeviceSlideBatch:
             c.gy.append(flat[off:off + 4 * B].view(torch.int32)); off += 4 * B
         c.max_dim = list(self.max_dim)
         return c
+
+
+class OnDemandSlide:
+    """A slide whose features are encoded ON DEMAND: nothing is preprocessed, the recursion asks ``encode`` for the cells it is about
+    to visit - all of level 0, then only the in-bounds children of the patches each level keeps (reference ``RawSlide.recurse``,
+    data_utils/slide.py:173-198).  At K = 2048 x 5 levels that is at most 34,816 of the pyramid's 698,368 cells per pass.
+
+    ``shapes[l]``: the (X, Y) grid size of level ``l`` (known from the slide's dimensions).  ``encode(level, cells)`` receives an int64
+    ``[n, 2]`` tensor of cell coordinates on ``device`` (n >= 1) and returns ``[n, dim]`` features on that device in ``dtype``, an
+    all-zero row meaning background (the grid contract of :class:`DeviceSlide`).  It is called with the recursion's stream current:
+    work it enqueues there (or on streams it joins into the current one before returning) is ordered before the kernels that read the
+    rows.  It is never asked for a cell outside the level's grid and never twice for the same cell within one pass; ``requested[l]``
+    holds the cells asked of level ``l`` during the last pass (None: level not reached).
+
+    WSI reading, tissue masking of pixels and the encoder are the caller's.  Inference only."""
+
+    on_demand = True
+    host_resident = False
+
+    def __init__(self, shapes: Sequence[Tuple[int, int]], encode: Callable, dim: int, device, patch_size: int = 256,
+                 dtype=torch.float32, slide_id: str = "", subtype=None):
+        self.dtype = check_grid_dtype(dtype)
+        self.shapes = [(int(x), int(y)) for x, y in shapes]
+        if len(self.shapes) < 1 or any(x < 1 or y < 1 for x, y in self.shapes):
+            raise ValueError(f"OnDemandSlide: shapes are the (X, Y) grid sizes of the levels, all positive (got {list(shapes)})")
+        if not callable(encode):
+            raise ValueError("OnDemandSlide: encode(level, cells) must be callable")
+        if int(dim) < 4 or int(dim) % 4 != 0:
+            raise ValueError(f"OnDemandSlide: the feature width must be a positive multiple of 4 (got {dim})")
+        self.encode, self._dim = encode, int(dim)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.patch_size, self.slide_id, self.subtype = patch_size, slide_id, subtype
+        self.requested: List[Optional[torch.Tensor]] = [None] * len(self.shapes)
+
+    @property
+    def num_levels(self) -> int:
+        return len(self.shapes)
+
+    def shape(self, level: int) -> Tuple[int, int]:
+        return self.shapes[level]
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    def begin_pass(self):
+        self.requested = [None] * len(self.shapes)
+
+    def request(self, level: int, cells: torch.Tensor) -> Optional[torch.Tensor]:
+        """Ask the encoder for ``cells`` (int64 [n, 2], inside the grid, no cell twice: the recursion's candidates are) of ``level``,
+        once per level and pass; checks what comes back (ValueError) and returns it.  n = 0: nothing is asked, None."""
+        if self.requested[level] is not None:
+            raise RuntimeError(f"OnDemandSlide {self.slide_id!r}: level {level} was already requested in this pass")
+        self.requested[level] = cells
+        n = int(cells.shape[0])
+        if n == 0:
+            return None
+        rows = self.encode(level, cells)
+        if not torch.is_tensor(rows) or tuple(rows.shape) != (n, self._dim):
+            got = tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__
+            raise ValueError(f"OnDemandSlide {self.slide_id!r}: encode(level {level}) must return [{n}, {self._dim}] features, got {got}")
+        if rows.dtype != self.dtype:
+            raise ValueError(f"OnDemandSlide {self.slide_id!r}: encode(level {level}) returned {rows.dtype}, the slide's dtype is {self.dtype}")
+        if rows.device != self.device:
+            raise ValueError(f"OnDemandSlide {self.slide_id!r}: encode(level {level}) returned rows on {rows.device}, the slide lives on {self.device}")
+        return rows
+
+    @staticmethod
+    def from_slide(slide) -> "OnDemandSlide":
+        """A :class:`DeviceSlide` or :class:`HostSlide` behind the on-demand interface: ``encode`` indexes its grids (a preprocessed
+        cohort replayed through this path; the twin of the tests and of tools/on_demand_time.py)."""
+        dev = slide.device if slide.host_resident else slide.grids[0].device
+
+        def encode(level, cells):
+            g = slide.grids[level]
+            c = cells.to(g.device)
+            return g[c[:, 0], c[:, 1]].to(dev)
+
+        s = OnDemandSlide([slide.shape(l) for l in range(slide.num_levels)], encode, slide.dim, dev, patch_size=slide.patch_size,
+                          dtype=slide.dtype, slide_id=slide.slide_id, subtype=slide.subtype)
+        if hasattr(slide, "synthetic_spec"):
+            s.synthetic_spec = slide.synthetic_spec
+        return s
+
+
+class OnDemandSlideBatch:
+    """The batch type of :class:`OnDemandSlide`, beside :class:`DeviceSlideBatch`: the static per-level tables come from the shapes
+    (``gx`` / ``gy`` / ``max_dim`` / ``n0`` / ``dim`` / ``dtype``); what a resident batch knows up front and this one cannot - the rows'
+    addresses (``grid_ptrs[l]``: per slide, the first of the rows supplied for level ``l``) and max|x| (``feat_absmax``, of the rows
+    supplied so far) - is per-pass state, filled by :meth:`supply` as the recursion goes (paths_amd/utils.py)."""
+
+    on_demand = True
+    host_resident = False
+
+    def __init__(self, slides):
+        assert len(slides) > 0
+        self.slides = list(slides)
+        if not all(getattr(s, "on_demand", False) for s in self.slides):
+            raise ValueError("OnDemandSlideBatch: slides of one batch are all on-demand (OnDemandSlide); resident and host-resident "
+                             "slides go into a DeviceSlideBatch")
+        dev = self.slides[0].device
+        if dev.type != "cuda":
+            raise _lib.PathsHipError("paths_amd runs on the GPU only: the slides of a batch live on a GPU device (no CPU fallback)")
+        if any(s.device != dev for s in self.slides):
+            raise ValueError("OnDemandSlideBatch: slides of one batch live on one device")
+        L = min(s.num_levels for s in self.slides)
+        self.device, self.num_levels = dev, L
+        self.dim = self.slides[0].dim
+        if any(s.dim != self.dim for s in self.slides):
+            raise ValueError("OnDemandSlideBatch: slides of one batch share the feature width")
+        self.dtype = self.slides[0].dtype
+        if any(s.dtype != self.dtype for s in self.slides):
+            raise ValueError("OnDemandSlideBatch: slides of one batch must share the feature dtype (got "
+                             + ", ".join(sorted({str(s.dtype) for s in self.slides})) + ")")
+
+        def table(k):
+            return [torch.tensor([s.shape(l)[k] for s in self.slides], device=dev, dtype=torch.int32) for l in range(L)]
+
+        self.gx, self.gy = table(0), table(1)
+        self.n0 = max(s.shape(0)[0] * s.shape(0)[1] for s in self.slides)
+        self.max_dim = [max(max(s.shape(l)) for s in self.slides) for l in range(L)]
+        # level 0 asks for every cell, row-major (reference data_utils/slide.py:257-269): the request tensors are built once
+        self.cells0 = [torch.cartesian_prod(torch.arange(s.shape(0)[0], device=dev), torch.arange(s.shape(0)[1], device=dev)).reshape(-1, 2)
+                       for s in self.slides]
+        self._host = torch.empty((len(self.slides) + 1,), dtype=torch.int64).pin_memory()      # one read-back per level: num_out | max|x| bits
+        self.begin_pass()
+
+    def __len__(self):
+        return len(self.slides)
+
+    def begin_pass(self):
+        for s in self.slides:
+            s.begin_pass()
+        self.grid_ptrs: List[Optional[torch.Tensor]] = [None] * self.num_levels
+        self.feat_absmax = 0.0
+        self.absmax_bits = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.supplied: List[torch.Tensor] = []        # the rows of every level: read in place until the pass's streams have joined
+
+    def end_pass(self):
+        self.supplied = []
+
+    def supply(self, level: int, cells: Sequence[torch.Tensor], cap: int) -> torch.Tensor:
+        """Ask slide b for ``cells[b]`` of ``level`` and put what it returns into rows [b, 0:n_b] of one ``[B, cap, D]`` buffer (the
+        rest zero); ``grid_ptrs[level]`` then holds the address of every slide's first row.  Everything is enqueued on the current
+        stream: the encoder's work is ordered before whatever the caller launches there next."""
+        B, D = len(self.slides), self.dim
+        buf = torch.empty((B, cap, D), dtype=self.dtype, device=self.device)
+        for b, s in enumerate(self.slides):
+            n = int(cells[b].shape[0])
+            assert n <= cap
+            rows = s.request(level, cells[b])
+            if rows is not None:
+                buf[b, :n].copy_(rows)
+            if n < cap:
+                buf[b, n:].zero_()
+        self.supplied.append(buf)
+        # (base + b * slide stride, computed on the device: torch.tensor(list) would be a blocking upload)
+        self.grid_ptrs[level] = torch.arange(B, device=self.device, dtype=torch.int64) * (cap * D * buf.element_size()) + buf.data_ptr()
+        return buf
+
+    def read_back(self, num_out: Optional[torch.Tensor]) -> List[int]:
+        """ONE host synchronisation with the current stream: max|x| of the rows supplied so far goes into ``feat_absmax`` (inf for an
+        inf or NaN anywhere) and ``num_out`` [B] (optional) is returned as a list."""
+        B = len(self.slides)
+        if num_out is not None:
+            self._host[:B].copy_(num_out, non_blocking=True)
+        self._host[B:].copy_(self.absmax_bits, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        self.feat_absmax = _lib.float_from_bits(int(self._host[B]))
+        return self._host[:B].tolist() if num_out is not None else []
+
+
+def slide_batch(slides):
+    """The batch of a list of slides: an :class:`OnDemandSlideBatch` for :class:`OnDemandSlide`s, else a :class:`DeviceSlideBatch`
+    (which refuses a mix); a batch passes through."""
+    if isinstance(slides, (DeviceSlideBatch, OnDemandSlideBatch)):
+        return slides
+    slides = list(slides)
+    if slides and all(getattr(s, "on_demand", False) for s in slides):
+        return OnDemandSlideBatch(slides)
+    return DeviceSlideBatch(slides)

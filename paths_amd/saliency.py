@@ -90,12 +90,11 @@ def input_gradients(model, slides, keep_patches: Sequence[int], num_levels: int,
     Dropout is off for the call (the model is switched to eval and its mode restored); no parameter's ``.grad`` is created or
     changed.  A slide whose kept patches have no tissue children repeats the pass on the careful path, as training does."""
     from . import utils as putils
-    from .data_utils.slide import DeviceSlideBatch
     if not model.use_lstm:
         raise NotImplementedError("input_gradients: feature gradients are not implemented for the lstm=false variant "
                                   "(selection_backward_nolstm)")
     fn = parse_target(target)
-    batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+    batch = putils._stored_batch(slides, "input_gradients")
     was_training = model.training
     model.eval()
     try:

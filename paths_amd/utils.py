@@ -14,11 +14,12 @@ from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import contextlib
+import math
 import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide
+from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide, slide_batch
 
 OVERLAP_AGGREGATOR = os.environ.get("PATHS_OVERLAP_AGGREGATOR", "1") != "0"
 ROCTX_RANGES = os.environ.get("PATHS_ROCTX", "0") != "0"     # roctx ranges "level i: selection / aggregator / expansion" around the launches
@@ -98,6 +99,15 @@ def _checked(rec, out) -> Dict[str, torch.Tensor]:
     return out
 
 
+def _stored_batch(slides, what: str) -> DeviceSlideBatch:
+    """The batch of an entry point that needs every level's rows BEFORE its first launch (recorded or captured launch sequences,
+    training): resident or host-resident slides.  On-demand slides raise - their rows come from a host callback between the levels."""
+    if getattr(slides, "on_demand", False) or (not isinstance(slides, DeviceSlideBatch) and any(getattr(s, "on_demand", False) for s in slides)):
+        raise NotImplementedError(f"{what}: on-demand slides (OnDemandSlide) are served by recurse() / inference_end2end() only - "
+                                  "their rows are supplied by a host callback between the levels")
+    return slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+
+
 class GraphedRecursion:
     """One batch's whole recursion (all levels, all three streams) captured ONCE into a HIP graph and replayed per step.
 
@@ -115,7 +125,7 @@ class GraphedRecursion:
 
     def __init__(self, model, slides, keep_patches: Sequence[int], num_levels: int):
         self.model, self.keep, self.levels = model, list(keep_patches), int(num_levels)
-        self.batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+        self.batch = _stored_batch(slides, "GraphedRecursion")
         if self.batch.host_resident:
             raise NotImplementedError("GraphedRecursion: host-resident slides (HostSlide) are not captured into a HIP graph; use "
                                       "TapedRecursion / PipelinedRecursion or recurse()")
@@ -162,7 +172,7 @@ class TapedRecursion:
 
     def __init__(self, model, slides, keep_patches: Sequence[int], num_levels: int, lane: int = 0):
         self.model, self.keep, self.levels, self.lane = model, list(keep_patches), int(num_levels), int(lane)
-        self.batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+        self.batch = _stored_batch(slides, "TapedRecursion")
         self.tape, self.out, self.versions, self.stream_handle = None, None, None, None
         self._unjoined = False               # a replay(join=False) whose streams the caller stream has not waited for yet
         self._rec_batch = None               # private copy of the recorded batch's table TENSORS: what the tape addresses (rebind() re-points them)
@@ -229,7 +239,7 @@ class TapedRecursion:
         with the same slide count, feature width and level count whose level-0 cell count, grid extents and operand range fit the
         recorded ones is bound by copying its tables into those tensors (a few hundred bytes per level, device to device, enqueued
         on the current stream: no host sync).  Anything else drops the tape; the next replay records for the new batch."""
-        new = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+        new = _stored_batch(slides, "TapedRecursion.rebind")
         rec = self._rec_batch
         if new.dtype != self.batch.dtype:           # (the launches differ by grid dtype: a tape never serves both)
             raise ValueError(f"rebind: the tape serves {self.batch.dtype} grids, the new batch holds {new.dtype} grids")
@@ -361,7 +371,21 @@ def _streams(dev, lane: Optional[int] = None):
 
 def _recurse(model, slides, keep_patches: Sequence[int], num_levels: int,
              trace: Optional[list] = None, careful: bool = False, attention: bool = False, rollout: bool = False) -> Dict[str, torch.Tensor]:
-    batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+    batch = slide_batch(slides)
+    if batch.on_demand:
+        # max|x| is only known as the rows arrive: every level whose rows raise it enters a range_guard of its own on this stack
+        # (_note_range), all left when the pass ends
+        with contextlib.ExitStack() as guards:
+            batch.begin_pass()
+            batch.guards = guards
+            guards.callback(batch.end_pass)
+            try:
+                return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout)
+            except BaseException:
+                # (a refused slide, a bad encode() result, inf / NaN rows: the pass's streams have not been joined - nothing of it
+                # is in flight any more when its buffers are dropped and the error leaves)
+                torch.cuda.synchronize(batch.device)
+                raise
     with ops.range_guard(batch.feat_absmax):       # out-of-range features run on the exact bf16 split (no fp16 overflow)
         return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout)
 
@@ -414,8 +438,10 @@ def _expand_children(batch, nxt: int, patch_size: int, keep_idx, keep_count, loc
     B, cap_keep, p = len(batch), keep_idx.shape[1], _lib.ptr
     i32 = dict(device=batch.device, dtype=torch.int32)
     i64 = dict(device=batch.device, dtype=torch.int64)
-    gx, gy, masks = p(batch.gx[nxt]), p(batch.gy[nxt]), p(batch.mask_ptrs[nxt])
     child_pos = torch.empty((B, 4 * cap_keep), **i32) if want_child_pos else None
+    if batch.on_demand:
+        return (Nn, *_expand_on_demand(batch, nxt, patch_size, keep_idx, keep_count, locs, N, Nn, status, stream, child_pos, want_hp_row))
+    gx, gy, masks = p(batch.gx[nxt]), p(batch.gy[nxt]), p(batch.mask_ptrs[nxt])
 
     def expand(cap):
         bufs = (torch.empty((B,), **i64), torch.empty((B, cap, 2), **i64), torch.empty((B, cap), **i64),
@@ -440,6 +466,59 @@ def _expand_children(batch, nxt: int, patch_size: int, keep_idx, keep_count, loc
     return (Nn, *bufs[:5], child_pos, bufs[5])
 
 
+def _mask_supplied(batch, buf, want_mask: bool, stream: int):
+    """The resident slides' mask pass over rows an on-demand batch was just supplied with (``buf`` [B, cap, D], a grid of B * cap
+    cells): max|x| accumulates into the batch's running maximum; returns the tissue mask [B, cap] (``want_mask``).  The same kernel
+    as DeviceSlide's, so the tissue predicate sums in the same order."""
+    B, cap, D = buf.shape
+    mask = torch.empty((B, cap), device=batch.device, dtype=torch.uint8) if want_mask else None
+    _lib.call("paths_tissue_mask_absmax_h16" if batch.dtype == torch.float16 else "paths_tissue_mask_absmax", buf.data_ptr(), B * cap, D,
+              _lib.ptr(mask), batch.absmax_bits.data_ptr(), stream)
+    return mask
+
+
+def _note_range(batch, amax_before: float):
+    """On-demand batch, after a read-back: the range contract for the rows supplied so far.  A level whose rows raised max|x| enters
+    its own ops.range_guard (out of the fp16-split range: the rest of the pass runs on the three-plane kernels; inf / NaN raises)."""
+    if batch.feat_absmax > amax_before:
+        batch.guards.enter_context(ops.range_guard(batch.feat_absmax))
+
+
+def _expand_on_demand(batch, nxt: int, patch_size: int, keep_idx, keep_count, locs, N: int, Nn: int, status, stream: int, child_pos,
+                      want_hp_row: bool):
+    """_expand_children for on-demand slides: the expansion split around the caller's encoder.  candidates -> one host
+    read of their counts -> ``encode`` per slide into one [B, 4 cap_keep, D] buffer -> mask + max|x| -> admit -> one host read of the
+    admitted counts and max|x|.  Everything runs on ``stream``, which is torch's current stream: the first read waits for the candidate
+    kernel, the encoder's writes precede the mask launch, and the rows stay alive in ``batch.supplied`` until the pass has joined its
+    streams.  Returns _expand_children's tuple without its first entry."""
+    assert stream == _lib.stream(), "the on-demand expansion synchronises with torch's current stream"
+    B, cap_keep, p = len(batch), keep_idx.shape[1], _lib.ptr
+    i32 = dict(device=batch.device, dtype=torch.int32)
+    i64 = dict(device=batch.device, dtype=torch.int64)
+    Nc = 4 * cap_keep
+    cand_count, cand_cells, cand_slot = torch.empty((B,), **i32), torch.empty((B, Nc, 2), **i64), torch.empty((B, Nc), **i32)
+    ops.timed("candidates", lambda: _lib.call("paths_candidate_children", p(keep_idx), cap_keep, p(keep_count), p(locs), N, patch_size,
+                                              p(batch.gx[nxt]), p(batch.gy[nxt]), B, p(cand_count), p(cand_cells), p(cand_slot), stream))
+    counts = cand_count.cpu().tolist()                    # the host read: waits for the current stream, i.e. for the candidate kernel
+    buf = batch.supply(nxt, [cand_cells[b, :counts[b]] for b in range(B)], Nc)
+    mask = _mask_supplied(batch, buf, True, stream)
+    bufs = (torch.empty((B,), **i64), torch.empty((B, Nn, 2), **i64), torch.empty((B, Nn), **i64),
+            torch.empty((B, Nn), **i32), torch.empty((B, Nn), **i32), torch.empty((B, Nn), **i32) if want_hp_row else None)
+    ops.timed("admit", lambda: _lib.call("paths_admit_children", p(cand_count), p(cand_cells), p(cand_slot), p(mask), p(keep_idx), cap_keep,
+                                         p(keep_count), patch_size, B, Nn, *(p(t) for t in bufs[:5]), p(status), p(child_pos), p(bufs[5]), stream))
+    before = batch.feat_absmax
+    num_out = batch.read_back(bufs[0])
+    empty = [b for b in range(B) if num_out[b] == 0]
+    if empty:
+        names = ", ".join(repr(batch.slides[b].slide_id or f"#{b}") for b in empty)
+        raise _lib.PathsHipError(
+            f"on-demand slide {names}: none of the {[counts[b] for b in empty]} cells requested at level {nxt} is tissue.  The reference "
+            "would continue with every cell of that level's grid (data_utils/slide.py:336-352), i.e. encode the whole grid - what "
+            "on-demand slides exist to avoid; preprocess such a slide (DeviceSlide / HostSlide) or keep more patches")
+    _note_range(batch, before)
+    return (*bufs[:5], child_pos, bufs[5])
+
+
 def _stage_rows(batch, rows, n: int, zero_row, stream: int):
     """Host-resident slides whose rows are read in place: pull the rows the address table ``rows`` [B,n] names over the host link into a
     compact HBM buffer and point the table at the copies.  Returns the buffer (alive for as long as a level reads through the table)."""
@@ -447,6 +526,13 @@ def _stage_rows(batch, rows, n: int, zero_row, stream: int):
     p = _lib.ptr
     ops.timed("stage", lambda: _lib.call("paths_stage_rows", p(rows), len(batch) * n, batch.dim * buf.element_size(), p(buf), p(zero_row), stream))
     return buf
+
+
+def _rows_in_place(r) -> bool:
+    """Whether the current GEMM mode reads feature rows where they live (row-pointer operands) instead of gathered fp32 copies."""
+    mc, D, Dp = r.mc, r.D, r.Dp
+    return bool(r.share_parent and ops.use_x6(D, Dp - D) and ops.split_planes() == 2 and ROWS_IN_PLACE
+                and (ops.fast_path(mc) or (ops.GENERIC_ADD and ops.GENERIC_SPLIT and D % 128 == 0)))
 
 
 def _level0(r) -> SimpleNamespace:
@@ -513,6 +599,8 @@ def _child_step(r, i: int, lv, out, keep: int):
         Nn, num_next, locs_next, parent_next, src_row, src_cell, _, hp_row = _expand_children(
             batch, i + 1, r.mc.patch_size, keep_idx, keep_count, lv.locs, N, Nn, r.status, st2, r.careful, False, share_parent)
         nx.N, nx.num_ims, nx.locs, nx.parent_inds = Nn, num_next, locs_next, parent_next
+        if batch.on_demand:          # the rows just supplied may have moved the pass to the three-plane kernels (_note_range)
+            rows_in_place = r.rows_in_place = _rows_in_place(r)
         grid = p(batch.grid_ptrs[i + 1])
         if share_parent:
             # children only need their parent's c row (h enters through the per-parent partials)
@@ -563,10 +651,6 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
     h16 = batch.dtype == torch.float16
     lstm_pack = ops.pack_lstm(model.lstm) if model.use_lstm else None
     share_parent = model.use_lstm          # siblings share the parent's h: h-half of the gate GEMM once per kept parent
-    # default split mode: feature rows are read in place in the resident grids (row-pointer GEMM operands) instead of being
-    # copied (level 0) or gathered (children)
-    rows_in_place = (share_parent and ops.use_x6(D, Dp - D) and ops.split_planes() == 2 and ROWS_IN_PLACE
-                     and (ops.fast_path(mc) or (ops.GENERIC_ADD and ops.GENERIC_SPLIT and D % 128 == 0)))
     # The aggregator of level i (attention, token chain, classifier) feeds nothing of level i+1 except the slide context, so
     # it runs on a second HIP stream beside the selection chain of level i+1 (top-K, expansion, gathers, gate GEMMs).  Several
     # of those kernels cannot fill 256 CUs alone (116-232 workgroups, one per CU); the other chain's waves take the idle CUs.
@@ -578,10 +662,20 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
     # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
     r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(), sfx="_h16" if h16 else "", f32=f32,
                         i32=dict(device=dev, dtype=torch.int32), i64=dict(device=dev, dtype=torch.int64),
-                        lstm_pack=lstm_pack, share_parent=share_parent, rows_in_place=rows_in_place,
-                        zero_row=torch.zeros((D,), **f32) if rows_in_place else None, stage_host=batch.host_resident and rows_in_place,
+                        lstm_pack=lstm_pack, share_parent=share_parent,
                         careful=careful, attention=attention, rollout=rollout, overlap=overlap, main_stream=main_stream,
                         par_stream=par_stream, keepalive=keepalive, status=None)
+    if batch.on_demand:
+        # level 0 asks every slide for all of its level-0 cells (the reference keeps every level-0 cell, data_utils/slide.py:257-269);
+        # their max|x| is read before the first GEMM mode is chosen
+        _mask_supplied(batch, batch.supply(0, batch.cells0, batch.n0), False, r.st)
+        batch.read_back(None)
+        _note_range(batch, 0.0)
+    # default split mode: feature rows are read in place in the resident grids (row-pointer GEMM operands) instead of being
+    # copied (level 0) or gathered (children)
+    r.rows_in_place = rows_in_place = _rows_in_place(r)
+    r.zero_row = torch.zeros((D,), **f32) if rows_in_place else None
+    r.stage_host = batch.host_resident and rows_in_place
     lv = _level0(r)
     # importance of padded rows is 0 (reference utils.py:106-115): ONE zero fill for all levels (sizes are known up front
     # unless the careful path has to grow a level)
@@ -604,7 +698,7 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
                 (_lib.fork_behind([agg_stream], main_stream) if overlap else contextlib.nullcontext()):
             sel = ops.selection_forward(mc, lstm_pack, lvl_pack, lv.fts, lv.locs, lv.num_ims, lv.state_prev, True, parent=lv.parent,
                                         max_pos=batch.max_dim[i], x_rows=lv.x_rows, feat_dim=D, importance_out=imp_buf,
-                                        last_level=last, x_rows_h16=h16 and rows_in_place)
+                                        last_level=last, x_rows_h16=h16 and r.rows_in_place)
         if overlap:                                       # (agg_stream already waits for this level's tokens / num_ims: fork_behind above)
             keepalive.append((sel["tokens"], sel["num_ims"], sel.get("qkv_img"), sel.get("_qkv_ws")))
         with (torch.cuda.stream(agg_stream) if overlap else contextlib.nullcontext()), \
@@ -651,7 +745,7 @@ def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, c
     level's feature rows become a detached leaf that requires a gradient, the parameters enter detached (no parameter gradient is
     computed or accumulated) and the list receives one dict per level in the format of :func:`recurse`'s trace - num_ims / locs /
     parent_inds / importance / logits, keep_idx / keep_count below the last level - plus ``fts``, the leaf [B,N,D]."""
-    batch = slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
+    batch = _stored_batch(slides, "recurse_train")
     with ops.range_guard(batch.feat_absmax):
         return _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace)
 
@@ -799,10 +893,10 @@ def train_step(model, optimizer, batch, num_levels, keep_patches, task: str = "s
 
 
 def inference_end2end(num_levels, keep_patches, model, base_power, batch, task: str):
-    """reference utils.py:228-279.  ``batch["slide"]`` is a list of :class:`DeviceSlide` (or of :class:`HostSlide`); labels as in the reference
+    """reference utils.py:228-279.  ``batch["slide"]`` is a list of :class:`DeviceSlide` (or of :class:`HostSlide`, or of :class:`OnDemandSlide`); labels as in the reference
     (``survival_bin`` / ``censored`` or ``subtype``).  Returns (hazards or logits, loss)."""
-    slides = batch["slide"]
-    dev = slides.device if isinstance(slides, DeviceSlideBatch) else slides[0].masks[0].device
+    slides = slide_batch(batch["slide"])
+    dev = slides.device
     out = recurse(model, slides, keep_patches, num_levels)
     logits = out["logits"]
     if task == "survival":
