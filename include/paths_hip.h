@@ -650,6 +650,39 @@ int paths_stage_rows(int64_t* row_ptrs, int64_t rows, int row_bytes, void* stage
 int paths_saliency_rows(const float* dx, int64_t ldd, const float* x, int64_t ldx, const int64_t* num_ims, int rows_per_slide, int D,
                         int B, float* gxi, float* gnorm, paths_stream_t stream);
 
+/* Row kernels of the attributions taken along the recursion's frozen path (paths_amd/saliency.py:integrated_gradients / smooth_grad;
+ * csrc/path_rows.hip).  C chunk members of B slides form B * C virtual slides, virtual slide v = c * B + b.  x: the
+ * recorded fp32 rows [B, rows_per_slide, D] with element stride ldx between rows (a multiple of 4, >= D; 16-byte aligned base);
+ * D % 128 == 0; base: [D] fp32, 16-byte aligned, or NULL (zero); alpha, sigma, w: DEVICE tables [C] fp32; num_ims: [B].  One
+ * wavefront per recorded row, members in ascending c, fixed summation order (bit-reproducible), no workspace, no atomics.
+ *
+ * paths_path_points: out [C * B, rows_per_slide, D] (contiguous, 16-byte aligned).  For r < num_ims[b]:
+ *     t = x[b,r,d] - base[d]                               (base NULL: t = x exactly)
+ *     out[v,r,d] = fmaf(alpha[c], t, base[d])  +  sigma[c] * rms(x[b,r,:]) * z(keys[v], r * D + d)
+ * (base NULL: the first term is alpha[c] * x), rms = sqrt(sum_d x^2 / D) in the row's fixed order; rows at or beyond num_ims[b] are
+ * not read and get exact zeros.  sigma[c] == 0 skips the noise term (no hash is computed): alpha = 1, sigma = 0, base = NULL
+ * returns x bit for bit.  keys: DEVICE table [C * B] of 64-bit keys (low word key_lo, high word key_hi); may be NULL when every
+ * sigma is 0.  z is a counter-based standard normal draw on csrc/dropout.h's drop_hash, one Box-Muller pair per element pair; with
+ * e = r * D + d:
+ *     h0 = drop_hash(e & ~1, key_lo, key_hi)     h1 = drop_hash(e | 1, key_lo, key_hi)
+ *     u1 = ((h0 >> 8) + 0.5) * 2^-24             u2 = (h1 >> 8) * 2^-24             rad = sqrt(-2 ln u1)
+ *     z(even e) = rad * cos(2 pi u2)             z(odd e)  = rad * sin(2 pi u2)
+ * |z| <= 5.89.  Nothing is stored: the same (key, e) gives the same draw in any chunking.
+ *
+ * paths_path_accumulate: dx [C * B, rows_per_slide, D] fp32 with element stride ldd between rows (as ldx).  For r < num_ims[b], in
+ * ascending c:
+ *     g_c = sum_d dx[v,r,d] * (x[b,r,d] - base[d])          q_c = sum_d dx[v,r,d]^2
+ *     acc_gxi[b,r] = (init ? 0 : acc_gxi[b,r]) + w[0] g_0 + w[1] g_1 + ...      (in this order)
+ *     acc_sq[b,r]  = (init ? 0 : acc_sq[b,r])  + w[0] q_0 + w[1] q_1 + ...
+ * acc_dx [B, rows_per_slide, D] (contiguous, 16-byte aligned; may be NULL): (init ? 0 : acc_dx[b,r,:]) + w[0] dx[0 B + b,r,:] + ...
+ * With init, rows at or beyond num_ims[b] are written as exact zeros (in all three); otherwise they are not touched.  x is the
+ * un-perturbed recorded row. */
+int paths_path_points(const float* x, int64_t ldx, const float* base, const float* alpha, const float* sigma, const uint64_t* keys,
+                      const int64_t* num_ims, int rows_per_slide, int D, int B, int C, float* out, paths_stream_t stream);
+int paths_path_accumulate(const float* dx, int64_t ldd, const float* x, int64_t ldx, const float* base, const float* w,
+                          const int64_t* num_ims, int rows_per_slide, int D, int B, int C, int init, float* acc_gxi, float* acc_sq,
+                          float* acc_dx, paths_stream_t stream);
+
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */
 int paths_scale_add_rows(const float* x, const float* alpha, const float* h, const int64_t* num_ims, int rows_per_slide,

@@ -132,6 +132,8 @@ SIGNATURES = {
     "paths_synth_grid": [_vp, _i32, _i32, _i32, _u32, _i32, _u64, _vp],
     "paths_stage_rows": [_vp, _i64, _i32, _vp, _vp, _vp],
     "paths_saliency_rows": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "paths_path_points": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "paths_path_accumulate": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
 }
 # fp16 slide grids (DeviceSlide dtype torch.float16): the same arguments as the fp32 entry points above
 for _n in ("paths_lstm_cell_x6", "paths_importance_proj_x6", "paths_importance_qkv_x6", "paths_gemm_add_nt_x6", "paths_gather_rows",

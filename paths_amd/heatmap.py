@@ -18,6 +18,10 @@ from typing import Dict, List, Optional
 import numpy as np
 
 
+# per-row attributions a saliency trace may carry: input_gradients', integrated_gradients' and smooth_grad's
+SALIENCY_KINDS = ("grad_x_input", "grad_norm", "integrated_gradients", "smooth_grad_x_input", "smooth_grad_sq")
+
+
 def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.ndarray]]:
     out = []
     for lv in trace:
@@ -32,7 +36,7 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
         if "rollout" in lv:
             d["rollout"] = lv["rollout"][slide, :n].cpu().numpy()                      # [n]
             d["rollout_self"] = float(lv["rollout_self"][slide])
-        for key in ("grad_x_input", "grad_norm"):                                      # (saliency.input_gradients)
+        for key in SALIENCY_KINDS:                                  # (saliency.input_gradients / integrated_gradients / smooth_grad)
             if key in lv:
                 d[key] = lv[key][slide, :n].cpu().numpy()                              # [n]
         out.append(d)
@@ -103,16 +107,19 @@ def saliency_map(levels: List[Dict[str, np.ndarray]], base_grid, kind: str = "gr
     """One [X0 * f, Y0 * f] float map per level (f = magnification_factor**(L-1)): every patch's gradient x input (``kind``
     "grad_x_input", signed) or gradient norm ("grad_norm"), painted over the patch's footprint like :func:`rollout_map`; 0 where the
     level did not visit, no fold across levels.  ``levels`` from :func:`hierarchy_from_trace` of a
-    :func:`paths_amd.saliency.input_gradients` trace."""
-    if kind not in ("grad_x_input", "grad_norm"):
-        raise ValueError("kind must be 'grad_x_input' or 'grad_norm', got %r" % (kind,))
+    :func:`paths_amd.saliency.input_gradients` trace.  The traces of :func:`paths_amd.saliency.integrated_gradients` and
+    :func:`paths_amd.saliency.smooth_grad` also carry "integrated_gradients" (signed), "smooth_grad_x_input" (signed) and
+    "smooth_grad_sq"."""
+    if kind not in SALIENCY_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(repr(k) for k in SALIENCY_KINDS), kind))
     L = len(levels)
     f = magnification_factor ** (L - 1)
     shape = (base_grid[0] * f, base_grid[1] * f)
     maps = []
     for depth, lv in enumerate(levels):
         if kind not in lv:
-            raise KeyError("level %d carries no %s: take the trace from saliency.input_gradients" % (depth, kind))
+            raise KeyError("level %d carries no %s: take the trace from saliency.input_gradients / integrated_gradients / smooth_grad"
+                           % (depth, kind))
         raster = np.zeros(shape, dtype=np.float64)
         _paint(raster, lv["locs"], lv[kind], magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)

@@ -731,7 +731,7 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
 
 
 def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, careful: bool = False,
-                  trace: Optional[list] = None) -> Dict[str, torch.Tensor]:
+                  trace: Optional[list] = None, path: Optional[Sequence] = None, points=None) -> Dict[str, torch.Tensor]:
     """Differentiable recursion for training: same kernels as :func:`recurse`, but every level goes through
     paths_amd.autograd.LevelFn / GatherFn so that ``loss.backward()`` runs the hand-written backward kernels.
     Padded rows are zero-filled and computed (no tile skipping) so that every saved activation is finite.
@@ -744,13 +744,20 @@ def recurse_train(model, slides, keep_patches: Sequence[int], num_levels: int, c
     ``trace`` (a list) turns the pass into the one feature gradients are taken from (paths_amd/saliency.py:input_gradients): every
     level's feature rows become a detached leaf that requires a gradient, the parameters enter detached (no parameter gradient is
     computed or accumulated) and the list receives one dict per level in the format of :func:`recurse`'s trace - num_ims / locs /
-    parent_inds / importance / logits, keep_idx / keep_count below the last level - plus ``fts``, the leaf [B,N,D]."""
+    parent_inds / importance / logits, keep_idx / keep_count below the last level - plus ``fts``, the leaf [B,N,D].
+
+    ``path`` freezes the selection: per level below the last, (keep_idx [B, cap_keep] int32, keep_count [B] int32) as a
+    trace records them.  paths_topk is not launched; the recorded indices go to the child expansion, the gathers and the
+    once-per-parent form, which read nothing but them, the locations and the precomputed masks - the pass visits the recorded
+    patches whatever the feature values are.  ``points(level, fts, num_ims) -> fts'`` replaces a level's feature rows [B,N,D] (padded
+    rows zero) before they enter the level (and before they become the leaf of the ``trace`` mode).  Both None: every launch and
+    every result is what it is without them."""
     batch = _stored_batch(slides, "recurse_train")
     with ops.range_guard(batch.feat_absmax):
-        return _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace)
+        return _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace, path, points)
 
 
-def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=None):
+def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=None, path=None, points=None):
     from . import autograd as pag
     mc = model.procs[0].config
     ops.check_supported(mc, training=True)
@@ -780,6 +787,10 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
     for i in range(num_levels):
         if mc.slide_ctx_mode == "concat":          # the classifier reads every previous level's slide context (model/paths.py:134-137)
             ctx_prev = torch.stack(ctx_hist, dim=1) if ctx_hist else None
+        if points is not None:
+            new = points(i, fts, num_ims)
+            assert new.shape == fts.shape and new.dtype == fts.dtype and new.is_contiguous(), "points: [B,N,D] fp32 rows like the level's"
+            fts = new
         if trace is not None:                      # (the gathers mark their feature rows non-differentiable: a fresh leaf per level)
             fts = fts.detach().requires_grad_(True)
         logits, ctx_slide, state_out, importance = pag.level_apply(model.procs[i], model.lstm if model.use_lstm else None, fts, locs,
@@ -796,9 +807,16 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
             break
         keep = int(keep_patches[i])
         cap_keep, Nn = _child_capacity(N, keep)
-        keep_idx = torch.empty((B, cap_keep), **i32)
-        keep_count = torch.empty((B,), **i32)
-        _lib.call("paths_topk", p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
+        if path is not None:                       # the frozen path: the recorded selection instead of this pass's top-K
+            keep_idx, keep_count = path[i]
+            if not (keep_idx.shape == (B, cap_keep) and keep_count.shape == (B,) and keep_idx.dtype == keep_count.dtype == torch.int32
+                    and keep_idx.is_contiguous() and keep_idx.device == keep_count.device == dev):
+                raise ValueError(f"path[{i}]: (keep_idx [{B}, {cap_keep}] int32, keep_count [{B}] int32) on {dev} expected, got "
+                                 f"{tuple(keep_idx.shape)} {keep_idx.dtype} / {tuple(keep_count.shape)} {keep_count.dtype}")
+        else:
+            keep_idx = torch.empty((B, cap_keep), **i32)
+            keep_count = torch.empty((B,), **i32)
+            _lib.call("paths_topk", p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
         Nn, num_next, locs_next, parent_next, src_row, src_cell, child_pos, hp_row = _expand_children(
             batch, i + 1, mc.patch_size, keep_idx, keep_count, locs, N, Nn, status, st, careful, True, parent_form)
         if rec is not None:
