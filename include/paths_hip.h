@@ -683,6 +683,36 @@ int paths_path_accumulate(const float* dx, int64_t ldd, const float* x, int64_t 
                           const int64_t* num_ims, int rows_per_slide, int D, int B, int C, int init, float* acc_gxi, float* acc_sq,
                           float* acc_dx, paths_stream_t stream);
 
+/* Deletion and insertion curves along the frozen path (paths_amd/saliency.py:perturbation_curves; csrc/perturb_rows.hip).
+ *
+ * paths_rank_joint: one rank per visited patch of a slide, jointly over the chosen levels.  scores [B, n_tot] fp32 (contiguous): the
+ * capacities N_l of the L levels laid end to end; seg_end: DEVICE table [L] int32, seg_end[l] = N_0 + ... + N_l (ascending,
+ * seg_end[L-1] <= n_tot; clamped by the kernel); level_on: DEVICE table [L] int32, non-zero = the level is chosen; num_ims [L, B]
+ * int64.  Joint element j of level l (row r = j - seg_end[l-1]) is VALID iff level_on[l] != 0 and r < num_ims[l, b].  rank
+ * [B, n_tot] int32: for a valid element the number of valid elements of the same slide that precede it in the total order (score
+ * descending, joint index ascending; with ascending != 0 the score order is inverted, the index order is not), -1 otherwise; the
+ * ranks of a slide's valid elements are a permutation of 0 .. count[b] - 1.  count [B] int32: the number of valid elements.
+ * -0 orders as +0, +-inf are ordinary values, so the order is that of a stable descending (ascending) sort of the values; a NaN gets
+ * some rank (the caller excludes them).  Scores of elements that are not valid are never read.  Rank counting on the 64-bit key of
+ * paths_topk streamed through LDS in tiles of paths_rank_joint_tile() keys: n_tot is not bounded by LDS (1 <= n_tot <= 2^30,
+ * L <= 16, B <= 65535).  No atomics, no workspace; the result does not depend on the launch geometry.
+ *
+ * paths_path_mask_points: the rows of C chunk members for B slides at one level, in the layout of paths_path_points (virtual slide
+ * v = c * B + b; x [B, rows_per_slide, D] fp32 with element stride ldx between rows, a multiple of 4, >= D, 16-byte aligned base;
+ * D % 128 == 0; base [D] fp32, 16-byte aligned, or NULL; out [C * B, rows_per_slide, D] contiguous, 16-byte aligned).  rank: this
+ * level's slice of the joint rank, rank[b * ldr + r] (ldr >= rows_per_slide); thr [C, B] int32 and insert [C] int32: DEVICE tables;
+ * num_ims [B].  For r < num_ims[b] the row is KEPT iff
+ *     rank < 0                                   (the level is not perturbed), or
+ *     insert[c] == 0 and rank >= thr[c, b]       (deletion: the first thr ranks are removed), or
+ *     insert[c] != 0 and rank <  thr[c, b]       (insertion: only the first thr ranks are present);
+ * a kept row is x[b, r, :] bit for bit, a removed row is base bit for bit (exact +0 when NULL).  Rows at or beyond num_ims[b] are not
+ * read and get exact zeros.  One wavefront per recorded row, no arithmetic on the values, no workspace, no atomics. */
+int paths_rank_joint_tile(void);
+int paths_rank_joint(const float* scores, const int* seg_end, const int* level_on, const int64_t* num_ims, int L, int B, int n_tot,
+                     int ascending, int* rank, int* count, paths_stream_t stream);
+int paths_path_mask_points(const float* x, int64_t ldx, const float* base, const int* rank, int64_t ldr, const int* thr, const int* insert,
+                           const int64_t* num_ims, int rows_per_slide, int D, int B, int C, float* out, paths_stream_t stream);
+
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */
 int paths_scale_add_rows(const float* x, const float* alpha, const float* h, const int64_t* num_ims, int rows_per_slide,

@@ -108,6 +108,11 @@ __device__ __forceinline__ f32x4 ldg_f32x4(const float* p) {
   typedef const f32x4 __attribute__((address_space(1))) * gptr;
   return *reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p));
 }
+// ... and the 16-byte store through one (a plain vector store)
+__device__ __forceinline__ void stg_f32x4(float* p, f32x4 v) {
+  typedef f32x4 __attribute__((address_space(1))) * gptr;
+  *reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p)) = v;
+}
 
 // XCD-aware workgroup order (speed only): the hardware places workgroup `lin` of a launch on XCD lin % 8, each with a private L2.
 // Returns the position workgroup `lin` takes in the kernel's own tile sequence such that XCD x owns one contiguous run of it

@@ -16,11 +16,6 @@
 
 constexpr int PR_WAVES = 4;        // rows per workgroup
 
-__device__ __forceinline__ void stg_f32x4(float* p, f32x4 v) {
-  typedef f32x4 __attribute__((address_space(1))) * gptr;
-  *reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p)) = v;
-}
-
 // The Box-Muller pair of elements (e, e + 1), e even:  u1 = ((h0 >> 8) + 0.5) 2^-24 in (0, 1),  u2 = (h1 >> 8) 2^-24 in [0, 1),
 // (z0, z1) = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).  k + 0.5 has 25 significant bits for k >= 2^23: there ln u1 is taken as
 // log1p(-(1 - u1)) with 1 - u1 = ((2^24 - k) - 0.5) 2^-24 exact, so the radius keeps its relative accuracy where u1 -> 1 (a rounded

@@ -8,6 +8,7 @@
 // All of it is HBM-bound integer / copy work: rows are 4 KB (features) and 5 KB (LSTM state) and move as
 // coalesced 16-byte-per-lane copies; the per-slide bookkeeping (sort, scan) lives in LDS.
 #include "common.h"
+#include "rank_key.h"
 
 namespace {
 
@@ -41,12 +42,6 @@ __device__ __forceinline__ f32x4 load4(const T* row, int64_t i) {     // element
 // the four waves count over a quarter of the keys each (key pairs read by LDS broadcast), partial counts meet in LDS.
 // ------------------------------------------------------------------------------------------------
 constexpr int TOPK_MAX = 8192;
-
-__device__ __forceinline__ unsigned long long topk_key(float score, int idx) {
-  uint32_t u = __float_as_uint(score);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // monotone float -> uint
-  return ((unsigned long long)(~u) << 32) | (uint32_t)idx;
-}
 
 __global__ void __launch_bounds__(256)
 topk_rank_kernel(const float* __restrict__ scores, int64_t ld, const int64_t* __restrict__ num_ims, int keep,

@@ -1,4 +1,5 @@
-"""Gradient patch attributions: gradient x input, integrated gradients and SmoothGrad along the frozen path.
+"""Gradient patch attributions: gradient x input, integrated gradients and SmoothGrad along the frozen path,
+and the deletion / insertion curves that tell which per-patch map is faithful.
 
 The importance, attention and rollout exports say what the model looked at; :func:`input_gradients` says what moved the prediction:
 the gradient of a slide's score with respect to every visited patch's feature vector, reduced per patch to
@@ -17,6 +18,10 @@ recorded result (utils.recurse_train ``path``) the model is an ordinary differen
 either method visits the same patches, so their maps can be summed; the S points of one slide run as virtual slides that share the
 path, ``chunk`` at a time through the level kernels.  The points are built and the gradients folded by the two row kernels of
 csrc/path_rows.hip.  These are attributions of the function along the path taken - not of the selection itself.
+
+:func:`perturbation_curves` judges a map - any of the above, importance, attention, rollout - on the same frozen path: the visited
+patches are ranked jointly over the levels (paths_rank_joint) and removed from, or restored to, the rows in that order
+(paths_path_mask_points; both in csrc/perturb_rows.hip), one no-grad forward along the path per point.
 """
 from __future__ import annotations
 
@@ -195,16 +200,10 @@ def noise_key(seed: int, level: int, sample: int, slide: int) -> int:
     return lo | (hi << 32)
 
 
-def _along_path(model, slides, keep_patches, num_levels, fn, what, alphas, sigmas, weights, baseline, seed, chunk, want_dx, want_points,
-                want_baseline_target):
-    """The shared sequence of both methods: the path pass (today's input_gradients pass, its rows kept), its careful repeat when a
-    slide had no tissue children, then ceil(S / chunk) frozen passes of B * chunk virtual slides, each one autograd.grad of the
-    summed target with respect to the level leaves and one paths_path_accumulate per level.  Returns (out, trace, per-level
-    (acc_gxi, acc_sq, acc_dx or None), per-level points [S,B,N,D] or None)."""
-    from . import ops, utils as putils
-    from .data_utils.slide import DeviceSlideBatch
-    batch = putils._stored_batch(slides, what)
-    B, D, dev, S = len(batch), batch.dim, batch.device, len(alphas)
+def _chunk_and_base(batch, baseline, chunk):
+    """(chunk, base) of a call along the path: the members per frozen pass (default max(1, 8 // B)) and the baseline as a contiguous
+    fp32 [D] device tensor (None: zeros)."""
+    B, D = len(batch), batch.dim
     if chunk is None:
         chunk = max(1, 8 // B)
     if not isinstance(chunk, int) or chunk < 1:
@@ -213,18 +212,47 @@ def _along_path(model, slides, keep_patches, num_levels, fn, what, alphas, sigma
     if baseline is not None:
         if baseline.shape != (D,):
             raise ValueError(f"baseline must be None or a [{D}] tensor, got {tuple(baseline.shape)}")
-        base = baseline.detach().to(device=dev, dtype=torch.float32).contiguous()
+        base = baseline.detach().to(device=batch.device, dtype=torch.float32).contiguous()
+    return chunk, base
+
+
+def _path_pass(model, batch, keep_patches, num_levels, fn):
+    """The path pass (today's input_gradients pass, its rows kept) and its careful repeat when a slide had no tissue children.
+    Returns (out, trace, careful).  Gradients must be enabled."""
+    from . import utils as putils
+    careful = False
+    out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=False, keep_rows=True)
+    if putils.check_status_word(out["status"]):
+        careful = True
+        out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=True, keep_rows=True)
+        putils.check_status_word(out["status"], fallback_done=True)
+    return out, trace, careful
+
+
+def _virtual(virtual: dict, batch, path, c: int):
+    """(the batch repeated c times, the path repeated c times): c chunk members of every slide as virtual slides c' * B + b."""
+    from .data_utils.slide import DeviceSlideBatch
+    if c not in virtual:
+        virtual[c] = (batch if c == 1 else DeviceSlideBatch(list(batch.slides) * c), [(ki.repeat(c, 1), kc.repeat(c)) for ki, kc in path])
+    return virtual[c]
+
+
+def _along_path(model, slides, keep_patches, num_levels, fn, what, alphas, sigmas, weights, baseline, seed, chunk, want_dx, want_points,
+                want_baseline_target):
+    """The shared sequence of both methods: the path pass (today's input_gradients pass, its rows kept), its careful repeat when a
+    slide had no tissue children, then ceil(S / chunk) frozen passes of B * chunk virtual slides, each one autograd.grad of the
+    summed target with respect to the level leaves and one paths_path_accumulate per level.  Returns (out, trace, per-level
+    (acc_gxi, acc_sq, acc_dx or None), per-level points [S,B,N,D] or None)."""
+    from . import ops, utils as putils
+    batch = putils._stored_batch(slides, what)
+    B, D, dev, S = len(batch), batch.dim, batch.device, len(alphas)
+    chunk, base = _chunk_and_base(batch, baseline, chunk)
     was_training = model.training
     model.eval()
     guard = None
     try:
         with torch.enable_grad():
-            careful = False
-            out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=False, keep_rows=True)
-            if putils.check_status_word(out["status"]):
-                careful = True
-                out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=True, keep_rows=True)
-                putils.check_status_word(out["status"], fallback_done=True)
+            out, trace, careful = _path_pass(model, batch, keep_patches, num_levels, fn)
             xs = [rec.pop("fts").detach() for rec in trace]
             nums = [rec["num_ims"] for rec in trace]
             path = [(rec["keep_idx"], rec["keep_count"]) for rec in trace[:-1]]
@@ -244,10 +272,7 @@ def _along_path(model, slides, keep_patches, num_levels, fn, what, alphas, sigma
 
             def frozen(c, alpha, sigma, key_of, grad):
                 """One pass of B * c virtual slides along the path, their rows built by paths_path_points from alpha / sigma [c]."""
-                if c not in virtual:
-                    virtual[c] = (batch if c == 1 else DeviceSlideBatch(list(batch.slides) * c),
-                                  [(ki.repeat(c, 1), kc.repeat(c)) for ki, kc in path])
-                vb, vpath = virtual[c]
+                vb, vpath = _virtual(virtual, batch, path, c)
                 t2 = [] if grad else None
                 o = putils.recurse_train(model, vb, keep_patches, num_levels, careful=careful, trace=t2, path=vpath,
                                          points=lambda level, fts, num_ims: path_points(xs[level], base, alpha, sigma, key_of(level), nums[level]))
@@ -350,4 +375,227 @@ def smooth_grad(model, slides, keep_patches: Sequence[int], num_levels: int, tar
             rec["smooth_grad"] = adx
         if keep_points:
             rec["points"] = pts[l]
+    return out, trace
+
+
+# ------------------------------------------------------------------------------------------------
+# deletion and insertion curves along the frozen path
+# ------------------------------------------------------------------------------------------------
+MODES = ("deletion", "insertion", "both")
+
+
+def rank_joint_tile() -> int:
+    """Keys per LDS tile of paths_rank_joint (csrc/perturb_rows.hip: RJ_TILE)."""
+    return int(_lib.load().paths_rank_joint_tile())
+
+
+def rank_joint(scores: torch.Tensor, seg_end: torch.Tensor, level_on: torch.Tensor, num_ims: torch.Tensor,
+               ascending: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(rank [B, Ntot] int32, count [B] int32) of scores [B, Ntot] fp32 (the levels' capacities end to end), jointly over the chosen
+    levels (include/paths_hip.h: paths_rank_joint): seg_end / level_on [L] int32 device tables, num_ims [L, B] int64.  -1 on padded
+    rows and on levels that are not chosen; their scores are not read."""
+    _lib.require_cuda(scores, seg_end, level_on, num_ims)
+    B, Ntot = scores.shape
+    L = seg_end.numel()
+    assert scores.dtype == torch.float32 and scores.is_contiguous()
+    assert seg_end.dtype == level_on.dtype == torch.int32 and level_on.numel() == L and seg_end.is_contiguous() and level_on.is_contiguous()
+    assert num_ims.dtype == torch.int64 and num_ims.shape == (L, B) and num_ims.is_contiguous()
+    rank = torch.empty((B, Ntot), device=scores.device, dtype=torch.int32)
+    count = torch.empty((B,), device=scores.device, dtype=torch.int32)
+    p = _lib.ptr
+    _lib.call("paths_rank_joint", p(scores), p(seg_end), p(level_on), p(num_ims), L, B, Ntot, 1 if ascending else 0, p(rank), p(count),
+              _lib.stream())
+    return rank, count
+
+
+def path_mask_points(x: torch.Tensor, base: Optional[torch.Tensor], rank: torch.Tensor, thr: torch.Tensor, insert: torch.Tensor,
+                     num_ims: torch.Tensor) -> torch.Tensor:
+    """The rows of C chunk members for B slides (include/paths_hip.h: paths_path_mask_points): x [B,N,D] fp32 (rows may be strided),
+    base [D] or None, rank [B,N] int32 (a level's slice of the joint rank: the slide stride is free), thr [C,B] / insert [C] int32
+    device tables, num_ims [B] int64.  Returns [C*B, N, D], virtual slide c * B + b: a copy of the row or of the baseline, exact
+    zeros at or beyond num_ims[b]."""
+    _lib.require_cuda(x, base, rank, thr, insert, num_ims)
+    B, N, D = x.shape
+    C = insert.numel()
+    _rows_ok(x, N)
+    assert rank.dtype == torch.int32 and rank.shape == (B, N) and rank.stride(1) == 1 and (B == 1 or rank.stride(0) >= N)
+    assert thr.dtype == insert.dtype == torch.int32 and thr.shape == (C, B) and thr.is_contiguous() and insert.is_contiguous()
+    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,)
+    assert base is None or (base.shape == (D,) and base.dtype == torch.float32 and base.is_contiguous())
+    out = torch.empty((C * B, N, D), device=x.device, dtype=torch.float32)
+    p = _lib.ptr
+    _lib.call("paths_path_mask_points", p(x), x.stride(1), p(base), p(rank), rank.stride(0) if B > 1 else N, p(thr), p(insert),
+              p(num_ims.contiguous()), N, D, B, C, p(out), _lib.stream())
+    return out
+
+
+def perturbation_counts(n: Sequence[int], steps: int) -> np.ndarray:
+    """counts [steps + 1, B] int64: the patches removed (inserted) at fraction s / steps of a slide with n_b ranked patches,
+    (2 s n_b + steps) // (2 steps) - s n_b / steps rounded half up, so counts[0] = 0 and counts[steps] = n_b."""
+    s = np.arange(steps + 1, dtype=np.int64)[:, None]
+    return (2 * s * np.asarray(n, dtype=np.int64)[None, :] + steps) // (2 * steps)
+
+
+def _level_scores(scores, trace, num_levels: int, shapes, dev) -> List[torch.Tensor]:
+    """The per-level score tensors [B, N_l] (fp32, on the device) of ``scores``: the name of a trace entry or a sequence of tensors."""
+    if isinstance(scores, str):
+        missing = [l for l, rec in enumerate(trace) if scores not in rec]
+        if missing:
+            raise ValueError(f"scores {scores!r}: the trace has no such entry at level(s) {missing}; it has {sorted(trace[missing[0]])}")
+        per_level = [rec[scores] for rec in trace]
+    else:
+        per_level = list(scores)
+        if len(per_level) != num_levels:
+            raise ValueError(f"scores: one [B, N] tensor per level ({num_levels}) expected, got {len(per_level)}")
+    out = []
+    for l, (t, shape) in enumerate(zip(per_level, shapes)):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"scores{'' if not isinstance(scores, str) else ' ' + repr(scores)}: level {l} needs one value per patch, "
+                             f"[B, N] = {list(shape)}, got {got}")
+        _lib.require_cuda(t)
+        out.append(t.detach().to(device=dev, dtype=torch.float32))
+    return out
+
+
+def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: int, scores, trace: Optional[List[dict]] = None,
+                        target: Target = "risk", steps: int = 16, mode: str = "both", levels: Optional[Sequence[int]] = None,
+                        baseline: Optional[torch.Tensor] = None, descending: bool = True,
+                        chunk: Optional[int] = None) -> Tuple[Dict[str, torch.Tensor], List[dict]]:
+    """Deletion and insertion curves (Petsiuk et al. 2018; Samek et al. 2017) of ``target`` for a per-patch map, along the frozen path.
+
+    The visited patches of the chosen ``levels`` (None: all) are ranked jointly by ``scores`` (most relevant first: highest first with
+    ``descending``; ties by level, then row).  The deletion curve replaces the first counts[s] of them by ``baseline`` (None: zeros,
+    or one [D] vector) and records the target; the insertion curve starts from the baseline on all of them and restores the first
+    counts[s].  fractions[s] = s / steps, counts[s, b] = (2 s n_b + steps) // (2 steps) with n_b the slide's ranked patches.  A
+    faithful map has a small ``deletion_auc`` and a large ``insertion_auc``.  The selection is held at the recorded path: every
+    point visits the same patches, a removed row is a token with baseline features (not background), and curves of different maps
+    over the same path are comparable point by point.
+
+    ``scores``: the name of a [B, N] entry of the trace records, or a sequence of ``num_levels`` device tensors [B, N_l].  ``trace``
+    None: the call makes the :func:`input_gradients` pass itself (entries "importance", "grad_x_input", "grad_norm").  ``trace``
+    given (from recurse(..., trace=[]), the functions of this module or the model's exports): its keep_idx / keep_count are the path;
+    a no-grad pass along it must reproduce its num_ims and locs, else ValueError.  Records gain ``perturbation_rank`` [B, N] int32
+    (-1 on padded rows and levels not chosen).
+
+    Returns (out, trace): ``fractions`` [steps + 1] (float64, CPU), ``counts`` [steps + 1, B] (int64, CPU), ``deletion`` /
+    ``insertion`` [B, steps + 1] fp32 and ``deletion_auc`` / ``insertion_auc`` [B] float64 (trapezoid over fractions) as ``mode``
+    asks, ``target`` = F(X), ``target_baseline`` = F(baseline on the chosen levels), ``status``.  The end points are computed once:
+    deletion[:, 0] and insertion[:, steps] are ``target``, deletion[:, steps] and insertion[:, 0] are ``target_baseline``.  The
+    points between run as virtual slides, ``chunk`` at a time (default max(1, 8 // B)), each curve's members in chunks of their own
+    so that a curve has the same bits whichever ``mode`` asked for it.  No gradient is taken beyond the path pass; dropout is off,
+    the model's mode is restored and no ``.grad`` is touched."""
+    from . import ops, utils as putils
+    _check_model(model, "perturbation_curves")
+    fn = parse_target(target)
+    if not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    if mode not in MODES:
+        raise ValueError(f"unknown mode {mode!r}: 'deletion', 'insertion' or 'both'")
+    chosen = list(range(num_levels)) if levels is None else [int(l) for l in levels]
+    if any(not 0 <= l < num_levels for l in chosen):
+        raise ValueError(f"levels {list(levels)}: level indices must be in [0, {num_levels})")
+    if baseline is not None and not (torch.is_tensor(baseline) and baseline.dim() == 1):
+        raise ValueError("baseline must be None or a [D] tensor, got "
+                         + (str(tuple(baseline.shape)) if torch.is_tensor(baseline) else repr(type(baseline))))
+    if not isinstance(scores, str) and (torch.is_tensor(scores) or not hasattr(scores, "__len__") or len(scores) != num_levels):
+        raise ValueError(f"scores: the name of a trace entry or a sequence of {num_levels} tensors [B, N_l] expected")
+    if trace is not None and (len(trace) != num_levels or any("keep_idx" not in rec or "keep_count" not in rec for rec in trace[:-1])):
+        raise ValueError(f"trace: {num_levels} records with keep_idx / keep_count below the last level expected")
+    batch = putils._stored_batch(slides, "perturbation_curves")
+    B, dev = len(batch), batch.device
+    chunk, base = _chunk_and_base(batch, baseline, chunk)
+    want_del, want_ins = mode != "insertion", mode != "deletion"
+    was_training = model.training
+    model.eval()
+    guard = None
+    try:
+        given = trace is not None
+        if not given:
+            with torch.enable_grad():
+                out, trace, careful = _path_pass(model, batch, keep_patches, num_levels, fn)
+            xs = [rec.pop("fts").detach() for rec in trace]
+        with torch.no_grad():
+            guard = ops.range_guard(max(batch.feat_absmax, float(base.abs().max()) if base is not None else 0.0))
+            guard.__enter__()
+            path = [(rec["keep_idx"], rec["keep_count"]) for rec in trace[:-1]]
+            statuses = []
+            if given:                                          # one frozen pass without points collects the rows and F(X)
+                careful, t2 = False, []
+                o = putils.recurse_train(model, batch, keep_patches, num_levels, careful=False, trace=t2, path=path)
+                if putils.check_status_word(o["status"]):
+                    careful, t2 = True, []
+                    o = putils.recurse_train(model, batch, keep_patches, num_levels, careful=True, trace=t2, path=path)
+                    putils.check_status_word(o["status"], fallback_done=True)
+                for l, (rec, r2) in enumerate(zip(trace, t2)):
+                    same = rec["num_ims"].shape == r2["num_ims"].shape and rec["locs"].shape == r2["locs"].shape
+                    if same:                                   # (the locations of the valid rows: padding is nobody's)
+                        valid = (torch.arange(r2["locs"].shape[1], device=dev)[None, :] < r2["num_ims"][:, None])[..., None]
+                        same = torch.equal(rec["num_ims"], r2["num_ims"]) and torch.equal(rec["locs"] * valid, r2["locs"] * valid)
+                    if not same:
+                        raise ValueError(f"trace: a pass along its path does not reproduce its num_ims / locs at level {l}: it belongs to "
+                                         "other slides, keep_patches or levels")
+                xs = [r2["fts"].detach() for r2 in t2]
+                tgt = fn(o["logits"])
+                if tgt.shape != (B,):
+                    raise ValueError(f"the target must map logits [B,C] to [B]; got {tuple(tgt.shape)}")
+                out = {"logits": o["logits"].detach(), "target": tgt.detach(), "status": o["status"]}
+            nums = [rec["num_ims"] for rec in trace]
+            Ns = [int(x.shape[1]) for x in xs]
+            sc = torch.cat(_level_scores(scores, trace, num_levels, [(B, n) for n in Ns], dev), dim=1).contiguous()
+            seg = np.cumsum(Ns)
+            on = [1 if l in chosen else 0 for l in range(num_levels)]
+            seg_tab = torch.tensor(np.stack([seg, on]), device=dev, dtype=torch.int32)
+            rank, count = rank_joint(sc, seg_tab[0], seg_tab[1], torch.stack(nums), ascending=not descending)
+            # ONE host check: the valid counts and whether a valid score is NaN (its rank would mean nothing)
+            host = torch.cat([count.long(), (torch.isnan(sc) & (rank >= 0)).any(dim=1).long()]).cpu().numpy()
+            if host[B:].any():
+                raise ValueError(f"scores: NaN among the valid patches of slide(s) {np.nonzero(host[B:])[0].tolist()}")
+            ranks = [rank[:, e - n:e] for e, n in zip(seg, Ns)]
+            for rec, rk in zip(trace, ranks):
+                rec["perturbation_rank"] = rk
+            counts = perturbation_counts(host[:B], steps)
+            # ONE upload per call: the thresholds and flags of every member - [deletion s = 1 .. steps - 1 | insertion s = 1 .. steps - 1 |
+            # everything removed]; the end points are F(X) and F(baseline), shared by both curves
+            inner = counts[1:steps]
+            thr_np = np.concatenate(([inner] if want_del else []) + ([inner] if want_ins else []) + [counts[steps:]])
+            ins_np = np.concatenate(([np.zeros(steps - 1)] if want_del else []) + ([np.ones(steps - 1)] if want_ins else []) + [np.zeros(1)])
+            M = len(ins_np)
+            tab = torch.tensor(np.concatenate([thr_np.reshape(-1), ins_np]), device=dev, dtype=torch.int32)
+            thr, ins = tab[:M * B].view(M, B), tab[M * B:]
+            virtual = {}
+
+            def frozen(m0, c):
+                """Members m0 .. m0 + c - 1 as one pass of B * c virtual slides along the path.  Returns their targets [c, B]."""
+                vb, vpath = _virtual(virtual, batch, path, c)
+                o = putils.recurse_train(model, vb, keep_patches, num_levels, careful=careful, path=vpath,
+                                         points=lambda level, fts, num_ims: path_mask_points(xs[level], base, ranks[level], thr[m0:m0 + c],
+                                                                                             ins[m0:m0 + c], nums[level]))
+                statuses.append(o["status"])
+                return fn(o["logits"]).detach().view(c, B)
+
+            out["target_baseline"] = frozen(M - 1, 1)[0]
+            curves, m0 = {}, 0
+            for name in (["deletion"] if want_del else []) + (["insertion"] if want_ins else []):
+                first, last = (out["target"], out["target_baseline"]) if name == "deletion" else (out["target_baseline"], out["target"])
+                pts = [first[None]]
+                for s0 in range(0, steps - 1, chunk):
+                    c = min(chunk, steps - 1 - s0)
+                    pts.append(frozen(m0 + s0, c))
+                m0 += steps - 1
+                curves[name] = torch.cat(pts + [last[None]]).t().contiguous()
+            for st in statuses:                                # bit 0 repeats what the careful path pass already handled
+                putils.check_status_word(st, fallback_done=True)
+    finally:
+        if guard is not None:
+            guard.__exit__(None, None, None)
+        model.train(was_training)
+    frac = np.arange(steps + 1, dtype=np.float64) / steps
+    out["fractions"] = torch.from_numpy(frac)
+    out["counts"] = torch.from_numpy(counts)
+    w = torch.from_numpy(np.diff(frac)).to(dev)
+    for name, cv in curves.items():
+        out[name] = cv
+        d = cv.double()
+        out[name + "_auc"] = ((d[:, :-1] + d[:, 1:]) * 0.5 * w[None, :]).sum(dim=1)
     return out, trace

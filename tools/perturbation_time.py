@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Cost of the deletion / insertion curves along the frozen path (paths_amd.saliency.perturbation_curves, csrc/perturb_rows.hip) for
+ONE slide and for EIGHT slides at K = 2048 x 5 levels, dropout off, steps = 16, mode = "both", scores = "grad_x_input".  One JSON line
+per batch size:
+
+    curves_ms                perturbation_curves: the path pass, the joint ranking, 1 + 2 ceil(15 / chunk) frozen no-grad passes
+    forward_ms               one no-grad recurse_train forward of the same batch (the unit the expectation "close to 2 steps
+                             forwards" is stated in)
+    curves_over_forward      the ratio of the two medians
+    rank_us                  paths_rank_joint alone, event-timed on an otherwise idle device, with its joint length and valid count
+    mask_us_per_level        paths_path_mask_points of every level alone at the default chunk, event-timed, with its algorithmic bytes
+                             ((1 + C) valid rows x D x 4) and the rate they give
+
+The whole-call figures come from one process, alternating rounds (A/B/A/B, then reversed) after warm-up, a host clock around calls
+that end in a device synchronise.
+
+    python tools/perturbation_time.py [--limit 420] [--rounds 4] [--batches 1,8]
+
+The measurement runs in a fresh child process under ``timeout -k 10 <limit>``."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--limit", type=int, default=420, help="seconds for the child process")
+ap.add_argument("--child", action="store_true", help="(internal) measure in this process")
+ap.add_argument("--rounds", type=int, default=4)
+ap.add_argument("--warmup", type=int, default=1)
+ap.add_argument("--batches", default="1,8", help="batch sizes to time")
+args = ap.parse_args()
+
+if not args.child:
+    rc = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child",
+                         "--rounds", str(args.rounds), "--warmup", str(args.warmup), "--batches", args.batches]).returncode
+    if rc != 0:
+        print(f"perturbation_time: ended with status {rc}", flush=True)
+    sys.exit(rc)
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from paths_amd import _lib, utils as putils  # noqa: E402
+from paths_amd.data_utils.slide import DeviceSlide, DeviceSlideBatch  # noqa: E402
+from paths_amd.saliency import perturbation_curves  # noqa: E402
+
+K, STEPS = 2048, 16
+dev = torch.device("cuda:0")
+cfg, model, _ = bench.build_model(K, dev, 0.0)
+model.eval()
+keep, L = cfg.top_k_patches, cfg.num_levels
+ids = bench.CPU_SLIDE_IDS[K]
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+summ = lambda v: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+
+for B in [int(b) for b in args.batches.split(",")]:
+    sb = DeviceSlideBatch([DeviceSlide.synthetic(bench.CPU_DSEED, ids[i % len(ids)], bench.BASE_SHAPES[K], device=dev) for i in range(B)])
+    D = sb.dim
+
+    def forward():
+        with torch.no_grad():
+            putils.recurse_train(model, sb, keep, L)
+
+    runs = {"curves": lambda: perturbation_curves(model, sb, keep, L, "grad_x_input", steps=STEPS, mode="both"), "forward": forward}
+    for name in runs:
+        for _ in range(args.warmup):
+            runs[name]()
+    ms = {name: [] for name in runs}
+    for r in range(args.rounds):
+        for name in (tuple(runs) if r % 2 == 0 else tuple(runs)[::-1]):
+            ms[name].append(timed(runs[name]))
+
+    # --- the two kernels alone: a call whose launches of them are bracketed by events on an idle device
+    real_call, seen = _lib.call, []
+
+    def timed_call(name, *a):
+        if name not in ("paths_rank_joint", "paths_path_mask_points"):
+            return real_call(name, *a)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        stream = torch.cuda.ExternalStream(a[-1], device=dev)
+        e0.record(stream)
+        real_call(name, *a)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        # rank_joint: ..., L, B, n_tot at 4..6;  path_mask_points: ..., rows_per_slide, D, B, C at 8..11
+        seen.append((name, a[6], 0, e0.elapsed_time(e1) * 1e3) if name == "paths_rank_joint" else (name, a[8], a[11], e0.elapsed_time(e1) * 1e3))
+
+    _lib.call = timed_call
+    try:
+        out, trace = perturbation_curves(model, sb, keep, L, "grad_x_input", steps=STEPS, mode="both")
+    finally:
+        _lib.call = real_call
+    chunk = max(1, 8 // B)
+    Ns = [int(t["perturbation_rank"].shape[1]) for t in trace]
+    valid = [int(t["num_ims"].sum()) for t in trace]
+    rank_us = [u for n, _, _, u in seen if n == "paths_rank_joint"]
+    mask = []
+    for l in range(L):                                  # (levels can share a padded length: their launches are pooled)
+        us = [u for n, N, C, u in seen if n == "paths_path_mask_points" and N == Ns[l] and C == chunk]
+        if not us:
+            continue
+        med, nbytes = statistics.median(us), (1 + chunk) * valid[l] * D * 4
+        mask.append({"level": l, "rows": Ns[l], "valid": valid[l], "members": chunk, "launches": len(us), "MB": round(nbytes / 1e6, 1),
+                     "us": round(med, 1), "GB_per_s": round(nbytes / (med * 1e-6) / 1e9, 1)})
+    res = {"workload": f"{B} slide(s), K = {K} x {L} levels, fp32 grids, dropout off, steps = {STEPS}, mode = both, chunk = {chunk}",
+           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
+           "curves_ms": summ(ms["curves"]), "forward_ms": summ(ms["forward"]),
+           "curves_over_forward": round(statistics.median(ms["curves"]) / statistics.median(ms["forward"]), 2),
+           "frozen_passes_with_points": 1 + 2 * -(-(STEPS - 1) // chunk),
+           "rank_us": {"joint_length": sum(Ns), "valid": int(out["counts"][STEPS].sum()), "launches": len(rank_us), "us": round(rank_us[0], 1)},
+           "mask_us_per_level": mask,
+           "deletion_auc": [round(float(v), 5) for v in out["deletion_auc"]], "insertion_auc": [round(float(v), 5) for v in out["insertion_auc"]]}
+    print(json.dumps(res), flush=True)
+    del sb
