@@ -1,5 +1,5 @@
-// paths_rank_joint / paths_path_mask_points: the device side of the deletion and insertion curves taken along the recursion's
-// frozen path (paths_amd/saliency.py:perturbation_curves).
+// paths_rank_joint: the ranking behind the deletion and insertion curves taken along the recursion's frozen path
+// (paths_amd/saliency.py:perturbation_curves).  The rows themselves are built by paths_path_mask_points (path_rows.hip).
 //
 // rank_joint: one rank per visited patch of a slide, jointly over the chosen levels - rank_i = #{valid j of the slide : key_j <
 // key_i} on the 64-bit key of the top-K (rank_key.h; -0 read as +0, the score word inverted for `ascending`), so keys are unique and
@@ -10,18 +10,12 @@
 // the result does not depend on the launch.  Padded rows and rows of levels that are not chosen are never read as scores.
 // Per slide: n_tot^2 64-bit compares; every workgroup builds all n_tot keys once (the valid scores are read n_tot / RJ_THREADS + 1
 // times, from cache) and each of its four waves reads all of them back from LDS.  4 n_tot bytes in, 4 n_tot + 4 out, algorithmically.
-//
-// path_mask_points: the sibling of paths_path_points (path_rows.hip) with the same layout - virtual slide v = c * B + b, ONE wave
-// per recorded row (b, r) looping over the members in ascending c, 16-byte loads and stores, four rows per workgroup.  A member's
-// row is the recorded row or the baseline, chosen by the row's rank against the member's threshold: a copy, no arithmetic on the
-// values.  M D 4 bytes in (re-read per member from cache), C M D 4 bytes out.
 #include "common.h"
 #include "rank_key.h"
 
 constexpr int RJ_THREADS = 256;      // elements per workgroup
 constexpr int RJ_TILE = 2048;        // keys per LDS tile
 constexpr int RJ_MAX_LEVELS = 16;
-constexpr int PM_WAVES = 4;          // rows per workgroup
 static_assert(RJ_TILE % 8 == 0 && RJ_TILE % RJ_THREADS == 0, "the compare loop takes four key pairs per step");
 
 __device__ __forceinline__ unsigned long long joint_key(float score, int idx, int ascending) {
@@ -90,40 +84,6 @@ rank_joint_kernel(const float* __restrict__ scores, const int* __restrict__ seg_
   if (i < n_tot) out[i] = mine_ok ? cnt : -1;
 }
 
-__global__ void __launch_bounds__(PM_WAVES * 64)
-path_mask_points_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ base, const int* __restrict__ rank,
-                        int64_t ldr, const int* __restrict__ thr, const int* __restrict__ insert, const int64_t* __restrict__ num_ims,
-                        int rows_per_slide, int D, int B, int C, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t M = (int64_t)B * rows_per_slide;
-  const int64_t row = (int64_t)blockIdx.x * PM_WAVES + (threadIdx.x >> 6);
-  if (row >= M) return;                                            // (whole waves leave: row is uniform over a wave)
-  const int64_t b = row / rows_per_slide;
-  const int64_t r = row - b * rows_per_slide;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  if (r >= num_ims[b]) {
-    for (int c = 0; c < C; ++c) {
-      float* o = out + ((int64_t)c * M + row) * D;
-      for (int i = lane * 4; i < D; i += 256) stg_f32x4(o + i, zero);
-    }
-    return;
-  }
-  const int rk = rank[b * ldr + r];
-  const float* v = x + row * ldx;
-  for (int c = 0; c < C; ++c) {
-    const int t = thr[(int64_t)c * B + b];
-    const bool keep = rk < 0 || (insert[c] != 0 ? rk < t : rk >= t);        // (uniform over the wave)
-    float* o = out + ((int64_t)c * M + row) * D;
-    if (keep) {
-      for (int i = lane * 4; i < D; i += 256) stg_f32x4(o + i, ldg_f32x4(v + i));
-    } else if (base != nullptr) {
-      for (int i = lane * 4; i < D; i += 256) stg_f32x4(o + i, ldg_f32x4(base + i));
-    } else {
-      for (int i = lane * 4; i < D; i += 256) stg_f32x4(o + i, zero);
-    }
-  }
-}
-
 extern "C" {
 
 int paths_rank_joint_tile(void) { return RJ_TILE; }
@@ -141,29 +101,6 @@ int paths_rank_joint(const float* scores, const int* seg_end, const int* level_o
   hipLaunchKernelGGL(rank_joint_kernel, dim3((unsigned)((n_tot + RJ_THREADS - 1) / RJ_THREADS), (unsigned)B), dim3(RJ_THREADS), 0, stream,
                      scores, seg_end, level_on, num_ims, L, B, n_tot, ascending != 0 ? 1 : 0, rank, count);
   PATHS_LAUNCH_CHECK("rank_joint");
-  return PATHS_OK;
-}
-
-int paths_path_mask_points(const float* x, int64_t ldx, const float* base, const int* rank, int64_t ldr, const int* thr, const int* insert,
-                           const int64_t* num_ims, int rows_per_slide, int D, int B, int C, float* out, hipStream_t stream) {
-  PATHS_REQUIRE(x != nullptr && rank != nullptr && thr != nullptr && insert != nullptr && num_ims != nullptr && out != nullptr,
-                "path_mask_points: null pointer (x, rank, thr, insert, num_ims and out are required)");
-  PATHS_REQUIRE(D > 0 && D % 128 == 0, "path_mask_points: D (%d) must be a positive multiple of 128", D);
-  PATHS_REQUIRE(B > 0 && C > 0 && rows_per_slide > 0, "path_mask_points: B (%d), C (%d) and rows_per_slide (%d) must be positive", B, C,
-                rows_per_slide);
-  PATHS_REQUIRE(ldx >= D && ldx % 4 == 0, "path_mask_points: row stride (%lld) must be a multiple of 4 and at least D (%d)", (long long)ldx,
-                D);
-  PATHS_REQUIRE(ldr >= rows_per_slide, "path_mask_points: rank stride (%lld) must be at least rows_per_slide (%d)", (long long)ldr,
-                rows_per_slide);
-  PATHS_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)base % 16 == 0 && (uintptr_t)out % 16 == 0,
-                "path_mask_points: x, base and out must be 16-byte aligned");
-  PATHS_REQUIRE((uintptr_t)rank % 4 == 0 && (uintptr_t)thr % 4 == 0 && (uintptr_t)insert % 4 == 0,
-                "path_mask_points: rank, thr and insert must be 4-byte aligned");
-  const int64_t M = (int64_t)B * rows_per_slide;
-  PATHS_REQUIRE((M + PM_WAVES - 1) / PM_WAVES <= 0x7fffffffLL, "path_mask_points: too many rows (%lld)", (long long)M);
-  hipLaunchKernelGGL(path_mask_points_kernel, dim3((unsigned)((M + PM_WAVES - 1) / PM_WAVES)), dim3(PM_WAVES * 64), 0, stream, x, ldx, base,
-                     rank, ldr, thr, insert, num_ims, rows_per_slide, D, B, C, out);
-  PATHS_LAUNCH_CHECK("path_mask_points");
   return PATHS_OK;
 }
 

@@ -9,22 +9,24 @@ the gradient of a slide's score with respect to every visited patch's feature ve
 The pass is the training recursion (utils.recurse_train) with dropout off and the parameters detached: the hand-written backward
 carries dG and dY through every level anyway and forms dX = dG W_gates[:, :D] + dY on top (backward.selection_backward ``want_dx``);
 no weight-gradient product runs (backward.no_weight_grads) and no parameter's ``.grad`` is touched.  The per-patch reductions are
-one launch per level (csrc/saliency_rows.hip).  The top-K selection is not differentiable: the gradient is that of the score along
+one launch per level (paths_saliency_rows).  The top-K selection is not differentiable: the gradient is that of the score along
 the path the model took.  lstm = false is not covered.
 
 :func:`integrated_gradients` and :func:`smooth_grad` go beyond the one point: once a pass has been made its path is known (every
 level's keep_idx / keep_count, and with them every level's locations, parents and tissue filter), and with the top-K held at that
 recorded result (utils.recurse_train ``path``) the model is an ordinary differentiable function of the visited rows.  Every point of
 either method visits the same patches, so their maps can be summed; the S points of one slide run as virtual slides that share the
-path, ``chunk`` at a time through the level kernels.  The points are built and the gradients folded by the two row kernels of
-csrc/path_rows.hip.  These are attributions of the function along the path taken - not of the selection itself.
+path, ``chunk`` at a time through the level kernels.  The points are built and the gradients folded by two more row kernels
+(paths_path_points, paths_path_accumulate).  These are attributions of the function along the path taken - not of the selection itself.
 
 :func:`perturbation_curves` judges a map - any of the above, importance, attention, rollout - on the same frozen path: the visited
-patches are ranked jointly over the levels (paths_rank_joint) and removed from, or restored to, the rows in that order
-(paths_path_mask_points; both in csrc/perturb_rows.hip), one no-grad forward along the path per point.
+patches are ranked jointly over the levels (paths_rank_joint, csrc/perturb_rows.hip) and removed from, or restored to, the rows in
+that order (paths_path_mask_points), one no-grad forward along the path per point.
+The four per-row kernels share csrc/path_rows.hip; every call along a frozen path is one :class:`_FrozenPath`.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -60,13 +62,56 @@ def parse_target(target: Target) -> Callable[[torch.Tensor], torch.Tensor]:
     raise ValueError(f"unknown target {target!r}: 'risk', 'logit:<k>' or a callable [B,C] -> [B]")
 
 
+# ---- argument checks shared by the entry points (all before anything touches the device)
+def _positive_int(name: str, value):
+    if not isinstance(value, int) or value < 1:
+        raise ValueError(f"{name} must be a positive integer, got {value!r}")
+
+
+def _require_lstm(model, what: str):
+    if not model.use_lstm:
+        raise NotImplementedError(f"{what}: feature gradients are not implemented for the lstm=false variant "
+                                  "(selection_backward_nolstm)")
+
+
+def _baseline_arg(baseline, batch=None) -> Optional[torch.Tensor]:
+    """``baseline`` is None (zeros) or one [D] tensor; once the batch is known, D is the batch's and the result is that vector as a
+    contiguous fp32 device tensor."""
+    if baseline is None:
+        return None
+    if not (torch.is_tensor(baseline) and baseline.dim() == 1 and (batch is None or baseline.shape[0] == batch.dim)):
+        raise ValueError(f"baseline must be None or a [{'D' if batch is None else batch.dim}] tensor, got "
+                         + (str(tuple(baseline.shape)) if torch.is_tensor(baseline) else repr(type(baseline))))
+    return None if batch is None else baseline.detach().to(device=batch.device, dtype=torch.float32).contiguous()
+
+
+def _target_of(fn, logits: torch.Tensor) -> torch.Tensor:
+    tgt = fn(logits)
+    if tgt.shape != (logits.shape[0],):
+        raise ValueError(f"the target must map logits [B,C] to [B]; got {tuple(tgt.shape)}")
+    return tgt
+
+
+# ---- operand assertions shared by the ctypes wrappers of the per-row kernels
+def _rows_ok(x: torch.Tensor, *rows: torch.Tensor, num_ims: torch.Tensor, base: Optional[torch.Tensor] = None):
+    """x [B,N,D] and the other ``rows`` (each [k*B,N,D]): fp32, evenly strided; num_ims int64 [B]; base None or fp32 [D] contiguous."""
+    B, N, D = x.shape
+    for t in (x,) + rows:
+        assert t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(0) == N * t.stride(1), "rows must be fp32 and evenly strided"
+    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,)
+    assert base is None or (base.shape == (D,) and base.dtype == torch.float32 and base.is_contiguous())
+    return B, N, D
+
+
+def _tables_ok(dtype, *tables: Optional[torch.Tensor]):
+    assert all(t is None or (t.dtype == dtype and t.is_contiguous()) for t in tables), "device tables must be contiguous"
+
+
 def saliency_rows(dx: torch.Tensor, x: torch.Tensor, num_ims: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(grad_x_input [B,N], grad_norm [B,N]) of dx / x [B,N,D] fp32 (rows may be strided; rows at or beyond num_ims[b]: exact zeros)."""
     _lib.require_cuda(dx, x, num_ims)
-    B, N, D = dx.shape
-    assert x.shape == dx.shape and dx.dtype == x.dtype == torch.float32 and num_ims.dtype == torch.int64 and num_ims.shape == (B,)
-    for t in (dx, x):
-        assert t.stride(2) == 1 and t.stride(0) == N * t.stride(1), "rows must be evenly strided"
+    B, N, D = _rows_ok(x, dx, num_ims=num_ims)
+    assert x.shape == dx.shape
     gxi = torch.empty((B, N), device=dx.device, dtype=torch.float32)
     gnorm = torch.empty((B, N), device=dx.device, dtype=torch.float32)
     p = _lib.ptr
@@ -78,9 +123,7 @@ def _pass(model, batch, keep_patches, num_levels, fn, keep_gradients: bool, care
     from . import utils as putils
     trace: List[dict] = []
     out = putils.recurse_train(model, batch, keep_patches, num_levels, careful=careful, trace=trace)
-    tgt = fn(out["logits"])
-    if tgt.shape != (out["logits"].shape[0],):
-        raise ValueError(f"the target must map logits [B,C] to [B]; got {tuple(tgt.shape)}")
+    tgt = _target_of(fn, out["logits"])
     # slides do not interact: the gradient of the batch sum is every slide's own gradient
     grads = torch.autograd.grad(tgt.sum(), [rec["fts"] for rec in trace])
     for rec, dx in zip(trace, grads):
@@ -88,6 +131,18 @@ def _pass(model, batch, keep_patches, num_levels, fn, keep_gradients: bool, care
         if keep_gradients:
             rec["grad"] = dx
     return {"logits": out["logits"].detach(), "target": tgt.detach(), "status": out["status"]}, trace
+
+
+def _careful_repeat(run):
+    """``run(careful)`` makes one pass and returns a tuple that starts with its output dict.  Run it, read the status word, and when a
+    slide had no tissue children repeat it on the careful path and check again, as training does.  Returns (the tuple, careful)."""
+    from . import utils as putils
+    res = run(False)
+    if not putils.check_status_word(res[0]["status"]):
+        return res, False
+    res = run(True)
+    putils.check_status_word(res[0]["status"], fallback_done=True)
+    return res, True
 
 
 def input_gradients(model, slides, keep_patches: Sequence[int], num_levels: int, target: Target = "risk",
@@ -103,19 +158,14 @@ def input_gradients(model, slides, keep_patches: Sequence[int], num_levels: int,
     Dropout is off for the call (the model is switched to eval and its mode restored); no parameter's ``.grad`` is created or
     changed.  A slide whose kept patches have no tissue children repeats the pass on the careful path, as training does."""
     from . import utils as putils
-    if not model.use_lstm:
-        raise NotImplementedError("input_gradients: feature gradients are not implemented for the lstm=false variant "
-                                  "(selection_backward_nolstm)")
+    _require_lstm(model, "input_gradients")
     fn = parse_target(target)
     batch = putils._stored_batch(slides, "input_gradients")
     was_training = model.training
     model.eval()
     try:
         with torch.enable_grad():
-            out, trace = _pass(model, batch, keep_patches, num_levels, fn, keep_gradients, careful=False)
-            if putils.check_status_word(out["status"]):
-                out, trace = _pass(model, batch, keep_patches, num_levels, fn, keep_gradients, careful=True)
-                putils.check_status_word(out["status"], fallback_done=True)
+            (out, trace), _ = _careful_repeat(lambda careful: _pass(model, batch, keep_patches, num_levels, fn, keep_gradients, careful))
     finally:
         model.train(was_training)
     return out, trace
@@ -124,23 +174,17 @@ def input_gradients(model, slides, keep_patches: Sequence[int], num_levels: int,
 # ------------------------------------------------------------------------------------------------
 # integrated gradients and SmoothGrad along the frozen path
 # ------------------------------------------------------------------------------------------------
-def _rows_ok(t: torch.Tensor, N: int):
-    assert t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(0) == N * t.stride(1), "rows must be fp32 and evenly strided"
-
-
 def path_points(x: torch.Tensor, base: Optional[torch.Tensor], alpha: torch.Tensor, sigma: torch.Tensor, keys: Optional[torch.Tensor],
                 num_ims: torch.Tensor) -> torch.Tensor:
     """The points of C chunk members for B slides (include/paths_hip.h: paths_path_points): x [B,N,D] fp32 (rows may be strided),
     base [D] or None, alpha / sigma [C] fp32 device tables, keys [C*B] (or [C,B]) int64 device table (None: every sigma is 0),
     num_ims [B] int64.  Returns [C*B, N, D], virtual slide c * B + b; rows at or beyond num_ims[b] are exact zeros."""
     _lib.require_cuda(x, base, alpha, sigma, keys, num_ims)
-    B, N, D = x.shape
+    B, N, D = _rows_ok(x, num_ims=num_ims, base=base)
     C = alpha.numel()
-    _rows_ok(x, N)
-    assert alpha.dtype == sigma.dtype == torch.float32 and sigma.numel() == C and alpha.is_contiguous() and sigma.is_contiguous()
-    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,)
-    assert base is None or (base.shape == (D,) and base.dtype == torch.float32 and base.is_contiguous())
-    assert keys is None or (keys.dtype == torch.int64 and keys.numel() == C * B and keys.is_contiguous())
+    _tables_ok(torch.float32, alpha, sigma)
+    _tables_ok(torch.int64, keys)
+    assert sigma.numel() == C and (keys is None or keys.numel() == C * B)
     out = torch.empty((C * B, N, D), device=x.device, dtype=torch.float32)
     p = _lib.ptr
     _lib.call("paths_path_points", p(x), x.stride(1), p(base), p(alpha), p(sigma), p(keys), p(num_ims.contiguous()), N, D, B, C, p(out),
@@ -153,16 +197,10 @@ def path_accumulate(dx: torch.Tensor, x: torch.Tensor, base: Optional[torch.Tens
     """Fold the gradients dx [C*B, N, D] of C chunk members into the running sums acc_gxi / acc_sq [B,N] (and acc_dx [B,N,D]) with the
     weights w [C] (fp32 device table), against the recorded rows x [B,N,D] (include/paths_hip.h: paths_path_accumulate).  In place."""
     _lib.require_cuda(dx, x, base, w, num_ims, acc_gxi, acc_sq, acc_dx)
-    B, N, D = x.shape
+    B, N, D = _rows_ok(x, dx, num_ims=num_ims, base=base)
     C = w.numel()
-    assert dx.shape == (C * B, N, D) and w.dtype == torch.float32 and w.is_contiguous()
-    _rows_ok(x, N)
-    _rows_ok(dx, N)
-    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,)
-    assert base is None or (base.shape == (D,) and base.dtype == torch.float32 and base.is_contiguous())
-    for a in (acc_gxi, acc_sq):
-        assert a.shape == (B, N) and a.dtype == torch.float32 and a.is_contiguous()
-    assert acc_dx is None or (acc_dx.shape == (B, N, D) and acc_dx.dtype == torch.float32 and acc_dx.is_contiguous())
+    _tables_ok(torch.float32, w, acc_gxi, acc_sq, acc_dx)
+    assert dx.shape == (C * B, N, D) and acc_gxi.shape == acc_sq.shape == (B, N) and (acc_dx is None or acc_dx.shape == (B, N, D))
     p = _lib.ptr
     _lib.call("paths_path_accumulate", p(dx), dx.stride(1), p(x), x.stride(1), p(base), p(w), p(num_ims.contiguous()), N, D, B, C,
               1 if init else 0, p(acc_gxi), p(acc_sq), p(acc_dx), _lib.stream())
@@ -171,8 +209,7 @@ def path_accumulate(dx: torch.Tensor, x: torch.Tensor, base: Optional[torch.Tens
 def quadrature(rule: str, steps: int) -> Tuple[np.ndarray, np.ndarray]:
     """(nodes alpha_s in (0, 1), weights w_s) in float64 of the rule over [0, 1]: ``"midpoint"`` (alpha_s = (s + 1/2) / S, w = 1 / S) or
     ``"gausslegendre"`` (numpy's leggauss mapped from [-1, 1]; exact for polynomials in alpha up to degree 2 S - 1)."""
-    if not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    _positive_int("steps", steps)
     if rule == "midpoint":
         return (np.arange(steps, dtype=np.float64) + 0.5) / steps, np.full(steps, 1.0 / steps)
     if rule == "gausslegendre":
@@ -200,118 +237,135 @@ def noise_key(seed: int, level: int, sample: int, slide: int) -> int:
     return lo | (hi << 32)
 
 
-def _chunk_and_base(batch, baseline, chunk):
-    """(chunk, base) of a call along the path: the members per frozen pass (default max(1, 8 // B)) and the baseline as a contiguous
-    fp32 [D] device tensor (None: zeros)."""
-    B, D = len(batch), batch.dim
-    if chunk is None:
-        chunk = max(1, 8 // B)
-    if not isinstance(chunk, int) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, got {chunk!r}")
-    base = None
-    if baseline is not None:
-        if baseline.shape != (D,):
-            raise ValueError(f"baseline must be None or a [{D}] tensor, got {tuple(baseline.shape)}")
-        base = baseline.detach().to(device=batch.device, dtype=torch.float32).contiguous()
-    return chunk, base
+class _FrozenPath:
+    """One call along a frozen path, as a context manager: what integrated_gradients / smooth_grad and perturbation_curves share.
 
+    Entering resolves ``slides``, settles ``chunk`` (members per frozen pass, default max(1, 8 // B)) and ``base`` (the baseline as
+    a contiguous fp32 [D] device tensor; None: zeros), switches the model to eval and finds the path: without a ``trace`` it is that
+    of the :func:`input_gradients` pass, its rows kept; a given trace's keep_idx / keep_count are the path, and one no-grad pass
+    along them must reproduce its num_ims / locs.  Then ``xs`` / ``nums`` hold every level's recorded rows and valid counts,
+    ``path`` the selection, ``careful`` whether a slide had no tissue children, ``out`` = {"logits", "target", "status"} and
+    ``trace``.  :meth:`frozen` runs inside ops.range_guard(what its rows can reach): a convex combination stays within max(max|x|,
+    max|base|), a noisy copy within max|x| (1 + 5.89 sigma) (rms <= max|x|, |z| <= 5.89).  Leaving checks the status words of the
+    frozen passes and restores the model's mode - the latter on every way out."""
 
-def _path_pass(model, batch, keep_patches, num_levels, fn):
-    """The path pass (today's input_gradients pass, its rows kept) and its careful repeat when a slide had no tissue children.
-    Returns (out, trace, careful).  Gradients must be enabled."""
-    from . import utils as putils
-    careful = False
-    out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=False, keep_rows=True)
-    if putils.check_status_word(out["status"]):
-        careful = True
-        out, trace = _pass(model, batch, keep_patches, num_levels, fn, False, careful=True, keep_rows=True)
-        putils.check_status_word(out["status"], fallback_done=True)
-    return out, trace, careful
+    def __init__(self, what: str, model, slides, keep_patches, num_levels: int, fn, baseline=None, chunk: Optional[int] = None,
+                 trace: Optional[List[dict]] = None, sigma: float = 0.0):
+        if chunk is not None:
+            _positive_int("chunk", chunk)
+        _baseline_arg(baseline)
+        self.what, self.model, self.slides, self.keep_patches, self.num_levels, self.fn = what, model, slides, keep_patches, num_levels, fn
+        self.baseline, self.chunk, self.trace, self.sigma = baseline, chunk, trace, sigma
+        self.statuses: List[torch.Tensor] = []
+        self._virtual: dict = {}                               # c -> (the batch repeated c times, the path repeated c times)
 
+    def __enter__(self):
+        from . import ops, utils as putils
+        batch = self.batch = putils._stored_batch(self.slides, self.what)
+        if self.chunk is None:
+            self.chunk = max(1, 8 // len(batch))
+        base = self.base = _baseline_arg(self.baseline, batch)
+        with contextlib.ExitStack() as stack:
+            stack.callback(self.model.train, self.model.training)
+            self.model.eval()
+            given = self.trace is not None
+            if not given:                                      # (outside the guard: the free pass keeps the range contract of its own rows)
+                with torch.enable_grad():
+                    (self.out, self.trace), self.careful = _careful_repeat(
+                        lambda careful: _pass(self.model, batch, self.keep_patches, self.num_levels, self.fn, False, careful, keep_rows=True))
+                self.xs = [rec.pop("fts").detach() for rec in self.trace]
+            stack.enter_context(ops.range_guard(max(batch.feat_absmax * (1.0 + 5.89 * self.sigma),
+                                                    float(base.abs().max()) if base is not None else 0.0)))
+            self.path = [(rec["keep_idx"], rec["keep_count"]) for rec in self.trace[:-1]]
+            self.nums = [rec["num_ims"] for rec in self.trace]
+            if given:
+                with torch.no_grad():
+                    self._along_the_given_trace()
+            self._stack = stack.pop_all()
+        return self
 
-def _virtual(virtual: dict, batch, path, c: int):
-    """(the batch repeated c times, the path repeated c times): c chunk members of every slide as virtual slides c' * B + b."""
-    from .data_utils.slide import DeviceSlideBatch
-    if c not in virtual:
-        virtual[c] = (batch if c == 1 else DeviceSlideBatch(list(batch.slides) * c), [(ki.repeat(c, 1), kc.repeat(c)) for ki, kc in path])
-    return virtual[c]
+    def _along_the_given_trace(self):
+        """One frozen pass without points collects the rows and F(X), and shows that the trace belongs to these slides."""
+        from . import utils as putils
+
+        def run(careful):
+            t2: List[dict] = []
+            return putils.recurse_train(self.model, self.batch, self.keep_patches, self.num_levels, careful=careful, trace=t2, path=self.path), t2
+        (o, t2), self.careful = _careful_repeat(run)
+        for l, (rec, r2) in enumerate(zip(self.trace, t2)):
+            same = rec["num_ims"].shape == r2["num_ims"].shape and rec["locs"].shape == r2["locs"].shape
+            if same:                                           # (the locations of the valid rows: padding is nobody's)
+                valid = (torch.arange(r2["locs"].shape[1], device=self.batch.device)[None, :] < r2["num_ims"][:, None])[..., None]
+                same = torch.equal(rec["num_ims"], r2["num_ims"]) and torch.equal(rec["locs"] * valid, r2["locs"] * valid)
+            if not same:
+                raise ValueError(f"trace: a pass along its path does not reproduce its num_ims / locs at level {l}: it belongs to "
+                                 "other slides, keep_patches or levels")
+        self.xs = [r2["fts"].detach() for r2 in t2]
+        self.out = {"logits": o["logits"].detach(), "target": _target_of(self.fn, o["logits"]).detach(), "status": o["status"]}
+
+    def frozen(self, c: int, build_points, trace: Optional[list] = None):
+        """One pass of B * c virtual slides (c members of every slide, virtual slide c' * B + b) along the path, the rows of every
+        level supplied by ``build_points(level)`` [c*B, N, D].  Returns the pass's output; its records go to ``trace``."""
+        from . import utils as putils
+        from .data_utils.slide import DeviceSlideBatch
+        if c not in self._virtual:
+            self._virtual[c] = (self.batch if c == 1 else DeviceSlideBatch(list(self.batch.slides) * c),
+                                [(ki.repeat(c, 1), kc.repeat(c)) for ki, kc in self.path])
+        vb, vpath = self._virtual[c]
+        o = putils.recurse_train(self.model, vb, self.keep_patches, self.num_levels, careful=self.careful, trace=trace, path=vpath,
+                                 points=lambda level, fts, num_ims: build_points(level))
+        self.statuses.append(o["status"])
+        return o
+
+    def __exit__(self, exc_type, exc, tb):
+        from . import utils as putils
+        with self._stack:                                      # leaves the range guard, restores the model's mode
+            if exc_type is None:
+                for st in self.statuses:                       # bit 0 repeats what the careful path pass already handled
+                    putils.check_status_word(st, fallback_done=True)
+        return False
 
 
 def _along_path(model, slides, keep_patches, num_levels, fn, what, alphas, sigmas, weights, baseline, seed, chunk, want_dx, want_points,
                 want_baseline_target):
-    """The shared sequence of both methods: the path pass (today's input_gradients pass, its rows kept), its careful repeat when a
-    slide had no tissue children, then ceil(S / chunk) frozen passes of B * chunk virtual slides, each one autograd.grad of the
-    summed target with respect to the level leaves and one paths_path_accumulate per level.  Returns (out, trace, per-level
-    (acc_gxi, acc_sq, acc_dx or None), per-level points [S,B,N,D] or None)."""
-    from . import ops, utils as putils
-    batch = putils._stored_batch(slides, what)
-    B, D, dev, S = len(batch), batch.dim, batch.device, len(alphas)
-    chunk, base = _chunk_and_base(batch, baseline, chunk)
-    was_training = model.training
-    model.eval()
-    guard = None
-    try:
-        with torch.enable_grad():
-            out, trace, careful = _path_pass(model, batch, keep_patches, num_levels, fn)
-            xs = [rec.pop("fts").detach() for rec in trace]
-            nums = [rec["num_ims"] for rec in trace]
-            path = [(rec["keep_idx"], rec["keep_count"]) for rec in trace[:-1]]
-            f32 = dict(device=dev, dtype=torch.float32)
-            # ONE upload per call: nodes, noise scales and weights of all S members, and the keys of every (level, sample, slide)
-            tab = torch.tensor(np.stack([alphas, sigmas, weights]), **f32)
-            noisy = bool(np.any(np.asarray(sigmas) != 0))
-            keys = None
-            if noisy:
-                k = np.array([[[noise_key(seed, l, s, b) for b in range(B)] for s in range(S)] for l in range(num_levels)], dtype=np.uint64)
-                keys = torch.from_numpy(k.view(np.int64)).to(dev)
-            accs = [(torch.empty(x.shape[:2], **f32), torch.empty(x.shape[:2], **f32), torch.empty(x.shape, **f32) if want_dx else None)
-                    for x in xs]
-            pts = [[] for _ in xs] if want_points else None
-            virtual = {}                                       # chunk size -> (the batch repeated, the path repeated)
-            statuses = []
+    """The shared sequence of both methods on a :class:`_FrozenPath`: ceil(S / chunk) frozen passes of B * chunk virtual slides, each
+    one autograd.grad of the summed target with respect to the level leaves and one paths_path_accumulate per level.  Returns (out,
+    trace, per-level (acc_gxi, acc_sq, acc_dx or None), per-level points [S,B,N,D] or None)."""
+    S = len(alphas)
+    with _FrozenPath(what, model, slides, keep_patches, num_levels, fn, baseline, chunk, sigma=float(np.max(np.abs(sigmas)))) as fp, \
+            torch.enable_grad():
+        B, xs, out = len(fp.batch), fp.xs, fp.out
+        f32 = dict(device=fp.batch.device, dtype=torch.float32)
+        # ONE upload per call: nodes, noise scales and weights of all S members, and the keys of every (level, sample, slide)
+        tab = torch.tensor(np.stack([alphas, sigmas, weights]), **f32)
+        keys = None
+        if np.any(np.asarray(sigmas) != 0):
+            k = np.array([[[noise_key(seed, l, s, b) for b in range(B)] for s in range(S)] for l in range(num_levels)], dtype=np.uint64)
+            keys = torch.from_numpy(k.view(np.int64)).to(fp.batch.device)
+        accs = [(torch.empty(x.shape[:2], **f32), torch.empty(x.shape[:2], **f32), torch.empty(x.shape, **f32) if want_dx else None)
+                for x in xs]
+        pts = [[] for _ in xs] if want_points else None
 
-            def frozen(c, alpha, sigma, key_of, grad):
-                """One pass of B * c virtual slides along the path, their rows built by paths_path_points from alpha / sigma [c]."""
-                vb, vpath = _virtual(virtual, batch, path, c)
-                t2 = [] if grad else None
-                o = putils.recurse_train(model, vb, keep_patches, num_levels, careful=careful, trace=t2, path=vpath,
-                                         points=lambda level, fts, num_ims: path_points(xs[level], base, alpha, sigma, key_of(level), nums[level]))
-                statuses.append(o["status"])
-                return o, t2
+        def points(s0, c):                                     # the rows of members s0 .. s0 + c - 1
+            return lambda level: path_points(xs[level], fp.base, tab[0, s0:s0 + c], tab[1, s0:s0 + c],
+                                             None if keys is None else keys[level, s0:s0 + c], fp.nums[level])
 
-            # the range contract (ops.range_guard) for what the points can reach: a convex combination stays within max(max|x|, max|base|),
-            # a noisy copy within max|x| (1 + 5.89 sigma) (rms <= max|x|, |z| <= 5.89)
-            reach = max(batch.feat_absmax * (1.0 + 5.89 * float(np.max(np.abs(sigmas)))), float(base.abs().max()) if base is not None else 0.0)
-            guard = ops.range_guard(reach)
-            guard.__enter__()
-            for s0 in range(0, S, chunk):
-                c = min(chunk, S - s0)
-                o, t2 = frozen(c, tab[0, s0:s0 + c], tab[1, s0:s0 + c], lambda level: keys[level, s0:s0 + c] if noisy else None, True)
-                # virtual slides do not interact either: the gradient of the sum is every member's own gradient
-                grads = torch.autograd.grad(fn(o["logits"]).sum(), [rec["fts"] for rec in t2])
-                for l, dx in enumerate(grads):
-                    path_accumulate(dx, xs[l], base, tab[2, s0:s0 + c], nums[l], s0 == 0, *accs[l])
-                    if want_points:
-                        pts[l].append(t2[l]["fts"].detach().view(c, B, *xs[l].shape[1:]))
-                del o, t2, grads
-            if want_baseline_target:
-                with torch.no_grad():
-                    zero = torch.zeros((1,), **f32)
-                    o, _ = frozen(1, zero, zero, lambda level: None, False)
-                    out["target_baseline"] = fn(o["logits"]).detach()
-            for st in statuses:                                # bit 0 repeats what the careful path pass already handled
-                putils.check_status_word(st, fallback_done=True)
-    finally:
-        if guard is not None:
-            guard.__exit__(None, None, None)
-        model.train(was_training)
-    return out, trace, accs, ([torch.cat(p) for p in pts] if want_points else None)
-
-
-def _check_model(model, what: str):
-    if not model.use_lstm:
-        raise NotImplementedError(f"{what}: feature gradients are not implemented for the lstm=false variant "
-                                  "(selection_backward_nolstm)")
+        for s0 in range(0, S, fp.chunk):
+            c, t2 = min(fp.chunk, S - s0), []
+            o = fp.frozen(c, points(s0, c), trace=t2)
+            # virtual slides do not interact either: the gradient of the sum is every member's own gradient
+            grads = torch.autograd.grad(fn(o["logits"]).sum(), [rec["fts"] for rec in t2])
+            for l, dx in enumerate(grads):
+                path_accumulate(dx, xs[l], fp.base, tab[2, s0:s0 + c], fp.nums[l], s0 == 0, *accs[l])
+                if want_points:
+                    pts[l].append(t2[l]["fts"].detach().view(c, B, *xs[l].shape[1:]))
+            del o, t2, grads
+        if want_baseline_target:
+            with torch.no_grad():
+                zero = torch.zeros((1,), **f32)
+                out["target_baseline"] = fn(fp.frozen(1, lambda level: path_points(xs[level], fp.base, zero, zero, None, fp.nums[level]))
+                                            ["logits"]).detach()
+    return out, fp.trace, accs, ([torch.cat(p) for p in pts] if want_points else None)
 
 
 def integrated_gradients(model, slides, keep_patches: Sequence[int], num_levels: int, target: Target = "risk", steps: int = 32,
@@ -329,12 +383,9 @@ def integrated_gradients(model, slides, keep_patches: Sequence[int], num_levels:
 
     This is the attribution of the function along the path the model took, not of the selection.  Dropout is off, the model's mode is
     restored, no weight-gradient product runs and no ``.grad`` is touched; slides as for :func:`input_gradients`."""
-    _check_model(model, "integrated_gradients")
+    _require_lstm(model, "integrated_gradients")
     fn = parse_target(target)
     alphas, weights = quadrature(rule, steps)
-    if baseline is not None and not (torch.is_tensor(baseline) and baseline.dim() == 1):
-        raise ValueError("baseline must be None or a [D] tensor, got "
-                         + (str(tuple(baseline.shape)) if torch.is_tensor(baseline) else repr(type(baseline))))
     out, trace, accs, _ = _along_path(model, slides, keep_patches, num_levels, fn, "integrated_gradients", alphas, np.zeros(steps), weights,
                                       baseline, 0, chunk, keep_gradients, False, True)
     total = None
@@ -360,10 +411,9 @@ def smooth_grad(model, slides, keep_patches: Sequence[int], num_levels: int, tar
     [B,N], the mean of ||dX_s||^2 (SmoothGrad-squared); ``keep_gradients`` adds ``smooth_grad`` [B,N,D], the mean gradient;
     ``keep_points`` adds ``points`` [S,B,N,D], the noisy rows themselves - S copies of every level: for tests and small slides.
     Everything else as :func:`integrated_gradients`."""
-    _check_model(model, "smooth_grad")
+    _require_lstm(model, "smooth_grad")
     fn = parse_target(target)
-    if not isinstance(samples, int) or samples < 1:
-        raise ValueError(f"samples must be a positive integer, got {samples!r}")
+    _positive_int("samples", samples)
     if not sigma >= 0:
         raise ValueError(f"sigma must not be negative, got {sigma!r}")
     out, trace, accs, pts = _along_path(model, slides, keep_patches, num_levels, fn, "smooth_grad", np.ones(samples),
@@ -397,9 +447,10 @@ def rank_joint(scores: torch.Tensor, seg_end: torch.Tensor, level_on: torch.Tens
     _lib.require_cuda(scores, seg_end, level_on, num_ims)
     B, Ntot = scores.shape
     L = seg_end.numel()
-    assert scores.dtype == torch.float32 and scores.is_contiguous()
-    assert seg_end.dtype == level_on.dtype == torch.int32 and level_on.numel() == L and seg_end.is_contiguous() and level_on.is_contiguous()
-    assert num_ims.dtype == torch.int64 and num_ims.shape == (L, B) and num_ims.is_contiguous()
+    _tables_ok(torch.float32, scores)
+    _tables_ok(torch.int32, seg_end, level_on)
+    _tables_ok(torch.int64, num_ims)
+    assert level_on.numel() == L and num_ims.shape == (L, B)
     rank = torch.empty((B, Ntot), device=scores.device, dtype=torch.int32)
     count = torch.empty((B,), device=scores.device, dtype=torch.int32)
     p = _lib.ptr
@@ -415,13 +466,11 @@ def path_mask_points(x: torch.Tensor, base: Optional[torch.Tensor], rank: torch.
     device tables, num_ims [B] int64.  Returns [C*B, N, D], virtual slide c * B + b: a copy of the row or of the baseline, exact
     zeros at or beyond num_ims[b]."""
     _lib.require_cuda(x, base, rank, thr, insert, num_ims)
-    B, N, D = x.shape
+    B, N, D = _rows_ok(x, num_ims=num_ims, base=base)
     C = insert.numel()
-    _rows_ok(x, N)
+    _tables_ok(torch.int32, thr, insert)
     assert rank.dtype == torch.int32 and rank.shape == (B, N) and rank.stride(1) == 1 and (B == 1 or rank.stride(0) >= N)
-    assert thr.dtype == insert.dtype == torch.int32 and thr.shape == (C, B) and thr.is_contiguous() and insert.is_contiguous()
-    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,)
-    assert base is None or (base.shape == (D,) and base.dtype == torch.float32 and base.is_contiguous())
+    assert thr.shape == (C, B)
     out = torch.empty((C * B, N, D), device=x.device, dtype=torch.float32)
     p = _lib.ptr
     _lib.call("paths_path_mask_points", p(x), x.stride(1), p(base), p(rank), rank.stride(0) if B > 1 else N, p(thr), p(insert),
@@ -458,6 +507,41 @@ def _level_scores(scores, trace, num_levels: int, shapes, dev) -> List[torch.Ten
     return out
 
 
+def _rank_levels(fp: _FrozenPath, scores, chosen: Sequence[int], descending: bool):
+    """The joint rank of the visited patches of the ``chosen`` levels by ``scores`` (one launch), with the call's ONE host check.
+    Returns (rank per level [B, N_l] - the records gain it as ``perturbation_rank`` -, the ranked patches per slide [B] on the host)."""
+    B, dev = len(fp.batch), fp.batch.device
+    Ns = [int(x.shape[1]) for x in fp.xs]
+    sc = torch.cat(_level_scores(scores, fp.trace, fp.num_levels, [(B, n) for n in Ns], dev), dim=1).contiguous()
+    seg = np.cumsum(Ns)
+    seg_tab = torch.tensor(np.stack([seg, [1 if l in chosen else 0 for l in range(fp.num_levels)]]), device=dev, dtype=torch.int32)
+    rank, count = rank_joint(sc, seg_tab[0], seg_tab[1], torch.stack(fp.nums), ascending=not descending)
+    # ONE host check: the valid counts and whether a valid score is NaN (its rank would mean nothing)
+    host = torch.cat([count.long(), (torch.isnan(sc) & (rank >= 0)).any(dim=1).long()]).cpu().numpy()
+    if host[B:].any():
+        raise ValueError(f"scores: NaN among the valid patches of slide(s) {np.nonzero(host[B:])[0].tolist()}")
+    ranks = [rank[:, e - n:e] for e, n in zip(seg, Ns)]
+    for rec, rk in zip(fp.trace, ranks):
+        rec["perturbation_rank"] = rk
+    return ranks, host[:B]
+
+
+def _member_tables(counts: np.ndarray, steps: int, names: Sequence[str], dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(thr [M, B], insert [M]) int32 of every member, ONE upload per call: [s = 1 .. steps - 1 of each curve in ``names`` | everything
+    removed]; the end points are F(X) and F(baseline), shared by both curves."""
+    inner, B = counts[1:steps], counts.shape[1]
+    thr = np.concatenate([inner] * len(names) + [counts[steps:]])
+    ins = np.concatenate([np.full(steps - 1, float(name == "insertion")) for name in names] + [np.zeros(1)])
+    tab = torch.tensor(np.concatenate([thr.reshape(-1), ins]), device=dev, dtype=torch.int32)
+    return tab[:len(ins) * B].view(len(ins), B), tab[len(ins) * B:]
+
+
+def _auc(curve: torch.Tensor, frac: np.ndarray) -> torch.Tensor:
+    """Trapezoid of curve [B, steps + 1] over frac, in float64."""
+    d, w = curve.double(), torch.from_numpy(np.diff(frac)).to(curve.device)
+    return ((d[:, :-1] + d[:, 1:]) * 0.5 * w[None, :]).sum(dim=1)
+
+
 def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: int, scores, trace: Optional[List[dict]] = None,
                         target: Target = "risk", steps: int = 16, mode: str = "both", levels: Optional[Sequence[int]] = None,
                         baseline: Optional[torch.Tensor] = None, descending: bool = True,
@@ -485,117 +569,39 @@ def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: 
     points between run as virtual slides, ``chunk`` at a time (default max(1, 8 // B)), each curve's members in chunks of their own
     so that a curve has the same bits whichever ``mode`` asked for it.  No gradient is taken beyond the path pass; dropout is off,
     the model's mode is restored and no ``.grad`` is touched."""
-    from . import ops, utils as putils
-    _check_model(model, "perturbation_curves")
+    _require_lstm(model, "perturbation_curves")
     fn = parse_target(target)
-    if not isinstance(steps, int) or steps < 1:
-        raise ValueError(f"steps must be a positive integer, got {steps!r}")
+    _positive_int("steps", steps)
     if mode not in MODES:
         raise ValueError(f"unknown mode {mode!r}: 'deletion', 'insertion' or 'both'")
     chosen = list(range(num_levels)) if levels is None else [int(l) for l in levels]
     if any(not 0 <= l < num_levels for l in chosen):
         raise ValueError(f"levels {list(levels)}: level indices must be in [0, {num_levels})")
-    if baseline is not None and not (torch.is_tensor(baseline) and baseline.dim() == 1):
-        raise ValueError("baseline must be None or a [D] tensor, got "
-                         + (str(tuple(baseline.shape)) if torch.is_tensor(baseline) else repr(type(baseline))))
+    fp = _FrozenPath("perturbation_curves", model, slides, keep_patches, num_levels, fn, baseline, chunk, trace)
     if not isinstance(scores, str) and (torch.is_tensor(scores) or not hasattr(scores, "__len__") or len(scores) != num_levels):
         raise ValueError(f"scores: the name of a trace entry or a sequence of {num_levels} tensors [B, N_l] expected")
     if trace is not None and (len(trace) != num_levels or any("keep_idx" not in rec or "keep_count" not in rec for rec in trace[:-1])):
         raise ValueError(f"trace: {num_levels} records with keep_idx / keep_count below the last level expected")
-    batch = putils._stored_batch(slides, "perturbation_curves")
-    B, dev = len(batch), batch.device
-    chunk, base = _chunk_and_base(batch, baseline, chunk)
-    want_del, want_ins = mode != "insertion", mode != "deletion"
-    was_training = model.training
-    model.eval()
-    guard = None
-    try:
-        given = trace is not None
-        if not given:
-            with torch.enable_grad():
-                out, trace, careful = _path_pass(model, batch, keep_patches, num_levels, fn)
-            xs = [rec.pop("fts").detach() for rec in trace]
-        with torch.no_grad():
-            guard = ops.range_guard(max(batch.feat_absmax, float(base.abs().max()) if base is not None else 0.0))
-            guard.__enter__()
-            path = [(rec["keep_idx"], rec["keep_count"]) for rec in trace[:-1]]
-            statuses = []
-            if given:                                          # one frozen pass without points collects the rows and F(X)
-                careful, t2 = False, []
-                o = putils.recurse_train(model, batch, keep_patches, num_levels, careful=False, trace=t2, path=path)
-                if putils.check_status_word(o["status"]):
-                    careful, t2 = True, []
-                    o = putils.recurse_train(model, batch, keep_patches, num_levels, careful=True, trace=t2, path=path)
-                    putils.check_status_word(o["status"], fallback_done=True)
-                for l, (rec, r2) in enumerate(zip(trace, t2)):
-                    same = rec["num_ims"].shape == r2["num_ims"].shape and rec["locs"].shape == r2["locs"].shape
-                    if same:                                   # (the locations of the valid rows: padding is nobody's)
-                        valid = (torch.arange(r2["locs"].shape[1], device=dev)[None, :] < r2["num_ims"][:, None])[..., None]
-                        same = torch.equal(rec["num_ims"], r2["num_ims"]) and torch.equal(rec["locs"] * valid, r2["locs"] * valid)
-                    if not same:
-                        raise ValueError(f"trace: a pass along its path does not reproduce its num_ims / locs at level {l}: it belongs to "
-                                         "other slides, keep_patches or levels")
-                xs = [r2["fts"].detach() for r2 in t2]
-                tgt = fn(o["logits"])
-                if tgt.shape != (B,):
-                    raise ValueError(f"the target must map logits [B,C] to [B]; got {tuple(tgt.shape)}")
-                out = {"logits": o["logits"].detach(), "target": tgt.detach(), "status": o["status"]}
-            nums = [rec["num_ims"] for rec in trace]
-            Ns = [int(x.shape[1]) for x in xs]
-            sc = torch.cat(_level_scores(scores, trace, num_levels, [(B, n) for n in Ns], dev), dim=1).contiguous()
-            seg = np.cumsum(Ns)
-            on = [1 if l in chosen else 0 for l in range(num_levels)]
-            seg_tab = torch.tensor(np.stack([seg, on]), device=dev, dtype=torch.int32)
-            rank, count = rank_joint(sc, seg_tab[0], seg_tab[1], torch.stack(nums), ascending=not descending)
-            # ONE host check: the valid counts and whether a valid score is NaN (its rank would mean nothing)
-            host = torch.cat([count.long(), (torch.isnan(sc) & (rank >= 0)).any(dim=1).long()]).cpu().numpy()
-            if host[B:].any():
-                raise ValueError(f"scores: NaN among the valid patches of slide(s) {np.nonzero(host[B:])[0].tolist()}")
-            ranks = [rank[:, e - n:e] for e, n in zip(seg, Ns)]
-            for rec, rk in zip(trace, ranks):
-                rec["perturbation_rank"] = rk
-            counts = perturbation_counts(host[:B], steps)
-            # ONE upload per call: the thresholds and flags of every member - [deletion s = 1 .. steps - 1 | insertion s = 1 .. steps - 1 |
-            # everything removed]; the end points are F(X) and F(baseline), shared by both curves
-            inner = counts[1:steps]
-            thr_np = np.concatenate(([inner] if want_del else []) + ([inner] if want_ins else []) + [counts[steps:]])
-            ins_np = np.concatenate(([np.zeros(steps - 1)] if want_del else []) + ([np.ones(steps - 1)] if want_ins else []) + [np.zeros(1)])
-            M = len(ins_np)
-            tab = torch.tensor(np.concatenate([thr_np.reshape(-1), ins_np]), device=dev, dtype=torch.int32)
-            thr, ins = tab[:M * B].view(M, B), tab[M * B:]
-            virtual = {}
+    names = [name for name in ("deletion", "insertion") if mode in (name, "both")]
+    with fp, torch.no_grad():
+        B, out = len(fp.batch), fp.out
+        ranks, n = _rank_levels(fp, scores, chosen, descending)
+        counts = perturbation_counts(n, steps)
+        thr, ins = _member_tables(counts, steps, names, fp.batch.device)
 
-            def frozen(m0, c):
-                """Members m0 .. m0 + c - 1 as one pass of B * c virtual slides along the path.  Returns their targets [c, B]."""
-                vb, vpath = _virtual(virtual, batch, path, c)
-                o = putils.recurse_train(model, vb, keep_patches, num_levels, careful=careful, path=vpath,
-                                         points=lambda level, fts, num_ims: path_mask_points(xs[level], base, ranks[level], thr[m0:m0 + c],
-                                                                                             ins[m0:m0 + c], nums[level]))
-                statuses.append(o["status"])
-                return fn(o["logits"]).detach().view(c, B)
+        def targets(m0, c):                                    # [c, B] of members m0 .. m0 + c - 1
+            o = fp.frozen(c, lambda level: path_mask_points(fp.xs[level], fp.base, ranks[level], thr[m0:m0 + c], ins[m0:m0 + c], fp.nums[level]))
+            return fn(o["logits"]).detach().view(c, B)
 
-            out["target_baseline"] = frozen(M - 1, 1)[0]
-            curves, m0 = {}, 0
-            for name in (["deletion"] if want_del else []) + (["insertion"] if want_ins else []):
-                first, last = (out["target"], out["target_baseline"]) if name == "deletion" else (out["target_baseline"], out["target"])
-                pts = [first[None]]
-                for s0 in range(0, steps - 1, chunk):
-                    c = min(chunk, steps - 1 - s0)
-                    pts.append(frozen(m0 + s0, c))
-                m0 += steps - 1
-                curves[name] = torch.cat(pts + [last[None]]).t().contiguous()
-            for st in statuses:                                # bit 0 repeats what the careful path pass already handled
-                putils.check_status_word(st, fallback_done=True)
-    finally:
-        if guard is not None:
-            guard.__exit__(None, None, None)
-        model.train(was_training)
+        out["target_baseline"] = targets(len(ins) - 1, 1)[0]
+        curves = {}
+        for k, name in enumerate(names):                       # each curve's members in chunks of their own
+            ends = [out["target"][None], out["target_baseline"][None]]
+            inner = [targets(k * (steps - 1) + s0, min(fp.chunk, steps - 1 - s0)) for s0 in range(0, steps - 1, fp.chunk)]
+            curves[name] = torch.cat(ends[:1] + inner + ends[1:] if name == "deletion" else ends[1:] + inner + ends[:1]).t().contiguous()
     frac = np.arange(steps + 1, dtype=np.float64) / steps
     out["fractions"] = torch.from_numpy(frac)
     out["counts"] = torch.from_numpy(counts)
-    w = torch.from_numpy(np.diff(frac)).to(dev)
     for name, cv in curves.items():
-        out[name] = cv
-        d = cv.double()
-        out[name + "_auc"] = ((d[:, :-1] + d[:, 1:]) * 0.5 * w[None, :]).sum(dim=1)
-    return out, trace
+        out[name], out[name + "_auc"] = cv, _auc(cv, frac)
+    return out, fp.trace

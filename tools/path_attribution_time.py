@@ -18,12 +18,12 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _attribution_timing as T  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--limit", type=int, default=420, help="seconds for the child process")
@@ -34,16 +34,11 @@ ap.add_argument("--chunks", default="8,1", help="chunk sizes to time, e.g. 1,2,4
 args = ap.parse_args()
 
 if not args.child:
-    rc = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child",
-                         "--rounds", str(args.rounds), "--warmup", str(args.warmup), "--chunks", args.chunks]).returncode
-    if rc != 0:
-        print(f"path_attribution_time: ended with status {rc}", flush=True)
-    sys.exit(rc)
+    T.run_in_child(__file__, args.limit, ["--rounds", args.rounds, "--warmup", args.warmup, "--chunks", args.chunks])
 
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from paths_amd import _lib  # noqa: E402
 from paths_amd.data_utils.slide import DeviceSlide, DeviceSlideBatch  # noqa: E402
 from paths_amd.saliency import input_gradients, integrated_gradients  # noqa: E402
 
@@ -56,14 +51,6 @@ D = sb.dim
 chunks = [int(c) for c in args.chunks.split(",")]
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
 def loop32():
     for _ in range(STEPS):
         input_gradients(model, sb, keep, L)
@@ -74,34 +61,12 @@ runs["input_gradients_x32"] = loop32
 for name in runs:
     for _ in range(args.warmup):
         runs[name]()
-ms = {name: [] for name in runs}
-for r in range(args.rounds):
-    for name in (tuple(runs) if r % 2 == 0 else tuple(runs)[::-1]):
-        ms[name].append(timed(runs[name]))
+ms = T.alternating(runs, args.rounds)
 
 # --- the two row kernels of every level alone: a call whose launches of them are bracketed by events on an idle device
-real_call, seen = _lib.call, []
-
-
-def timed_call(name, *a):
-    if name not in ("paths_path_points", "paths_path_accumulate"):
-        return real_call(name, *a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream = torch.cuda.ExternalStream(a[-1], device=dev)
-    e0.record(stream)
-    real_call(name, *a)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    C = a[10]                                    # (both entry points: ..., rows_per_slide, D, B, C at positions 7..10)
-    seen.append((name, a[7], C, e0.elapsed_time(e1) * 1e3))
-
-
-_lib.call = timed_call
-try:
+with T.event_timed(("paths_path_points", "paths_path_accumulate"), dev) as raw:
     out, trace = integrated_gradients(model, sb, keep, L, steps=STEPS, chunk=8)
-finally:
-    _lib.call = real_call
+seen = [(name, a[7], a[10], us) for name, a, us in raw]     # (both entry points: ..., rows_per_slide, D, B, C at positions 7..10)
 Ns = [int(t["grad_norm"].shape[1]) for t in trace]
 valid = [int(t["num_ims"].sum()) for t in trace]
 
@@ -119,7 +84,7 @@ def per_level(name, nbytes):
 
 points = per_level("paths_path_points", lambda m: (1 + 8) * m * D * 4)
 accum = per_level("paths_path_accumulate", lambda m: (8 + 1) * m * D * 4 + 16 * m)
-summ = lambda v: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+summ = T.summ
 res = {"workload": f"one slide, K = {K} x {L} levels, fp32 grids, dropout off, steps = {STEPS}, gausslegendre",
        "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
 for name in runs:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the deletion / insertion curves along the frozen path (paths_amd.saliency.perturbation_curves, csrc/perturb_rows.hip) for
+"""Cost of the deletion / insertion curves along the frozen path (paths_amd.saliency.perturbation_curves, csrc/perturb_rows.hip, csrc/path_rows.hip) for
 ONE slide and for EIGHT slides at K = 2048 x 5 levels, dropout off, steps = 16, mode = "both", scores = "grad_x_input".  One JSON line
 per batch size:
 
@@ -21,12 +21,12 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _attribution_timing as T  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--limit", type=int, default=420, help="seconds for the child process")
@@ -37,16 +37,12 @@ ap.add_argument("--batches", default="1,8", help="batch sizes to time")
 args = ap.parse_args()
 
 if not args.child:
-    rc = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child",
-                         "--rounds", str(args.rounds), "--warmup", str(args.warmup), "--batches", args.batches]).returncode
-    if rc != 0:
-        print(f"perturbation_time: ended with status {rc}", flush=True)
-    sys.exit(rc)
+    T.run_in_child(__file__, args.limit, ["--rounds", args.rounds, "--warmup", args.warmup, "--batches", args.batches])
 
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from paths_amd import _lib, utils as putils  # noqa: E402
+from paths_amd import utils as putils  # noqa: E402
 from paths_amd.data_utils.slide import DeviceSlide, DeviceSlideBatch  # noqa: E402
 from paths_amd.saliency import perturbation_curves  # noqa: E402
 
@@ -58,15 +54,7 @@ keep, L = cfg.top_k_patches, cfg.num_levels
 ids = bench.CPU_SLIDE_IDS[K]
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-summ = lambda v: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+summ = T.summ
 
 for B in [int(b) for b in args.batches.split(",")]:
     sb = DeviceSlideBatch([DeviceSlide.synthetic(bench.CPU_DSEED, ids[i % len(ids)], bench.BASE_SHAPES[K], device=dev) for i in range(B)])
@@ -80,32 +68,13 @@ for B in [int(b) for b in args.batches.split(",")]:
     for name in runs:
         for _ in range(args.warmup):
             runs[name]()
-    ms = {name: [] for name in runs}
-    for r in range(args.rounds):
-        for name in (tuple(runs) if r % 2 == 0 else tuple(runs)[::-1]):
-            ms[name].append(timed(runs[name]))
+    ms = T.alternating(runs, args.rounds)
 
     # --- the two kernels alone: a call whose launches of them are bracketed by events on an idle device
-    real_call, seen = _lib.call, []
-
-    def timed_call(name, *a):
-        if name not in ("paths_rank_joint", "paths_path_mask_points"):
-            return real_call(name, *a)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        stream = torch.cuda.ExternalStream(a[-1], device=dev)
-        e0.record(stream)
-        real_call(name, *a)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        # rank_joint: ..., L, B, n_tot at 4..6;  path_mask_points: ..., rows_per_slide, D, B, C at 8..11
-        seen.append((name, a[6], 0, e0.elapsed_time(e1) * 1e3) if name == "paths_rank_joint" else (name, a[8], a[11], e0.elapsed_time(e1) * 1e3))
-
-    _lib.call = timed_call
-    try:
+    with T.event_timed(("paths_rank_joint", "paths_path_mask_points"), dev) as raw:
         out, trace = perturbation_curves(model, sb, keep, L, "grad_x_input", steps=STEPS, mode="both")
-    finally:
-        _lib.call = real_call
+    # rank_joint: ..., L, B, n_tot at 4..6;  path_mask_points: ..., rows_per_slide, D, B, C at 8..11
+    seen = [(name, a[6], 0, us) if name == "paths_rank_joint" else (name, a[8], a[11], us) for name, a, us in raw]
     chunk = max(1, 8 // B)
     Ns = [int(t["perturbation_rank"].shape[1]) for t in trace]
     valid = [int(t["num_ims"].sum()) for t in trace]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the gradient x input attributions (paths_amd.saliency.input_gradients, csrc/saliency_rows.hip) at the headline shape: 8
+"""Cost of the gradient x input attributions (paths_amd.saliency.input_gradients, csrc/path_rows.hip) at the headline shape: 8
 slides at K = 2048 x 5 levels, dropout off.  One JSON line:
 
     input_gradients_ms      one whole pass (forward recursion, backward without weight gradients, dX, row reductions)
@@ -16,12 +16,13 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _attribution_timing as T  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--limit", type=int, default=420, help="seconds for the child process")
@@ -32,17 +33,13 @@ ap.add_argument("--warmup", type=int, default=3)
 args = ap.parse_args()
 
 if not args.child:
-    rc = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child",
-                         "--steps", str(args.steps), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]).returncode
-    if rc != 0:
-        print(f"saliency_time: ended with status {rc}", flush=True)
-    sys.exit(rc)
+    T.run_in_child(__file__, args.limit, ["--steps", args.steps, "--rounds", args.rounds, "--warmup", args.warmup])
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from paths_amd import _lib, backward as bw  # noqa: E402
+from paths_amd import backward as bw  # noqa: E402
 from paths_amd import utils as putils  # noqa: E402
 from paths_amd.data_utils.slide import DeviceSlide, DeviceSlideBatch  # noqa: E402
 from paths_amd.saliency import input_gradients  # noqa: E402
@@ -84,38 +81,15 @@ def run_train(steps):
 runs = {"input_gradients": run_saliency, "forward_backward": run_train}
 for name in runs:
     runs[name](args.warmup)
-ms = {name: [] for name in runs}
-for r in range(args.rounds):
-    for name in (tuple(runs) if r % 2 == 0 else tuple(runs)[::-1]):
-        ms[name].append(runs[name](args.steps))
+ms = T.alternating(runs, args.rounds, lambda run: run(args.steps))
 
 # --- the row kernel of every level alone: a pass whose paths_saliency_rows calls are bracketed by events on an idle device
-real_call, rows_us = _lib.call, []
-
-
-def timed_call(name, *a):
-    if name != "paths_saliency_rows":
-        return real_call(name, *a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream = torch.cuda.ExternalStream(a[-1], device=dev)
-    e0.record(stream)
-    real_call(name, *a)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    rows_us.append(e0.elapsed_time(e1) * 1e3)
-
-
 per_level = []
 for rep in range(5):
-    rows_us.clear()
-    _lib.call = timed_call
-    try:
+    with T.event_timed(("paths_saliency_rows",), dev) as seen:
         out, trace = input_gradients(model, sb, keep, L)
-    finally:
-        _lib.call = real_call
-    assert len(rows_us) == L and int(out["status"].item()) == 0
-    per_level.append(list(rows_us))
+    assert len(seen) == L and int(out["status"].item()) == 0
+    per_level.append([us for _, _, us in seen])
 Ms = [int(t["grad_norm"].numel()) for t in trace]
 rows_med = [statistics.median(r[l] for r in per_level) for l in range(L)]
 rows = [{"level": l, "M": Ms[l], "MB": round((2 * Ms[l] * D * 4 + 8 * Ms[l]) / 1e6, 1), "us": round(rows_med[l], 1),
@@ -144,7 +118,7 @@ for l in range(L):
                  "TFLOP_per_s": round(2.0 * M * D * G / (statistics.median(ts) * 1e-6) / 1e12, 1)})
     del dG, dy, dx
 
-summ = lambda v: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
+summ = T.summ
 a, b = statistics.median(ms["input_gradients"]), statistics.median(ms["forward_backward"])
 print(json.dumps({
     "workload": f"K = {K} x {L} levels, {SPG} slides per batch, fp32 grids, dropout off", "device": torch.cuda.get_device_name(dev),
