@@ -713,6 +713,36 @@ int paths_rank_joint(const float* scores, const int* seg_end, const int* level_o
 int paths_path_mask_points(const float* x, int64_t ldx, const float* base, const int* rank, int64_t ldr, const int* thr, const int* insert,
                            const int64_t* num_ims, int rows_per_slide, int D, int B, int C, float* out, paths_stream_t stream);
 
+/* Removal curves on the free path (paths_amd/saliency.py:removal_curves; csrc/perturb_rows.hip): a member of a curve is a
+ * slide with other tissue masks (DeviceSlide.with_masks), so the two kernels work on uint8 cell masks, one launch per level.
+ *
+ * paths_removal_masks: the masks of C members of B slides at one level.  src_ptrs: DEVICE table [B] of the addresses of the slides'
+ * source masks (uint8 [gx[b], gy[b]], row-major; NULL table: every source is all zero); gx / gy: DEVICE tables [B] int32 of the
+ * level's grid dims, max_cells >= every gx[b] * gy[b] (it sizes the launch); locs [B, N, 2] int64: the recorded locations in pixels,
+ * cell = locs / patch_size, linear index cx * gy[b] + cy; num_ims [B] int64; rank: this level's slice of the joint rank,
+ * rank[b * ldr + r] (ldr >= N); thr [C, B] int32 DEVICE table.  Row r of slide b is CHOSEN by member c iff r < num_ims[b] and
+ * 0 <= rank < thr[c, b] (rank and thr both NULL: every valid row).  masks [C, B, ldm] uint8 (ldm >= max_cells, a multiple of 16,
+ * 16-byte aligned base): bytes 0 .. gx[b] gy[b] - 1 of member (c, b) are the source mask with the cells of its chosen rows set to 0
+ * (set != 0: to 1); the rest of the stride is not written.  left [C, B] int32: the non-zero bytes of that result.  The locations of
+ * rows that are not chosen are never read (nor the ranks at or beyond num_ims[b]); a chosen location outside the grid is ignored.
+ * Two valid rows of a slide never share a cell (the caller's contract): left is an integer count reduced in a fixed order, every
+ * byte is written once - no atomics, no workspace, bit-identical on repeat.  16-byte copies where the source is 16-byte aligned.
+ *
+ * paths_visited_overlap: overlap[v] (int32 [C * B], v = c * B + b) = the number of rows r < num_m[v] of locs_m [C * B, Nm, 2] whose
+ * cell is non-zero in bitmap[b * ldb + cell] (uint8; the cells the recorded pass of slide b visited at this level: a
+ * paths_removal_masks result with set != 0 over a NULL source).  Integer count, fixed order, no atomics, no workspace.
+ *
+ * paths_level0_mask_rows: behind paths_level0_batch for a batch of masked views.  The reference loads every level-0 cell, background
+ * included (an all-zero row); so for every level-0 cell j < gx[b] gy[b] whose mask byte (mask_ptrs: DEVICE table [B]) is 0 the copy
+ * fts[b, j, :] (NULL: none) is zeroed and row_ptrs[b, j] (NULL: none) is pointed at zero_row.  Other rows are not touched. */
+int paths_removal_masks(const int64_t* src_ptrs, const int* gx, const int* gy, int64_t max_cells, const int64_t* locs, int patch_size,
+                        const int64_t* num_ims, const int* rank, int64_t ldr, const int* thr, int N, int B, int C, int set, uint8_t* masks,
+                        int64_t ldm, int* left, paths_stream_t stream);
+int paths_visited_overlap(const uint8_t* bitmap, int64_t ldb, const int* gx, const int* gy, const int64_t* locs_m, const int64_t* num_m,
+                          int patch_size, int Nm, int B, int C, int* overlap, paths_stream_t stream);
+int paths_level0_mask_rows(const int64_t* mask_ptrs, const int* gx, const int* gy, int B, int D, int64_t n0, float* fts, int64_t* row_ptrs,
+                           const float* zero_row, paths_stream_t stream);
+
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */
 int paths_scale_add_rows(const float* x, const float* alpha, const float* h, const int64_t* num_ims, int rows_per_slide,

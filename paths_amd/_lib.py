@@ -136,6 +136,9 @@ SIGNATURES = {
     "paths_path_accumulate": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "paths_rank_joint": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "paths_path_mask_points": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "paths_removal_masks": [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
+    "paths_visited_overlap": [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "paths_level0_mask_rows": [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
 }
 # fp16 slide grids (DeviceSlide dtype torch.float16): the same arguments as the fp32 entry points above
 for _n in ("paths_lstm_cell_x6", "paths_importance_proj_x6", "paths_importance_qkv_x6", "paths_gemm_add_nt_x6", "paths_gather_rows",

@@ -8,6 +8,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
   return v;
 }
+__device__ __forceinline__ int wave_sum_i(int v) {            // integer counts: exact in any order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));

@@ -10,7 +10,28 @@
 // the result does not depend on the launch.  Padded rows and rows of levels that are not chosen are never read as scores.
 // Per slide: n_tot^2 64-bit compares; every workgroup builds all n_tot keys once (the valid scores are read n_tot / RJ_THREADS + 1
 // times, from cache) and each of its four waves reads all of them back from LDS.  4 n_tot bytes in, 4 n_tot + 4 out, algorithmically.
+//
+// The removal curves on the free path (paths_amd/saliency.py:removal_curves) perturb a slide through its tissue masks, not
+// its rows: a member of a curve is the slide's grids with other uint8 [X, Y] masks (DeviceSlide.with_masks).
+//
+// removal_masks: member (c, b)'s mask of one level = the source mask of slide b with the cell of every valid recorded row of rank <
+// thr[c, b] cleared (mode 1: set).  A workgroup owns RM_CELLS cells of one member: it marks the chosen rows' cells that fall into
+// its range in an LDS flag tile, then writes source-merged-with-flags in one pass of 16-byte copies (a source that is not 16-byte
+// aligned and the ragged tail go byte by byte) - every output byte is written once, by one thread: no atomics, no ordering between
+// workgroups.  left[c, b], the cells still set, is an integer count by the member's first workgroup alone: the source's non-zero
+// bytes minus the chosen rows whose source byte is set (plus those whose byte is clear, mode 1) - two valid rows never share a
+// cell - reduced over the workgroup in a fixed order.  cells in + C cells out per slide; N ranks and the chosen locations re-read
+// per workgroup from cache.
+//
+// visited_overlap: per virtual slide v = c B + b the number of the member's valid rows whose cell is set in slide b's bitmap of
+// recorded cells (a removal_masks mask in mode 1 over a NULL source).  One workgroup per v, a wave per 64-row chunk, integer wave
+// sums, the four waves' partials added in wave order.
+//
+// level0_mask_rows: the reference loads EVERY level-0 cell, background included (a background cell is an all-zero row there);
+// for a masked view the rows of cleared level-0 cells are therefore made the zero row (the copy zeroed / the row address pointed at
+// the zero row) behind paths_level0_batch.
 #include "common.h"
+#include "lanes.h"
 #include "rank_key.h"
 
 constexpr int RJ_THREADS = 256;      // elements per workgroup
@@ -84,6 +105,128 @@ rank_joint_kernel(const float* __restrict__ scores, const int* __restrict__ seg_
   if (i < n_tot) out[i] = mine_ok ? cnt : -1;
 }
 
+// ---- removal masks and path overlap
+constexpr int RM_THREADS = 256;
+constexpr int RM_CELLS = RM_THREADS * 16;        // cells (bytes) per workgroup: one 16-byte vector per thread
+
+// the cell index of a recorded location, -1 when it lies outside the grid (device data: never trusted)
+__device__ __forceinline__ int64_t cell_of(const int64_t* __restrict__ loc, int patch_size, int X, int Y) {
+  const int64_t cx = loc[0] / patch_size, cy = loc[1] / patch_size;
+  return (loc[0] < 0 || loc[1] < 0 || cx >= X || cy >= Y) ? -1 : cx * Y + cy;
+}
+
+// sum over the workgroup's RM_THREADS threads, valid in thread 0: wave sums, then the waves' partials in wave order
+__device__ __forceinline__ int block_sum_i(int v, int* s_part) {
+  v = wave_sum_i(v);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < RM_THREADS / 64; ++w) t += s_part[w];
+  return t;
+}
+
+__global__ void __launch_bounds__(RM_THREADS)
+removal_masks_kernel(const int64_t* __restrict__ src_ptrs, const int* __restrict__ gx, const int* __restrict__ gy,
+                     const int64_t* __restrict__ locs, int patch_size, const int64_t* __restrict__ num_ims, const int* __restrict__ rank,
+                     int64_t ldr, const int* __restrict__ thr, int N, int B, int set, uint8_t* __restrict__ masks, int64_t ldm,
+                     int* __restrict__ left) {
+  __shared__ __attribute__((aligned(16))) uint8_t flag[RM_CELLS];
+  __shared__ int s_part[RM_THREADS / 64];
+  const int b = blockIdx.y, c = blockIdx.z, tid = threadIdx.x;
+  const int X = gx[b], Y = gy[b];
+  const int64_t cells = min((int64_t)X * Y, ldm);
+  const int64_t c0 = (int64_t)blockIdx.x * RM_CELLS;
+  if (c0 >= cells && blockIdx.x != 0) return;                              // (workgroup-uniform)
+  const uint8_t* src = src_ptrs != nullptr ? reinterpret_cast<const uint8_t*>(src_ptrs[b]) : nullptr;
+  uint8_t* out = masks + ((int64_t)c * B + b) * ldm;
+  const int n = (int)max((int64_t)0, min(num_ims[b], (int64_t)N));
+  const int t = thr != nullptr ? thr[(int64_t)c * B + b] : 0x7fffffff;
+  reinterpret_cast<u32x4*>(flag)[tid] = u32x4{0u, 0u, 0u, 0u};
+  __syncthreads();
+  int hit = 0;                                                             // chosen rows on a set source cell (whole slide)
+  int chosen = 0;
+  for (int r = tid; r < n; r += RM_THREADS) {
+    const int rk = rank != nullptr ? rank[b * ldr + r] : 0;
+    if (rk < 0 || rk >= t) continue;
+    const int64_t cell = cell_of(locs + ((int64_t)b * N + r) * 2, patch_size, X, Y);
+    if (cell < 0 || cell >= cells) continue;
+    if (cell >= c0 && cell < c0 + RM_CELLS) flag[cell - c0] = 0xFF;
+    if (blockIdx.x == 0) {
+      ++chosen;
+      hit += (src != nullptr && src[cell] != 0) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  const int64_t v0 = c0 + (int64_t)tid * 16;
+  const bool vec = src == nullptr || (reinterpret_cast<uintptr_t>(src) & 15) == 0;     // (uniform over the member)
+  if (v0 + 16 <= cells && vec) {
+    const u32x4 f = reinterpret_cast<const u32x4*>(flag)[tid];
+    const u32x4 s = src != nullptr ? *reinterpret_cast<const u32x4*>(src + v0) : u32x4{0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(out + v0) = set ? ((s & ~f) | (f & 0x01010101u)) : (s & ~f);
+  } else {
+    for (int64_t i = v0; i < min(v0 + 16, cells); ++i) {
+      const uint8_t f = flag[i - c0], s = src != nullptr ? src[i] : (uint8_t)0;
+      out[i] = f ? (set ? (uint8_t)1 : (uint8_t)0) : s;
+    }
+  }
+  if (blockIdx.x != 0) return;
+  int cnt = 0;                                                             // the source's non-zero bytes
+  if (src != nullptr) {
+    if (vec) {
+      const int64_t nv = cells >> 4;
+      for (int64_t q = tid; q < nv; q += RM_THREADS) {
+        const u32x4 s = reinterpret_cast<const u32x4*>(src)[q];
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) cnt += ((s[w] >> (8 * k)) & 0xFFu) != 0u;
+      }
+      for (int64_t i = (nv << 4) + tid; i < cells; i += RM_THREADS) cnt += src[i] != 0;
+    } else {
+      for (int64_t i = tid; i < cells; i += RM_THREADS) cnt += src[i] != 0;
+    }
+  }
+  cnt += set ? chosen - hit : -hit;
+  const int total = block_sum_i(cnt, s_part);
+  if (tid == 0) left[(int64_t)c * B + b] = total;
+}
+
+__global__ void __launch_bounds__(RM_THREADS)
+visited_overlap_kernel(const uint8_t* __restrict__ bitmap, int64_t ldb, const int* __restrict__ gx, const int* __restrict__ gy,
+                       const int64_t* __restrict__ locs_m, const int64_t* __restrict__ num_m, int patch_size, int Nm, int B,
+                       int* __restrict__ overlap) {
+  __shared__ int s_part[RM_THREADS / 64];
+  const int v = blockIdx.x, b = v % B;
+  const int X = gx[b], Y = gy[b];
+  const int64_t cells = min((int64_t)X * Y, ldb);
+  const uint8_t* bm = bitmap + (int64_t)b * ldb;
+  const int n = (int)max((int64_t)0, min(num_m[v], (int64_t)Nm));
+  int cnt = 0;
+  for (int r = threadIdx.x; r < n; r += RM_THREADS) {                       // (a wave takes 64 consecutive rows per step)
+    const int64_t cell = cell_of(locs_m + ((int64_t)v * Nm + r) * 2, patch_size, X, Y);
+    cnt += (cell >= 0 && cell < cells && bm[cell] != 0) ? 1 : 0;
+  }
+  const int total = block_sum_i(cnt, s_part);
+  if (threadIdx.x == 0) overlap[v] = total;
+}
+
+// one workgroup per level-0 cell (paths_level0_batch's geometry): a cleared cell's copy becomes zeros, its row address the zero row's
+__global__ void __launch_bounds__(256)
+level0_mask_rows_kernel(const int64_t* __restrict__ mask_ptrs, const int* __restrict__ gx, const int* __restrict__ gy, int D, int64_t n0,
+                        float* __restrict__ fts, int64_t* __restrict__ row_ptrs, const float* __restrict__ zero_row) {
+  const int b = blockIdx.y;
+  const int64_t j = blockIdx.x;
+  if (j >= (int64_t)gx[b] * gy[b]) return;
+  if (reinterpret_cast<const uint8_t*>(mask_ptrs[b])[j] != 0) return;
+  const int64_t o = (int64_t)b * n0 + j;
+  if (fts != nullptr) {
+    const f32x4 z{0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < D / 4; i += 256) stg_f32x4(fts + o * D + 4 * i, z);
+  }
+  if (row_ptrs != nullptr && threadIdx.x == 0) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(zero_row);
+}
+
 extern "C" {
 
 int paths_rank_joint_tile(void) { return RJ_TILE; }
@@ -101,6 +244,59 @@ int paths_rank_joint(const float* scores, const int* seg_end, const int* level_o
   hipLaunchKernelGGL(rank_joint_kernel, dim3((unsigned)((n_tot + RJ_THREADS - 1) / RJ_THREADS), (unsigned)B), dim3(RJ_THREADS), 0, stream,
                      scores, seg_end, level_on, num_ims, L, B, n_tot, ascending != 0 ? 1 : 0, rank, count);
   PATHS_LAUNCH_CHECK("rank_joint");
+  return PATHS_OK;
+}
+
+int paths_removal_masks(const int64_t* src_ptrs, const int* gx, const int* gy, int64_t max_cells, const int64_t* locs, int patch_size,
+                        const int64_t* num_ims, const int* rank, int64_t ldr, const int* thr, int N, int B, int C, int set, uint8_t* masks,
+                        int64_t ldm, int* left, hipStream_t stream) {
+  PATHS_REQUIRE(gx != nullptr && gy != nullptr && locs != nullptr && num_ims != nullptr && masks != nullptr && left != nullptr,
+                "removal_masks: null pointer (gx, gy, locs, num_ims, masks and left are required)");
+  PATHS_REQUIRE((rank == nullptr) == (thr == nullptr), "removal_masks: rank and thr come together (both NULL: every valid row is chosen)");
+  PATHS_REQUIRE(N > 0 && patch_size > 0, "removal_masks: N (%d) and patch_size (%d) must be positive", N, patch_size);
+  PATHS_REQUIRE(B > 0 && B <= 65535 && C > 0 && C <= 65535, "removal_masks: B (%d) and C (%d) must be in [1, 65535]", B, C);
+  PATHS_REQUIRE(max_cells > 0 && max_cells <= ((int64_t)1 << 31) - RM_CELLS, "removal_masks: max_cells (%lld) must be in [1, 2^31)",
+                (long long)max_cells);
+  PATHS_REQUIRE(ldm >= max_cells && ldm % 16 == 0, "removal_masks: mask stride (%lld) must be a multiple of 16 and at least max_cells (%lld)",
+                (long long)ldm, (long long)max_cells);
+  PATHS_REQUIRE(rank == nullptr || ldr >= N, "removal_masks: rank stride (%lld) must be at least N (%d)", (long long)ldr, N);
+  PATHS_REQUIRE((uintptr_t)masks % 16 == 0 && (uintptr_t)left % 4 == 0 && (uintptr_t)rank % 4 == 0 && (uintptr_t)thr % 4 == 0 &&
+                    (uintptr_t)gx % 4 == 0 && (uintptr_t)gy % 4 == 0 && (uintptr_t)locs % 8 == 0 && (uintptr_t)num_ims % 8 == 0 &&
+                    (uintptr_t)src_ptrs % 8 == 0,
+                "removal_masks: masks must be 16-byte aligned, left, rank, thr, gx and gy 4-byte, locs, num_ims and src_ptrs 8-byte");
+  hipLaunchKernelGGL(removal_masks_kernel, dim3((unsigned)((max_cells + RM_CELLS - 1) / RM_CELLS), (unsigned)B, (unsigned)C), dim3(RM_THREADS), 0,
+                     stream, src_ptrs, gx, gy, locs, patch_size, num_ims, rank, ldr, thr, N, B, set != 0 ? 1 : 0, masks, ldm, left);
+  PATHS_LAUNCH_CHECK("removal_masks");
+  return PATHS_OK;
+}
+
+int paths_visited_overlap(const uint8_t* bitmap, int64_t ldb, const int* gx, const int* gy, const int64_t* locs_m, const int64_t* num_m,
+                          int patch_size, int Nm, int B, int C, int* overlap, hipStream_t stream) {
+  PATHS_REQUIRE(bitmap != nullptr && gx != nullptr && gy != nullptr && locs_m != nullptr && num_m != nullptr && overlap != nullptr,
+                "visited_overlap: null pointer (bitmap, gx, gy, locs_m, num_m and overlap are required)");
+  PATHS_REQUIRE(Nm > 0 && patch_size > 0 && ldb > 0, "visited_overlap: Nm (%d), patch_size (%d) and the bitmap stride (%lld) must be positive", Nm,
+                patch_size, (long long)ldb);
+  PATHS_REQUIRE(B > 0 && C > 0 && (int64_t)B * C <= 0x7fffffff, "visited_overlap: B (%d) and C (%d) must be positive, B * C below 2^31", B, C);
+  PATHS_REQUIRE((uintptr_t)gx % 4 == 0 && (uintptr_t)gy % 4 == 0 && (uintptr_t)overlap % 4 == 0 && (uintptr_t)locs_m % 8 == 0 &&
+                    (uintptr_t)num_m % 8 == 0,
+                "visited_overlap: gx, gy and overlap must be 4-byte aligned, locs_m and num_m 8-byte aligned");
+  hipLaunchKernelGGL(visited_overlap_kernel, dim3((unsigned)(B * C)), dim3(RM_THREADS), 0, stream, bitmap, ldb, gx, gy, locs_m, num_m, patch_size,
+                     Nm, B, overlap);
+  PATHS_LAUNCH_CHECK("visited_overlap");
+  return PATHS_OK;
+}
+
+int paths_level0_mask_rows(const int64_t* mask_ptrs, const int* gx, const int* gy, int B, int D, int64_t n0, float* fts, int64_t* row_ptrs,
+                           const float* zero_row, hipStream_t stream) {
+  PATHS_REQUIRE(mask_ptrs != nullptr && gx != nullptr && gy != nullptr, "level0_mask_rows: null pointer (mask_ptrs, gx and gy are required)");
+  PATHS_REQUIRE(B > 0 && B <= 65535 && n0 > 0 && n0 <= 0x7fffffff && D > 0 && D % 4 == 0, "level0_mask_rows: bad shape (B %d, n0 %lld, D %d)", B,
+                (long long)n0, D);
+  PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr),
+                "level0_mask_rows: the rows are a copy (fts) or row pointers with the zero row");
+  PATHS_REQUIRE((uintptr_t)fts % 16 == 0, "level0_mask_rows: fts must be 16-byte aligned");
+  hipLaunchKernelGGL(level0_mask_rows_kernel, dim3((unsigned)n0, (unsigned)B), dim3(256), 0, stream, mask_ptrs, gx, gy, D, n0, fts, row_ptrs,
+                     zero_row);
+  PATHS_LAUNCH_CHECK("level0_mask_rows");
   return PATHS_OK;
 }
 

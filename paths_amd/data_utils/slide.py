@@ -14,6 +14,9 @@ refuses values an fp16 grid cannot hold.  bf16 is not supported.
 :class:`HostSlide` is the sibling for cohorts that do not fit in HBM: its grids stay in PINNED host memory, only the tissue masks
 live on the device, and the recursion fetches just the rows it selects over the host link (paths_stage_rows).
 
+:meth:`DeviceSlide.with_masks` / :meth:`HostSlide.with_masks` give a MASKED VIEW of a stored slide: the same grids behind other tissue
+masks - a slide with some of its tissue turned to background, at the cost of the masks alone (saliency.removal_curves).
+
 :class:`OnDemandSlide` holds no grid at all: the recursion asks the caller's ``encode`` for the features of exactly the cells it is
 about to visit (reference ``RawSlide.recurse``, data_utils/slide.py:173-198).
 """
@@ -67,8 +70,28 @@ def to_float16(grid, chunk_rows: int = 1 << 16) -> Tuple[torch.Tensor, float]:
     return out.reshape(g.shape), err
 
 
+def _masked_view(slide, masks):
+    """The view behind DeviceSlide.with_masks / HostSlide.with_masks: a shallow copy of ``slide`` that carries ``masks``."""
+    masks = list(masks)
+    if len(masks) != slide.num_levels:
+        raise ValueError(f"with_masks: one mask per level ({slide.num_levels}) expected, got {len(masks)}")
+    for l, (m, own) in enumerate(zip(masks, slide.masks)):
+        if not torch.is_tensor(m) or m.dtype != torch.uint8 or tuple(m.shape) != tuple(slide.shape(l)) or not m.is_contiguous():
+            got = f"{m.dtype} {tuple(m.shape)}" if torch.is_tensor(m) else type(m).__name__
+            raise ValueError(f"with_masks: level {l} needs a contiguous uint8 [X, Y] = {list(slide.shape(l))} tensor, got {got}")
+        if m.device != own.device:
+            raise ValueError(f"with_masks: the mask of level {l} lives on {m.device}, the slide's masks on {own.device}")
+    view = object.__new__(type(slide))
+    view.__dict__.update(slide.__dict__)
+    view.masks = masks
+    view.masked_view = True
+    view._absmax = slide.feature_absmax()             # the recorded max|x| of the source (its cached value: no launch)
+    return view
+
+
 class DeviceSlide:
     host_resident = False           # the grids live in HBM (HostSlide: in pinned host memory)
+    masked_view = False             # (with_masks: the same grids behind other tissue masks)
 
     def __init__(self, grids: Sequence[torch.Tensor], patch_size: int = 256, slide_id: str = "", subtype=None):
         """``grids``: device tensors [X, Y, D], all torch.float32 or all torch.float16 (kept as they are: no fp32 copy is made)."""
@@ -102,6 +125,14 @@ class DeviceSlide:
         if self._absmax is None:
             self._absmax = _lib.float_from_bits(int(self._absmax_bits.item()))
         return self._absmax
+
+    def with_masks(self, masks: Sequence[torch.Tensor]):
+        """A masked view of this slide: the same ``grids`` (shared, not copied), dtype, ``patch_size`` and recorded max|x| behind the
+        given per-level tissue masks - contiguous uint8 [X, Y] tensors on the device of the slide's own masks (ValueError otherwise).  A
+        cell whose byte is 0 is background to the recursion: the child filter drops it, and at level 0 - where every cell is loaded,
+        background included - it reads as the all-zero row a background cell is.  Nothing is launched and nothing is allocated; batches
+        take views like any slide, several views of one slide in one batch included."""
+        return _masked_view(self, masks)
 
     @property
     def num_levels(self) -> int:
@@ -250,6 +281,8 @@ class HostSlide:
         # the host must not re-use or free the bounce buffer's view of the last chunk early; the pass is once per slide
         torch.cuda.current_stream(dev).synchronize()
 
+    masked_view = False
+    with_masks = DeviceSlide.with_masks
     feature_absmax = DeviceSlide.feature_absmax
     num_levels = DeviceSlide.num_levels
     shape = DeviceSlide.shape
@@ -335,6 +368,7 @@ class DeviceSlideBatch:
         if len(kinds) != 1:
             raise ValueError("DeviceSlideBatch: slides of one batch are all resident (DeviceSlide) or all host-resident (HostSlide)")
         self.host_resident = kinds.pop()
+        self.masked = any(getattr(s, "masked_view", False) for s in self.slides)     # (level 0 then reads cleared cells as zero rows)
         dev = (self.slides[0].masks if self.host_resident else self.slides[0].grids)[0].device
         L = min(s.num_levels for s in self.slides)
         self.device, self.num_levels = dev, L
@@ -440,6 +474,10 @@ class OnDemandSlide:
     @property
     def dim(self) -> int:
         return self._dim
+
+    def with_masks(self, masks):
+        raise NotImplementedError("OnDemandSlide.with_masks: an on-demand slide holds no tissue masks (background is what its encoder "
+                                  "returns as all-zero rows); masked views are for DeviceSlide and HostSlide")
 
     def begin_pass(self):
         self.requested = [None] * len(self.shapes)

@@ -8,7 +8,9 @@ trace of :func:`paths_amd.utils.recurse`.
 ``importance_map`` rasterises the importances exactly like the reference's overlay code: every patch of depth d paints
 ``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with weight 1/2 wherever they exist
 (heatmap_visualise.py:147-171).  ``attention_map`` rasterises the special token's attention of one decoder layer (one head or
-the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout and ``saliency_map`` for the gradient attributions.  Rasters are in units of the FINEST level's patches (one
+the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout,
+``saliency_map`` for the gradient attributions and ``removed_map`` for the cells a member of
+:func:`paths_amd.saliency.removal_curves` turned to background.  Rasters are in units of the FINEST level's patches (one
 cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
 """
 from __future__ import annotations
@@ -20,6 +22,8 @@ import numpy as np
 
 # per-row attributions a saliency trace may carry: input_gradients', integrated_gradients' and smooth_grad's
 SALIENCY_KINDS = ("grad_x_input", "grad_norm", "integrated_gradients", "smooth_grad_x_input", "smooth_grad_sq")
+# the joint ranks saliency.removal_curves leaves in its trace, per order
+REMOVAL_RANKS = ("removal_rank_morf", "removal_rank_lerf")
 
 
 def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.ndarray]]:
@@ -36,7 +40,7 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
         if "rollout" in lv:
             d["rollout"] = lv["rollout"][slide, :n].cpu().numpy()                      # [n]
             d["rollout_self"] = float(lv["rollout_self"][slide])
-        for key in SALIENCY_KINDS:                                  # (saliency.input_gradients / integrated_gradients / smooth_grad)
+        for key in SALIENCY_KINDS + REMOVAL_RANKS:                  # (the attribution functions' and removal_curves' per-row entries)
             if key in lv:
                 d[key] = lv[key][slide, :n].cpu().numpy()                              # [n]
         out.append(d)
@@ -122,5 +126,28 @@ def saliency_map(levels: List[Dict[str, np.ndarray]], base_grid, kind: str = "gr
                            % (depth, kind))
         raster = np.zeros(shape, dtype=np.float64)
         _paint(raster, lv["locs"], lv[kind], magnification_factor ** (L - 1 - depth), patch_size)
+        maps.append(raster)
+    return maps
+
+
+def removed_map(levels: List[Dict[str, np.ndarray]], base_grid, count: int, order: str = "morf", patch_size: int = 256,
+                magnification_factor: int = 2) -> List[np.ndarray]:
+    """One [X0 * f, Y0 * f] uint8 map per level (f = magnification_factor**(L-1)): 1 over the footprint of every cell the member of
+    :func:`paths_amd.saliency.removal_curves` that removes ``count`` patches (``out["counts"][s, slide]``) turned to background at
+    that level - the patches of joint rank below ``count`` in ``order`` ("morf" / "lerf") -, 0 elsewhere; no fold across levels.
+    ``levels`` from :func:`hierarchy_from_trace` of the trace removal_curves returns."""
+    key = "removal_rank_" + order
+    if key not in REMOVAL_RANKS:
+        raise ValueError("order must be 'morf' or 'lerf', got %r" % (order,))
+    L = len(levels)
+    f = magnification_factor ** (L - 1)
+    shape = (base_grid[0] * f, base_grid[1] * f)
+    maps = []
+    for depth, lv in enumerate(levels):
+        if key not in lv:
+            raise KeyError("level %d carries no %s: take the trace from saliency.removal_curves(order=%r or 'both')" % (depth, key, order))
+        gone = (lv[key] >= 0) & (lv[key] < count)
+        raster = np.zeros(shape, dtype=np.uint8)
+        _paint(raster, lv["locs"][gone], np.ones(int(gone.sum()), np.uint8), magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)
     return maps

@@ -23,6 +23,10 @@ path, ``chunk`` at a time through the level kernels.  The points are built and t
 patches are ranked jointly over the levels (paths_rank_joint, csrc/perturb_rows.hip) and removed from, or restored to, the rows in
 that order (paths_path_mask_points), one no-grad forward along the path per point.
 The four per-row kernels share csrc/path_rows.hip; every call along a frozen path is one :class:`_FrozenPath`.
+
+:func:`removal_curves` leaves the frozen path: the ranked patches are turned to BACKGROUND - masked views of the slides
+(DeviceSlide.with_masks; paths_removal_masks, csrc/perturb_rows.hip), no row is touched - and every point is an ordinary free pass
+in which the top-K reacts; paths_visited_overlap says how far its path moved.
 """
 from __future__ import annotations
 
@@ -507,9 +511,9 @@ def _level_scores(scores, trace, num_levels: int, shapes, dev) -> List[torch.Ten
     return out
 
 
-def _rank_levels(fp: _FrozenPath, scores, chosen: Sequence[int], descending: bool):
+def _rank_levels(fp: _FrozenPath, scores, chosen: Sequence[int], descending: bool, key: str = "perturbation_rank"):
     """The joint rank of the visited patches of the ``chosen`` levels by ``scores`` (one launch), with the call's ONE host check.
-    Returns (rank per level [B, N_l] - the records gain it as ``perturbation_rank`` -, the ranked patches per slide [B] on the host)."""
+    Returns (rank per level [B, N_l] - the records gain it as ``key`` -, the ranked patches per slide [B] on the host)."""
     B, dev = len(fp.batch), fp.batch.device
     Ns = [int(x.shape[1]) for x in fp.xs]
     sc = torch.cat(_level_scores(scores, fp.trace, fp.num_levels, [(B, n) for n in Ns], dev), dim=1).contiguous()
@@ -522,7 +526,7 @@ def _rank_levels(fp: _FrozenPath, scores, chosen: Sequence[int], descending: boo
         raise ValueError(f"scores: NaN among the valid patches of slide(s) {np.nonzero(host[B:])[0].tolist()}")
     ranks = [rank[:, e - n:e] for e, n in zip(seg, Ns)]
     for rec, rk in zip(fp.trace, ranks):
-        rec["perturbation_rank"] = rk
+        rec[key] = rk
     return ranks, host[:B]
 
 
@@ -540,6 +544,20 @@ def _auc(curve: torch.Tensor, frac: np.ndarray) -> torch.Tensor:
     """Trapezoid of curve [B, steps + 1] over frac, in float64."""
     d, w = curve.double(), torch.from_numpy(np.diff(frac)).to(curve.device)
     return ((d[:, :-1] + d[:, 1:]) * 0.5 * w[None, :]).sum(dim=1)
+
+
+def _chosen_levels(levels, num_levels: int) -> List[int]:
+    chosen = list(range(num_levels)) if levels is None else [int(l) for l in levels]
+    if any(not 0 <= l < num_levels for l in chosen):
+        raise ValueError(f"levels {list(levels)}: level indices must be in [0, {num_levels})")
+    return chosen
+
+
+def _scores_trace_args(scores, trace, num_levels: int):
+    if not isinstance(scores, str) and (torch.is_tensor(scores) or not hasattr(scores, "__len__") or len(scores) != num_levels):
+        raise ValueError(f"scores: the name of a trace entry or a sequence of {num_levels} tensors [B, N_l] expected")
+    if trace is not None and (len(trace) != num_levels or any("keep_idx" not in rec or "keep_count" not in rec for rec in trace[:-1])):
+        raise ValueError(f"trace: {num_levels} records with keep_idx / keep_count below the last level expected")
 
 
 def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: int, scores, trace: Optional[List[dict]] = None,
@@ -574,14 +592,9 @@ def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: 
     _positive_int("steps", steps)
     if mode not in MODES:
         raise ValueError(f"unknown mode {mode!r}: 'deletion', 'insertion' or 'both'")
-    chosen = list(range(num_levels)) if levels is None else [int(l) for l in levels]
-    if any(not 0 <= l < num_levels for l in chosen):
-        raise ValueError(f"levels {list(levels)}: level indices must be in [0, {num_levels})")
+    chosen = _chosen_levels(levels, num_levels)
     fp = _FrozenPath("perturbation_curves", model, slides, keep_patches, num_levels, fn, baseline, chunk, trace)
-    if not isinstance(scores, str) and (torch.is_tensor(scores) or not hasattr(scores, "__len__") or len(scores) != num_levels):
-        raise ValueError(f"scores: the name of a trace entry or a sequence of {num_levels} tensors [B, N_l] expected")
-    if trace is not None and (len(trace) != num_levels or any("keep_idx" not in rec or "keep_count" not in rec for rec in trace[:-1])):
-        raise ValueError(f"trace: {num_levels} records with keep_idx / keep_count below the last level expected")
+    _scores_trace_args(scores, trace, num_levels)
     names = [name for name in ("deletion", "insertion") if mode in (name, "both")]
     with fp, torch.no_grad():
         B, out = len(fp.batch), fp.out
@@ -604,4 +617,170 @@ def perturbation_curves(model, slides, keep_patches: Sequence[int], num_levels: 
     out["counts"] = torch.from_numpy(counts)
     for name, cv in curves.items():
         out[name], out[name + "_auc"] = cv, _auc(cv, frac)
+    return out, fp.trace
+
+
+# ------------------------------------------------------------------------------------------------
+# removal curves on the free path
+# ------------------------------------------------------------------------------------------------
+ORDERS = ("morf", "lerf", "both")
+
+
+def removal_masks(src_ptrs: Optional[torch.Tensor], gx: torch.Tensor, gy: torch.Tensor, max_cells: int, locs: torch.Tensor, patch_size: int,
+                  num_ims: torch.Tensor, rank: Optional[torch.Tensor], thr: Optional[torch.Tensor],
+                  set_cells: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(masks [C, B, ldm] uint8, left [C, B] int32) of one level (include/paths_hip.h: paths_removal_masks): src_ptrs [B] int64 device
+    table of the source masks' addresses (None: all-zero sources), gx / gy [B] int32 device tables, locs [B, N, 2] int64 in pixels,
+    num_ims [B] int64, rank [B, N] int32 (a level's slice of the joint rank: the slide stride is free), thr [C, B] int32 device table
+    (rank and thr None: C = 1, every valid row is chosen).  ldm = max_cells rounded up to 16; the bytes of a member beyond its
+    slide's gx * gy cells are not written."""
+    _lib.require_cuda(src_ptrs, gx, gy, locs, num_ims, rank, thr)
+    B, N = locs.shape[:2]
+    _tables_ok(torch.int64, src_ptrs, locs, num_ims)
+    _tables_ok(torch.int32, gx, gy, thr)
+    assert locs.shape == (B, N, 2) and num_ims.shape == gx.shape == gy.shape == (B,) and (src_ptrs is None or src_ptrs.shape == (B,))
+    assert (rank is None) == (thr is None)
+    C, ldr = 1, N
+    if rank is not None:
+        assert rank.dtype == torch.int32 and rank.shape == (B, N) and rank.stride(1) == 1 and (B == 1 or rank.stride(0) >= N)
+        assert thr.dim() == 2 and thr.shape[1] == B
+        C, ldr = thr.shape[0], (rank.stride(0) if B > 1 else N)
+    ldm = (int(max_cells) + 15) // 16 * 16
+    masks = torch.empty((C, B, ldm), device=locs.device, dtype=torch.uint8)
+    left = torch.empty((C, B), device=locs.device, dtype=torch.int32)
+    p = _lib.ptr
+    _lib.call("paths_removal_masks", p(src_ptrs), p(gx), p(gy), int(max_cells), p(locs), int(patch_size), p(num_ims), p(rank), ldr, p(thr), N, B,
+              C, 1 if set_cells else 0, p(masks), ldm, p(left), _lib.stream())
+    return masks, left
+
+
+def visited_overlap(bitmap: torch.Tensor, gx: torch.Tensor, gy: torch.Tensor, locs_m: torch.Tensor, num_m: torch.Tensor,
+                    patch_size: int) -> torch.Tensor:
+    """overlap [C * B] int32 (include/paths_hip.h: paths_visited_overlap): bitmap [B, ldb] uint8 (the recorded cells of this level),
+    gx / gy [B] int32 device tables, locs_m [C * B, Nm, 2] int64 in pixels and num_m [C * B] int64 of the members' passes."""
+    _lib.require_cuda(bitmap, gx, gy, locs_m, num_m)
+    B, ldb = bitmap.shape
+    V, Nm = locs_m.shape[:2]
+    _tables_ok(torch.uint8, bitmap)
+    _tables_ok(torch.int32, gx, gy)
+    _tables_ok(torch.int64, locs_m, num_m)
+    assert V % B == 0 and locs_m.shape == (V, Nm, 2) and num_m.shape == (V,) and gx.shape == gy.shape == (B,)
+    overlap = torch.empty((V,), device=bitmap.device, dtype=torch.int32)
+    p = _lib.ptr
+    _lib.call("paths_visited_overlap", p(bitmap), ldb, p(gx), p(gy), p(locs_m), p(num_m), int(patch_size), Nm, B, V // B, p(overlap), _lib.stream())
+    return overlap
+
+
+def removal_counts(n: Sequence[int], steps: int, max_fraction: float) -> np.ndarray:
+    """counts [steps + 1, B] int64: the cells turned to background at point s of a slide with n_b ranked patches,
+    (2 s m_b + steps) // (2 steps) with m_b = floor(max_fraction * n_b) - s m_b / steps rounded half up."""
+    m = np.array([int(np.floor(max_fraction * int(nb))) for nb in n], dtype=np.int64)
+    return perturbation_counts(m, steps)
+
+
+def removal_curves(model, slides, keep_patches: Sequence[int], num_levels: int, scores, trace: Optional[List[dict]] = None,
+                   target: Target = "risk", steps: int = 8, order: str = "both", max_fraction: float = 0.5,
+                   levels: Optional[Sequence[int]] = None, chunk: Optional[int] = None) -> Tuple[Dict[str, torch.Tensor], List[dict]]:
+    """Removal curves (Samek et al. 2017) of ``target`` for a per-patch map on the FREE path: removed patches become background and
+    the selection reacts.
+
+    The visited patches of the chosen ``levels`` (None: all) are ranked jointly by ``scores`` as for :func:`perturbation_curves` -
+    ``order`` "morf": most relevant (highest) first, "lerf": least relevant first, "both".  Point s of a curve is the slide with the
+    cells of the counts[s, b] first-ranked patches turned to background, counts[s, b] = (2 s m_b + steps) // (2 steps), m_b =
+    floor(max_fraction n_b), fractions[s] = s / steps * max_fraction.  A point is a masked view of the slide (same grids, other tissue
+    masks) run through the ordinary no-grad :func:`paths_amd.utils.recurse`: a background cell is dropped by the child filter, its
+    subtree is unreachable, the top-K of the remaining patches picks others, and a member whose kept patches have no tissue children
+    takes the careful re-run; at level 0, where every cell is loaded, a removed cell reads as the all-zero row of a background cell.
+    It is what the model computes on the slide with those rows zeroed.  There is no insertion curve: restoring a patch whose
+    ancestors are absent has no meaning here.  A map that ranks what the prediction depends on has a small ``morf_auc`` and a large
+    ``lerf_auc``.
+
+    ``scores`` / ``trace`` / ``levels`` / ``target`` as for :func:`perturbation_curves` (``trace`` None: the :func:`input_gradients`
+    pass is made; a given trace must be reproduced by a pass along its path); with a given trace the lstm = false variant runs too.
+    The records gain ``removal_rank_morf`` / ``removal_rank_lerf`` [B, N] int32.  A member that leaves a slide without level-0 tissue
+    raises ValueError before any point runs.
+
+    Returns (out, trace): ``fractions`` [steps + 1] (float64, CPU), ``counts`` [steps + 1, B] (int64, CPU), ``morf`` / ``lerf``
+    [B, steps + 1] fp32 with ``morf_auc`` / ``lerf_auc`` [B] float64 (trapezoid over fractions) and, with both, ``aopc_gap`` =
+    lerf_auc - morf_auc; ``visited`` / ``path_overlap`` {order: [B, steps + 1, L] int32}: the member's valid rows per level and how
+    many of them sit on a cell the recorded pass visited at that level; ``masks`` {order: per level uint8 [steps, B, ldm]}: the
+    members' masks (member s + 1 of slide b: the first X * Y bytes of [s, b]); ``logits`` / ``target``: the unperturbed free pass
+    (point 0 of both orders, bit for bit); ``status``: the OR of every point's status word.  Points run ``chunk`` members at a time
+    (default max(1, 8 // B)), each order in chunks of its own.  Dropout is off, the model's mode is restored, no ``.grad`` is touched."""
+    from . import utils as putils
+    from .data_utils.slide import DeviceSlideBatch
+    fn = parse_target(target)
+    _positive_int("steps", steps)
+    if order not in ORDERS:
+        raise ValueError(f"unknown order {order!r}: 'morf', 'lerf' or 'both'")
+    if isinstance(max_fraction, bool) or not isinstance(max_fraction, (int, float)) or not 0 < max_fraction <= 1:
+        raise ValueError(f"max_fraction must be in (0, 1], got {max_fraction!r}")
+    chosen = _chosen_levels(levels, num_levels)
+    if trace is None:
+        _require_lstm(model, "removal_curves")
+    fp = _FrozenPath("removal_curves", model, slides, keep_patches, num_levels, fn, None, chunk, trace)
+    _scores_trace_args(scores, trace, num_levels)
+    names = [name for name in ("morf", "lerf") if order in (name, "both")]
+    L = num_levels
+    with fp, torch.no_grad():
+        batch, B, dev = fp.batch, len(fp.batch), fp.batch.device
+        ps = model.procs[0].config.patch_size
+        shapes = [[s.shape(l) for s in batch.slides] for l in range(L)]
+        max_cells = [max(x * y for x, y in sh) for sh in shapes]
+        ranks = {}
+        for name in names:                                     # one paths_rank_joint (and its host check) per order
+            ranks[name], n = _rank_levels(fp, scores, chosen, name == "morf", key="removal_rank_" + name)
+        counts = removal_counts(n, steps, float(max_fraction))
+        thr = torch.tensor(counts[1:], device=dev, dtype=torch.int32)        # ONE upload: members s = 1 .. steps, the same for both orders
+        locs = [rec["locs"].contiguous() for rec in fp.trace]
+        masks, left0 = {}, []
+        for name in names:                                     # every member's masks, all levels: L launches per order
+            built = [removal_masks(batch.mask_ptrs[l], batch.gx[l], batch.gy[l], max_cells[l], locs[l], ps, fp.nums[l], ranks[name][l], thr)
+                     for l in range(L)]
+            masks[name] = [m for m, _ in built]
+            left0.append(built[0][1])
+        left = torch.stack(left0).cpu().numpy()                # ONE host read: [orders, steps, B]
+        gone = np.argwhere(left <= 0)
+        if len(gone):
+            k, s, b = (int(v) for v in gone[0])
+            raise ValueError(f"removal_curves: order {names[k]!r}, step {s + 1} (of {steps}) leaves slide {b} without level-0 tissue: "
+                             f"{int(counts[s + 1, b])} cells removed; lower max_fraction or leave level 0 out of levels")
+        bitmaps = [removal_masks(None, batch.gx[l], batch.gy[l], max_cells[l], locs[l], ps, fp.nums[l], None, None, set_cells=True)[0][0]
+                   for l in range(L)]                          # the cells the recorded pass visited, per level [B, ldm]
+
+        def run(vb, c):                                        # one free pass of c members of every slide
+            t: List[dict] = []
+            o = putils.recurse(model, vb, keep_patches, L, trace=t)
+            vis = torch.stack([rec["num_ims"] for rec in t], dim=-1).view(c, B, L).to(torch.int32)
+            ov = torch.stack([visited_overlap(bitmaps[l], batch.gx[l], batch.gy[l], t[l]["locs"].contiguous(), t[l]["num_ims"], ps)
+                              for l in range(L)], dim=-1).view(c, B, L)
+            return o, _target_of(fn, o["logits"]).view(c, B), vis, ov
+
+        def member_view(name, s, b):                          # slide b behind member s + 1's masks (levels beyond L keep its own)
+            slide = batch.slides[b]
+            own = [masks[name][l][s, b, :x * y].view(x, y) for l, (x, y) in enumerate(sh[b] for sh in shapes)]
+            return slide.with_masks(own + list(slide.masks[L:]))
+
+        o0, tg0, vis0, ov0 = run(batch, 1)
+        out = {"logits": o0["logits"], "target": tg0[0], "status": o0["status"].clone()}
+        curves, visited, overlap = {}, {}, {}
+        for name in names:                                     # each order's members in chunks of their own
+            tgs, vis, ovs = [tg0], [vis0], [ov0]
+            for s0 in range(0, steps, fp.chunk):
+                c = min(fp.chunk, steps - s0)
+                views = [member_view(name, s0 + ci, b) for ci in range(c) for b in range(B)]
+                o, tg, vi, ov = run(DeviceSlideBatch(views), c)
+                out["status"] |= o["status"]
+                tgs.append(tg), vis.append(vi), ovs.append(ov)
+            curves[name] = torch.cat(tgs).t().contiguous()
+            visited[name] = torch.cat(vis).permute(1, 0, 2).contiguous()
+            overlap[name] = torch.cat(ovs).permute(1, 0, 2).contiguous()
+    frac = np.arange(steps + 1, dtype=np.float64) / steps * float(max_fraction)
+    out["fractions"] = torch.from_numpy(frac)
+    out["counts"] = torch.from_numpy(counts)
+    for name, cv in curves.items():
+        out[name], out[name + "_auc"] = cv, _auc(cv, frac)
+    if len(names) == 2:
+        out["aopc_gap"] = out["lerf_auc"] - out["morf_auc"]
+    out["visited"], out["path_overlap"], out["masks"] = visited, overlap, masks
     return out, fp.trace

@@ -249,7 +249,8 @@ class TapedRecursion:
         fits = (self.tape is not None and rec is not None and len(new) == len(rec) and new.dim == rec.dim and new.device == rec.device
                 and new.num_levels >= self.levels and new.n0 <= rec.n0
                 and all(new.max_dim[l] <= rec.max_dim[l] for l in range(self.levels))
-                and ops.h3_in_range(new.feat_absmax) == ops.h3_in_range(rec.feat_absmax))
+                and ops.h3_in_range(new.feat_absmax) == ops.h3_in_range(rec.feat_absmax)
+                and new.masked == rec.masked)            # (masked views add a launch at level 0)
         if not fits:
             self.tape, self._rec_batch = None, None
             self.batch = new
@@ -546,6 +547,9 @@ def _level0(r) -> SimpleNamespace:
     lv.num_ims = torch.empty((B,), **r.i64)
     _lib.call("paths_level0_batch" + r.sfx, p(r.batch.grid_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, r.mc.patch_size, N,
               p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), r.st)
+    if getattr(r.batch, "masked", False):        # views (DeviceSlide.with_masks): a cleared level-0 cell reads as a background cell's zero row
+        _lib.call("paths_level0_mask_rows", p(r.batch.mask_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, N, p(lv.fts), p(lv.x_rows),
+                  p(r.zero_row), r.st)
     if r.stage_host:
         lv.staged = _stage_rows(r.batch, lv.x_rows, N, r.zero_row, r.st)
     return lv
@@ -776,6 +780,8 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
     h16 = batch.dtype == torch.float16                     # fp16 grids: the gathers write fp32 copies, the training kernels are unchanged
     _lib.call("paths_level0_batch_h16" if h16 else "paths_level0_batch", p(batch.grid_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, mc.patch_size, N,
               p(fts), p(locs), p(parent), p(num_ims), 1, None, None, st)
+    if batch.masked:
+        _lib.call("paths_level0_mask_rows", p(batch.mask_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, N, p(fts), None, None, st)
     state_prev, ctx_prev, ctx_hist = None, None, []
     logits = None
     # Once-per-parent form (LSTM, optimistic pass): siblings share their parent's h, so the h half of the gate pre-activations is one
