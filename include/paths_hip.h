@@ -537,7 +537,11 @@ int paths_layernorm_f32(const float* x, const float* gamma, const float* beta, f
                         float eps, paths_stream_t stream);
 
 /* torch.topk(importance[:n], min(n, keep)).indices per slide (reference data_utils/slide.py:294-301).
- * Order: score descending, ties by index ascending.  keep = -1 keeps every patch in original order. */
+ * Order: score descending, ties by index ascending.  keep = -1 keeps every patch in original order.
+ * "Descending" is the order of the scores' BIT PATTERNS (csrc/rank_key.h), which is the numeric order of all ordinary values, puts
+ * +0.0 before -0.0, a NaN with a clear sign bit before +inf and a NaN with the sign bit set after -inf (torch.topk ranks every NaN
+ * first: a negative NaN is the one case where the two differ).  Only scores[b, 0:num_ims[b]] are read (ld >= n_max is the row
+ * stride); keep_idx[b, keep_count[b]:ldk] is left untouched. */
 int paths_topk(const float* scores, int64_t ld, const int64_t* num_ims, int B, int n_max, int keep,
                int* keep_idx, int64_t ldk, int* keep_count, paths_stream_t stream);
 /* paths_topk + kept_rows[b, i] = address of row_base[b, keep_idx[b, i], 0] of a row-major [B, slide_rows, row_ld] float table
@@ -550,7 +554,10 @@ int paths_topk_rows(const float* scores, int64_t ld, const int64_t* num_ims, int
  *   mask_ptrs[b] -> uint8 [X*Y] tissue mask of the NEXT level (1 = row sum != 0).  status bit0: a slide
  *   produced zero children (reference fallback slide.py:336-352 needed), bit1: capacity n_next exceeded.
  *   child_pos (optional, [B, 4*ldk]): output row of every candidate child (-1 if dropped), for paths_gather_rows_bwd.
- *   hp_row (optional, [B, n_next]): row b*ldk + i of the kept-parent table for every child (-1 on padding), see paths_lstm_cell. */
+ *   hp_row (optional, [B, n_next]): row b*ldk + i of the kept-parent table for every child (-1 on padding), see paths_lstm_cell.
+ *   src_cell is the child's cell x * Y + y in the next grid.  keep_count[b] is clamped to [0, ldk] like in the split form below; a
+ *   slide over capacity writes num_out[b] only.  Returns -1 without launching unless ldk > 0 and every pointer but child_pos / hp_row
+ *   is non-null. */
 int paths_expand_children(const int* keep_idx, int64_t ldk, const int* keep_count, const int64_t* locs, int64_t n_cur,
                           int patch_size, const int* next_x, const int* next_y, const int64_t* mask_ptrs, int B,
                           int64_t n_next, int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row,
@@ -581,7 +588,8 @@ int paths_admit_children(const int* cand_count, const int64_t* cand_cells, const
 
 /* Rare fallback of reference data_utils/slide.py:336-352 for slides with num_out[b] == 0 after paths_expand_children:
  * continue with every tissue cell of the next grid (every cell if it has no tissue), zero patch context (src_row = -1),
- * parent_inds = cell index.  Other slides are untouched.  status bit1 set if n_next is too small. */
+ * parent_inds = cell index.  Other slides are untouched.  status bit1 set if n_next is too small (that slide writes num_out[b]
+ * only); rows at and beyond num_out[b] are not rewritten.  Returns -1 without launching if any pointer but hp_row is null. */
 int paths_fallback_all_cells(const int* next_x, const int* next_y, const int64_t* mask_ptrs, int patch_size, int B,
                              int64_t n_next, int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row,
                              int* src_cell, int* status, int* hp_row, paths_stream_t stream);

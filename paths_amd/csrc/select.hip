@@ -126,12 +126,12 @@ expand_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restri
               int* __restrict__ hp_row /*[B, n_next] or null: row of the kept-parent table (b*ldk + i) of every child*/) {
   __shared__ int part[2 * EXP_NW];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int count = keep_count[b];
+  const int count = max(0, min(keep_count[b], (int)ldk));      // (keep_idx holds ldk entries per slide, child_pos 4 * ldk)
   const int total = 4 * count;
   const int X = next_x[b], Y = next_y[b];
   const uint8_t* mask = reinterpret_cast<const uint8_t*>(mask_ptrs[b]);
   const int per = (total + EXP_NT - 1) / EXP_NT;
-  const int c0 = tid * per, c1 = min(c0 + per, total);
+  const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
 
   auto child = [&](int c, int& cx, int& cy, int& i) -> bool {
     const int blk = c / count;
@@ -745,8 +745,10 @@ int paths_expand_children(const int* keep_idx, int64_t ldk, const int* keep_coun
                           int patch_size, const int* next_x, const int* next_y, const int64_t* mask_ptrs, int B,
                           int64_t n_next, int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row,
                           int* src_cell, int* status, int* child_pos, int* hp_row, hipStream_t stream) {
-  PATHS_REQUIRE(B > 0 && n_cur > 0 && n_next > 0 && patch_size > 0, "expand_children: bad shape");
+  PATHS_REQUIRE(B > 0 && n_cur > 0 && n_next > 0 && patch_size > 0 && ldk > 0, "expand_children: bad shape");
   PATHS_REQUIRE(4 * ldk <= (int64_t)1 << 30, "expand_children: too many candidates");
+  PATHS_REQUIRE(keep_idx && keep_count && locs && next_x && next_y && mask_ptrs && num_out && locs_out && parent_out && src_row &&
+                src_cell && status, "expand_children: null pointer");
   hipLaunchKernelGGL(expand_kernel, dim3(B), dim3(EXP_NT), 0, stream, keep_idx, ldk, keep_count, locs, n_cur, patch_size,
                      next_x, next_y, mask_ptrs, n_next, num_out, locs_out, parent_out, src_row, src_cell, status, child_pos, hp_row);
   PATHS_LAUNCH_CHECK("expand_children");
@@ -783,6 +785,8 @@ int paths_fallback_all_cells(const int* next_x, const int* next_y, const int64_t
                              int64_t n_next, int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row,
                              int* src_cell, int* status, int* hp_row, hipStream_t stream) {
   PATHS_REQUIRE(B > 0 && n_next > 0 && patch_size > 0, "fallback_all_cells: bad shape");
+  PATHS_REQUIRE(next_x && next_y && mask_ptrs && num_out && locs_out && parent_out && src_row && src_cell && status,
+                "fallback_all_cells: null pointer");
   hipLaunchKernelGGL(fallback_all_cells_kernel, dim3(B), dim3(1024), 0, stream, next_x, next_y, mask_ptrs, patch_size, n_next,
                      num_out, locs_out, parent_out, src_row, src_cell, status, hp_row);
   PATHS_LAUNCH_CHECK("fallback_all_cells");
