@@ -320,6 +320,30 @@ int paths_attention_rollout_seed(const float* attn_patch, int64_t patch_ld, cons
                                  float* r, float* rollout, int64_t rollout_ld, float* rollout_self, int B, int T, int H, paths_stream_t stream);
 int paths_attention_rollout_step(const float* ws, const int64_t* num_ims, const float* r_in, float* r_out, float* rollout, int64_t rollout_ld,
                                  float* rollout_self, int B, int T, int d, int H, paths_stream_t stream);
+/* Gradient-weighted attention relevance of the special token (Chefer, Gur & Wolf 2021; attribution side path of the backward pass,
+ * csrc/attn_relevance.hip): with A_l^h the softmax attention of layer l, head h over the valid tokens (row 0 = special
+ * token) and gradA_l^h[i][j] = dO_i^h . V_j^h its gradient, Abar_l = mean_h (A_l^h * gradA_l^h)^+ and
+ * r = e_s^T (I + Abar_{L-1}) ... (I + Abar_0).
+ * Operands of both calls: q / k / v element (b, h, t, e) at base + b*sb + h*sh + t*st + e (floats; strides multiples of 4, bases
+ * 16-byte aligned): head-major [B, H, T, hd] with pre-scaled q and qscale = 1, or the token-major qkv [B, T, 3 di] with bases at
+ * 0 / di / 2 di and the qscale of paths_attention_bwd_any; scores are qscale * q . k in the log2 domain.  head_dim 16 / 32 / 48 / 64,
+ * H the true head count.  num_ims is clamped to [0, T-1] on the device, rows past it are never read, and a slide with num_ims = 0
+ * keeps r = e_s (seed) / r_in (step).
+ * seed (the last layer, read at token 0): r[b][j] = [j == 0] + 1/H sum_h max(0, p * (da0^h . v_j^h)), p = exp2(qscale q_0 . k_j -
+ * lse0) from the saved statistic; da0 [B][da0_ld] with head h at columns [h*hd, (h+1)*hd), lse0 element (b, h) at b*lse0_sb + h*lse0_sh.
+ * step (a full layer): r_out[b][j] = r_in[b][j] + 1/H sum_h sum_i r_in[b][i] max(0, exp2(qscale q_i . k_j - lse[b][h][i]) * (dO_i^h . v_j^h));
+ * d_o [B][T][ld_o] with head h at columns [h*hd, (h+1)*hd), lse [B][H][T]; r_out must not be r_in.  Both products on the f32-input
+ * MFMA, no T x T buffer, no atomics: reruns are bit-identical.
+ * r / r_out [B][T] (0 past num_ims); NULL: write the outputs instead: relevance[b * relevance_ld + j] (patch j = row 1 + j, exactly 0
+ * for j >= num_ims[b]; may be NULL when T = 1), relevance_self[b]. */
+int paths_attention_relevance_seed(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, float qscale,
+                                   const float* da0, int64_t da0_ld, const float* lse0, int64_t lse0_sb, int64_t lse0_sh,
+                                   const int64_t* num_ims, float* r, float* relevance, int64_t relevance_ld, float* relevance_self, int B,
+                                   int T, int H, int head_dim, paths_stream_t stream);
+int paths_attention_relevance_step(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, float qscale,
+                                   const float* d_o, int64_t ld_o, const float* lse, const int64_t* num_ims, const float* r_in, float* r_out,
+                                   float* relevance, int64_t relevance_ld, float* relevance_self, int B, int T, int H, int head_dim,
+                                   paths_stream_t stream);
 
 /* Generic out = act(a W^T + b) on the fp32 matrix cores (W rows zero-padded to Npad, a multiple of 128). */
 int paths_linear_f32(const float* a, int64_t lda, const float* w, const float* b, float* out, int64_t ldo,

@@ -58,6 +58,10 @@ SIGNATURES = {
     "paths_attention_rollout_prepare": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "paths_attention_rollout_seed": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp],
     "paths_attention_rollout_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
+    "paths_attention_relevance_seed": [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp,
+                                       _i32, _i32, _i32, _i32, _vp],
+    "paths_attention_relevance_step": [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                       _i32, _i32, _i32, _i32, _vp],
     "paths_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "paths_layernorm_bwd_sums": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "paths_reduce_slabs_f32": [_vp, _i32, _i32, _vp, _i32, _vp],

@@ -156,6 +156,76 @@ class no_weight_grads:
         return False
 
 
+# Gradient-weighted attention relevance (csrc/attn_relevance.hip).  Inside ``with attention_relevance(sink):`` every
+# transformer_backward also runs the relevance seed (once the last layer's chain_backward has produced da0) and one step per full
+# layer (once that layer's chain_backward has produced dattn) - the points where q / k / v, lse and the output gradient are alive -
+# and appends the level's (relevance [B, T-1], relevance_self [B]) to ``sink``.  Outside it nothing is launched or allocated.
+RELEVANCE_SINK: Optional[list] = None
+
+
+class attention_relevance:
+    def __init__(self, sink: list):
+        self.sink = sink
+
+    def __enter__(self):
+        global RELEVANCE_SINK
+        self.prev, RELEVANCE_SINK = RELEVANCE_SINK, self.sink
+        return self
+
+    def __exit__(self, *exc):
+        global RELEVANCE_SINK
+        RELEVANCE_SINK = self.prev
+        return False
+
+
+def relevance_unsupported(head_dim: int) -> Optional[str]:
+    """Why the relevance kernels cannot run for this (padded) head width / these switches, or None."""
+    if ops.wide_head(head_dim) or head_dim > 64:
+        return f"attention relevance covers head_dim <= 64 (got {head_dim}: the wide-head attention of csrc/attn_wide.hip)"
+    if ops.AGG_FP8 or ops.ATTN_FP8:
+        return "attention relevance is not implemented for the fp8 variants (PATHS_AGG_FP8 / PATHS_ATTN_FP8)"
+    return None
+
+
+class _Relevance:
+    """One level's relevance row on its way down the layers: seed(...) then step(...) per full layer, r ping-ponging between two
+    [B, T] buffers; the call that handles layer 0 writes the outputs."""
+
+    def __init__(self, sink, num_ims, B, T, H, hd, L, dev):
+        self.sink, self.num_ims, self.B, self.T, self.H, self.hd, self.L = sink, num_ims, B, T, H, hd, L
+        f32 = _f32(dev)
+        self.out, self.out_self = torch.empty((B, T - 1), **f32), torch.empty((B,), **f32)
+        self.r = [torch.empty((B, T), **f32) for _ in range(2)] if L > 1 else None
+        self.cur = 0
+
+    def _outputs(self):
+        return (P(self.out) if self.T > 1 else None, self.T - 1, P(self.out_self))
+
+    def seed(self, qkv_ops, qscale, da0, lse0, lse0_sb, lse0_sh):
+        last = self.L == 1
+        _lib.call("paths_attention_relevance_seed", *qkv_ops, qscale, P(da0), da0.stride(0), P(lse0), lse0_sb, lse0_sh, P(self.num_ims),
+                  None if last else P(self.r[0]), *(self._outputs() if last else (None, 0, None)), self.B, self.T, self.H, self.hd, _lib.stream())
+        if last:
+            self.sink.append((self.out, self.out_self))
+
+    def step(self, l, qkv_ops, qscale, d_o, ld_o, lse):
+        last = l == 0
+        r_in, r_out = self.r[self.cur], self.r[1 - self.cur]
+        _lib.call("paths_attention_relevance_step", *qkv_ops, qscale, P(d_o), ld_o, P(lse), P(self.num_ims), P(r_in),
+                  None if last else P(r_out), *(self._outputs() if last else (None, 0, None)), self.B, self.T, self.H, self.hd, _lib.stream())
+        self.cur = 1 - self.cur
+        if last:
+            self.sink.append((self.out, self.out_self))
+
+
+def _relevance_operands(lv, fast: bool, B, T, H, hd):
+    """(q, k, v, sb, sh, st) of a saved layer: head-major q / k / v (the shipped geometry) or the token-major qkv (shape-generic)."""
+    if fast:
+        return (P(lv["q"]), P(lv["k"]), P(lv["v"]), H * T * hd, T * hd, hd)
+    qkv, di = lv["qkv"], H * hd
+    return (qkv.data_ptr(), qkv.data_ptr() + 4 * di, qkv.data_ptr() + 8 * di, T * 3 * di, hd, 3 * di)
+
+
 def flush_reductions():
     if _DEFER["depth"] > 0:
         _lib.call("paths_flush_reductions", None, _lib.stream())
@@ -841,6 +911,12 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
     nlog = lvl_pack["wcls"].shape[0]
     fast = ops.fast_path(mc)
     assert nlog <= 128
+    rel = None
+    if RELEVANCE_SINK is not None:                             # (attention_relevance: refused before any launch of this backward)
+        why = relevance_unsupported(hd) or ("attention relevance runs with dropout off (model.eval())" if sv.get("drop") is not None else None)
+        if why:
+            raise NotImplementedError(why)
+        rel = _Relevance(RELEVANCE_SINK, num_ims, B, T, H, hd, L, dev)
 
     # ---- head: logits = F Wcls^T + bcls, F = decoder.norm(x3) (+ ctx_prev)
     wl = layers[L - 1]
@@ -899,6 +975,9 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
     # ---- last layer, token 0 only
     g, dx0, da0 = chain_backward(wl, x_last.data_ptr(), T * d, a0_ptr, a0_ld, B, dx3, dev, drop, L - 1, saved=chain0)
     dqkv, dx = zeros_group(dev, (B, T, 3 * di), (B, T, d))                      # (dx: gradient of the last layer's input)
+    if rel is not None:                                                         # (lse0: [B, H], or row 0 of the generic [B, H, T])
+        rel.seed(_relevance_operands(last, fast, B, T, H, hd), 1.0 if fast else qscale, da0, lse0 if fast else last["lse0"],
+                 H if fast else H * T, 1 if fast else T)
     if fast:
         ws = torch.empty((int(_lib.load().paths_attention_token0_workspace(B, T, H)),), **f32)
         _lib.call("paths_attention_token0_bwd", P(last["q"]), P(last["k"]), P(last["v"]), P(a0), P(da0), P(lse0), P(num_ims), P(dqkv), P(ws),
@@ -919,6 +998,8 @@ def transformer_backward(mc, lvl_pack, sv, d_logits: Optional[torch.Tensor], d_c
         M = B * T
         g, dx_in, dattn = chain_backward(w, lv["x_in"].data_ptr(), d, lv["attn"].data_ptr(), di, M, dx.view(M, d), dev, drop, l,
                                          saved=lv.get("chain"))
+        if rel is not None:
+            rel.step(l, _relevance_operands(lv, fast, B, T, H, hd), 1.0 if fast else qscale, dattn, di, lv["lse"])
         dqkv = torch.zeros((B, T, 3 * di), **f32)
         ws = torch.empty((B * H * T,), **f32)
         if not fast:

@@ -9,6 +9,7 @@ trace of :func:`paths_amd.utils.recurse`.
 ``importance + 1e-4`` over its footprint, then deeper levels are folded upwards with weight 1/2 wherever they exist
 (heatmap_visualise.py:147-171).  ``attention_map`` rasterises the special token's attention of one decoder layer (one head or
 the mean over heads), one raster per level and no fold across levels; ``rollout_map`` does the same for the attention rollout,
+``relevance_map`` for the gradient-weighted attention relevance (:func:`paths_amd.saliency.attention_relevance`),
 ``saliency_map`` for the gradient attributions and ``removed_map`` for the cells a member of
 :func:`paths_amd.saliency.removal_curves` turned to background.  Rasters are in units of the FINEST level's patches (one
 cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
@@ -40,6 +41,9 @@ def hierarchy_from_trace(trace: List[dict], slide: int) -> List[Dict[str, np.nda
         if "rollout" in lv:
             d["rollout"] = lv["rollout"][slide, :n].cpu().numpy()                      # [n]
             d["rollout_self"] = float(lv["rollout_self"][slide])
+        if "attention_relevance" in lv:
+            d["attention_relevance"] = lv["attention_relevance"][slide, :n].cpu().numpy()  # [n]
+            d["attention_relevance_self"] = float(lv["attention_relevance_self"][slide])
         for key in SALIENCY_KINDS + REMOVAL_RANKS:                  # (the attribution functions' and removal_curves' per-row entries)
             if key in lv:
                 d[key] = lv[key][slide, :n].cpu().numpy()                              # [n]
@@ -102,6 +106,23 @@ def rollout_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: int 
             raise KeyError("level %d carries no rollout: run recurse(..., rollout=True)" % depth)
         raster = np.zeros(shape, dtype=np.float64)
         _paint(raster, lv["locs"], lv["rollout"], magnification_factor ** (L - 1 - depth), patch_size)
+        maps.append(raster)
+    return maps
+
+
+def relevance_map(levels: List[Dict[str, np.ndarray]], base_grid, patch_size: int = 256, magnification_factor: int = 2) -> List[np.ndarray]:
+    """One [X0 * f, Y0 * f] float map per level (f = magnification_factor**(L-1)): the special token's gradient-weighted attention
+    relevance on each patch, painted over the patch's footprint like :func:`rollout_map`; 0 where the level did not visit, no fold
+    across levels.  ``levels`` from :func:`hierarchy_from_trace` of a :func:`paths_amd.saliency.attention_relevance` trace."""
+    L = len(levels)
+    f = magnification_factor ** (L - 1)
+    shape = (base_grid[0] * f, base_grid[1] * f)
+    maps = []
+    for depth, lv in enumerate(levels):
+        if "attention_relevance" not in lv:
+            raise KeyError("level %d carries no attention relevance: run saliency.attention_relevance" % depth)
+        raster = np.zeros(shape, dtype=np.float64)
+        _paint(raster, lv["locs"], lv["attention_relevance"], magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)
     return maps
 

@@ -1,5 +1,6 @@
 """Gradient patch attributions: gradient x input, integrated gradients and SmoothGrad along the frozen path,
-and the deletion / insertion curves that tell which per-patch map is faithful.
+the gradient-weighted attention relevance of the special token, and the deletion / insertion curves that tell which
+per-patch map is faithful.
 
 The importance, attention and rollout exports say what the model looked at; :func:`input_gradients` says what moved the prediction:
 the gradient of a slide's score with respect to every visited patch's feature vector, reduced per patch to
@@ -123,18 +124,41 @@ def saliency_rows(dx: torch.Tensor, x: torch.Tensor, num_ims: torch.Tensor) -> T
     return gxi, gnorm
 
 
-def _pass(model, batch, keep_patches, num_levels, fn, keep_gradients: bool, careful: bool, keep_rows: bool = False):
-    from . import utils as putils
+def _pass(model, batch, keep_patches, num_levels, fn, keep_gradients: bool, careful: bool, keep_rows: bool = False,
+          relevance: bool = False):
+    from . import backward as bw, utils as putils
     trace: List[dict] = []
     out = putils.recurse_train(model, batch, keep_patches, num_levels, careful=careful, trace=trace)
     tgt = _target_of(fn, out["logits"])
     # slides do not interact: the gradient of the batch sum is every slide's own gradient
-    grads = torch.autograd.grad(tgt.sum(), [rec["fts"] for rec in trace])
+    sink: List[Tuple[torch.Tensor, torch.Tensor]] = []
+    with (bw.attention_relevance(sink) if relevance else contextlib.nullcontext()):
+        grads = torch.autograd.grad(tgt.sum(), [rec["fts"] for rec in trace])
+    if relevance:
+        _relevance_records(model, trace, sink)
     for rec, dx in zip(trace, grads):
         rec["grad_x_input"], rec["grad_norm"] = saliency_rows(dx, rec["fts"] if keep_rows else rec.pop("fts"), rec["num_ims"])
         if keep_gradients:
             rec["grad"] = dx
     return {"logits": out["logits"].detach(), "target": tgt.detach(), "status": out["status"]}, trace
+
+
+def _relevance_records(model, trace: List[dict], sink):
+    """``sink``: what the backward appended, the last level first, one pair per level whose aggregator has a path to the target.
+    A level without one (non-final levels under slide_ctx_mode "none") gets r = e_s: zeros on the patches, 1 for self."""
+    L = len(trace)
+    with_agg = [l for l in range(L) if l == L - 1 or model.procs[l].config.slide_ctx_mode != "none"]
+    if len(sink) != len(with_agg):
+        raise RuntimeError(f"attention_relevance: {len(sink)} levels reported a relevance, {len(with_agg)} have an aggregator gradient")
+    got = dict(zip(reversed(with_agg), sink))
+    for l, rec in enumerate(trace):
+        B, N = rec["importance"].shape
+        if l in got:
+            rec["attention_relevance"], rec["attention_relevance_self"] = got[l]
+            assert rec["attention_relevance"].shape == (B, N) and rec["attention_relevance_self"].shape == (B,)
+        else:
+            rec["attention_relevance"] = torch.zeros((B, N), device=rec["importance"].device, dtype=torch.float32)
+            rec["attention_relevance_self"] = torch.ones((B,), device=rec["importance"].device, dtype=torch.float32)
 
 
 def _careful_repeat(run):
@@ -170,6 +194,101 @@ def input_gradients(model, slides, keep_patches: Sequence[int], num_levels: int,
     try:
         with torch.enable_grad():
             (out, trace), _ = _careful_repeat(lambda careful: _pass(model, batch, keep_patches, num_levels, fn, keep_gradients, careful))
+    finally:
+        model.train(was_training)
+    return out, trace
+
+
+# ------------------------------------------------------------------------------------------------
+# gradient-weighted attention relevance of the special token
+# ------------------------------------------------------------------------------------------------
+def _qkv_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_ims: torch.Tensor):
+    """q / k / v [B, H, T, hd] fp32 views (any strides along B / H / T, unit stride along hd, the three alike: head-major tensors or
+    the three slices of a token-major qkv): (B, H, T, hd, sb, sh, st)."""
+    B, H, T, hd = q.shape
+    for t in (q, k, v):
+        assert t.dtype == torch.float32 and t.shape == (B, H, T, hd) and t.stride(3) == 1 and t.stride() == q.stride(), \
+            "q, k, v must be fp32 [B, H, T, hd] views with the same strides"
+    assert hd in (16, 32, 48, 64), "head_dim must be 16, 32, 48 or 64"
+    assert num_ims.dtype == torch.int64 and num_ims.shape == (B,) and num_ims.is_contiguous()
+    return (B, H, T, hd) + tuple(q.stride()[:3])
+
+
+def _relevance_outputs(B: int, T: int, outputs: bool, dev):
+    if not outputs:
+        r = torch.empty((B, T), device=dev, dtype=torch.float32)
+        return r, (_lib.ptr(r), None, 0, None)
+    rel = torch.empty((B, T - 1), device=dev, dtype=torch.float32)
+    rel_self = torch.empty((B,), device=dev, dtype=torch.float32)
+    return (rel, rel_self), (None, _lib.ptr(rel) if T > 1 else None, T - 1, _lib.ptr(rel_self))
+
+
+def relevance_seed(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qscale: float, da0: torch.Tensor, lse0: torch.Tensor,
+                   num_ims: torch.Tensor, outputs: bool = False):
+    """The relevance row of the last layer, read at token 0 (include/paths_hip.h: paths_attention_relevance_seed): q / k / v
+    [B, H, T, hd] views (:func:`_qkv_ok`), da0 [B, H*hd] (rows may be strided), lse0 [B, H] (any strides; log2 domain), num_ims [B]
+    int64.  Returns r [B, T], or with ``outputs`` (relevance [B, T-1], relevance_self [B])."""
+    _lib.require_cuda(q, k, v, da0, lse0, num_ims)
+    B, H, T, hd, sb, sh, st = _qkv_ok(q, k, v, num_ims)
+    assert da0.dtype == torch.float32 and da0.shape == (B, H * hd) and da0.stride(1) == 1
+    assert lse0.dtype == torch.float32 and lse0.shape == (B, H)
+    res, out_args = _relevance_outputs(B, T, outputs, q.device)
+    p = _lib.ptr
+    _lib.call("paths_attention_relevance_seed", p(q), p(k), p(v), sb, sh, st, float(qscale), p(da0), da0.stride(0), p(lse0), lse0.stride(0),
+              lse0.stride(1), p(num_ims), *out_args, B, T, H, hd, _lib.stream())
+    return res
+
+
+def relevance_step(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qscale: float, d_o: torch.Tensor, lse: torch.Tensor,
+                   num_ims: torch.Tensor, r_in: torch.Tensor, outputs: bool = False):
+    """One relevance step through a full layer (include/paths_hip.h: paths_attention_relevance_step): q / k / v as for
+    :func:`relevance_seed`, d_o [B, T, ld] fp32 with head h at columns [h*hd, (h+1)*hd) (ld >= H*hd), lse [B, H, T] contiguous (log2
+    domain), r_in [B, T] contiguous.  Returns r_out [B, T], or with ``outputs`` (relevance [B, T-1], relevance_self [B])."""
+    _lib.require_cuda(q, k, v, d_o, lse, num_ims, r_in)
+    B, H, T, hd, sb, sh, st = _qkv_ok(q, k, v, num_ims)
+    assert d_o.dtype == torch.float32 and d_o.shape[:2] == (B, T) and d_o.shape[2] >= H * hd and d_o.is_contiguous()
+    assert lse.dtype == torch.float32 and lse.shape == (B, H, T) and lse.is_contiguous()
+    assert r_in.dtype == torch.float32 and r_in.shape == (B, T) and r_in.is_contiguous()
+    res, out_args = _relevance_outputs(B, T, outputs, q.device)
+    p = _lib.ptr
+    _lib.call("paths_attention_relevance_step", p(q), p(k), p(v), sb, sh, st, float(qscale), p(d_o), d_o.shape[2], p(lse), p(num_ims), p(r_in),
+              *out_args, B, T, H, hd, _lib.stream())
+    return res
+
+
+def attention_relevance(model, slides, keep_patches: Sequence[int], num_levels: int,
+                        target: Target = "risk") -> Tuple[Dict[str, torch.Tensor], List[dict]]:
+    """Gradient-weighted attention relevance of the special token (Chefer, Gur & Wolf 2021) per level: "what the aggregator looked
+    at" weighted by "what moved the prediction".
+
+    With A_l^h layer l's attention of head h over a slide's valid tokens and gradA_l^h the gradient of ``target`` with respect to it
+    (entry (i, j) = dO_i^h . V_j^h), Abar_l = mean_h (A_l^h * gradA_l^h)^+ and r = e_s^T (I + Abar_{L-1}) ... (I + Abar_0).  The
+    pass is :func:`input_gradients`' - same slides, same ``target``, same careful repeat for a slide without tissue children, the
+    model's mode restored, no ``.grad`` touched - with the relevance kernels launched from inside the hand-written backward
+    (backward.attention_relevance; csrc/attn_relevance.hip) where each layer's q / k / v, lse and output gradient are alive: one
+    seed per level plus one T x T step per full decoder layer, no T x T matrix stored.  Earlier levels receive their gradient
+    through the slide-context chain as in training; a level whose aggregator has no path to the target (non-final levels under
+    slide_ctx_mode "none") gets r = e_s.  FFN, LayerNorms and the degenerate cross-attention are ignored, as in the published
+    method.
+
+    Returns (out, trace) as :func:`input_gradients` (``grad_x_input`` / ``grad_norm`` are that function's, bit for bit); the records
+    gain ``attention_relevance`` [B, N] (>= 0, in the order of ``importance`` / ``locs``, exactly 0 on padded rows) and
+    ``attention_relevance_self`` [B] (>= 1).  Head widths above 64 and the fp8 variants are not covered."""
+    from . import backward as bw, ops, utils as putils
+    _require_lstm(model, "attention_relevance")
+    fn = parse_target(target)
+    for proc in list(getattr(model, "procs", ()))[:num_levels]:
+        mc = proc.config
+        why = bw.relevance_unsupported(ops.padded_head_dim(mc.trans_dim // mc.trans_heads))
+        if why:
+            raise NotImplementedError(why)
+    batch = putils._stored_batch(slides, "attention_relevance")
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.enable_grad():
+            (out, trace), _ = _careful_repeat(lambda careful: _pass(model, batch, keep_patches, num_levels, fn, False, careful,
+                                                                    relevance=True))
     finally:
         model.train(was_training)
     return out, trace
