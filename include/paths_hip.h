@@ -124,7 +124,11 @@ int paths_x6_pack_weights(const float* w, int64_t ldw, void* out, int N, int Npa
  * planes 3 or 4 (bf16 planes, scale 1).  One launch instead of paths_transpose_f32 + paths_x6_pack_weights (the backward's dX products). */
 int paths_x6_pack_weights_t(const float* w, int64_t ldw, void* out, int N, int Npad, int K, int Kvalid, int planes, paths_stream_t stream);
 /* w_gates_x6 = pack of the PACKED gate matrix [3Hc+D, 2D] of paths_lstm_cell (scale wg_scale); w_mem_x6 = pack of [D, Hc]
- * (scale wm_scale); D % 256 == 0; y may be NULL (Y = X + h1 not materialised).  x_rows (optional, planes = 2, needs hp / no
+ * (scale wm_scale); D % 256 == 0, Hc % 64 == 0 and Hc >= 128 (the mem_to_out product runs over K = Hc and the split-operand
+ * GEMM needs K >= 128; paths_lstm_cell takes Hc = 64).  These shape limits and the operand combinations named here are refused
+ * before the first launch; alignment and size limits of single operands (ldso % 4, 16-byte alignment of state_out + D, the
+ * 4 GiB extent of an operand) are checked by the launch that reads them, so such a refusal may follow earlier phases' writes.
+ * y may be NULL (Y = X + h1 not materialised).  x_rows (optional, planes = 2, needs hp / no
  * h0, y = NULL): [M] addresses of the feature rows - x is then read in place (paths_gather_rows row_ptrs), x / ldx unused.
  * ws_o: scratch of ceil(M / 256) * 256 x D floats (with y = NULL and no training saves the output gate crosses from phase 2 to
  * phase 4 as raw pre-activations in whole 32x32 accumulator tiles; otherwise as the [M, D] gate values) */
@@ -494,7 +498,8 @@ int paths_tokens_assemble(const float* P, int64_t ldp, const float* importance, 
 /* The importance-rows and tokens-assemble launches (above) as ONE launch over the rows of the [W1 ; Wp] product (csrc/generic.hip; reference
  * model/paths.py:95-98,119-124, model/aggregator.py:37-65, utils.py:16-23,47-67): hid [M, ldh] holds the importance MLP's hidden
  * pre-activations (Hi columns) and the projection (d columns) of every patch row; writes importance [M] (0 for padded rows) and
- * tokens [B, rows_per_slide + 1, d] (special token first; padded rows bp + PE).  The positional encoding is read from pe_table
+ * tokens [B, rows_per_slide + 1, d] (special token first; padded rows bp + PE for either imp_mul: their projection is not read,
+ * where paths_tokens_assemble and the paths_importance_proj* entry points with imp_mul = 0 add it like any row's).  The positional encoding is read from pe_table
  * (the table built by paths_pe_table for this pe_mode, d and pe_rows): same values as the sin / cos calls of the tokens-assemble launch. */
 int paths_importance_tokens_rows(const float* hid, int64_t ldh, const float* w2, const float* b2, const int64_t* num_ims, int rows_per_slide,
                                  int64_t M, int Hi, float* importance, int relu, int imp_mul, const float* bp, const float* special,

@@ -250,6 +250,7 @@ int paths_lstm_cell(const float* x, int64_t ldx, const float* h0, int64_t ldh0, 
   PATHS_REQUIRE(hp != nullptr || (h0 == nullptr) == (c0 == nullptr), "lstm_cell: h0 and c0 must both be given or both be null");
   PATHS_REQUIRE((hp == nullptr) == (hp_row == nullptr) && (hp == nullptr || h0 == nullptr),
                 "lstm_cell: hp/hp_row come together and replace h0 (the h half of the gate GEMM was done per parent)");
+  PATHS_REQUIRE(!(phases & 4) || y != nullptr, "lstm_cell: y is required (only paths_lstm_cell_x6 can skip it)");
   const int Ktot = 2 * D;
   GemmOperands g{x, ldx, D, h0, ldh0, h0 ? D : 0, w_gates, Ktot, M, num_ims, rows_per_slide};
   // phases: bit0 = memory-cell GEMM (f,r,m -> c1), bit1 = output-gate GEMM, bit2 = mem_to_out GEMM (+ residual).
@@ -271,7 +272,6 @@ int paths_lstm_cell(const float* x, int64_t ldx, const float* h0, int64_t ldh0, 
   // (3) h1 = o * tanh(Wc c1 + bc), Y = X + h1
   if (phases & 4) {
     GemmOperands gh{state_out + D, ldso, Hc, nullptr, 0, 0, w_mem, Hc, M, num_ims, rows_per_slide};
-    PATHS_REQUIRE(y != nullptr, "lstm_cell: y is required (only paths_lstm_cell_x6 can skip it)");
     int rc;
     if (save_tc != nullptr) {
       EpiLstmH<true, true> e{b_mem, ws_o, D, x, ldx, state_out, ldso, y, ldy, D, save_tc};

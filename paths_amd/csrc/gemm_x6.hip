@@ -610,7 +610,9 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
                  float* state_out, int64_t ldso, float* y, int64_t ldy, float* ws_o, float* save_frm, float* save_tc,
                  const float* hp, const int* hp_row, int M, int D, int Hc, const int64_t* num_ims, int rows_per_slide,
                  int phases, int planes, float wg_scale, float wm_scale, float a_scale, hipStream_t stream) {
-  PATHS_REQUIRE(D % 256 == 0 && Hc % 64 == 0, "lstm_cell_x6: D (%d) must be a multiple of 256 and Hc (%d) of 64", D, Hc);
+  // Hc >= 128: the mem_to_out product runs over K = Hc and the split-operand GEMM needs K >= 128 (launch_x6_np); refused here, before
+  // the gate launches, instead of by the third launch
+  PATHS_REQUIRE(D % 256 == 0 && Hc % 64 == 0 && Hc >= 128, "lstm_cell_x6: D (%d) must be a multiple of 256 and Hc (%d) a multiple of 64, >= 128", D, Hc);
   if constexpr (A16) {
     PATHS_REQUIRE(x_rows != nullptr && x == nullptr && planes == 2, "lstm_cell_x6_h16: fp16 rows are given as x_rows (planes = 2)");
     PATHS_REQUIRE(h16_scale_ok(a_scale), "lstm_cell_x6_h16: a_scale must be a power of two in [1, 2^15]");
@@ -620,6 +622,10 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
                 "lstm_cell_x6: hp/hp_row come together and replace h0 (the h half of the gate GEMM was done per parent)");
   PATHS_REQUIRE(planes == 3 || (pow2(wg_scale) && pow2(wm_scale) && pow2(a_scale)), "lstm_cell_x6: scales must be powers of two");
   PATHS_REQUIRE(x_rows == nullptr || (h0 == nullptr && y == nullptr && save_tc == nullptr), "lstm_cell_x6: x_rows (rows addressed in place) excludes h0, y and the training saves");
+  // (the shape and operand-combination refusals come before the first launch; launch_x6_np still checks each launch's own strides,
+  // alignment and extents)
+  PATHS_REQUIRE(save_tc == nullptr || y != nullptr, "lstm_cell_x6: save_tc (training) needs y");
+  PATHS_REQUIRE(planes == 2 || planes == 3, "lstm_cell_x6: planes must be 3 (bf16 x6) or 2 (fp16 x3), got %d", planes);
   if (planes == 3) wg_scale = wm_scale = a_scale = 1.0f;
   const char* wg = reinterpret_cast<const char*>(w_gates_x6);
   const int64_t gs = group_stride(planes, 2 * D);
@@ -665,8 +671,6 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
   if (phases & 4) {   // h1 = o * tanh(Wc c1 + bc), Y = X + h1
     X6Operands gh{state_out + D, ldso, Hc, nullptr, nullptr, 0, 0, nullptr, 0, reinterpret_cast<const char*>(w_mem_x6), group_stride(planes, Hc), M, num_ims, rows_per_slide, a_scale};
     int rc;
-    PATHS_REQUIRE(save_tc == nullptr || y != nullptr, "lstm_cell_x6: save_tc (training) needs y");
-    PATHS_REQUIRE(planes == 2 || planes == 3, "lstm_cell_x6: planes must be 3 (bf16 x6) or 2 (fp16 x3), got %d", planes);
     if (save_tc != nullptr) {
       EpiLstmH<true, true> e{b_mem, ws_o, D, x, ldx, state_out, ldso, y, ldy, D, save_tc, sm};
       // (round 5: the training form on the inference form's 128 x 128 tiles at H_TRAIN_OCC waves per SIMD: K = 256 is 16 k16 stages

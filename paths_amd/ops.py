@@ -276,10 +276,11 @@ def _pe_divs(d: int, dev) -> tuple:
     return _PE_DIVS[key]
 
 
-def use_x6(D: int, Hc: int = 64) -> bool:
-    """Split-operand GEMMs (either split) are used for this shape."""
+def use_x6(D: int, Hc: Optional[int] = None) -> bool:
+    """Split-operand GEMMs (either split) are used for this shape.  ``Hc``: the LSTM's hidden width (None: no LSTM) - its mem_to_out
+    product runs over K = Hc and the split-operand GEMM needs K >= 128, so Hc = 64 takes the f32 kernels (paths_lstm_cell)."""
     split_planes()
-    return GEMM_MODE != "f32" and D % 256 == 0 and Hc % 64 == 0
+    return GEMM_MODE != "f32" and D % 256 == 0 and (Hc is None or (Hc % 64 == 0 and Hc >= 128))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1015,7 +1016,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
     pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
     tokens = torch.empty((B, T, d), **f32)
 
-    x6 = use_x6(D, lstm_pack["Hc"] if mc.lstm else 64)
+    x6 = use_x6(D, lstm_pack["Hc"] if mc.lstm else None)
     assert x_rows is None or (x6 and split_planes() == 2 and mc.lstm), "row pointers need the default split mode and lstm=true"
     assert not x_rows_h16 or x_rows is not None, "x_rows_h16 describes x_rows"
     h16 = "_h16" if x_rows_h16 else ""
@@ -1181,9 +1182,16 @@ def parent_gate_product(lstm_pack, hk, hp, planes: int = 0, lagged: bool = False
         wg, wg_s = _x6_of(lstm_pack, "w_gates", planes, lagged=lagged)
         _lib.call("paths_gemm_nt_x6", p(hk), D, p(wg), 2 * D, D, None, p(hp), G, rows, G, G, D, 0, None, 0, None, 0, 0, planes, wg_s,
                   A_SCALE if planes == 2 else 1.0, _lib.stream())
-    else:
+    elif G % 128 == 0:
         _lib.call("paths_gemm_nt_f32", p(hk), D, lstm_pack["w_gates"].data_ptr() + 4 * D, 2 * D, None, p(hp), G, rows, G, G, D, 0,
                   None, 0, None, 0, 0, _lib.stream())
+    else:
+        # Hc an odd multiple of 64: the f32 kernel reads whole 128-row weight tiles, so it gets a zero-padded copy of the h half (kept
+        # with the pack, which is rebuilt when the parameters change)
+        wh = lstm_pack.get("w_gates_h_pad")
+        if wh is None:
+            wh = lstm_pack["w_gates_h_pad"] = _pad_rows(lstm_pack["w_gates"][:, D:2 * D])
+        _lib.call("paths_gemm_nt_f32", p(hk), D, p(wh), D, None, p(hp), G, rows, G, wh.shape[0], D, 0, None, 0, None, 0, 0, _lib.stream())
 
 
 def parent_partials(lstm_pack, state_out: torch.Tensor, keep_idx: torch.Tensor, keep_count: torch.Tensor,
