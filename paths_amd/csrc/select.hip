@@ -109,11 +109,162 @@ static int launch_topk(const float* scores, int64_t ld, const int64_t* num_ims, 
 // ------------------------------------------------------------------------------------------------
 // expansion: kept patch (x,y) -> blocks (2x,2y) | (2x,2y+1) | (2x+1,2y) | (2x+1,2y+1), each in top-K
 // order (slide.py:307-315); keep child iff in bounds and tissue (slide.py:320-325); stable compaction.
+//
+// Two forms.  expand_kernel does all of it for resident slides.  An on-demand slide (paths_amd/data_utils/slide.py:OnDemandSlide;
+// reference RawSlide.recurse, data_utils/slide.py:173-198) has no tissue mask of the next grid - whether a cell is tissue is known
+// only once the caller has encoded it - so there the expansion is split around the caller: candidate_kernel is the first half
+// (children, bounds, stable compaction: the cells the caller is asked for), admit_kernel the second (tissue filter over the rows the
+// caller supplied, stable compaction, bookkeeping).  One workgroup per slide in all of them; the pieces are stated once, below.
 // ------------------------------------------------------------------------------------------------
 // threads of the one workgroup per slide.  Alone the kernel is fastest at 1024 (11.7 us against 15.1 / 23.5 at 512 / 256), but a
 // 16-wave workgroup has to wait for a CU with four free wave slots per SIMD beside the aggregator's kernels: in the recursion 512
 // gives 3,591-3,624 slides/s against 3,527-3,535 (sustained 3,717-3,731 against 3,609-3,616), 256 gives 3,589-3,618
-constexpr int EXP_NT = 512, EXP_NW = EXP_NT / 64;
+constexpr int EXP_NT = 512;
+// candidates per thread whose evaluation is kept in registers between the counting and the writing pass (at keep = 512 a thread owns four)
+constexpr int EXP_CACHE = 4;
+
+// cell of the child in block blk (0..3, block order of slide.py:305-315) of the patch at pixel (lx, ly); true iff inside the X x Y grid
+__device__ __forceinline__ bool child_cell(int64_t lx, int64_t ly, int blk, int patch_size, int X, int Y, int& cx, int& cy) {
+  const bool small = (uint64_t)(lx | ly) < 0x80000000ull;       // (pixel coordinates: a 32-bit division is a fraction of the 64-bit one)
+  const int64_t px = small ? (int64_t)((int)lx / patch_size) : lx / patch_size;
+  const int64_t py = small ? (int64_t)((int)ly / patch_size) : ly / patch_size;
+  const int64_t x = 2 * px + (blk >> 1), y = 2 * py + (blk & 1);
+  cx = (int)x; cy = (int)y;                                     // (exact for every cell inside the grid)
+  return x >= 0 && y >= 0 && x < X && y < Y;
+}
+
+// exclusive prefix of `mine` over the NT threads of the workgroup; total = the sum over all of them.  Shuffles inside a wave, the
+// wave totals through LDS: two barriers instead of the twenty of a Hillis-Steele scan over LDS.  Once per kernel (the LDS is its own).
+template <int NT>
+__device__ __forceinline__ int exp_scan(int mine, int& total) {
+  constexpr int NW = NT / 64;
+  __shared__ int part[2 * NW];
+  const int tid = threadIdx.x;
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if ((tid & 63) >= off) incl += v;
+  }
+  if ((tid & 63) == 63) part[tid >> 6] = incl;
+  __syncthreads();
+  if (tid < NW) {
+    int t = part[tid];
+#pragma unroll
+    for (int off = 1; off < NW; off <<= 1) {
+      const int v = __shfl_up(t, off);
+      if (tid >= off) t += v;
+    }
+    part[NW + tid] = t;                                 // inclusive totals of waves 0 .. tid
+  }
+  __syncthreads();
+  total = part[2 * NW - 1];
+  return incl - mine + ((tid >> 6) ? part[NW + (tid >> 6) - 1] : 0);
+}
+
+// The candidates c = blk * count + i (i: kept slot) of one slide, in order, a contiguous run of them per thread.  A candidate is kept
+// iff its cell is inside the grid and (TISSUE) its mask byte is set.  head(number kept) runs once the count is known and says whether
+// to go on; then emit(c, kept, cx, cy, i, pos) runs for every candidate, pos = number of kept candidates before c.  Returns head's answer.
+// kidx: the slide's kept indices, loc: the slide's locations [., 2].
+//
+// The first EXP_CACHE candidates of a thread are evaluated ONCE and replayed from registers in the emit pass.  Each evaluation is a
+// chain of dependent loads (kept index -> its location -> the tissue byte), so they run in stages, the chains of a thread side by
+// side: all kept indices, then all locations, then all cells, then all mask bytes.  Candidates beyond the cache are evaluated twice.
+template <bool TISSUE, class Head, class Emit>
+__device__ __forceinline__ bool for_each_child(const int* __restrict__ kidx, int count, const int64_t* __restrict__ loc, int patch_size,
+                                               int X, int Y, const uint8_t* __restrict__ mask, Head head, Emit emit) {
+  const int tid = threadIdx.x, total = 4 * count;
+  const int per = (total + EXP_NT - 1) / EXP_NT;
+  const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
+  auto child = [&](int c, int& cx, int& cy, int& i) -> bool {
+    const int blk = c / count;
+    i = c - blk * count;
+    const int64_t* l = loc + 2 * (int64_t)kidx[i];
+    if (!child_cell(l[0], l[1], blk, patch_size, X, Y, cx, cy)) return false;
+    return !TISSUE || mask[(int64_t)cx * Y + cy] != 0;
+  };
+
+  int ccx[EXP_CACHE], ccy[EXP_CACHE], cci[EXP_CACHE];
+  bool ckeep[EXP_CACHE];
+  int mine = 0;
+  {
+    int blk[EXP_CACHE], prow[EXP_CACHE];
+    bool on[EXP_CACHE];
+    int64_t lx[EXP_CACHE], ly[EXP_CACHE];
+#pragma unroll
+    for (int u = 0; u < EXP_CACHE; ++u) {
+      on[u] = c0 + u < c1;
+      const int c = on[u] ? c0 + u : 0;
+      blk[u] = count > 0 ? c / count : 0;
+      cci[u] = c - blk[u] * count;
+      prow[u] = on[u] ? kidx[cci[u]] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < EXP_CACHE; ++u) {
+      lx[u] = on[u] ? loc[2 * (int64_t)prow[u]] : 0;
+      ly[u] = on[u] ? loc[2 * (int64_t)prow[u] + 1] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < EXP_CACHE; ++u) ckeep[u] = child_cell(lx[u], ly[u], blk[u], patch_size, X, Y, ccx[u], ccy[u]) && on[u];
+    if constexpr (TISSUE) {
+#pragma unroll
+      for (int u = 0; u < EXP_CACHE; ++u) ckeep[u] = ckeep[u] && mask[(int64_t)ccx[u] * Y + ccy[u]] != 0;
+    }
+#pragma unroll
+    for (int u = 0; u < EXP_CACHE; ++u) mine += ckeep[u] ? 1 : 0;
+  }
+  for (int c = c0 + EXP_CACHE; c < c1; ++c) { int cx, cy, i; mine += child(c, cx, cy, i) ? 1 : 0; }
+  int kept;
+  int pos = exp_scan<EXP_NT>(mine, kept);
+  if (!head(kept)) return false;
+  for (int c = c0; c < c1; ++c) {
+    int cx = 0, cy = 0, i = 0;
+    bool keepc;
+    const int u = c - c0;
+    if (u < EXP_CACHE) {
+      keepc = false;
+#pragma unroll
+      for (int v = 0; v < EXP_CACHE; ++v)
+        if (v == u) { keepc = ckeep[v]; cx = ccx[v]; cy = ccy[v]; i = cci[v]; }
+    } else {
+      keepc = child(c, cx, cy, i);
+    }
+    emit(c, keepc, cx, cy, i, pos);
+    pos += keepc ? 1 : 0;
+  }
+  return true;
+}
+
+// The bookkeeping rows of the children of slide b = base / n_next: where a child lies, which patch it descends from, and where its
+// parent state (src_row) and its features (src_cell) are read.  hp_row (child -> row of the kept-parent table) is optional.
+struct ChildRows {
+  int64_t* locs_out; int64_t* parent_out; int* src_row; int* src_cell; int* hp_row;
+  int64_t base;
+  __device__ __forceinline__ void put(int pos, int64_t cx, int64_t cy, int patch_size, int64_t parent, int srow, int scell, int hp) const {
+    const int64_t o = base + pos;
+    locs_out[2 * o] = cx * patch_size;
+    locs_out[2 * o + 1] = cy * patch_size;
+    parent_out[o] = parent;
+    src_row[o] = srow;
+    src_cell[o] = scell;
+    if (hp_row) hp_row[o] = hp;
+  }
+  // padding tail [n_out, n_next): zero rows like collate_fn's zero padding (dataset.py:216-218)
+  __device__ __forceinline__ void pad(int n_out, int64_t n_next) const {
+    for (int j = n_out + threadIdx.x; j < n_next; j += EXP_NT) put(j, 0, 0, 0, 0, -1, -1, -1);
+  }
+};
+
+// thread 0 publishes the number of children of its slide; false = over capacity: the workgroup writes nothing else
+__device__ __forceinline__ bool publish_count(int n_out, int64_t n_next, int64_t* __restrict__ num_out_b, int* __restrict__ status) {
+  if (threadIdx.x == 0) {
+    *num_out_b = n_out;
+    if (n_out == 0) atomicOr(status, 1);               // no tissue among the children: the reference falls back to "all cells" (slide.py:336-352)
+    if (n_out > n_next) atomicOr(status, 2);
+  }
+  return n_out <= n_next;
+}
+
 __global__ void __launch_bounds__(EXP_NT)
 expand_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restrict__ keep_count,
               const int64_t* __restrict__ locs, int64_t n_cur, int patch_size,
@@ -124,158 +275,20 @@ expand_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __restri
               int* __restrict__ src_row, int* __restrict__ src_cell, int* __restrict__ status,
               int* __restrict__ child_pos /*[B, 4*ldk] or null: output row of every candidate child, -1 if dropped*/,
               int* __restrict__ hp_row /*[B, n_next] or null: row of the kept-parent table (b*ldk + i) of every child*/) {
-  __shared__ int part[2 * EXP_NW];
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.x;
   const int count = max(0, min(keep_count[b], (int)ldk));      // (keep_idx holds ldk entries per slide, child_pos 4 * ldk)
-  const int total = 4 * count;
-  const int X = next_x[b], Y = next_y[b];
-  const uint8_t* mask = reinterpret_cast<const uint8_t*>(mask_ptrs[b]);
-  const int per = (total + EXP_NT - 1) / EXP_NT;
-  const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
-
-  auto child = [&](int c, int& cx, int& cy, int& i) -> bool {
-    const int blk = c / count;
-    i = c - blk * count;
-    const int prow = keep_idx[(int64_t)b * ldk + i];
-    const int64_t lx = locs[((int64_t)b * n_cur + prow) * 2], ly = locs[((int64_t)b * n_cur + prow) * 2 + 1];
-    const bool small = (uint64_t)(lx | ly) < 0x80000000ull;       // (pixel coordinates: a 32-bit division is a fraction of the 64-bit one)
-    const int64_t px = small ? (int64_t)((int)lx / patch_size) : lx / patch_size;
-    const int64_t py = small ? (int64_t)((int)ly / patch_size) : ly / patch_size;
-    const int64_t x = 2 * px + (blk >> 1), y = 2 * py + (blk & 1);
-    cx = (int)x; cy = (int)y;
-    if (x >= X || y >= Y) return false;
-    return mask[(int64_t)x * Y + y] != 0;
-  };
-
-  // the first candidates of this thread are evaluated ONCE (each evaluation is a chain of four dependent loads: kept index -> its
-  // location -> the tissue bit; at keep = 512 a thread owns two candidates) and kept in registers for the write pass below
-  constexpr int CACHE = 4;
-  int ccx[CACHE], ccy[CACHE], cci[CACHE];
-  bool ckeep[CACHE];
-  int mine = 0;
-  {
-    // ... in three stages, so that the CACHE chains of a thread run side by side (all kept indices, then all locations, then all bits)
-    int blk[CACHE], prow[CACHE];
-    bool on[CACHE], inb[CACHE];
-    int64_t lx[CACHE], ly[CACHE];
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      on[u] = c0 + u < c1;
-      const int c = on[u] ? c0 + u : 0;
-      blk[u] = count > 0 ? c / count : 0;
-      cci[u] = c - blk[u] * count;
-      prow[u] = on[u] ? keep_idx[(int64_t)b * ldk + cci[u]] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      lx[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2] : 0;
-      ly[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2 + 1] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      const bool small = (uint64_t)(lx[u] | ly[u]) < 0x80000000ull;
-      const int64_t px = small ? (int64_t)((int)lx[u] / patch_size) : lx[u] / patch_size;
-      const int64_t py = small ? (int64_t)((int)ly[u] / patch_size) : ly[u] / patch_size;
-      const int64_t x = 2 * px + (blk[u] >> 1), y = 2 * py + (blk[u] & 1);
-      ccx[u] = (int)x; ccy[u] = (int)y;
-      inb[u] = on[u] && x < X && y < Y;
-    }
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      ckeep[u] = inb[u] && mask[(int64_t)ccx[u] * Y + ccy[u]] != 0;
-      mine += ckeep[u] ? 1 : 0;
-    }
-  }
-  for (int c = c0 + CACHE; c < c1; ++c) { int cx, cy, i; mine += child(c, cx, cy, i) ? 1 : 0; }
-  // inclusive scan over the per-thread partials: shuffles inside a wave, the wave totals through LDS (two barriers instead of the
-  // twenty of a Hillis-Steele scan over LDS)
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int v = __shfl_up(incl, off);
-    if ((tid & 63) >= off) incl += v;
-  }
-  if ((tid & 63) == 63) part[tid >> 6] = incl;
-  __syncthreads();
-  if (tid < EXP_NW) {
-    int t = part[tid];
-#pragma unroll
-    for (int off = 1; off < EXP_NW; off <<= 1) {
-      const int v = __shfl_up(t, off);
-      if (tid >= off) t += v;
-    }
-    part[EXP_NW + tid] = t;                             // inclusive totals of waves 0 .. tid
-  }
-  __syncthreads();
-  int pos = incl - mine + ((tid >> 6) ? part[EXP_NW + (tid >> 6) - 1] : 0);
-  const int n_out = part[2 * EXP_NW - 1];
-  if (tid == 0) {
-    num_out[b] = n_out;
-    if (n_out == 0) atomicOr(status, 1);               // reference falls back to "all cells" (slide.py:336-352)
-    if (n_out > n_next) atomicOr(status, 2);
-  }
-  if (n_out > n_next) return;
-  for (int c = c0; c < c1; ++c) {
-    int cx, cy, i;
-    bool keepc;
-    const int u = c - c0;
-    if (u < CACHE) {
-      keepc = false;
-#pragma unroll
-      for (int v = 0; v < CACHE; ++v)
-        if (v == u) { keepc = ckeep[v]; cx = ccx[v]; cy = ccy[v]; i = cci[v]; }
-    } else {
-      keepc = child(c, cx, cy, i);
-    }
-    if (child_pos) child_pos[(int64_t)b * 4 * ldk + c] = keepc ? pos : -1;
-    if (keepc) {
-      const int64_t o = (int64_t)b * n_next + pos;
-      locs_out[2 * o] = (int64_t)cx * patch_size;
-      locs_out[2 * o + 1] = (int64_t)cy * patch_size;
-      parent_out[o] = i;
-      src_row[o] = keep_idx[(int64_t)b * ldk + i];
-      src_cell[o] = cx * Y + cy;
-      if (hp_row) hp_row[o] = (int)((int64_t)b * ldk + i);
-      ++pos;
-    }
-  }
-  // padding tail: zero the bookkeeping rows like collate_fn's zero padding (dataset.py:216-218)
-  for (int j = n_out + tid; j < n_next; j += EXP_NT) {
-    const int64_t o = (int64_t)b * n_next + j;
-    locs_out[2 * o] = 0; locs_out[2 * o + 1] = 0; parent_out[o] = 0; src_row[o] = -1; src_cell[o] = -1;
-    if (hp_row) hp_row[o] = -1;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The expansion split around the caller (on-demand slides, paths_amd/data_utils/slide.py:OnDemandSlide; reference RawSlide.recurse,
-// data_utils/slide.py:173-198): such a slide has no tissue mask of the next grid - whether a cell is tissue is known only once the
-// caller has encoded it.  candidate_kernel is expand_kernel's first half (children, bounds, stable compaction: the cells the caller
-// is asked for), admit_kernel its second half (tissue filter over the rows the caller supplied, stable compaction, the bookkeeping
-// expand_kernel writes).  Both: one workgroup per slide and expand_kernel's scan (shuffles inside a wave, wave totals through LDS).
-// ------------------------------------------------------------------------------------------------
-// exclusive prefix of `mine` over the workgroup's threads; total = the sum over all of them.  part: 2 * EXP_NW ints of LDS
-__device__ __forceinline__ int exp_scan(int mine, int* part, int tid, int& total) {
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int v = __shfl_up(incl, off);
-    if ((tid & 63) >= off) incl += v;
-  }
-  if ((tid & 63) == 63) part[tid >> 6] = incl;
-  __syncthreads();
-  if (tid < EXP_NW) {
-    int t = part[tid];
-#pragma unroll
-    for (int off = 1; off < EXP_NW; off <<= 1) {
-      const int v = __shfl_up(t, off);
-      if (tid >= off) t += v;
-    }
-    part[EXP_NW + tid] = t;                             // inclusive totals of waves 0 .. tid
-  }
-  __syncthreads();
-  total = part[2 * EXP_NW - 1];
-  return incl - mine + ((tid >> 6) ? part[EXP_NW + (tid >> 6) - 1] : 0);
+  const int Y = next_y[b];
+  const int* kidx = keep_idx + (int64_t)b * ldk;
+  const ChildRows rows{locs_out, parent_out, src_row, src_cell, hp_row, (int64_t)b * n_next};
+  int n_out = 0;
+  const bool fits = for_each_child<true>(
+      kidx, count, locs + (int64_t)b * n_cur * 2, patch_size, next_x[b], Y, reinterpret_cast<const uint8_t*>(mask_ptrs[b]),
+      [&](int kept) { n_out = kept; return publish_count(kept, n_next, num_out + b, status); },
+      [&](int c, bool keepc, int cx, int cy, int i, int pos) {
+        if (child_pos) child_pos[(int64_t)b * 4 * ldk + c] = keepc ? pos : -1;
+        if (keepc) rows.put(pos, cx, cy, patch_size, i, kidx[i], cx * Y + cy, (int)((int64_t)b * ldk + i));
+      });
+  if (fits) rows.pad(n_out, n_next);
 }
 
 __global__ void __launch_bounds__(EXP_NT)
@@ -283,85 +296,18 @@ candidate_kernel(const int* __restrict__ keep_idx, int64_t ldk, const int* __res
                  const int64_t* __restrict__ locs, int64_t n_cur, int patch_size,
                  const int* __restrict__ next_x, const int* __restrict__ next_y,
                  int* __restrict__ cand_count, int64_t* __restrict__ cand_cells /*[B, 4*ldk, 2]*/, int* __restrict__ cand_slot /*[B, 4*ldk]*/) {
-  __shared__ int part[2 * EXP_NW];
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.x;
   const int count = max(0, min(keep_count[b], (int)ldk));      // (the tables hold 4 * ldk entries per slide)
-  const int total = 4 * count;
-  const int X = next_x[b], Y = next_y[b];
-  const int per = (total + EXP_NT - 1) / EXP_NT;
-  const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
-
-  // cell of candidate c = blk * count + i (block order of slide.py:305-315) and whether it lies inside the next grid
-  auto cell = [&](int64_t lx, int64_t ly, int blk, int64_t& x, int64_t& y) -> bool {
-    const bool small = (uint64_t)(lx | ly) < 0x80000000ull;       // (the 32-bit division is only the fast path)
-    const int64_t px = small ? (int64_t)((int)lx / patch_size) : lx / patch_size;
-    const int64_t py = small ? (int64_t)((int)ly / patch_size) : ly / patch_size;
-    x = 2 * px + (blk >> 1); y = 2 * py + (blk & 1);
-    return x >= 0 && y >= 0 && x < X && y < Y;
-  };
-  auto child = [&](int c, int64_t& x, int64_t& y, int& i) -> bool {
-    const int blk = c / count;
-    i = c - blk * count;
-    const int prow = keep_idx[(int64_t)b * ldk + i];
-    return cell(locs[((int64_t)b * n_cur + prow) * 2], locs[((int64_t)b * n_cur + prow) * 2 + 1], blk, x, y);
-  };
-
-  // as in expand_kernel: the first candidates of a thread are evaluated once, their load chains side by side, and kept for the write pass
-  constexpr int CACHE = 4;
-  int64_t ccx[CACHE], ccy[CACHE];
-  int cci[CACHE];
-  bool ckeep[CACHE];
-  int mine = 0;
-  {
-    int blk[CACHE], prow[CACHE];
-    bool on[CACHE];
-    int64_t lx[CACHE], ly[CACHE];
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      on[u] = c0 + u < c1;
-      const int c = on[u] ? c0 + u : 0;
-      blk[u] = count > 0 ? c / count : 0;
-      cci[u] = c - blk[u] * count;
-      prow[u] = on[u] ? keep_idx[(int64_t)b * ldk + cci[u]] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      lx[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2] : 0;
-      ly[u] = on[u] ? locs[((int64_t)b * n_cur + prow[u]) * 2 + 1] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < CACHE; ++u) {
-      ckeep[u] = cell(lx[u], ly[u], blk[u], ccx[u], ccy[u]) && on[u];
-      mine += ckeep[u] ? 1 : 0;
-    }
-  }
-  for (int c = c0 + CACHE; c < c1; ++c) { int64_t x, y; int i; mine += child(c, x, y, i) ? 1 : 0; }
-  int n_cand;
-  int pos = exp_scan(mine, part, tid, n_cand);
-  if (tid == 0) cand_count[b] = n_cand;
   const int64_t row = (int64_t)b * 4 * ldk;
-  for (int c = c0; c < c1; ++c) {
-    int64_t x = 0, y = 0;
-    int i = 0;
-    bool keepc;
-    const int u = c - c0;
-    if (u < CACHE) {
-      keepc = false;
-#pragma unroll
-      for (int v = 0; v < CACHE; ++v)
-        if (v == u) { keepc = ckeep[v]; x = ccx[v]; y = ccy[v]; i = cci[v]; }
-    } else {
-      keepc = child(c, x, y, i);
-    }
-    if (keepc) {
-      cand_cells[2 * (row + pos)] = x;
-      cand_cells[2 * (row + pos) + 1] = y;
-      cand_slot[row + pos] = i;
-      ++pos;
-    }
-  }
+  int n_cand = 0;
+  for_each_child<false>(
+      keep_idx + (int64_t)b * ldk, count, locs + (int64_t)b * n_cur * 2, patch_size, next_x[b], next_y[b], nullptr,
+      [&](int kept) { n_cand = kept; if (threadIdx.x == 0) cand_count[b] = kept; return true; },
+      [&](int, bool keepc, int cx, int cy, int i, int pos) {
+        if (keepc) { cand_cells[2 * (row + pos)] = cx; cand_cells[2 * (row + pos) + 1] = cy; cand_slot[row + pos] = i; }
+      });
   // padding: no cell, no slot
-  for (int64_t j = n_cand + tid; j < 4 * ldk; j += EXP_NT) {
+  for (int64_t j = n_cand + threadIdx.x; j < 4 * ldk; j += EXP_NT) {
     cand_cells[2 * (row + j)] = -1; cand_cells[2 * (row + j) + 1] = -1; cand_slot[row + j] = -1;
   }
 }
@@ -373,7 +319,6 @@ admit_kernel(const int* __restrict__ cand_count, const int64_t* __restrict__ can
              int64_t* __restrict__ num_out, int64_t* __restrict__ locs_out, int64_t* __restrict__ parent_out,
              int* __restrict__ src_row, int* __restrict__ src_cell, int* __restrict__ status,
              int* __restrict__ child_pos /*[B, 4*ldk] or null*/, int* __restrict__ hp_row /*[B, n_next] or null*/) {
-  __shared__ int part[2 * EXP_NW];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int64_t row = (int64_t)b * 4 * ldk;
   const int n_cand = (int)max((int64_t)0, min((int64_t)cand_count[b], 4 * ldk));
@@ -385,40 +330,26 @@ admit_kernel(const int* __restrict__ cand_count, const int64_t* __restrict__ can
   int mine = 0;
   for (int j = j0; j < j1; ++j) mine += admitted(j) ? 1 : 0;
   int n_out;
-  int pos = exp_scan(mine, part, tid, n_out);
-  if (tid == 0) {
-    num_out[b] = n_out;
-    if (n_out == 0) atomicOr(status, 1);               // no tissue among the children (the reference would take every cell, slide.py:336-352)
-    if (n_out > n_next) atomicOr(status, 2);
-  }
-  if (n_out > n_next) return;
+  int pos = exp_scan<EXP_NT>(mine, n_out);
+  if (!publish_count(n_out, n_next, num_out + b, status)) return;
   if (child_pos) {
     // expand_kernel's table is indexed by the candidate BEFORE the bounds filter, c = blk * count + slot: every entry starts as
     // "dropped", the admitted ones are written behind the barrier (blk is the parity of the cell)
     for (int c = tid; c < 4 * count; c += EXP_NT) child_pos[row + c] = -1;
     __syncthreads();
   }
+  const ChildRows rows{locs_out, parent_out, src_row, src_cell, hp_row, (int64_t)b * n_next};
   for (int j = j0; j < j1; ++j) {
     if (!admitted(j)) continue;
     const int64_t cx = cand_cells[2 * (row + j)], cy = cand_cells[2 * (row + j) + 1];
     const int i = cand_slot[row + j];
-    const int64_t o = (int64_t)b * n_next + pos;
-    locs_out[2 * o] = cx * patch_size;
-    locs_out[2 * o + 1] = cy * patch_size;
-    parent_out[o] = i;
-    src_row[o] = keep_idx[(int64_t)b * ldk + i];
-    src_cell[o] = j;                                    // the row's index in the slide's candidate buffer
-    if (hp_row) hp_row[o] = (int)((int64_t)b * ldk + i);
+    // (src_cell: the row's index in the slide's candidate buffer)
+    rows.put(pos, cx, cy, patch_size, i, keep_idx[(int64_t)b * ldk + i], j, (int)((int64_t)b * ldk + i));
     if (child_pos) child_pos[row + (int)(((cx & 1) << 1) | (cy & 1)) * count + i] = pos;
     ++pos;
   }
-  for (int j = n_out + tid; j < n_next; j += EXP_NT) {   // padding tail, as expand_kernel
-    const int64_t o = (int64_t)b * n_next + j;
-    locs_out[2 * o] = 0; locs_out[2 * o + 1] = 0; parent_out[o] = 0; src_row[o] = -1; src_cell[o] = -1;
-    if (hp_row) hp_row[o] = -1;
-  }
+  rows.pad(n_out, n_next);
 }
-
 
 // Rare fallback (reference data_utils/slide.py:336-352): a slide whose kept patches have NO tissue children
 // continues with every tissue cell of the next grid (or every cell if the grid has no tissue at all), zero patch
@@ -428,7 +359,6 @@ fallback_all_cells_kernel(const int* __restrict__ next_x, const int* __restrict_
                           int patch_size, int64_t n_next, int64_t* __restrict__ num_out, int64_t* __restrict__ locs_out,
                           int64_t* __restrict__ parent_out, int* __restrict__ src_row, int* __restrict__ src_cell,
                           int* __restrict__ status, int* __restrict__ hp_row) {
-  __shared__ int part[1024];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (num_out[b] != 0) return;
   const int X = next_x[b], Y = next_y[b];
@@ -438,36 +368,19 @@ fallback_all_cells_kernel(const int* __restrict__ next_x, const int* __restrict_
   const int c0 = min(tid * per, total), c1 = min(c0 + per, total);
   int mine = 0;
   for (int c = c0; c < c1; ++c) mine += mask[c] != 0;
-  part[tid] = mine;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    int v = tid >= off ? part[tid - off] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  const int tissue = part[1023];
+  int tissue;
+  const int before = exp_scan<1024>(mine, tissue);
   const bool all = tissue == 0;                       // "hope that there will be tissue later" (slide.py:344-347)
   const int n_out = all ? total : tissue;
-  int pos = all ? c0 : part[tid] - mine;
-  __syncthreads();
+  int pos = all ? c0 : before;
   if (tid == 0) {
     num_out[b] = n_out;
     if (n_out > n_next) atomicOr(status, 2);
   }
   if (n_out > n_next) return;
-  for (int c = c0; c < c1; ++c) {
-    if (all || mask[c]) {
-      const int64_t o = (int64_t)b * n_next + pos;
-      locs_out[2 * o] = (int64_t)(c / Y) * patch_size;
-      locs_out[2 * o + 1] = (int64_t)(c % Y) * patch_size;
-      parent_out[o] = c;
-      src_row[o] = -1;
-      src_cell[o] = c;
-      if (hp_row) hp_row[o] = -1;
-      ++pos;
-    }
-  }
+  const ChildRows rows{locs_out, parent_out, src_row, src_cell, hp_row, (int64_t)b * n_next};
+  for (int c = c0; c < c1; ++c)
+    if (all || mask[c]) rows.put(pos++, c / Y, c % Y, patch_size, c, -1, c, -1);
 }
 
 // One WAVE per output row (four rows per workgroup): features from the next-level grid, LSTM state (h|c) from the kept parent.
@@ -621,21 +534,7 @@ level0_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ gx,
 }
 
 // tissue mask: 1 iff the row's fp32 sum != 0 (slide.py:324 `fts[...].sum(dim=1) != 0`); one wave per cell.
-__global__ void __launch_bounds__(256)
-tissue_mask_kernel(const float* __restrict__ grid, int64_t cells, int D, uint8_t* __restrict__ mask) {
-  const int lane = threadIdx.x & 63;
-  const int64_t cell = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (cell >= cells) return;
-  const f32x4* row = reinterpret_cast<const f32x4*>(grid + cell * D);
-  float s = 0.f;
-  for (int i = lane; i < D / 4; i += 64) { const f32x4 v = row[i]; s += (v[0] + v[1]) + (v[2] + v[3]); }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
-  if (lane == 0) mask[cell] = s != 0.f ? 1 : 0;
-}
-
-
-// The same pass + max|x| of the whole grid (fp16-split range contract of the default GEMM mode: |x| * a_scale must stay a finite
+// With absmax_bits (optional) also max|x| of the whole grid (fp16-split range contract of the default GEMM mode: |x| * a_scale must stay a finite
 // fp16).  absmax_bits holds the fp32 BIT PATTERN of the running maximum: non-negative floats order like their bit patterns and a
 // NaN's pattern is above +inf's, so a NaN anywhere reads back as "not finite".  The atomic is only issued by waves that beat the
 // value they last saw, i.e. a handful of times per grid.
@@ -658,7 +557,7 @@ tissue_mask_absmax_kernel(const T* __restrict__ grid, int64_t cells, int D, uint
   for (int o = 1; o < 64; o <<= 1) { s += __shfl_xor(s, o); m = max(m, (unsigned)__shfl_xor((int)m, o)); }
   if (lane == 0) {
     if (mask) mask[cell] = s != 0.f ? 1 : 0;
-    if (m > __hip_atomic_load(absmax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(absmax_bits, m);
+    if (absmax_bits && m > __hip_atomic_load(absmax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(absmax_bits, m);
   }
 }
 
@@ -895,7 +794,8 @@ int paths_scale_add_rows(const float* x, const float* alpha, const float* h, con
 
 int paths_tissue_mask(const float* grid, int64_t cells, int D, uint8_t* mask, hipStream_t stream) {
   PATHS_REQUIRE(cells > 0 && D % 4 == 0, "tissue_mask: bad shape");
-  hipLaunchKernelGGL(tissue_mask_kernel, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, stream, grid, cells, D, mask);
+  hipLaunchKernelGGL(tissue_mask_absmax_kernel<float>, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, stream, grid, cells, D, mask,
+                     (unsigned*)nullptr);
   PATHS_LAUNCH_CHECK("tissue_mask");
   return PATHS_OK;
 }

@@ -427,6 +427,14 @@ def _level_sizes(n0: int, keep_patches, num_levels: int) -> List[int]:
     return sizes
 
 
+def _child_buffers(B: int, cap: int, want_hp_row: bool, device):
+    """The expansion's output buffers for ``cap`` children per slide: (num_out [B] i64, locs [B,cap,2] i64, parent [B,cap] i64,
+    src_row [B,cap] i32, src_cell [B,cap] i32, hp_row [B,cap] i32 or None)."""
+    i32, i64 = dict(device=device, dtype=torch.int32), dict(device=device, dtype=torch.int64)
+    return (torch.empty((B,), **i64), torch.empty((B, cap, 2), **i64), torch.empty((B, cap), **i64),
+            torch.empty((B, cap), **i32), torch.empty((B, cap), **i32), torch.empty((B, cap), **i32) if want_hp_row else None)
+
+
 def _expand_children(batch, nxt: int, patch_size: int, keep_idx, keep_count, locs, N: int, Nn: int, status, stream: int, careful: bool,
                      want_child_pos: bool, want_hp_row: bool):
     """The children (level ``nxt``) of the kept patches: paths_expand_children into buffers of capacity ``Nn`` on ``stream``.  Returns
@@ -437,16 +445,13 @@ def _expand_children(batch, nxt: int, patch_size: int, keep_idx, keep_count, loc
     with zero parent state (reference data_utils/slide.py:336-352, paths_fallback_all_cells: src_row = -1, no gradient to any parent -
     child_pos of that slide is all -1), in buffers regrown to hold them (the returned Nn)."""
     B, cap_keep, p = len(batch), keep_idx.shape[1], _lib.ptr
-    i32 = dict(device=batch.device, dtype=torch.int32)
-    i64 = dict(device=batch.device, dtype=torch.int64)
-    child_pos = torch.empty((B, 4 * cap_keep), **i32) if want_child_pos else None
+    child_pos = torch.empty((B, 4 * cap_keep), device=batch.device, dtype=torch.int32) if want_child_pos else None
     if batch.on_demand:
         return (Nn, *_expand_on_demand(batch, nxt, patch_size, keep_idx, keep_count, locs, N, Nn, status, stream, child_pos, want_hp_row))
     gx, gy, masks = p(batch.gx[nxt]), p(batch.gy[nxt]), p(batch.mask_ptrs[nxt])
 
     def expand(cap):
-        bufs = (torch.empty((B,), **i64), torch.empty((B, cap, 2), **i64), torch.empty((B, cap), **i64),
-                torch.empty((B, cap), **i32), torch.empty((B, cap), **i32), torch.empty((B, cap), **i32) if want_hp_row else None)
+        bufs = _child_buffers(B, cap, want_hp_row, batch.device)
         _lib.call("paths_expand_children", p(keep_idx), cap_keep, p(keep_count), p(locs), N, patch_size, gx, gy, masks, B, cap,
                   *(p(t) for t in bufs[:5]), p(status), p(child_pos), p(bufs[5]), stream)
         return bufs
@@ -503,8 +508,7 @@ def _expand_on_demand(batch, nxt: int, patch_size: int, keep_idx, keep_count, lo
     counts = cand_count.cpu().tolist()                    # the host read: waits for the current stream, i.e. for the candidate kernel
     buf = batch.supply(nxt, [cand_cells[b, :counts[b]] for b in range(B)], Nc)
     mask = _mask_supplied(batch, buf, True, stream)
-    bufs = (torch.empty((B,), **i64), torch.empty((B, Nn, 2), **i64), torch.empty((B, Nn), **i64),
-            torch.empty((B, Nn), **i32), torch.empty((B, Nn), **i32), torch.empty((B, Nn), **i32) if want_hp_row else None)
+    bufs = _child_buffers(B, Nn, want_hp_row, batch.device)
     ops.timed("admit", lambda: _lib.call("paths_admit_children", p(cand_count), p(cand_cells), p(cand_slot), p(mask), p(keep_idx), cap_keep,
                                          p(keep_count), patch_size, B, Nn, *(p(t) for t in bufs[:5]), p(status), p(child_pos), p(bufs[5]), stream))
     before = batch.feat_absmax

@@ -217,3 +217,20 @@ def test_stored_entry_points_refuse_on_demand_slides_before_the_device():
                lambda: saliency.input_gradients(model, od, [2], 2)):
         with pytest.raises(NotImplementedError, match="on-demand"):
             fn()
+
+
+@pytest.mark.parametrize("want_hp_row", [True, False])
+def test_child_buffers_are_the_six_tables_of_the_expansion(want_hp_row):
+    """The resident and the split expansion hand their entry points the same tuple: shapes and dtypes of the C signature."""
+    from paths_amd import utils as putils
+    B, cap = 3, 5
+    bufs = putils._child_buffers(B, cap, want_hp_row, "cpu")
+    assert len(bufs) == 6
+    i32, i64 = torch.int32, torch.int64
+    want = [((B,), i64), ((B, cap, 2), i64), ((B, cap), i64), ((B, cap), i32), ((B, cap), i32), ((B, cap), i32)]
+    for t, (shape, dtype) in zip(bufs[:5], want):
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous()
+    if want_hp_row:
+        assert tuple(bufs[5].shape) == want[5][0] and bufs[5].dtype == want[5][1] and bufs[5].is_contiguous()
+    else:
+        assert bufs[5] is None
