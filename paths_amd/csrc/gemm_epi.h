@@ -150,6 +150,52 @@ struct EpiLstmC {
   }
 };
 
+// Depth 0 of the recursion (inference): c0 = 0, so c1 = sigmoid(r) * tanh(m) and the forget gate is multiplied by zero.  The GEMM
+// computes the remember | map column groups only (gemm_x6.hip: w_group() skips the forget group of every [f | r | m] triple of the
+// packed image while it stages W - a third of the product's columns, no second image): packed columns per wave = [r(32) | m(32)] of
+// one block of 32 memory units.  `bias` is the whole packed bias (f | r | m per block).  Bit-identical to EpiLstmC with c0 = NULL,
+// which adds an exact zero: 0 * sigmoid(f) is +0 (the sigmoid is finite) and sigmoid(r) * tanh(m) is never -0 (sigmoid_acc >= 1e-30,
+// tanh_acc is +0 or at least 2^-24 in magnitude), so neither the sum nor a fused multiply-add of the two changes a bit.
+struct EpiLstmC0 {
+  const float* bias;
+  float* c1; int64_t ldc1;         // state_out + D
+  float acc_scale = 1.0f;          // see EpiLstmC
+  template <int WTM, int WTN>
+  __device__ __forceinline__ void init(f32x16 (&acc)[WTM][WTN], int, int, int, int) const {
+#pragma unroll
+    for (int i = 0; i < WTM; ++i)
+#pragma unroll
+      for (int j = 0; j < WTN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  }
+  template <bool FULL, int WTM, int WTN>
+  __device__ __forceinline__ void run_impl(f32x16 (&acc)[WTM][WTN], int row0, int col0, int lane, int M) const {
+    const int jj = lane & 31;
+    const int unit = col0 >> 6;                    // this wave's block of 32 memory units
+    const int tcol = unit * 32;
+    const float br = bias[unit * 96 + 32 + jj], bm = bias[unit * 96 + 64 + jj];
+    const TileView c1v(c1, ldc1, lane);
+    static_for<0, WTM>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      const int trow = row0 + 32 * i;
+      char* o1 = c1v.tile(trow, tcol);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float rg = sigmoid_acc(fmaf(acc[i][0][r], acc_scale, br));
+        const float mp = tanh_acc(fmaf(acc[i][1][r], acc_scale, bm));
+        if (tile_row_ok<FULL>(trow, r, lane, M)) *tile_elem_o<FULL>(c1v, o1, trow, tcol, r, lane, M) = rg * mp;
+      }
+    });
+  }
+  template <int WTM, int WTN, int WGM, int WGN>
+  __device__ __forceinline__ void run(f32x16 (&acc)[WTM][WTN], int row0, int col0, int lane, int, int, int M, float*) const {
+    static_assert(WTN == 2, "depth-0 LSTM c epilogue wants r|m tiles");
+    if (row0 + 32 * WTM <= M) run_impl<true>(acc, row0, col0, lane, M);
+    else run_impl<false>(acc, row0, col0, lane, M);
+  }
+};
+
 // o = sigmoid(acc + b).
 // RAW (inference): the gate is only ever read back by the mem_to_out epilogue (EpiLstmH) on the same 32x32 tiles and lanes, so it
 // is stored (a) as the PRE-activation a = acc + b (the sigmoid moves into that HBM-bound epilogue, whose VALU has slack; with one

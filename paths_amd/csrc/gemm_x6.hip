@@ -64,6 +64,14 @@ struct X6Operands {
   int ksplit = 1;                  // > 1 (single-panel launches only): blockIdx.z owns the k window [z K0/ksplit, (z+1) K0/ksplit)
 };
 
+// The 32-row group of the packed weight image that holds column group `grp` of the product: the identity, except for the depth-0
+// memory-cell product (EpiLstmC0), whose column groups are the remember | map groups of the image's [f | r | m] triples.
+template <class Epi>
+__device__ __forceinline__ int w_group(int grp) {
+  if constexpr (std::is_same<Epi, EpiLstmC0>::value) return 3 * (grp >> 1) + 1 + (grp & 1);
+  else return grp;
+}
+
 // PF = how many stages ahead of its LDS write a stage is loaded into registers (1 or 2 register sets).  Stages of the
 // 128-row tiles are only ~1,500 cycles long, shorter than a loaded-L2 round trip, so those run two stages ahead.
 // OCC = waves per SIMD the register allocation is sized for: 1 (the whole 512-register file: the 256-row tiles) or more for the
@@ -143,7 +151,7 @@ gemm_x6_kernel(X6Operands g, Epi epi) {
     int pc = wave + 4 * i;
     if (pc >= NPB) pc -= 4;                            // re-stage this wave's previous piece (same bytes, same slot)
     const int sub = pc / PL, pl = pc % PL;
-    bbase[i] = g.Wt + ((int64_t)(n0 >> 5) + sub) * g.w_group_stride + pl * FRAG;
+    bbase[i] = g.Wt + (int64_t)w_group<Epi>((n0 >> 5) + sub) * g.w_group_stride + pl * FRAG;
     bwr[i] = (A1P ? SA * SUBTA + sub * SUBT : (SA + sub) * SUBT) + pl * FRAG + lane * 16;
   }
   static_assert(PF == 1 || PF == 2, "one or two register sets");
@@ -636,7 +644,25 @@ int lstm_cell_x6(const float* x, int64_t ldx, const int64_t* x_rows, const float
   // one full round of workgroups with half the work each; above 8192 rows they would spill into a second round and lose (round 2:
   // 165 against 280 TFLOP/s per workgroup pair).  Default split (two fp16 planes) only.
   const bool small_m = planes == 2 && M <= 8192 && (h0 == nullptr);
-  if (phases & 1) {   // c-part: N = 3Hc, block 256 x 192
+  // Depth 0 at inference (no previous state of any form, no training save): c0 = 0 never meets the forget gate, so the c-part runs
+  // over the remember | map column groups only - N = 2Hc on 256 x 128 (128 x 128) tiles, a third fewer MFMAs, the same bits
+  // (EpiLstmC0).  Default split only.
+  const bool depth0 = planes == 2 && h0 == nullptr && c0 == nullptr && hp == nullptr && save_frm == nullptr;
+  if ((phases & 1) && depth0) {
+    EpiLstmC0 e{b_gates, state_out + D, ldso, sg};
+    int rc;
+    if constexpr (A16) {
+      rc = small_m ? launch_x6_np<2, 2, 2, 2, false, true, decltype(e), 1, true>(g, 2 * Hc, e, stream, "lstm_cell_x6_h16(c, depth 0, 128-row tiles)")
+                   : launch_x6_np<2, 4, 2, 1, false, true, decltype(e), 1, true>(g, 2 * Hc, e, stream, "lstm_cell_x6_h16(c, depth 0)");
+    } else if (x_rows) {
+      rc = small_m ? launch_x6_np<2, 2, 2, 2, false, true>(g, 2 * Hc, e, stream, "lstm_cell_x6(c, depth 0, 128-row tiles)")
+                   : launch_x6_np<2, 4, 2, 1, false, true>(g, 2 * Hc, e, stream, "lstm_cell_x6(c, depth 0)");
+    } else {
+      rc = small_m ? launch_x6_np<2, 2, 2, 2, false, false>(g, 2 * Hc, e, stream, "lstm_cell_x6(c, depth 0, 128-row tiles)")
+                   : launch_x6_np<2, 4, 2, 1, false, false>(g, 2 * Hc, e, stream, "lstm_cell_x6(c, depth 0)");
+    }
+    if (rc) return rc;
+  } else if (phases & 1) {   // c-part: N = 3Hc, block 256 x 192
     EpiLstmC e{b_gates, c0, ldc0, state_out + D, ldso, save_frm, (int64_t)3 * Hc, hp, (int64_t)3 * Hc + D, hp_row, sg};
     int rc;
     if constexpr (A16) {
