@@ -673,6 +673,45 @@ int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* g
                            float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                            const float* zero_row, paths_stream_t stream);
 
+/* Tissue-only (PACKED) slides (paths_amd/data_utils/slide.py: DeviceSlide.pack / from_patches; no reference equivalent - the reference
+ * stores background cells as all-zero rows, preprocess/loader.py).  A packed level is rows [n, D] (fp32 or fp16; device memory or
+ * pinned device-mapped host memory) behind index: int32 [X*Y] DEVICE table, the row number of a cell or -1 for a cell whose row was
+ * all +0.0 and is not stored.
+ *
+ * paths_gather_rows_packed[_h16] / paths_level0_batch_packed[_h16]: the arguments and results of their twins above with
+ * grid_ptrs[b] = the address of slide b's first packed row (never dereferenced for a level without rows) and index_ptrs [B] = the
+ * addresses of the slides' index tables.  src_cell stays the cell x * Y + y of the dense grid.  A cell with index -1 reads as the
+ * all-zero row it was: zero_row in row_ptrs (required with row_ptrs), zeros in the copy (written whatever zero_pad says: it is a
+ * valid row).  State copy, padding rows and zero_pad are those of the twins. */
+int paths_gather_rows_packed(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                             int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                             float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                             const int64_t* index_ptrs, paths_stream_t stream);
+int paths_gather_rows_packed_h16(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                                 int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                                 float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                                 const int64_t* index_ptrs, paths_stream_t stream);
+int paths_level0_batch_packed(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                              float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                              const float* zero_row, const int64_t* index_ptrs, paths_stream_t stream);
+int paths_level0_batch_packed_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                                  float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                                  const float* zero_row, const int64_t* index_ptrs, paths_stream_t stream);
+
+/* Packing a dense grid [cells, D] on the device (csrc/pack_rows.hip), three passes on the caller's stream:
+ *   paths_pack_flags[_h16]  flags[cell] (uint8) = 1 iff any BIT of the row is set (only all-+0.0 rows give 0; -0.0 is a set bit);
+ *   paths_pack_index        index[cell] (int32) = flags[cell] ? number of flagged cells in front of it (row-major) : -1, and *count
+ *                           (device int32) = the number of flagged cells.  partials: scratch of paths_pack_index_partials(cells)
+ *                           int32.  Integer block sums in a fixed order, no atomics: bit-identical on repeat;
+ *   paths_pack_rows[_h16]   rows[index[cell]] = grid[cell] for index[cell] in [0, n_rows); other cells are not read.
+ * D % 4 == 0; rows move 16 bytes per lane where the row size and both bases allow, else 8; 1 <= cells < 2^31. */
+int paths_pack_flags(const float* grid, int64_t cells, int D, uint8_t* flags, paths_stream_t stream);
+int paths_pack_flags_h16(const void* grid, int64_t cells, int D, uint8_t* flags, paths_stream_t stream);
+int64_t paths_pack_index_partials(int64_t cells);
+int paths_pack_index(const uint8_t* flags, int64_t cells, int* index, int* count, int* partials, paths_stream_t stream);
+int paths_pack_rows(const float* grid, int64_t cells, int D, const int* index, int64_t n_rows, float* rows, paths_stream_t stream);
+int paths_pack_rows_h16(const void* grid, int64_t cells, int D, const int* index, int64_t n_rows, void* rows, paths_stream_t stream);
+
 /* Row staging for host-resident slides (paths_amd/data_utils/slide.py:HostSlide; the reference gathers rows on the CPU from grids in
  * host RAM, data_utils/slide.py:320-331).  row_ptrs [rows] is an address table written by paths_level0_batch* / paths_gather_rows*
  * whose grid_ptrs were pinned, device-mapped HOST addresses: for every m with row_ptrs[m] != zero_row the row_bytes bytes at

@@ -148,7 +148,16 @@ SIGNATURES = {
 for _n in ("paths_lstm_cell_x6", "paths_importance_proj_x6", "paths_importance_qkv_x6", "paths_gemm_add_nt_x6", "paths_gather_rows",
            "paths_level0_batch", "paths_tissue_mask_absmax", "paths_synth_grid"):
     SIGNATURES[_n + "_h16"] = SIGNATURES[_n]
-_PLAIN = {"paths_gemm_tn_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_x6_packed_bytes": (C.c_int64, [_i32, _i32, _i32]), "paths_tlayer_h3_image_bytes": (C.c_int64, [_i32]), "paths_tlayer_ws_image_bytes": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes": (C.c_int64, []), "paths_token0_ws_partials": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes_d": (C.c_int64, [_i32]), "paths_token0_ws_partials_d": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_ws_supported": (_i32, [_i32, _i32, _i32, _i32]), "paths_attention_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]), "paths_attention_fp8_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_bwd_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_token0_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_attention_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_rollout_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_h3_any_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_importance_proj_x6_workspace": (C.c_int64, [_i32]), "paths_last_error": (C.c_char_p, []), "paths_build_info": (C.c_char_p, []), "paths_abi_version": (_i32, []), "paths_stop_event_pending": (_i32, []), "paths_clear_stop_event": (_i32, []), "paths_adamw_chunk": (_i32, []), "paths_rank_joint_tile": (_i32, []), "paths_attention_wide_workspace": (C.c_int64, [_i32, _i32]), "paths_event_create": (_vp, []), "paths_stream_create_masked": (_vp, [_vp, _i32])}
+# tissue-only (packed) slides: the twins' arguments + index_ptrs in front of the stream; the pack passes (csrc/pack_rows.hip)
+for _n in ("paths_gather_rows", "paths_level0_batch"):
+    for _s in ("", "_h16"):
+        SIGNATURES[_n + "_packed" + _s] = SIGNATURES[_n][:-1] + [_vp, _vp]
+for _s in ("", "_h16"):
+    SIGNATURES["paths_pack_flags" + _s] = [_vp, _i64, _i32, _vp, _vp]
+    SIGNATURES["paths_pack_rows" + _s] = [_vp, _i64, _i32, _vp, _i64, _vp, _vp]
+SIGNATURES["paths_pack_index"] = [_vp, _i64, _vp, _vp, _vp, _vp]
+_PLAIN = {"paths_gemm_tn_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_x6_packed_bytes": (C.c_int64, [_i32, _i32, _i32]), "paths_tlayer_h3_image_bytes": (C.c_int64, [_i32]), "paths_tlayer_ws_image_bytes": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes": (C.c_int64, []), "paths_token0_ws_partials": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes_d": (C.c_int64, [_i32]), "paths_token0_ws_partials_d": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_ws_supported": (_i32, [_i32, _i32, _i32, _i32]), "paths_attention_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]), "paths_attention_fp8_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_bwd_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_token0_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_attention_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_rollout_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_h3_any_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_importance_proj_x6_workspace": (C.c_int64, [_i32]), "paths_last_error": (C.c_char_p, []), "paths_build_info": (C.c_char_p, []), "paths_abi_version": (_i32, []), "paths_stop_event_pending": (_i32, []), "paths_clear_stop_event": (_i32, []), "paths_adamw_chunk": (_i32, []), "paths_rank_joint_tile": (_i32, []), "paths_attention_wide_workspace": (C.c_int64, [_i32, _i32]), "paths_event_create": (_vp, []), "paths_stream_create_masked": (_vp, [_vp, _i32]),
+          "paths_pack_index_partials": (C.c_int64, [_i64])}
 
 ABI_VERSION = 3     # include/paths_hip.h: paths_abi_version() of the library this binding was written against
 _lib: Optional[C.CDLL] = None

@@ -333,14 +333,24 @@ class AggregatorFn(torch.autograd.Function):
         return (None, d_tok, None, *_aggregator_grads(mc, tg))
 
 
+def _gather_name(grid_h16: bool, index_ptrs) -> str:
+    """The gather entry point of the batch's storage: ``index_ptrs`` (packed slides' cell-index table) selects the _packed form."""
+    return "paths_gather_rows" + ("_packed" if index_ptrs is not None else "") + ("_h16" if grid_h16 else "")
+
+
+def _index_arg(index_ptrs) -> tuple:
+    return (_lib.ptr(index_ptrs),) if index_ptrs is not None else ()
+
+
 class GatherParentFn(torch.autograd.Function):
     """Children of the kept patches in the once-per-parent form: gathered feature rows (not differentiable), the children's inherited
     memory cell c0 [B,n_next,Hc] and the kept parents' h rows h_kept [B*cap, D].  Backward: the parents' state gradient =
     (scatter of d_h_kept | sum over the surviving children of d_c0), fixed order.  ``grid_h16``: the grids are fp16 (the gathered
-    feature rows are fp32 either way)."""
+    feature rows are fp32 either way); ``index_ptrs``: the slides are packed (paths_gather_rows_packed)."""
 
     @staticmethod
-    def forward(ctx, state_cur, grid_ptrs, src_cell, src_row, num_next, keep_idx, keep_count, child_pos, D, n_next, grid_h16=False):
+    def forward(ctx, state_cur, grid_ptrs, src_cell, src_row, num_next, keep_idx, keep_count, child_pos, D, n_next, grid_h16=False,
+                index_ptrs=None):
         B, n_cur, Dp = state_cur.shape
         Hc = Dp - D
         cap = keep_idx.shape[1]
@@ -349,8 +359,8 @@ class GatherParentFn(torch.autograd.Function):
         c0 = torch.empty((B, n_next, Hc), **f32)
         h_kept = torch.empty((B * cap, D), **f32)
         p = _lib.ptr
-        _lib.call("paths_gather_rows_h16" if grid_h16 else "paths_gather_rows", p(grid_ptrs), p(src_cell), D, state_cur.data_ptr() + 4 * D,
-                  n_cur, Dp, p(src_row), Hc, p(num_next), B, n_next, p(fts_next), p(c0), 1, None, None, _lib.stream())
+        _lib.call(_gather_name(grid_h16, index_ptrs), p(grid_ptrs), p(src_cell), D, state_cur.data_ptr() + 4 * D,
+                  n_cur, Dp, p(src_row), Hc, p(num_next), B, n_next, p(fts_next), p(c0), 1, None, None, *_index_arg(index_ptrs), _lib.stream())
         _lib.call("paths_gather_kept_rows", p(state_cur), n_cur, Dp, p(keep_idx), cap, p(keep_count), D, B, p(h_kept), _lib.stream())
         ctx.meta = (keep_idx, keep_count, child_pos, n_cur, n_next, Dp, D, B)
         ctx.mark_non_differentiable(fts_next)
@@ -368,7 +378,7 @@ class GatherParentFn(torch.autograd.Function):
                       d_cur.data_ptr() + 4 * D, n_cur, Dp, B, _lib.stream())
         if d_hk is not None:
             _lib.call("paths_scatter_kept_rows", p(d_hk.contiguous()), cap, D, p(keep_idx), p(keep_count), p(d_cur), n_cur, Dp, D, B, _lib.stream())
-        return (d_cur,) + (None,) * 10
+        return (d_cur,) + (None,) * 11
 
 
 def level_params_nolstm(proc) -> List[torch.nn.Parameter]:
@@ -392,14 +402,15 @@ class GatherFn(torch.autograd.Function):
     """fts_next, state_next = gather(next-level grid rows, parent state rows)  (paths_gather_rows, zero padded; ``grid_h16``: fp16 grids)."""
 
     @staticmethod
-    def forward(ctx, state_cur, grid_ptrs, src_cell, src_row, num_next, keep_idx, keep_count, child_pos, D, n_next, grid_h16=False):
+    def forward(ctx, state_cur, grid_ptrs, src_cell, src_row, num_next, keep_idx, keep_count, child_pos, D, n_next, grid_h16=False,
+                index_ptrs=None):
         B, n_cur, Dp = state_cur.shape
         f32 = dict(device=state_cur.device, dtype=torch.float32)
         fts_next = torch.empty((B, n_next, D), **f32)
         state_next = torch.empty((B, n_next, Dp), **f32)
         p = _lib.ptr
-        _lib.call("paths_gather_rows_h16" if grid_h16 else "paths_gather_rows", p(grid_ptrs), p(src_cell), D, p(state_cur), n_cur, Dp,
-                  p(src_row), Dp, p(num_next), B, n_next, p(fts_next), p(state_next), 1, None, None, _lib.stream())
+        _lib.call(_gather_name(grid_h16, index_ptrs), p(grid_ptrs), p(src_cell), D, p(state_cur), n_cur, Dp,
+                  p(src_row), Dp, p(num_next), B, n_next, p(fts_next), p(state_next), 1, None, None, *_index_arg(index_ptrs), _lib.stream())
         ctx.meta = (keep_idx, keep_count, child_pos, n_cur, n_next, Dp, B)
         ctx.mark_non_differentiable(fts_next)
         return fts_next, state_next
@@ -411,4 +422,4 @@ class GatherFn(torch.autograd.Function):
         p = _lib.ptr
         _lib.call("paths_gather_rows_bwd", p(keep_idx), keep_idx.shape[1], p(keep_count), p(child_pos),
                   p(d_state_next.contiguous()), n_next, Dp, p(d_cur), n_cur, B, _lib.stream())
-        return (d_cur,) + (None,) * 10
+        return (d_cur,) + (None,) * 11

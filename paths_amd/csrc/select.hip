@@ -9,6 +9,7 @@
 // coalesced 16-byte-per-lane copies; the per-slide bookkeeping (sort, scan) lives in LDS.
 #include "common.h"
 #include "rank_key.h"
+#include "select_packed.h"
 
 namespace {
 
@@ -386,14 +387,18 @@ fallback_all_cells_kernel(const int* __restrict__ next_x, const int* __restrict_
 // One WAVE per output row (four rows per workgroup): features from the next-level grid, LSTM state (h|c) from the kept parent.
 // (One 256-thread workgroup per row was 16,384 workgroups for 16 MB in the default path - only the 1-KiB memory-cell part of the
 // state is copied there, 64 of the 256 threads had anything to do: 14.6 us.)
+//
+// PACKED (tissue-only slides, pack_rows.hip): grid_ptrs[b] is the slide's first PACKED row and index_ptrs[b] its int32 [X*Y] cell
+// index - the row number of a cell, or -1 for a cell whose row was all +0.0 and is not stored.  Such a cell reads as what it was:
+// zero_row in the address table, zeros in the copy.  src_cell stays the cell of the dense grid.
 constexpr int GATHER_ROWS = 4;
-template <class T>
+template <class T, bool PACKED = false>
 __global__ void __launch_bounds__(256)
 gather_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ src_cell, int D,
               const float* __restrict__ state_cur /*already offset to the first copied column*/, int64_t n_cur, int64_t ld_state_cur,
               const int* __restrict__ src_row, int Dp /*columns copied*/, const int64_t* __restrict__ num_out, int64_t n_next,
               float* __restrict__ fts_out, float* __restrict__ state_out, int zero_pad,
-              int64_t* __restrict__ row_ptrs, const float* __restrict__ zero_row) {
+              int64_t* __restrict__ row_ptrs, const float* __restrict__ zero_row, const int64_t* __restrict__ index_ptrs = nullptr) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const int64_t j = (int64_t)blockIdx.x * GATHER_ROWS + (threadIdx.x >> 6);
@@ -402,9 +407,17 @@ gather_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ src
   f32x4* fo = fts_out ? reinterpret_cast<f32x4*>(fts_out + o * D) : nullptr;
   f32x4* so = state_out ? reinterpret_cast<f32x4*>(state_out + o * Dp) : nullptr;
   if (j < num_out[b]) {
-    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + (int64_t)src_cell[o] * D;
-    if (row_ptrs && lane == 0) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(fi);     // consumers read the row where it lives
-    if (fo) for (int i = lane; i < D / 4; i += 64) fo[i] = load4(fi, i);                    // (gathered copies are fp32)
+    int64_t row = src_cell[o];
+    if constexpr (PACKED) row = reinterpret_cast<const int*>(index_ptrs[b])[row];           // (-1: a dropped all-zero row)
+    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + row * D;
+    if (!PACKED || row >= 0) {
+      if (row_ptrs && lane == 0) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(fi);   // consumers read the row where it lives
+      if (fo) for (int i = lane; i < D / 4; i += 64) fo[i] = load4(fi, i);                  // (gathered copies are fp32)
+    } else {
+      const f32x4 z{0.f, 0.f, 0.f, 0.f};
+      if (row_ptrs && lane == 0) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(zero_row);
+      if (fo) for (int i = lane; i < D / 4; i += 64) fo[i] = z;
+    }
     if (so) {
       const int sr = src_row[o];
       if (sr >= 0) {
@@ -502,13 +515,13 @@ scatter_kept_rows_kernel(const float* __restrict__ src, int64_t ldk, int64_t ld_
   for (int c = tid; c < width / 4; c += 256) out[c] = in[c];
 }
 
-// Level 0: every grid cell, row-major, no background filter (slide.py:257-269).
-template <class T>
+// Level 0: every grid cell, row-major, no background filter (slide.py:257-269).  PACKED: as in gather_kernel.
+template <class T, bool PACKED = false>
 __global__ void __launch_bounds__(256)
 level0_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ gx, const int* __restrict__ gy, int D,
               int patch_size, int64_t n0, float* __restrict__ fts, int64_t* __restrict__ locs,
               int64_t* __restrict__ parent, int64_t* __restrict__ num_ims, int zero_pad,
-              int64_t* __restrict__ row_ptrs, const float* __restrict__ zero_row) {
+              int64_t* __restrict__ row_ptrs, const float* __restrict__ zero_row, const int64_t* __restrict__ index_ptrs = nullptr) {
   const int b = blockIdx.y;
   const int64_t j = blockIdx.x;
   const int X = gx[b], Y = gy[b];
@@ -518,11 +531,17 @@ level0_kernel(const int64_t* __restrict__ grid_ptrs, const int* __restrict__ gx,
   f32x4* fo = fts ? reinterpret_cast<f32x4*>(fts + o * D) : nullptr;
   if (j == 0 && tid == 0) num_ims[b] = n;
   if (j < n) {
-    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + j * D;
-    if (fo) for (int i = tid; i < D / 4; i += 256) fo[i] = load4(fi, i);
+    int64_t row = j;
+    if constexpr (PACKED) row = reinterpret_cast<const int*>(index_ptrs[b])[j];
+    const bool stored = !PACKED || row >= 0;
+    const T* fi = reinterpret_cast<const T*>(grid_ptrs[b]) + row * D;
+    if (fo) {
+      if (stored) { for (int i = tid; i < D / 4; i += 256) fo[i] = load4(fi, i); }
+      else { const f32x4 z{0.f, 0.f, 0.f, 0.f}; for (int i = tid; i < D / 4; i += 256) fo[i] = z; }
+    }
     if (tid == 0) {
       locs[2 * o] = (j / Y) * patch_size; locs[2 * o + 1] = (j % Y) * patch_size; parent[o] = j;
-      if (row_ptrs) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(fi);
+      if (row_ptrs) row_ptrs[o] = (int64_t)reinterpret_cast<uintptr_t>(stored ? reinterpret_cast<const void*>(fi) : reinterpret_cast<const void*>(zero_row));
     }
   } else {
     if (fo && zero_pad) { const f32x4 z{0.f, 0.f, 0.f, 0.f}; for (int i = tid; i < D / 4; i += 256) fo[i] = z; }
@@ -610,7 +629,57 @@ synth_grid_kernel(T* __restrict__ grid, int X, int Y, int D, uint32_t k2, int le
   }
 }
 
+// paths_gather_rows[_h16] over PACKED slides: grid_ptrs[b] = the slide's first packed row, index_ptrs[b] -> int32 [X*Y] (row of a cell
+// or -1).  A cell without a stored row gives zero_row in row_ptrs and zeros in fts_out.
+template <class T>
+static int gather_rows_packed(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* src_cell, int D, const float* state_cur,
+                              int64_t n_cur, int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                              float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n_next > 0 && D % 4 == 0 && Dp % 4 == 0 && ld_state_cur % 4 == 0, "%s: bad shape", what);
+  PATHS_REQUIRE(grid_ptrs != nullptr && index_ptrs != nullptr && src_cell != nullptr && num_out != nullptr, "%s: null pointer", what);
+  PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "%s: features must go somewhere (a copy or row pointers)", what);
+  PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "%s: row_ptrs needs a zero row for padding and dropped rows", what);
+  PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "%s: state in/out must both be given or null", what);
+  hipLaunchKernelGGL((gather_kernel<T, true>), dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D,
+                     state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, index_ptrs);
+  PATHS_LAUNCH_CHECK(what);
+  return PATHS_OK;
+}
+
+template <class T>
+static int level0_packed(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int D, int patch_size,
+                         int64_t n0, float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                         const float* zero_row, hipStream_t stream) {
+  PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "%s: bad shape", what);
+  PATHS_REQUIRE(grid_ptrs != nullptr && index_ptrs != nullptr && gx != nullptr && gy != nullptr, "%s: null pointer", what);
+  PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "%s: features need a destination (copy or row pointers + zero row)", what);
+  hipLaunchKernelGGL((level0_kernel<T, true>), dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
+                     fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row, index_ptrs);
+  PATHS_LAUNCH_CHECK(what);
+  return PATHS_OK;
+}
+
 }  // namespace
+
+// The launchers behind paths_gather_rows_packed[_h16] / paths_level0_batch_packed[_h16] (C entry points: pack_rows.hip, with the rest of
+// the packed-slide surface; declared in select_packed.h).
+int paths_select_gather_rows_packed(bool h16, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* src_cell, int D, const float* state_cur,
+                                    int64_t n_cur, int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                                    float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
+  return h16 ? gather_rows_packed<_Float16>("gather_rows_packed_h16", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp,
+                                            num_out, B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream)
+             : gather_rows_packed<float>("gather_rows_packed", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out,
+                                         B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
+}
+
+int paths_select_level0_packed(bool h16, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int D,
+                               int patch_size, int64_t n0, float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad,
+                               int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
+  return h16 ? level0_packed<_Float16>("level0_batch_packed_h16", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims,
+                                       zero_pad, row_ptrs, zero_row, stream)
+             : level0_packed<float>("level0_batch_packed", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad,
+                                    row_ptrs, zero_row, stream);
+}
 
 extern "C" {
 

@@ -246,6 +246,10 @@ class TapedRecursion:
         if new.host_resident != self.batch.host_resident:      # (a host batch's tape stages its rows, a resident batch's does not)
             kind = lambda h: "host-resident" if h else "resident"
             raise ValueError(f"rebind: the tape serves {kind(self.batch.host_resident)} slides, the new batch is {kind(new.host_resident)}")
+        if getattr(new, "packed", False) != getattr(self.batch, "packed", False):     # (other entry points, one more table per level)
+            form = lambda k: "packed" if k else "dense"
+            raise ValueError(f"rebind: the tape serves {form(getattr(self.batch, 'packed', False))} slides, the new batch is "
+                             f"{form(getattr(new, 'packed', False))}")
         fits = (self.tape is not None and rec is not None and len(new) == len(rec) and new.dim == rec.dim and new.device == rec.device
                 and new.num_levels >= self.levels and new.n0 <= rec.n0
                 and all(new.max_dim[l] <= rec.max_dim[l] for l in range(self.levels))
@@ -269,6 +273,8 @@ class TapedRecursion:
                     rec.mask_ptrs[l].copy_(new.mask_ptrs[l], non_blocking=True)
                     rec.gx[l].copy_(new.gx[l], non_blocking=True)
                     rec.gy[l].copy_(new.gy[l], non_blocking=True)
+                    if new.packed:
+                        rec.index_ptrs[l].copy_(new.index_ptrs[l], non_blocking=True)
         self.batch = new                 # (keeps the bound slides alive; run()'s fallback recurses on them)
         return self
 
@@ -533,6 +539,11 @@ def _stage_rows(batch, rows, n: int, zero_row, stream: int):
     return buf
 
 
+def _packed_args(batch, level: int) -> tuple:
+    """What a ``_packed`` entry point takes in front of its stream: the level's cell-index table of a packed batch (dense: nothing)."""
+    return (_lib.ptr(batch.index_ptrs[level]),) if getattr(batch, "packed", False) else ()
+
+
 def _rows_in_place(r) -> bool:
     """Whether the current GEMM mode reads feature rows where they live (row-pointer operands) instead of gathered fp32 copies."""
     mc, D, Dp = r.mc, r.D, r.Dp
@@ -550,7 +561,7 @@ def _level0(r) -> SimpleNamespace:
     lv.parent_inds = torch.empty((B, N), **r.i64)
     lv.num_ims = torch.empty((B,), **r.i64)
     _lib.call("paths_level0_batch" + r.sfx, p(r.batch.grid_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, r.mc.patch_size, N,
-              p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), r.st)
+              p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), *_packed_args(r.batch, 0), r.st)
     if getattr(r.batch, "masked", False):        # views (DeviceSlide.with_masks): a cleared level-0 cell reads as a background cell's zero row
         _lib.call("paths_level0_mask_rows", p(r.batch.mask_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, N, p(lv.fts), p(lv.x_rows),
                   p(r.zero_row), r.st)
@@ -609,7 +620,7 @@ def _child_step(r, i: int, lv, out, keep: int):
         nx.N, nx.num_ims, nx.locs, nx.parent_inds = Nn, num_next, locs_next, parent_next
         if batch.on_demand:          # the rows just supplied may have moved the pass to the three-plane kernels (_note_range)
             rows_in_place = r.rows_in_place = _rows_in_place(r)
-        grid = p(batch.grid_ptrs[i + 1])
+        grid, pk = p(batch.grid_ptrs[i + 1]), _packed_args(batch, i + 1)
         if share_parent:
             # children only need their parent's c row (h enters through the per-parent partials)
             Hc = Dp - D
@@ -619,19 +630,19 @@ def _child_step(r, i: int, lv, out, keep: int):
                 nx.x_rows = torch.empty((B, Nn), **r.i64)
                 ops.timed("gather", lambda: _lib.call(
                     "paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
-                    p(src_row), Hc, p(num_next), B, Nn, None, p(c0), 0, p(nx.x_rows), p(r.zero_row), st2))
+                    p(src_row), Hc, p(num_next), B, Nn, None, p(c0), 0, p(nx.x_rows), p(r.zero_row), *pk, st2))
                 if r.stage_host:
                     nx.staged = _stage_rows(batch, nx.x_rows, Nn, r.zero_row, st2)
             else:
                 nx.fts = torch.empty((B, Nn, D), **r.f32)
                 _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
-                          p(src_row), Hc, p(num_next), B, Nn, p(nx.fts), p(c0), 0, None, None, st2)
+                          p(src_row), Hc, p(num_next), B, Nn, p(nx.fts), p(c0), 0, None, None, *pk, st2)
             nx.parent = {"hp": hp, "hp_row": hp_row, "c0": c0}
         else:
             nx.fts = torch.empty((B, Nn, D), **r.f32)
             nx.state_prev = torch.empty((B, Nn, Dp), **r.f32)
             _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
-                      p(num_next), B, Nn, p(nx.fts), p(nx.state_prev), 0, None, None, st2)
+                      p(num_next), B, Nn, p(nx.fts), p(nx.state_prev), 0, None, None, *pk, st2)
         if forked:            # allocated on the expansion stream, read by the next level on the selection stream
             r.keepalive.append((nx, src_row, src_cell))
     return nx, keep_idx, keep_count
@@ -668,7 +679,9 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
     # Host-resident slides: the grid addresses are pinned host memory.  Where rows are copied (fts) the copying kernel reads them over
     # the host link once and nothing else does; where they are read in place, the address table is staged: the selected rows are
     # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
-    r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(), sfx="_h16" if h16 else "", f32=f32,
+    # packed slides: the two address-forming kernels take their _packed forms (+ the cell-index table); nothing else changes
+    r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(),
+                        sfx=("_packed" if getattr(batch, "packed", False) else "") + ("_h16" if h16 else ""), f32=f32,
                         i32=dict(device=dev, dtype=torch.int32), i64=dict(device=dev, dtype=torch.int64),
                         lstm_pack=lstm_pack, share_parent=share_parent,
                         careful=careful, attention=attention, rollout=rollout, overlap=overlap, main_stream=main_stream,
@@ -782,8 +795,8 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
     parent = torch.empty((B, N), **i64)
     num_ims = torch.empty((B,), **i64)
     h16 = batch.dtype == torch.float16                     # fp16 grids: the gathers write fp32 copies, the training kernels are unchanged
-    _lib.call("paths_level0_batch_h16" if h16 else "paths_level0_batch", p(batch.grid_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, mc.patch_size, N,
-              p(fts), p(locs), p(parent), p(num_ims), 1, None, None, st)
+    _lib.call("paths_level0_batch" + ("_packed" if batch.packed else "") + ("_h16" if h16 else ""), p(batch.grid_ptrs[0]), p(batch.gx[0]),
+              p(batch.gy[0]), B, D, mc.patch_size, N, p(fts), p(locs), p(parent), p(num_ims), 1, None, None, *_packed_args(batch, 0), st)
     if batch.masked:
         _lib.call("paths_level0_mask_rows", p(batch.mask_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, N, p(fts), None, None, st)
     state_prev, ctx_prev, ctx_hist = None, None, []
@@ -833,12 +846,12 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
             rec["keep_idx"], rec["keep_count"] = keep_idx, keep_count
         if parent_form:
             fts, c0, h_kept = pag.GatherParentFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx, keep_count,
-                                                       child_pos, D, Nn, h16)
+                                                       child_pos, D, Nn, h16, batch.index_ptrs[i + 1] if batch.packed else None)
             par = {"c0": c0, "h_kept": h_kept, "hp_row": hp_row, "child_pos": child_pos, "keep_count": keep_count, "cap": cap_keep}
             state_prev = None
         else:
             fts, state_prev = pag.GatherFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx,
-                                                 keep_count, child_pos, D, Nn, h16)
+                                                 keep_count, child_pos, D, Nn, h16, batch.index_ptrs[i + 1] if batch.packed else None)
         locs, parent, num_ims, N = locs_next, parent_next, num_next, Nn
     return {"logits": logits, "status": status}
 
