@@ -20,6 +20,7 @@ from typing import List, Optional
 import torch
 
 from . import _lib, backward as bw, ops
+from .data_utils.slide import entry_name, index_args
 
 LSTM_ORDER = ["forget_gate.0.weight", "forget_gate.0.bias", "remember_gate.0.weight", "remember_gate.0.bias",
               "remember_map.0.weight", "remember_map.0.bias", "out_select_gate.0.weight", "out_select_gate.0.bias",
@@ -333,15 +334,6 @@ class AggregatorFn(torch.autograd.Function):
         return (None, d_tok, None, *_aggregator_grads(mc, tg))
 
 
-def _gather_name(grid_h16: bool, index_ptrs) -> str:
-    """The gather entry point of the batch's storage: ``index_ptrs`` (packed slides' cell-index table) selects the _packed form."""
-    return "paths_gather_rows" + ("_packed" if index_ptrs is not None else "") + ("_h16" if grid_h16 else "")
-
-
-def _index_arg(index_ptrs) -> tuple:
-    return (_lib.ptr(index_ptrs),) if index_ptrs is not None else ()
-
-
 class GatherParentFn(torch.autograd.Function):
     """Children of the kept patches in the once-per-parent form: gathered feature rows (not differentiable), the children's inherited
     memory cell c0 [B,n_next,Hc] and the kept parents' h rows h_kept [B*cap, D].  Backward: the parents' state gradient =
@@ -359,8 +351,8 @@ class GatherParentFn(torch.autograd.Function):
         c0 = torch.empty((B, n_next, Hc), **f32)
         h_kept = torch.empty((B * cap, D), **f32)
         p = _lib.ptr
-        _lib.call(_gather_name(grid_h16, index_ptrs), p(grid_ptrs), p(src_cell), D, state_cur.data_ptr() + 4 * D,
-                  n_cur, Dp, p(src_row), Hc, p(num_next), B, n_next, p(fts_next), p(c0), 1, None, None, *_index_arg(index_ptrs), _lib.stream())
+        _lib.call(entry_name("paths_gather_rows", grid_h16, index_ptrs is not None), p(grid_ptrs), p(src_cell), D, state_cur.data_ptr() + 4 * D,
+                  n_cur, Dp, p(src_row), Hc, p(num_next), B, n_next, p(fts_next), p(c0), 1, None, None, *index_args(index_ptrs), _lib.stream())
         _lib.call("paths_gather_kept_rows", p(state_cur), n_cur, Dp, p(keep_idx), cap, p(keep_count), D, B, p(h_kept), _lib.stream())
         ctx.meta = (keep_idx, keep_count, child_pos, n_cur, n_next, Dp, D, B)
         ctx.mark_non_differentiable(fts_next)
@@ -409,8 +401,8 @@ class GatherFn(torch.autograd.Function):
         fts_next = torch.empty((B, n_next, D), **f32)
         state_next = torch.empty((B, n_next, Dp), **f32)
         p = _lib.ptr
-        _lib.call(_gather_name(grid_h16, index_ptrs), p(grid_ptrs), p(src_cell), D, p(state_cur), n_cur, Dp,
-                  p(src_row), Dp, p(num_next), B, n_next, p(fts_next), p(state_next), 1, None, None, *_index_arg(index_ptrs), _lib.stream())
+        _lib.call(entry_name("paths_gather_rows", grid_h16, index_ptrs is not None), p(grid_ptrs), p(src_cell), D, p(state_cur), n_cur, Dp,
+                  p(src_row), Dp, p(num_next), B, n_next, p(fts_next), p(state_next), 1, None, None, *index_args(index_ptrs), _lib.stream())
         ctx.meta = (keep_idx, keep_count, child_pos, n_cur, n_next, Dp, B)
         ctx.mark_non_differentiable(fts_next)
         return fts_next, state_next

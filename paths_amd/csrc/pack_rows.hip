@@ -9,7 +9,6 @@
 //   paths_pack_index  block partials (1024 cells per block) + every block summing the partials before it: fixed order, no atomics
 //   paths_pack_rows   one wave per cell, kept rows copied 16 (or 8) bytes per lane to rows[index[cell]]
 #include "common.h"
-#include "select_packed.h"
 
 namespace {
 
@@ -174,37 +173,6 @@ int paths_pack_rows(const float* grid, int64_t cells, int D, const int* index, i
 int paths_pack_rows_h16(const void* grid, int64_t cells, int D, const int* index, int64_t n_rows, void* rows, hipStream_t stream) {
   PATHS_REQUIRE(D > 0 && D % 4 == 0, "pack_rows_h16: D (%d) must be a positive multiple of 4", D);
   return pack_rows("pack_rows_h16", grid, cells, D * 2, index, n_rows, rows, stream);
-}
-
-// The packed forms of paths_gather_rows[_h16] / paths_level0_batch[_h16] (kernels and launchers: select.hip).
-int paths_gather_rows_packed(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
-                             int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
-                             float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
-                             const int64_t* index_ptrs, hipStream_t stream) {
-  return paths_select_gather_rows_packed(false, grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, B, n_next,
-                                         fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
-}
-
-int paths_gather_rows_packed_h16(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
-                                 int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
-                                 float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
-                                 const int64_t* index_ptrs, hipStream_t stream) {
-  return paths_select_gather_rows_packed(true, grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, B, n_next,
-                                         fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
-}
-
-int paths_level0_batch_packed(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
-                              float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
-                              const float* zero_row, const int64_t* index_ptrs, hipStream_t stream) {
-  return paths_select_level0_packed(false, grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad, row_ptrs,
-                                    zero_row, stream);
-}
-
-int paths_level0_batch_packed_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
-                                  float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
-                                  const float* zero_row, const int64_t* index_ptrs, hipStream_t stream) {
-  return paths_select_level0_packed(true, grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad, row_ptrs,
-                                    zero_row, stream);
 }
 
 }  // extern "C"

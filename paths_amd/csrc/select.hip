@@ -9,7 +9,6 @@
 // coalesced 16-byte-per-lane copies; the per-slide bookkeeping (sort, scan) lives in LDS.
 #include "common.h"
 #include "rank_key.h"
-#include "select_packed.h"
 
 namespace {
 
@@ -629,57 +628,38 @@ synth_grid_kernel(T* __restrict__ grid, int X, int Y, int D, uint32_t k2, int le
   }
 }
 
-// paths_gather_rows[_h16] over PACKED slides: grid_ptrs[b] = the slide's first packed row, index_ptrs[b] -> int32 [X*Y] (row of a cell
-// or -1).  A cell without a stored row gives zero_row in row_ptrs and zeros in fts_out.
-template <class T>
-static int gather_rows_packed(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* src_cell, int D, const float* state_cur,
-                              int64_t n_cur, int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
-                              float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
+// THE host launchers of the two address-forming kernels, behind paths_gather_rows[_packed][_h16] / paths_level0_batch[_packed][_h16]
+// (`what`: the entry point's name in messages).  PACKED: grid_ptrs[b] = the slide's first packed row, index_ptrs[b] -> int32 [X*Y] (row
+// of a cell or -1); a cell without a stored row gives zero_row in row_ptrs and zeros in the copy.  Dense: index_ptrs is null.
+template <class T, bool PACKED>
+int launch_gather(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* src_cell, int D, const float* state_cur,
+                  int64_t n_cur, int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                  float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
   PATHS_REQUIRE(B > 0 && n_next > 0 && D % 4 == 0 && Dp % 4 == 0 && ld_state_cur % 4 == 0, "%s: bad shape", what);
-  PATHS_REQUIRE(grid_ptrs != nullptr && index_ptrs != nullptr && src_cell != nullptr && num_out != nullptr, "%s: null pointer", what);
+  PATHS_REQUIRE(grid_ptrs != nullptr && (!PACKED || index_ptrs != nullptr) && src_cell != nullptr && num_out != nullptr, "%s: null pointer", what);
   PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "%s: features must go somewhere (a copy or row pointers)", what);
   PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "%s: row_ptrs needs a zero row for padding and dropped rows", what);
   PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "%s: state in/out must both be given or null", what);
-  hipLaunchKernelGGL((gather_kernel<T, true>), dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D,
+  hipLaunchKernelGGL((gather_kernel<T, PACKED>), dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D,
                      state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, index_ptrs);
   PATHS_LAUNCH_CHECK(what);
   return PATHS_OK;
 }
 
-template <class T>
-static int level0_packed(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int D, int patch_size,
-                         int64_t n0, float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
-                         const float* zero_row, hipStream_t stream) {
+template <class T, bool PACKED>
+int launch_level0(const char* what, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int D, int patch_size,
+                  int64_t n0, float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                  const float* zero_row, hipStream_t stream) {
   PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "%s: bad shape", what);
-  PATHS_REQUIRE(grid_ptrs != nullptr && index_ptrs != nullptr && gx != nullptr && gy != nullptr, "%s: null pointer", what);
+  PATHS_REQUIRE(grid_ptrs != nullptr && (!PACKED || index_ptrs != nullptr) && gx != nullptr && gy != nullptr, "%s: null pointer", what);
   PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "%s: features need a destination (copy or row pointers + zero row)", what);
-  hipLaunchKernelGGL((level0_kernel<T, true>), dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
+  hipLaunchKernelGGL((level0_kernel<T, PACKED>), dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
                      fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row, index_ptrs);
   PATHS_LAUNCH_CHECK(what);
   return PATHS_OK;
 }
 
 }  // namespace
-
-// The launchers behind paths_gather_rows_packed[_h16] / paths_level0_batch_packed[_h16] (C entry points: pack_rows.hip, with the rest of
-// the packed-slide surface; declared in select_packed.h).
-int paths_select_gather_rows_packed(bool h16, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* src_cell, int D, const float* state_cur,
-                                    int64_t n_cur, int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
-                                    float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
-  return h16 ? gather_rows_packed<_Float16>("gather_rows_packed_h16", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp,
-                                            num_out, B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream)
-             : gather_rows_packed<float>("gather_rows_packed", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out,
-                                         B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
-}
-
-int paths_select_level0_packed(bool h16, const int64_t* grid_ptrs, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int D,
-                               int patch_size, int64_t n0, float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad,
-                               int64_t* row_ptrs, const float* zero_row, hipStream_t stream) {
-  return h16 ? level0_packed<_Float16>("level0_batch_packed_h16", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims,
-                                       zero_pad, row_ptrs, zero_row, stream)
-             : level0_packed<float>("level0_batch_packed", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad,
-                                    row_ptrs, zero_row, stream);
-}
 
 extern "C" {
 
@@ -765,14 +745,8 @@ int paths_gather_rows(const int64_t* grid_ptrs, const int* src_cell, int D, cons
                       int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
                       float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
                       hipStream_t stream) {
-  PATHS_REQUIRE(B > 0 && n_next > 0 && D % 4 == 0 && Dp % 4 == 0 && ld_state_cur % 4 == 0, "gather_rows: bad shape");
-  PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "gather_rows: features must go somewhere (a copy or row pointers)");
-  PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "gather_rows: row_ptrs needs a zero row for padding");
-  PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "gather_rows: state in/out must both be given or null");
-  hipLaunchKernelGGL(gather_kernel<float>, dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D, state_cur,
-                     n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row);
-  PATHS_LAUNCH_CHECK("gather_rows");
-  return PATHS_OK;
+  return launch_gather<float, false>("gather_rows", grid_ptrs, nullptr, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, B, n_next,
+                                     fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
 }
 
 // paths_gather_rows over FP16 grids: row_ptrs address fp16 rows, fts_out (if given) receives fp32 copies.  zero_row: D floats of zero
@@ -781,14 +755,25 @@ int paths_gather_rows_h16(const int64_t* grid_ptrs, const int* src_cell, int D, 
                           int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
                           float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
                           hipStream_t stream) {
-  PATHS_REQUIRE(B > 0 && n_next > 0 && D % 4 == 0 && Dp % 4 == 0 && ld_state_cur % 4 == 0, "gather_rows_h16: bad shape");
-  PATHS_REQUIRE(fts_out != nullptr || row_ptrs != nullptr, "gather_rows_h16: features must go somewhere (a copy or row pointers)");
-  PATHS_REQUIRE(row_ptrs == nullptr || zero_row != nullptr, "gather_rows_h16: row_ptrs needs a zero row for padding");
-  PATHS_REQUIRE((state_cur == nullptr) == (state_out == nullptr), "gather_rows_h16: state in/out must both be given or null");
-  hipLaunchKernelGGL(gather_kernel<_Float16>, dim3((unsigned)((n_next + GATHER_ROWS - 1) / GATHER_ROWS), B), dim3(256), 0, stream, grid_ptrs, src_cell, D,
-                     state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row);
-  PATHS_LAUNCH_CHECK("gather_rows_h16");
-  return PATHS_OK;
+  return launch_gather<_Float16, false>("gather_rows_h16", grid_ptrs, nullptr, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out, B,
+                                        n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
+}
+
+// paths_gather_rows[_h16] over PACKED slides (tissue-only storage, pack_rows.hip): index_ptrs, the cell-index table, in front of the stream
+int paths_gather_rows_packed(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                             int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                             float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                             const int64_t* index_ptrs, hipStream_t stream) {
+  return launch_gather<float, true>("gather_rows_packed", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp, num_out,
+                                    B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
+}
+
+int paths_gather_rows_packed_h16(const int64_t* grid_ptrs, const int* src_cell, int D, const float* state_cur, int64_t n_cur,
+                                 int64_t ld_state_cur, const int* src_row, int Dp, const int64_t* num_out, int B, int64_t n_next,
+                                 float* fts_out, float* state_out, int zero_pad, int64_t* row_ptrs, const float* zero_row,
+                                 const int64_t* index_ptrs, hipStream_t stream) {
+  return launch_gather<_Float16, true>("gather_rows_packed_h16", grid_ptrs, index_ptrs, src_cell, D, state_cur, n_cur, ld_state_cur, src_row, Dp,
+                                       num_out, B, n_next, fts_out, state_out, zero_pad, row_ptrs, zero_row, stream);
 }
 
 // d_cur [B, n_cur, Dp] must be zero-initialised (rows that were not kept receive no gradient).
@@ -833,24 +818,31 @@ int paths_scatter_kept_rows(const float* src, int64_t ldk, int64_t ld_src, const
 int paths_level0_batch(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
                        float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                        const float* zero_row, hipStream_t stream) {
-  PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "level0_batch: bad shape");
-  PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "level0_batch: features need a destination (copy or row pointers + zero row)");
-  hipLaunchKernelGGL(level0_kernel<float>, dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
-                     fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row);
-  PATHS_LAUNCH_CHECK("level0_batch");
-  return PATHS_OK;
+  return launch_level0<float, false>("level0_batch", grid_ptrs, nullptr, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad, row_ptrs,
+                                     zero_row, stream);
 }
 
 // paths_level0_batch over FP16 grids (row_ptrs address fp16 rows; fts receives fp32 copies)
 int paths_level0_batch_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
                            float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
                            const float* zero_row, hipStream_t stream) {
-  PATHS_REQUIRE(B > 0 && n0 > 0 && D % 4 == 0, "level0_batch_h16: bad shape");
-  PATHS_REQUIRE((fts != nullptr || row_ptrs != nullptr) && (row_ptrs == nullptr || zero_row != nullptr), "level0_batch_h16: features need a destination (copy or row pointers + zero row)");
-  hipLaunchKernelGGL(level0_kernel<_Float16>, dim3((unsigned)n0, B), dim3(256), 0, stream, grid_ptrs, gx, gy, D, patch_size, n0,
-                     fts, locs, parent, num_ims, zero_pad, row_ptrs, zero_row);
-  PATHS_LAUNCH_CHECK("level0_batch_h16");
-  return PATHS_OK;
+  return launch_level0<_Float16, false>("level0_batch_h16", grid_ptrs, nullptr, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad,
+                                        row_ptrs, zero_row, stream);
+}
+
+// paths_level0_batch[_h16] over PACKED slides: index_ptrs in front of the stream
+int paths_level0_batch_packed(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                              float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                              const float* zero_row, const int64_t* index_ptrs, hipStream_t stream) {
+  return launch_level0<float, true>("level0_batch_packed", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims, zero_pad,
+                                    row_ptrs, zero_row, stream);
+}
+
+int paths_level0_batch_packed_h16(const int64_t* grid_ptrs, const int* gx, const int* gy, int B, int D, int patch_size, int64_t n0,
+                                  float* fts, int64_t* locs, int64_t* parent, int64_t* num_ims, int zero_pad, int64_t* row_ptrs,
+                                  const float* zero_row, const int64_t* index_ptrs, hipStream_t stream) {
+  return launch_level0<_Float16, true>("level0_batch_packed_h16", grid_ptrs, index_ptrs, gx, gy, B, D, patch_size, n0, fts, locs, parent, num_ims,
+                                       zero_pad, row_ptrs, zero_row, stream);
 }
 
 int paths_scale_add_rows(const float* x, const float* alpha, const float* h, const int64_t* num_ims, int rows_per_slide,

@@ -23,9 +23,13 @@ about to visit (reference ``RawSlide.recurse``, data_utils/slide.py:173-198; DES
 PACKED slides (``slide.pack()``, ``packed=True``, ``from_patches``) leave the background out: per level the kept rows
 ``rows[l]`` [n_l, D] behind a cell index ``index[l]`` (int32 [X, Y] on the device: the row of a cell, or -1).  Only rows that are all
 +0.0 are dropped, and such a cell reads as the zero row it was, so every result is bit-identical to the dense twin's.
+
+One storage model serves all of these (:class:`_Slide`): per level ONE ROW TABLE - the dense grid seen as [X*Y, D], or the kept rows -
+plus an optional cell index, in fp32 or fp16, in HBM or in pinned host memory.
 """
 from __future__ import annotations
 
+import copy
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -44,6 +48,22 @@ def check_grid_dtype(dtype) -> torch.dtype:
     if dtype not in GRID_DTYPES:
         raise ValueError(f"feature grids must be torch.float32 or torch.float16, got {dtype}")
     return dtype
+
+
+def entry_name(name: str, h16: bool, packed: bool = False) -> str:
+    """The C entry point of ``name`` for a storage form, ``name[_packed][_h16]``: the ``_h16`` forms read fp16 rows, the ``_packed``
+    forms take one more table (the level's cell index, :func:`index_args`) in front of the stream."""
+    return name + ("_packed" if packed else "") + ("_h16" if h16 else "")
+
+
+def index_args(index_ptrs: Optional[torch.Tensor]) -> tuple:
+    """What a ``_packed`` entry point takes in front of its stream: a level's cell-index table (None - dense slides: nothing)."""
+    return () if index_ptrs is None else (_lib.ptr(index_ptrs),)
+
+
+def mask_kernel(dtype) -> str:
+    """The mask pass over rows of ``dtype``: per-row tissue flags + max|x| bits accumulated into a one-word buffer."""
+    return entry_name("paths_tissue_mask_absmax", dtype == torch.float16)
 
 
 def to_float16(grid, chunk_rows: int = 1 << 16) -> Tuple[torch.Tensor, float]:
@@ -171,93 +191,119 @@ def _pack_device_grid(g: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     g = g.contiguous()
     X, Y, D = g.shape
     cells, dev = X * Y, g.device
-    sfx = "_h16" if check_grid_dtype(g.dtype) == torch.float16 else ""
+    h16 = check_grid_dtype(g.dtype) == torch.float16
     flags = torch.empty((cells,), dtype=torch.uint8, device=dev)
     index = torch.empty((X, Y), dtype=torch.int32, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
     partials = torch.empty((int(_lib.load().paths_pack_index_partials(cells)),), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         st = _lib.stream()
-        _lib.call("paths_pack_flags" + sfx, g.data_ptr(), cells, D, flags.data_ptr(), st)
+        _lib.call(entry_name("paths_pack_flags", h16), g.data_ptr(), cells, D, flags.data_ptr(), st)
         _lib.call("paths_pack_index", flags.data_ptr(), cells, index.data_ptr(), count.data_ptr(), partials.data_ptr(), st)
         n = int(count.item())
         rows = torch.empty((n, D), dtype=g.dtype, device=dev)
         if n > 0:
-            _lib.call("paths_pack_rows" + sfx, g.data_ptr(), cells, D, index.data_ptr(), n, rows.data_ptr(), st)
+            _lib.call(entry_name("paths_pack_rows", h16), g.data_ptr(), cells, D, index.data_ptr(), n, rows.data_ptr(), st)
     return rows, index
 
 
-def _packed_slide(cls, rows, index, masks, patch_size, slide_id, subtype, **attrs):
-    """A packed slide of ``cls`` around its level tables (no launch; the callers fill ``_absmax`` / ``_absmax_bits``)."""
-    s = object.__new__(cls)
-    s.dtype = check_grid_dtype(rows[0].dtype)
-    if any(r.dtype != s.dtype for r in rows):
-        raise ValueError(f"{cls.__name__}: all levels of a slide must have the same dtype")
-    s.packed, s.grids = True, None
-    s.rows, s.index, s.masks = list(rows), list(index), list(masks)
-    s.patch_size, s.slide_id, s.subtype = patch_size, slide_id, subtype
-    s._absmax_bits, s._absmax = None, None
-    s.__dict__.update(attrs)
-    return s
+def _level_dtype(levels: Sequence[torch.Tensor], who: str) -> torch.dtype:
+    """The one storage dtype of a slide's levels (before any I/O or device touch)."""
+    assert len(levels) >= 1
+    dtype = check_grid_dtype(levels[0].dtype)
+    if any(t.dtype != dtype for t in levels):
+        raise ValueError(f"{who}: all levels of a slide must have the same dtype")
+    return dtype
 
 
-def _copy_spec(src, dst):
-    if hasattr(src, "synthetic_spec"):
-        dst.synthetic_spec = src.synthetic_spec
-    return dst
+def _nbytes(tensors) -> int:
+    return sum(t.numel() * t.element_size() for t in tensors)
 
 
-def _masked_view(slide, masks):
-    """The view behind DeviceSlide.with_masks / HostSlide.with_masks: a shallow copy of ``slide`` that carries ``masks``."""
-    masks = list(masks)
-    if len(masks) != slide.num_levels:
-        raise ValueError(f"with_masks: one mask per level ({slide.num_levels}) expected, got {len(masks)}")
-    for l, (m, own) in enumerate(zip(masks, slide.masks)):
-        if not torch.is_tensor(m) or m.dtype != torch.uint8 or tuple(m.shape) != tuple(slide.shape(l)) or not m.is_contiguous():
-            got = f"{m.dtype} {tuple(m.shape)}" if torch.is_tensor(m) else type(m).__name__
-            raise ValueError(f"with_masks: level {l} needs a contiguous uint8 [X, Y] = {list(slide.shape(l))} tensor, got {got}")
-        if m.device != own.device:
-            raise ValueError(f"with_masks: the mask of level {l} lives on {m.device}, the slide's masks on {own.device}")
-    view = object.__new__(type(slide))
-    view.__dict__.update(slide.__dict__)
-    view.masks = masks
-    view.masked_view = True
-    view._absmax = slide.feature_absmax()             # the recorded max|x| of the source (its cached value: no launch)
-    return view
+class _Slide:
+    """The storage model behind :class:`DeviceSlide` and :class:`HostSlide`.  Per level a slide holds ONE ROW TABLE and an optional cell
+    index: dense, the table is ``grids[l]`` seen as [X*Y, D] and there is no index (``rows`` / ``index`` are None); packed, the table is
+    the kept rows ``rows[l]`` behind ``index[l]`` (``grids`` is None).  ``masks[l]`` are uint8 [X, Y] device tensors either way.  The
+    two classes differ in where a table lives (:meth:`_put`), how a dense level is packed (:meth:`_pack_grid`), how a synthetic level
+    is produced (:meth:`_synth_level`) and how a table's rows reach the mask kernel (:meth:`_row_chunks`); everything else is here."""
 
-
-class DeviceSlide:
-    host_resident = False           # the grids live in HBM (HostSlide: in pinned host memory)
-    masked_view = False             # (with_masks: the same grids behind other tissue masks)
-    packed = False                  # (pack() / packed=True / from_patches: ``rows`` + ``index`` instead of ``grids``)
+    host_resident = False           # the tables live in HBM (HostSlide: in pinned host memory)
+    on_demand = False
+    packed = False                  # (the dense form's values; every slide carries its own)
     rows = None
     index = None
 
-    def __init__(self, grids: Sequence[torch.Tensor], patch_size: int = 256, slide_id: str = "", subtype=None):
-        """``grids``: device tensors [X, Y, D], all torch.float32 or all torch.float16 (kept as they are: no fp32 copy is made)."""
-        assert len(grids) >= 1
-        self.dtype = check_grid_dtype(grids[0].dtype)
-        if any(g.dtype != self.dtype for g in grids):
-            raise ValueError("DeviceSlide: all levels of a slide must have the same dtype")
-        self.patch_size = patch_size
-        self.slide_id = slide_id
-        self.subtype = subtype
-        self.grids: List[torch.Tensor] = []
-        self.masks: List[torch.Tensor] = []
-        self._absmax_bits = None          # fp32 bit pattern of max|feature| over all levels, written by the mask pass
-        self._absmax: Optional[float] = None
-        for g in grids:
-            _lib.require_cuda(g)
-            assert g.dim() == 3
-            g = g.contiguous()
-            X, Y, D = g.shape
-            m = torch.empty((X, Y), dtype=torch.uint8, device=g.device)
-            if self._absmax_bits is None:
-                self._absmax_bits = torch.zeros((1,), dtype=torch.int32, device=g.device)
-            _lib.call("paths_tissue_mask_absmax_h16" if self.dtype == torch.float16 else "paths_tissue_mask_absmax", g.data_ptr(), X * Y, D,
-                      m.data_ptr(), self._absmax_bits.data_ptr(), _lib.stream())
-            self.grids.append(g)
-            self.masks.append(m)
+    @classmethod
+    def _new(cls, dtype, device, masks, grids=None, rows=None, index=None, absmax: Optional[float] = None, absmax_bits=None,
+             patch_size: int = 256, slide_id: str = "", subtype=None, masked_view: bool = False, synthetic_spec=None, into=None):
+        """THE private constructor: a slide of ``cls`` (``into``: the object a public ``__init__`` is filling) made of exactly what it is
+        handed - ``grids``, or ``rows`` + ``index`` - with every attribute set; nothing is checked, placed or launched."""
+        s = object.__new__(cls) if into is None else into
+        s.dtype, s.device = dtype, device                       # device: where the masks (and a packed slide's index) live
+        s.packed = grids is None
+        s.grids, s.rows, s.index, s.masks = grids, rows, index, list(masks)
+        s._absmax, s._absmax_bits = absmax, absmax_bits         # max|feature| over all levels / its fp32 bit pattern from the mask pass
+        s.patch_size, s.slide_id, s.subtype = patch_size, slide_id, subtype
+        s.masked_view = masked_view                             # (with_masks: the same tables behind other tissue masks)
+        s.synthetic_spec = synthetic_spec                       # (synthetic(): the generator of the grids, else None)
+        return s
+
+    def _ident(self) -> dict:
+        """What every conversion of a slide keeps."""
+        return dict(patch_size=self.patch_size, slide_id=self.slide_id, subtype=self.subtype, masked_view=self.masked_view,
+                    synthetic_spec=self.synthetic_spec)
+
+    @classmethod
+    def _build(cls, levels, device, dtype, packed: bool, masks=None, absmax=None, patch_size: int = 256, slide_id: str = "", subtype=None,
+               masked_view: bool = False, synthetic_spec=None, into=None, **pass_kw):
+        """The slide of ``levels``: an iterable of dense grids [X, Y, D] or - ``packed`` only - of (rows, index) pairs, all in ``dtype``
+        and anywhere.  Every table is put where the class keeps it; ``packed``: a dense level is packed and dropped before the next one
+        is asked for (peak memory is the packed slide plus one dense level), the index goes to the device.  Masks and max|x| come from
+        the mask pass over the tables (``pass_kw``: the class's :meth:`_row_chunks` options) unless cached ``masks=`` + ``absmax=`` are
+        given."""
+        if (masks is None) != (absmax is None):
+            raise ValueError(f"{cls.__name__}: cached masks= and absmax= come together")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.PathsHipError(f"paths_amd runs on the GPU only: {cls._NEEDS_GPU} (no CPU fallback)")
+        grids, rows, index = (None, [], []) if packed else ([], None, None)
+        for lv in levels:
+            if device.index is None:        # (the device is first touched here: after the host-side conversion of the first level)
+                device = torch.device("cuda", torch.cuda.current_device())
+            if packed:
+                r, ix = lv if isinstance(lv, tuple) else cls._pack_grid(lv, device)
+                del lv
+                rows.append(cls._put(r, device))
+                index.append(ix.to(device))
+            else:
+                if lv.dim() != 3:
+                    raise ValueError(f"{cls.__name__}: grids are tensors [X, Y, D]")
+                grids.append(cls._put(lv, device))
+        s = cls._new(dtype, device, masks or (), grids, rows, index, None if absmax is None else float(absmax), patch_size=patch_size,
+                     slide_id=slide_id, subtype=subtype, masked_view=masked_view, synthetic_spec=synthetic_spec, into=into)
+        if masks is None:
+            s._mask_pass(**pass_kw)
+        else:
+            _lib.require_cuda(*s.masks)
+            if len(s.masks) != s.num_levels or any(m.dtype != torch.uint8 or tuple(m.shape) != s.shape(l) or not m.is_contiguous()
+                                                   for l, m in enumerate(s.masks)):
+                raise ValueError(f"{cls.__name__}: masks are contiguous uint8 [X, Y] device tensors, one per grid")
+        return s
+
+    def _mask_pass(self, **kw):
+        """THE mask pass: paths_tissue_mask_absmax[_h16] over every row table -> per-row flags + max|x| bits in a one-word buffer; the
+        flags are the per-cell mask of a dense level and go to their cells through the index of a packed one."""
+        dev = self.device
+        tables = self.rows if self.packed else [g.view(-1, g.shape[2]) for g in self.grids]
+        with torch.cuda.device(dev):
+            bits = self._absmax_bits = torch.zeros((1,), dtype=torch.int32, device=dev)
+            flags = [torch.empty((t.shape[0],), dtype=torch.uint8, device=dev) if t.shape[0] else None for t in tables]
+            for l, r0, ptr, n in self._row_chunks(tables, **kw):
+                _lib.call(mask_kernel(self.dtype), ptr, n, self.dim, flags[l].data_ptr() + r0, bits.data_ptr(), _lib.stream())
+            self.masks = [_scatter_flags(f, self.index[l]) if self.packed else f.view(self.grids[l].shape[:2]) for l, f in enumerate(flags)]
+            if self.host_resident:
+                # the host must not re-use or free the bounce buffer's view of the last chunk early; the pass is once per slide
+                torch.cuda.current_stream(dev).synchronize()
 
     def feature_absmax(self) -> float:
         """max|x| over every grid of the slide (inf if any element is inf or NaN): the operand-range check of the default
@@ -272,7 +318,18 @@ class DeviceSlide:
         cell whose byte is 0 is background to the recursion: the child filter drops it, and at level 0 - where every cell is loaded,
         background included - it reads as the all-zero row a background cell is.  Nothing is launched and nothing is allocated; batches
         take views like any slide, several views of one slide in one batch included."""
-        return _masked_view(self, masks)
+        masks = list(masks)
+        if len(masks) != self.num_levels:
+            raise ValueError(f"with_masks: one mask per level ({self.num_levels}) expected, got {len(masks)}")
+        for l, (m, own) in enumerate(zip(masks, self.masks)):
+            if not torch.is_tensor(m) or m.dtype != torch.uint8 or tuple(m.shape) != tuple(self.shape(l)) or not m.is_contiguous():
+                got = f"{m.dtype} {tuple(m.shape)}" if torch.is_tensor(m) else type(m).__name__
+                raise ValueError(f"with_masks: level {l} needs a contiguous uint8 [X, Y] = {list(self.shape(l))} tensor, got {got}")
+            if m.device != own.device:
+                raise ValueError(f"with_masks: the mask of level {l} lives on {m.device}, the slide's masks on {own.device}")
+        # (the recorded max|x| of the source - its cached value: no launch)
+        return self._new(self.dtype, self.device, masks, self.grids, self.rows, self.index, self.feature_absmax(),
+                         **dict(self._ident(), masked_view=True))
 
     @property
     def num_levels(self) -> int:
@@ -287,120 +344,127 @@ class DeviceSlide:
         return self.rows[0].shape[1] if self.packed else self.grids[0].shape[2]
 
     def resident_bytes(self) -> int:
-        """Device memory held by the slide: grids + masks, packed rows + index + masks."""
-        nbytes = lambda ts: sum(t.numel() * t.element_size() for t in ts)
-        return nbytes(self.rows) + nbytes(self.index) + nbytes(self.masks) if self.packed else nbytes(self.grids) + nbytes(self.masks)
+        """Device memory held by the slide: the masks, a packed slide's cell index and - DeviceSlide - the grids or the packed rows."""
+        tables = [] if self.host_resident else (self.rows if self.packed else self.grids)
+        return _nbytes(tables) + _nbytes(self.index or ()) + _nbytes(self.masks)
 
-    @staticmethod
-    def _packed_levels(levels, patch_size: int = 256, slide_id: str = "", subtype=None) -> "DeviceSlide":
-        """The packed slide of ``levels``, an iterable of (rows, index) device pairs or of dense device grids (packed here and dropped
-        before the next one is asked for: peak memory is the packed slide plus one dense level).  Masks and max|x| come from the mask
-        pass over the PACKED rows (the per-row flags go to their cells through the index)."""
-        rows, index, masks, bits = [], [], [], None
-        for lv in levels:
-            r, ix = lv if isinstance(lv, tuple) else _pack_device_grid(lv)
-            del lv
-            _lib.require_cuda(r, ix)
-            if bits is None:
-                bits = torch.zeros((1,), dtype=torch.int32, device=ix.device)
-            flags = None
-            if r.shape[0] > 0:
-                flags = torch.empty((r.shape[0],), dtype=torch.uint8, device=r.device)
-                with torch.cuda.device(r.device):
-                    _lib.call("paths_tissue_mask_absmax_h16" if r.dtype == torch.float16 else "paths_tissue_mask_absmax", r.data_ptr(),
-                              r.shape[0], r.shape[1], flags.data_ptr(), bits.data_ptr(), _lib.stream())
-            rows.append(r); index.append(ix); masks.append(_scatter_flags(flags, ix))
-        return _packed_slide(DeviceSlide, rows, index, masks, patch_size, slide_id, subtype, _absmax_bits=bits)
-
-    def pack(self) -> "DeviceSlide":
+    def pack(self):
         """The packed twin (this slide is left as it is): per level the rows with any bit set, in row-major cell order, behind the cell
-        index - packed on the device (csrc/pack_rows.hip).  A masked view packs to a view: its masks and recorded max|x| are kept."""
+        index on the device - a DeviceSlide is packed on the device (csrc/pack_rows.hip), a HostSlide on the host
+        (:func:`pack_host_grid`; the kept rows go to pinned memory).  A masked view packs to a view: its masks and recorded max|x| are
+        kept; else both come from the mask pass over the packed rows."""
         if self.packed:
             return self
-        if self.masked_view:
-            pairs = [_pack_device_grid(g) for g in self.grids]
-            s = _packed_slide(DeviceSlide, [r for r, _ in pairs], [ix for _, ix in pairs], self.masks, self.patch_size, self.slide_id,
-                              self.subtype, _absmax=self.feature_absmax(), masked_view=True)
-        else:
-            s = DeviceSlide._packed_levels(self.grids, self.patch_size, self.slide_id, self.subtype)
-        return _copy_spec(self, s)
+        cached = dict(masks=self.masks, absmax=self.feature_absmax()) if self.masked_view else {}
+        return self._build(self.grids, self.device, self.dtype, True, **cached, **self._ident())
 
-    def to_dense(self) -> "DeviceSlide":
-        """The dense twin: every cell without a row becomes an all-zero row again (torch indexing: a construction-time path)."""
+    def to_dense(self):
+        """The dense twin: every cell without a row becomes an all-zero row again (torch indexing: a construction-time path); its masks
+        and max|x| are this slide's (no mask pass)."""
         if not self.packed:
             return self
-        s = DeviceSlide([unpack_grid(r, ix) for r, ix in zip(self.rows, self.index)], patch_size=self.patch_size, slide_id=self.slide_id,
-                        subtype=self.subtype)
-        return _copy_spec(self, s.with_masks(self.masks) if self.masked_view else s)
+        grids = [unpack_grid(r, ix.to(r.device)) for r, ix in zip(self.rows, self.index)]
+        return self._build(grids, self.device, self.dtype, False, masks=self.masks, absmax=self.feature_absmax(), **self._ident())
 
-    @staticmethod
-    def from_patches(coords: Sequence, features: Sequence, shapes: Sequence, device, dtype=torch.float32, patch_size: int = 256,
-                     slide_id: str = "", subtype=None) -> "DeviceSlide":
+    @classmethod
+    def from_patches(cls, coords: Sequence, features: Sequence, shapes: Sequence, device="cuda", dtype=torch.float32, patch_size: int = 256,
+                     slide_id: str = "", subtype=None, **kw):
         """A packed slide straight from the coords + features lists feature extractors write: ``coords[l]`` int64 [n_l, 2] cell
         coordinates (the convention of ``OnDemandSlide.encode``'s ``cells``), ``features[l]`` [n_l, D], ``shapes[l]`` = (X, Y).  Cells not
         listed are background; rows keep the given order; n_l = 0 is a level without tissue.  ValueError (before anything is launched:
         :func:`check_patches`) on a cell named twice or outside its grid, mismatched lengths, or a refused dtype; fp16 goes through
-        :func:`to_float16`."""
+        :func:`to_float16`.  A HostSlide keeps the rows in pinned host memory (the same arguments, checks and row order)."""
         cells = check_patches(coords, features, shapes, dtype)
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.PathsHipError("paths_amd runs on the GPU only: a DeviceSlide lives on a GPU device (no CPU fallback)")
-        levels = [(_patch_rows(f, dtype).to(device), _patch_index(c, sh).to(device)) for c, f, sh in zip(cells, features, shapes)]
-        return DeviceSlide._packed_levels(levels, patch_size, slide_id, subtype)
+        levels = [(_patch_rows(f, dtype), _patch_index(c, sh)) for c, f, sh in zip(cells, features, shapes)]
+        return cls._build(levels, device, dtype, True, patch_size=patch_size, slide_id=slide_id, subtype=subtype, **kw)
 
-    @staticmethod
-    def from_host(grids: Sequence, device, dtype=torch.float32, packed: bool = False, **kw) -> "DeviceSlide":
-        """Upload host grids (numpy or CPU tensors, e.g. ``torch.load('<slide>_<power:.3f>.pt')``) as ``dtype`` grids
-        (torch.float16: converted on the host by :func:`to_float16`, which raises on values fp16 cannot hold).  ``packed``: every level
-        is uploaded, packed and dropped before the next one (what :meth:`pack` of the dense slide gives)."""
-        if check_grid_dtype(dtype) == torch.float16:
-            up = lambda g: to_float16(g)[0].to(device)
-        else:
-            up = lambda g: torch.as_tensor(g, dtype=torch.float32).to(device)
-        if packed:
-            return DeviceSlide._packed_levels((up(g) for g in grids), **kw)
-        return DeviceSlide([up(g) for g in grids], **kw)
+    @classmethod
+    def from_host(cls, grids: Sequence, device="cuda", dtype=torch.float32, packed: bool = False, **kw):
+        """Host grids (numpy or CPU tensors, e.g. ``torch.load('<slide>_<power:.3f>.pt')``) as ``dtype`` grids of the class: uploaded
+        (DeviceSlide) or pinned (HostSlide; grids that already are pinned tensors of ``dtype`` are used where they are).  torch.float16:
+        converted on the host by :func:`to_float16`, which raises on values fp16 cannot hold.  ``packed``: every level is converted,
+        packed and dropped before the next one (what :meth:`pack` of the dense slide gives)."""
+        if check_grid_dtype(dtype) == torch.float32:
+            conv = lambda g: torch.as_tensor(g, dtype=torch.float32)
+        else:       # (a HostSlide takes fp16 tensors as they are)
+            conv = lambda g: g if (cls.host_resident and torch.is_tensor(g) and g.dtype == torch.float16) else to_float16(g)[0]
+        return cls._build((conv(g) for g in grids), device, dtype, packed, **kw)
 
-    @staticmethod
-    def from_preprocessed(root: str, slide_id: str, powers: Sequence[float], device="cuda", patch_size: int = 256,
-                          subtype=None, dtype=torch.float32, packed: bool = False) -> "DeviceSlide":
+    @classmethod
+    def from_preprocessed(cls, root: str, slide_id: str, powers: Sequence[float], device="cuda", patch_size: int = 256,
+                          subtype=None, dtype=torch.float32, packed: bool = False, **kw):
         """Load the reference's preprocessed-grid files ``<root>/<slide_id>_<power:.3f>.pt`` (one ``[X, Y, D]`` float
         tensor per magnification, all-zero row = background; written by reference preprocess/preprocess.py:89,134 and
-        read by preprocess/loader.py:14-18 / data_utils/slide.py:247-253) and make them resident in HBM as ``dtype`` grids
-        (see :meth:`from_host`)."""
+        read by preprocess/loader.py:14-18 / data_utils/slide.py:247-253) and keep them as ``dtype`` grids of the class (see
+        :meth:`from_host`).  The dtype is checked before any file is read or the device is touched; a HostSlide also checks every path
+        (FileNotFoundError) before it loads any."""
         import os
-        check_grid_dtype(dtype)                 # before any file is read or the device is touched
+        check_grid_dtype(dtype)
+        paths = [os.path.join(root, slide_id + f"_{power:.3f}.pt") for power in powers]
+        for path in paths if cls.host_resident else ():
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"Pre-process load: path '{path}' not found!")
         grids = []
-        for power in powers:
-            path = os.path.join(root, slide_id + f"_{power:.3f}.pt")
+        for path in paths:
             assert os.path.isfile(path), f"Pre-process load: path '{path}' not found!"
             g = torch.load(path, map_location="cpu")
             assert g.dim() == 3, f"{path}: expected a [X, Y, D] grid, got {tuple(g.shape)}"
             grids.append(g.float() if dtype == torch.float32 else g)
-        return DeviceSlide.from_host(grids, device, dtype=dtype, packed=packed, patch_size=patch_size, slide_id=slide_id, subtype=subtype)
+        return cls.from_host(grids, device, dtype=dtype, packed=packed, patch_size=patch_size, slide_id=slide_id, subtype=subtype, **kw)
+
+    @classmethod
+    def synthetic(cls, seed: int, slide: int, base_shape: Tuple[int, int], dim: int = 1024, num_levels: int = 5, p_bg: float = 0.1,
+                  device="cuda", patch_size: int = 256, dtype=torch.float32, packed: bool = False, **kw):
+        """The counter-based synthetic pyramid: a DeviceSlide generates it directly in HBM (paths_synth_grid; torch.float16:
+        paths_synth_grid_h16, the same values rounded to nearest even), a HostSlide on the host (synthetic.SyntheticSlide.grid: the same
+        bytes) straight into pinned memory."""
+        h16 = check_grid_dtype(dtype) == torch.float16
+        spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg, feature_dtype="float16" if h16 else "float32")
+        levels = (cls._synth_level(spec, l, dtype, device, packed) for l in range(num_levels))
+        return cls._build(levels, device, dtype, packed, patch_size=patch_size, slide_id=f"synthetic-{seed}-{slide}", synthetic_spec=spec, **kw)
+
+
+class DeviceSlide(_Slide):
+    _NEEDS_GPU = "a DeviceSlide lives on a GPU device"
+
+    def __init__(self, grids: Sequence[torch.Tensor], patch_size: int = 256, slide_id: str = "", subtype=None):
+        """``grids``: device tensors [X, Y, D], all torch.float32 or all torch.float16 (kept as they are: no fp32 copy is made)."""
+        dtype = _level_dtype(grids, "DeviceSlide")
+        for g in grids:
+            _lib.require_cuda(g)
+            assert g.dim() == 3
+        self._build(grids, grids[0].device, dtype, False, patch_size=patch_size, slide_id=slide_id, subtype=subtype, into=self)
 
     @staticmethod
-    def synthetic(seed: int, slide: int, base_shape: Tuple[int, int], dim: int = 1024, num_levels: int = 5,
-                  p_bg: float = 0.1, device="cuda", patch_size: int = 256, dtype=torch.float32, packed: bool = False) -> "DeviceSlide":
-        """Generate the counter-based synthetic pyramid directly in HBM (paths_synth_grid; torch.float16: paths_synth_grid_h16, the same
-        values rounded to nearest even)."""
-        h16 = check_grid_dtype(dtype) == torch.float16
-        thr = synthetic.bg_threshold(p_bg)
+    def _put(t: torch.Tensor, device) -> torch.Tensor:
+        return t.to(device).contiguous()
 
-        def level(l):
-            X, Y = base_shape[0] << l, base_shape[1] << l
-            g = torch.empty((X, Y, dim), dtype=dtype, device=device)
-            key = int(synthetic.slide_level_key(seed, slide, l))
-            _lib.call("paths_synth_grid_h16" if h16 else "paths_synth_grid", g.data_ptr(), X, Y, dim, key, l, thr, _lib.stream())
-            return g
+    @staticmethod
+    def _pack_grid(g: torch.Tensor, device):
+        return _pack_device_grid(g.to(device))
 
-        if packed:
-            s = DeviceSlide._packed_levels((level(l) for l in range(num_levels)), patch_size, f"synthetic-{seed}-{slide}")
-        else:
-            s = DeviceSlide([level(l) for l in range(num_levels)], patch_size=patch_size, slide_id=f"synthetic-{seed}-{slide}")
-        s.synthetic_spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg,
-                                                    feature_dtype="float16" if h16 else "float32")
-        return s
+    def _row_chunks(self, tables):
+        """One launch over each table, where it lives."""
+        return ((l, 0, t.data_ptr(), t.shape[0]) for l, t in enumerate(tables) if t.shape[0])
+
+    @staticmethod
+    def _synth_level(spec, l: int, dtype, device, packed: bool) -> torch.Tensor:
+        X, Y = spec.shape(l)
+        g = torch.empty((X, Y, spec.dim), dtype=dtype, device=device)
+        _lib.call(entry_name("paths_synth_grid", dtype == torch.float16), g.data_ptr(), X, Y, spec.dim,
+                  int(synthetic.slide_level_key(spec.seed, spec.slide, l)), l, synthetic.bg_threshold(spec.p_bg), _lib.stream())
+        return g
+
+    @classmethod
+    def from_patches(cls, coords: Sequence, features: Sequence, shapes: Sequence, device, dtype=torch.float32, patch_size: int = 256,
+                     slide_id: str = "", subtype=None) -> "DeviceSlide":
+        """:meth:`_Slide.from_patches`; a resident slide names its ``device``, and takes no mask-pass options."""
+        return super().from_patches(coords, features, shapes, device, dtype, patch_size, slide_id, subtype)
+
+    @classmethod
+    def from_host(cls, grids: Sequence, device, dtype=torch.float32, packed: bool = False, **kw) -> "DeviceSlide":
+        """:meth:`_Slide.from_host`; a resident slide names its ``device``."""
+        return super().from_host(grids, device, dtype, packed, **kw)
 
 
 def plan_mask_chunks(cells: int, D: int, itemsize: int, budget_bytes: int) -> List[Tuple[int, int]]:
@@ -416,16 +480,12 @@ def plan_mask_chunks(cells: int, D: int, itemsize: int, budget_bytes: int) -> Li
     return [(r0, min(per, cells - r0)) for r0 in range(0, cells, per)]
 
 
-def _pinned(g: torch.Tensor) -> torch.Tensor:
-    """``g`` (CPU, contiguous) in pinned memory: itself when it already is, else a pinned copy."""
-    return g if g.is_pinned() else g.pin_memory()
-
-
-class HostSlide:
+class HostSlide(_Slide):
     """A slide whose feature grids stay in PINNED host memory (the reference keeps them in host RAM too and gathers on the CPU,
     data_utils/slide.py:320-331).  The read surface is :class:`DeviceSlide`'s; ``grids[l]`` are CPU tensors [X, Y, D] that the
     device can address (pinned = device-mapped), ``masks[l]`` are the usual uint8 [X, Y] DEVICE tensors.  Device memory per slide is
-    the masks alone (0.7 MB at K = 2048 x 5 levels against 2.86 GB of grids).
+    the masks alone (0.7 MB at K = 2048 x 5 levels against 2.86 GB of grids).  Packed: pinned ``rows`` + device ``index`` instead of
+    ``grids``.
 
     The masks and max|x| come from ONE pass of the resident slides' kernel (paths_tissue_mask_absmax[_h16]) over the grid, streamed
     in row chunks through a bounded device bounce buffer (``bounce_bytes``, or a caller-owned uint8 device tensor ``bounce`` shared by
@@ -433,207 +493,108 @@ class HostSlide:
     pinned memory here: a kernel must never be handed pageable memory."""
 
     host_resident = True
-    packed = False                  # (pack() / packed=True / from_patches: pinned ``rows`` + device ``index`` instead of ``grids``)
-    rows = None
-    index = None
+    _NEEDS_GPU = "a HostSlide needs a GPU device for its masks"
 
     def __init__(self, grids: Sequence[torch.Tensor], device="cuda", patch_size: int = 256, slide_id: str = "", subtype=None,
                  masks: Optional[Sequence[torch.Tensor]] = None, absmax: Optional[float] = None, bounce_bytes: int = 64 << 20,
                  bounce: Optional[torch.Tensor] = None):
-        assert len(grids) >= 1
-        self.dtype = check_grid_dtype(grids[0].dtype)
-        if any(g.dtype != self.dtype for g in grids):
-            raise ValueError("HostSlide: all levels of a slide must have the same dtype")
+        dtype = _level_dtype(grids, "HostSlide")
         if any(g.device.type != "cpu" or g.dim() != 3 for g in grids):
             raise ValueError("HostSlide: grids are CPU tensors [X, Y, D] (DeviceSlide holds device grids)")
-        if (masks is None) != (absmax is None):
-            raise ValueError("HostSlide: cached masks= and absmax= come together")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.PathsHipError("paths_amd runs on the GPU only: a HostSlide needs a GPU device for its masks (no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.patch_size = patch_size
-        self.slide_id = slide_id
-        self.subtype = subtype
-        self.grids: List[torch.Tensor] = [_pinned(g.contiguous()) for g in grids]
-        self.masks: List[torch.Tensor] = []
-        self._absmax_bits = None
-        self._absmax: Optional[float] = None
-        if masks is not None:
-            for g, m in zip(self.grids, masks):
-                _lib.require_cuda(m)
-                if m.dtype != torch.uint8 or tuple(m.shape) != tuple(g.shape[:2]) or not m.is_contiguous():
-                    raise ValueError("HostSlide: masks are contiguous uint8 [X, Y] device tensors, one per grid")
-            self.masks = list(masks)
-            self._absmax = float(absmax)
-            return
-        with torch.cuda.device(self.device):
-            self._mask_pass(int(bounce_bytes), bounce)
+        self._build(grids, device, dtype, False, masks, absmax, patch_size, slide_id, subtype, into=self, bounce_bytes=bounce_bytes,
+                    bounce=bounce)
 
-    def _mask_pass(self, bounce_bytes: int, bounce: Optional[torch.Tensor]):
-        # (packed: the pass streams the PACKED rows; the per-row flags go to their cells through the index)
-        tables = self.rows if self.packed else [g.view(-1, g.shape[2]) for g in self.grids]
-        dev, es = self.device, tables[0].element_size()
+    @staticmethod
+    def _put(t: torch.Tensor, device) -> torch.Tensor:
+        """``t`` as a contiguous CPU tensor in pinned memory: itself when it already is, else a pinned copy (no rows: nothing to pin)."""
+        t = t.cpu().contiguous()
+        return t if (t.numel() == 0 or t.is_pinned()) else t.pin_memory()
+
+    @staticmethod
+    def _pack_grid(g: torch.Tensor, device):
+        return pack_host_grid(g)
+
+    def _row_chunks(self, tables, bounce_bytes: int = 64 << 20, bounce: Optional[torch.Tensor] = None):
+        """Every table in row chunks through the bounce buffer (:func:`plan_mask_chunks`)."""
+        dev, es, D = self.device, tables[0].element_size(), self.dim
         if bounce is None:
             # (no larger than the largest grid; whole rows)
-            largest = max(max(t.numel() for t in tables), self.dim) * es
-            plan_mask_chunks(1, self.dim, es, bounce_bytes)                       # raises if the budget holds no row
+            largest = max(max(t.numel() for t in tables), D) * es
+            plan_mask_chunks(1, D, es, bounce_bytes)                       # raises if the budget holds no row
             bounce = torch.empty((min(int(bounce_bytes), largest),), dtype=torch.uint8, device=dev)
         else:
             _lib.require_cuda(bounce)
             assert bounce.dtype == torch.uint8 and bounce.is_contiguous() and bounce.data_ptr() % 16 == 0
-        self._absmax_bits = torch.zeros((1,), dtype=torch.int32, device=dev)
-        name = "paths_tissue_mask_absmax_h16" if self.dtype == torch.float16 else "paths_tissue_mask_absmax"
         for l, flat in enumerate(tables):
-            cells, D = flat.shape
-            m = torch.empty((cells,), dtype=torch.uint8, device=dev) if cells else None
-            for r0, rows in (plan_mask_chunks(cells, D, es, bounce.numel()) if cells else []):
+            for r0, rows in (plan_mask_chunks(flat.shape[0], D, es, bounce.numel()) if flat.shape[0] else []):
                 assert flat.is_pinned()
                 chunk = bounce[:rows * D * es].view(self.dtype).view(rows, D)
                 chunk.copy_(flat[r0:r0 + rows], non_blocking=True)               # same stream as the kernel: chunks follow each other
-                _lib.call(name, chunk.data_ptr(), rows, D, m.data_ptr() + r0, self._absmax_bits.data_ptr(), _lib.stream())
-            self.masks.append(_scatter_flags(m, self.index[l]) if self.packed else m.view(self.grids[l].shape[:2]))
-        # the host must not re-use or free the bounce buffer's view of the last chunk early; the pass is once per slide
-        torch.cuda.current_stream(dev).synchronize()
+                yield l, r0, chunk.data_ptr(), rows
 
-    masked_view = False
-    with_masks = DeviceSlide.with_masks
-    feature_absmax = DeviceSlide.feature_absmax
-    num_levels = DeviceSlide.num_levels
-    shape = DeviceSlide.shape
-    dim = DeviceSlide.dim
+    @staticmethod
+    def _synth_level(spec, l: int, dtype, device, packed: bool) -> torch.Tensor:
+        X, Y = spec.shape(l)
+        g = torch.empty((X, Y, spec.dim), dtype=dtype, pin_memory=not packed)
+        g.copy_(torch.from_numpy(spec.grid(l)))             # (fp16: the values are fp16-representable already, the cast is exact)
+        return g
 
     def host_bytes(self) -> int:
         """Pinned host memory held by the grids (packed: by the kept rows)."""
-        return sum(g.numel() * g.element_size() for g in (self.rows if self.packed else self.grids))
-
-    def resident_bytes(self) -> int:
-        """Device memory held by the slide: the masks, and a packed slide's cell index."""
-        return sum(t.numel() * t.element_size() for t in (self.index if self.packed else []) + self.masks)
+        return _nbytes(self.rows if self.packed else self.grids)
 
     def to_device(self) -> DeviceSlide:
-        """The equivalent resident slide (a full upload of every grid; packed: of the kept rows - the twin is packed too)."""
-        if self.packed:
-            s = _packed_slide(DeviceSlide, [r.to(self.device, non_blocking=True) for r in self.rows], self.index, self.masks, self.patch_size,
-                              self.slide_id, self.subtype, _absmax=self.feature_absmax(), masked_view=self.masked_view)
-            torch.cuda.current_stream(self.device).synchronize()
-            return _copy_spec(self, s)
-        s = DeviceSlide([g.to(self.device, non_blocking=True) for g in self.grids], patch_size=self.patch_size, slide_id=self.slide_id,
-                        subtype=self.subtype)
-        if hasattr(self, "synthetic_spec"):
-            s.synthetic_spec = self.synthetic_spec
-        return s
-
-    @staticmethod
-    def _packed_levels(levels, device="cuda", patch_size: int = 256, slide_id: str = "", subtype=None, masks=None, absmax=None,
-                       bounce_bytes: int = 64 << 20, bounce: Optional[torch.Tensor] = None, masked_view: bool = False) -> "HostSlide":
-        """The packed slide of ``levels``, an iterable of (rows, index) CPU pairs or of dense CPU grids (packed by
-        :func:`pack_host_grid` and dropped before the next one is asked for).  Rows go to pinned memory, the index to the device; the
-        mask pass streams the packed rows through the bounce buffer (``masks=`` + ``absmax=`` skip it)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.PathsHipError("paths_amd runs on the GPU only: a HostSlide needs a GPU device for its masks (no CPU fallback)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if (masks is None) != (absmax is None):
-            raise ValueError("HostSlide: cached masks= and absmax= come together")
-        rows, index = [], []
-        for lv in levels:
-            r, ix = lv if isinstance(lv, tuple) else pack_host_grid(lv)
-            del lv
-            if r.device.type != "cpu" or r.dim() != 2:
-                raise ValueError("HostSlide: packed rows are CPU tensors [n, D]")
-            rows.append(_pinned(r.contiguous()) if r.numel() else r)
-            index.append(ix.to(device))
-        s = _packed_slide(HostSlide, rows, index, [], patch_size, slide_id, subtype, device=device, masked_view=masked_view)
-        if masks is not None:
-            s.masks, s._absmax = list(masks), float(absmax)
-        else:
-            with torch.cuda.device(device):
-                s._mask_pass(int(bounce_bytes), bounce)
-                torch.cuda.current_stream(device).synchronize()
-        return s
-
-    def pack(self) -> "HostSlide":
-        """The packed twin (this slide is left as it is), packed on the host by :func:`pack_host_grid`: the kept rows in pinned memory,
-        the cell index on the device.  A masked view packs to a view: its masks and recorded max|x| are kept."""
-        if self.packed:
-            return self
-        kw = dict(masks=self.masks, absmax=self.feature_absmax(), masked_view=True) if self.masked_view else {}
-        return _copy_spec(self, HostSlide._packed_levels(self.grids, self.device, self.patch_size, self.slide_id, self.subtype, **kw))
-
-    def to_dense(self) -> "HostSlide":
-        """The dense twin in pinned memory (its masks and max|x| are this slide's: no mask pass)."""
-        if not self.packed:
-            return self
-        s = HostSlide([unpack_grid(r, ix.cpu()) for r, ix in zip(self.rows, self.index)], device=self.device, patch_size=self.patch_size,
-                      slide_id=self.slide_id, subtype=self.subtype, masks=self.masks, absmax=self.feature_absmax())
-        s.masked_view = self.masked_view
-        return _copy_spec(self, s)
-
-    @staticmethod
-    def from_patches(coords: Sequence, features: Sequence, shapes: Sequence, device="cuda", dtype=torch.float32, patch_size: int = 256,
-                     slide_id: str = "", subtype=None, **kw) -> "HostSlide":
-        """:meth:`DeviceSlide.from_patches` with the rows kept in pinned host memory (the same arguments, checks and row order)."""
-        cells = check_patches(coords, features, shapes, dtype)
-        levels = [(_patch_rows(f, dtype).cpu(), _patch_index(c, sh)) for c, f, sh in zip(cells, features, shapes)]
-        return HostSlide._packed_levels(levels, device, patch_size, slide_id, subtype, **kw)
-
-    @staticmethod
-    def from_host(grids: Sequence, device="cuda", dtype=torch.float32, packed: bool = False, **kw) -> "HostSlide":
-        """Host grids (numpy or CPU tensors) as pinned ``dtype`` grids (torch.float16: converted by :func:`to_float16`, which raises on
-        values fp16 cannot hold).  Grids that already are pinned tensors of ``dtype`` are used where they are.  ``packed``: every level
-        is converted, packed and dropped before the next one."""
-        if check_grid_dtype(dtype) == torch.float16:
-            conv = lambda g: g if (torch.is_tensor(g) and g.dtype == torch.float16) else to_float16(g)[0]
-        else:
-            conv = lambda g: torch.as_tensor(g, dtype=torch.float32)
-        if packed:
-            return HostSlide._packed_levels((conv(g) for g in grids), device, **kw)
-        return HostSlide([conv(g) for g in grids], device=device, **kw)
-
-    @staticmethod
-    def from_preprocessed(root: str, slide_id: str, powers: Sequence[float], device="cuda", patch_size: int = 256,
-                          subtype=None, dtype=torch.float32, packed: bool = False, **kw) -> "HostSlide":
-        """The file contract of :meth:`DeviceSlide.from_preprocessed` (``<root>/<slide_id>_<power:.3f>.pt``, one [X, Y, D] float tensor
-        per magnification), kept in pinned host memory.  The dtype and every path are checked before the device is touched."""
-        import os
-        check_grid_dtype(dtype)
-        paths = [os.path.join(root, slide_id + f"_{power:.3f}.pt") for power in powers]
-        for path in paths:
-            if not os.path.isfile(path):
-                raise FileNotFoundError(f"Pre-process load: path '{path}' not found!")
-        grids = []
-        for path in paths:
-            g = torch.load(path, map_location="cpu")
-            assert g.dim() == 3, f"{path}: expected a [X, Y, D] grid, got {tuple(g.shape)}"
-            grids.append(g.float() if dtype == torch.float32 else g)
-        return HostSlide.from_host(grids, device, dtype=dtype, packed=packed, patch_size=patch_size, slide_id=slide_id, subtype=subtype, **kw)
-
-    @staticmethod
-    def synthetic(seed: int, slide: int, base_shape: Tuple[int, int], dim: int = 1024, num_levels: int = 5, p_bg: float = 0.1,
-                  device="cuda", patch_size: int = 256, dtype=torch.float32, packed: bool = False, **kw) -> "HostSlide":
-        """The counter-based synthetic pyramid of :meth:`DeviceSlide.synthetic`, generated on the host (synthetic.SyntheticSlide.grid:
-        the same bytes) straight into pinned memory."""
-        h16 = check_grid_dtype(dtype) == torch.float16
-        spec = synthetic.SyntheticSlide(seed, slide, tuple(base_shape), dim, num_levels, p_bg, feature_dtype="float16" if h16 else "float32")
-
-        def level(l):
-            X, Y = spec.shape(l)
-            g = torch.empty((X, Y, dim), dtype=dtype, pin_memory=not packed)
-            g.copy_(torch.from_numpy(spec.grid(l)))             # (fp16: the values are fp16-representable already, the cast is exact)
-            return g
-
-        if packed:
-            s = HostSlide._packed_levels((level(l) for l in range(num_levels)), device, patch_size, f"synthetic-{seed}-{slide}", **kw)
-        else:
-            s = HostSlide([level(l) for l in range(num_levels)], device=device, patch_size=patch_size, slide_id=f"synthetic-{seed}-{slide}", **kw)
-        s.synthetic_spec = spec
-        return s
+        """The equivalent resident slide (a full upload of every grid; packed: of the kept rows - the twin is packed too) behind this
+        slide's masks and max|x|."""
+        levels = zip(self.rows, self.index) if self.packed else self.grids
+        return DeviceSlide._build(levels, self.device, self.dtype, self.packed, masks=self.masks, absmax=self.feature_absmax(), **self._ident())
 
 
-class DeviceSlideBatch:
+class _SlideBatch:
+    """What :class:`DeviceSlideBatch` and :class:`OnDemandSlideBatch` share: the static per-level tables every recursion reads (``gx`` /
+    ``gy`` / ``max_dim`` / ``n0`` / ``dim`` / ``dtype`` / ``num_levels``), the storage form of the slides, and the two things the launch
+    code asks of it (:meth:`entry`, :meth:`index_args`)."""
+
+    on_demand = False               # the rows of a level are supplied by the caller's encoder during the pass
+    host_resident = False           # grid_ptrs hold pinned host addresses (the recursion stages the selected rows into HBM)
+    packed = False                  # grid_ptrs hold every slide's first packed row, index_ptrs its cell index
+    masked = False                  # some slide is a masked view (level 0 then reads cleared cells as zero rows)
+    index_ptrs = None
+
+    def __len__(self):
+        return len(self.slides)
+
+    def _derive(self, dev, rows_word: str):
+        """``device`` and the tables that follow from the slides' shapes; ValueError when the slides differ in width or dtype."""
+        who, slides = type(self).__name__, self.slides
+        L = min(s.num_levels for s in slides)
+        self.device, self.num_levels = dev, L
+        self.dim = slides[0].dim
+        if any(s.dim != self.dim for s in slides):
+            raise ValueError(f"{who}: slides of one batch share the feature width")
+        self.dtype = slides[0].dtype            # dtype of the whole batch: the recursion picks its kernels by it
+        if any(s.dtype != self.dtype for s in slides):
+            raise ValueError(f"{who}: slides of one batch must share the {rows_word} dtype (got "
+                             + ", ".join(sorted({str(s.dtype) for s in slides})) + ")")
+        extent = lambda k: [torch.tensor([s.shape(l)[k] for s in slides], device=dev, dtype=torch.int32) for l in range(L)]
+        self.gx, self.gy = extent(0), extent(1)
+        self.n0 = max(s.shape(0)[0] * s.shape(0)[1] for s in slides)
+        self.max_dim = [max(max(s.shape(l)) for s in slides) for l in range(L)]   # bound of locs // patch_size per level
+
+    def entry(self, name: str) -> str:
+        """The entry point of an address-forming kernel (``paths_level0_batch``, ``paths_gather_rows``) for this batch's storage."""
+        return entry_name(name, self.dtype == torch.float16, self.packed)
+
+    def index_table(self, level: int) -> Optional[torch.Tensor]:
+        """The cell-index table of ``level`` (a packed batch), else None."""
+        return self.index_ptrs[level] if self.packed else None
+
+    def index_args(self, level: int) -> tuple:
+        """What that entry point takes in front of its stream for ``level``: the cell-index table of a packed batch, else nothing."""
+        return index_args(self.index_table(level))
+
+
+class DeviceSlideBatch(_SlideBatch):
     """Per-batch device tables (grid / mask base pointers and grid dims per level) built ONCE.
 
     ``torch.tensor(list, device=...)`` is a blocking host->device copy that also waits for everything queued on
@@ -643,11 +604,10 @@ class DeviceSlideBatch:
     addresses, which the device can dereference; the recursion stages the selected rows into HBM, paths_stage_rows).
     """
 
-    on_demand = False               # (OnDemandSlideBatch: the rows of a level are supplied by the caller's encoder during the pass)
-
     def __init__(self, slides):
         assert len(slides) > 0
         self.slides = list(slides)
+        # (the kind checks read tolerantly: stand-ins with the few attributes a check needs are enough to be refused)
         if any(getattr(s, "on_demand", False) for s in self.slides):
             raise ValueError("DeviceSlideBatch: on-demand slides (OnDemandSlide) form batches of their own (slide_batch / OnDemandSlideBatch), "
                              "not mixed with resident or host-resident slides")
@@ -658,20 +618,13 @@ class DeviceSlideBatch:
         forms = {bool(getattr(s, "packed", False)) for s in self.slides}
         if len(forms) != 1:
             raise ValueError("DeviceSlideBatch: slides of one batch are all packed or all dense (slide.pack() / slide.to_dense())")
-        self.packed = forms.pop()        # packed: grid_ptrs hold every slide's first packed row, index_ptrs its cell index
-        self.masked = any(getattr(s, "masked_view", False) for s in self.slides)     # (level 0 then reads cleared cells as zero rows)
+        self.packed = forms.pop()
+        self.masked = any(getattr(s, "masked_view", False) for s in self.slides)
         dev = (self.slides[0].masks if (self.host_resident or self.packed) else self.slides[0].grids)[0].device
-        L = min(s.num_levels for s in self.slides)
-        self.device, self.num_levels = dev, L
-        self.dim = self.slides[0].dim
-        assert all(s.dim == self.dim for s in self.slides)
-        self.dtype = self.slides[0].dtype            # grid dtype of the whole batch: the recursion picks its kernels by it
-        if any(s.dtype != self.dtype for s in self.slides):
-            raise ValueError("DeviceSlideBatch: slides of one batch must share the grid dtype (got "
-                             + ", ".join(sorted({str(s.dtype) for s in self.slides})) + ")")
+        self._derive(dev, "grid")
 
-        def table(fn, dtype):
-            return [torch.tensor([fn(s, l) for s in self.slides], device=dev, dtype=dtype) for l in range(L)]
+        def table(fn):
+            return [torch.tensor([fn(s, l) for s in self.slides], device=dev, dtype=torch.int64) for l in range(self.num_levels)]
 
         def grid_ptr(s, l):
             g = s.rows[l] if self.packed else s.grids[l]
@@ -681,50 +634,35 @@ class DeviceSlideBatch:
                 assert (not g.is_cuda) and g.is_pinned() and g.is_contiguous(), "HostSlide grids must be pinned host memory"
             return g.data_ptr()
 
-        self.grid_ptrs = table(grid_ptr, torch.int64)
-        self.mask_ptrs = table(lambda s, l: s.masks[l].data_ptr(), torch.int64)
-        self.index_ptrs = table(lambda s, l: s.index[l].data_ptr(), torch.int64) if self.packed else None
-        self.gx = table(lambda s, l: s.shape(l)[0], torch.int32)
-        self.gy = table(lambda s, l: s.shape(l)[1], torch.int32)
-        self.n0 = max(s.shape(0)[0] * s.shape(0)[1] for s in self.slides)
+        self.grid_ptrs = table(grid_ptr)
+        self.mask_ptrs = table(lambda s, l: s.masks[l].data_ptr())
+        self.index_ptrs = table(lambda s, l: s.index[l].data_ptr()) if self.packed else None
         self.feat_absmax = max(s.feature_absmax() for s in self.slides)
-        self.max_dim = [max(max(s.shape(l)) for s in self.slides) for l in range(L)]   # bound of locs // patch_size per level
+        self._flat_tables = None
 
-    def __len__(self):
-        return len(self.slides)
+    def _tables(self) -> list:
+        """The per-level table lists in the order of the flat layout: grid pointers, mask pointers, gx, gy; packed batches: + index
+        pointers."""
+        return [self.grid_ptrs, self.mask_ptrs, self.gx, self.gy] + ([self.index_ptrs] if self.packed else [])
 
     def flat_tables(self) -> torch.Tensor:
-        """Every per-level table in ONE byte buffer, level by level (grid pointers, mask pointers, gx, gy; packed batches: + index
-        pointers), built once per batch: binding a recorded launch tape to this batch is then a single small device-to-device copy."""
-        flat = getattr(self, "_flat_tables", None)
-        if flat is None:
-            parts = []
-            for l in range(self.num_levels):
-                parts += [self.grid_ptrs[l].view(torch.uint8), self.mask_ptrs[l].view(torch.uint8), self.gx[l].view(torch.uint8), self.gy[l].view(torch.uint8)]
-                if self.packed:
-                    parts.append(self.index_ptrs[l].view(torch.uint8))
-            flat = self._flat_tables = torch.cat(parts)
-        return flat
+        """Every per-level table in ONE byte buffer, level by level in the order of :meth:`_tables`, built once per batch: binding a
+        recorded launch tape to this batch is then a single small device-to-device copy."""
+        if self._flat_tables is None:
+            self._flat_tables = torch.cat([t[l].view(torch.uint8) for l in range(self.num_levels) for t in self._tables()])
+        return self._flat_tables
 
     def clone_tables(self) -> "DeviceSlideBatch":
         """The same batch with PRIVATE copies of the table tensors (a recorded launch tape addresses these, and re-points them at
         other batches: paths_amd.utils.TapedRecursion.rebind); the slides themselves are shared.  The copies are views of one flat
         buffer laid out like :meth:`flat_tables`."""
-        c = object.__new__(DeviceSlideBatch)
-        c.__dict__.update(self.__dict__)
-        flat = self.flat_tables().clone()
-        B = len(self.slides)
-        c._flat_tables = flat
-        c.grid_ptrs, c.mask_ptrs, c.gx, c.gy = [], [], [], []
-        c.index_ptrs = [] if self.packed else None
-        off = 0
-        for l in range(self.num_levels):
-            c.grid_ptrs.append(flat[off:off + 8 * B].view(torch.int64)); off += 8 * B
-            c.mask_ptrs.append(flat[off:off + 8 * B].view(torch.int64)); off += 8 * B
-            c.gx.append(flat[off:off + 4 * B].view(torch.int32)); off += 4 * B
-            c.gy.append(flat[off:off + 4 * B].view(torch.int32)); off += 4 * B
-            if self.packed:
-                c.index_ptrs.append(flat[off:off + 8 * B].view(torch.int64)); off += 8 * B
+        c = copy.copy(self)
+        c._flat_tables = self.flat_tables().clone()
+        order = [t[l] for l in range(self.num_levels) for t in self._tables()]
+        views = [b.view(t.dtype) for b, t in zip(c._flat_tables.split([t.numel() * t.element_size() for t in order]), order)]
+        k = len(order) // self.num_levels
+        c.grid_ptrs, c.mask_ptrs, c.gx, c.gy = (views[j::k] for j in range(4))
+        c.index_ptrs = views[4::k] if self.packed else None
         c.max_dim = list(self.max_dim)
         return c
 
@@ -761,6 +699,7 @@ class OnDemandSlide:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.patch_size, self.slide_id, self.subtype = patch_size, slide_id, subtype
+        self.synthetic_spec = None              # (from_slide: the source's)
         self.requested: List[Optional[torch.Tensor]] = [None] * len(self.shapes)
 
     @property
@@ -803,7 +742,8 @@ class OnDemandSlide:
     @staticmethod
     def from_slide(slide) -> "OnDemandSlide":
         """A :class:`DeviceSlide` or :class:`HostSlide` behind the on-demand interface: ``encode`` indexes its grids (a preprocessed
-        cohort replayed through this path; the twin of the tests and of tools/on_demand_time.py)."""
+        cohort replayed through this path; the twin of the tests and of tools/on_demand_time.py).  Anything with a slide's read surface
+        will do: ``packed`` and ``synthetic_spec`` are read tolerantly."""
         packed = getattr(slide, "packed", False)
         dev = slide.device if slide.host_resident else (slide.index if packed else slide.grids)[0].device
 
@@ -822,19 +762,17 @@ class OnDemandSlide:
 
         s = OnDemandSlide([slide.shape(l) for l in range(slide.num_levels)], encode, slide.dim, dev, patch_size=slide.patch_size,
                           dtype=slide.dtype, slide_id=slide.slide_id, subtype=slide.subtype)
-        if hasattr(slide, "synthetic_spec"):
-            s.synthetic_spec = slide.synthetic_spec
+        s.synthetic_spec = getattr(slide, "synthetic_spec", None)
         return s
 
 
-class OnDemandSlideBatch:
+class OnDemandSlideBatch(_SlideBatch):
     """The batch type of :class:`OnDemandSlide`, beside :class:`DeviceSlideBatch`: the static per-level tables come from the shapes
     (``gx`` / ``gy`` / ``max_dim`` / ``n0`` / ``dim`` / ``dtype``); what a resident batch knows up front and this one cannot - the rows'
     addresses (``grid_ptrs[l]``: per slide, the first of the rows supplied for level ``l``) and max|x| (``feat_absmax``, of the rows
     supplied so far) - is per-pass state, filled by :meth:`supply` as the recursion goes (paths_amd/utils.py)."""
 
     on_demand = True
-    host_resident = False
 
     def __init__(self, slides):
         assert len(slides) > 0
@@ -847,30 +785,12 @@ class OnDemandSlideBatch:
             raise _lib.PathsHipError("paths_amd runs on the GPU only: the slides of a batch live on a GPU device (no CPU fallback)")
         if any(s.device != dev for s in self.slides):
             raise ValueError("OnDemandSlideBatch: slides of one batch live on one device")
-        L = min(s.num_levels for s in self.slides)
-        self.device, self.num_levels = dev, L
-        self.dim = self.slides[0].dim
-        if any(s.dim != self.dim for s in self.slides):
-            raise ValueError("OnDemandSlideBatch: slides of one batch share the feature width")
-        self.dtype = self.slides[0].dtype
-        if any(s.dtype != self.dtype for s in self.slides):
-            raise ValueError("OnDemandSlideBatch: slides of one batch must share the feature dtype (got "
-                             + ", ".join(sorted({str(s.dtype) for s in self.slides})) + ")")
-
-        def table(k):
-            return [torch.tensor([s.shape(l)[k] for s in self.slides], device=dev, dtype=torch.int32) for l in range(L)]
-
-        self.gx, self.gy = table(0), table(1)
-        self.n0 = max(s.shape(0)[0] * s.shape(0)[1] for s in self.slides)
-        self.max_dim = [max(max(s.shape(l)) for s in self.slides) for l in range(L)]
+        self._derive(dev, "feature")
         # level 0 asks for every cell, row-major (reference data_utils/slide.py:257-269): the request tensors are built once
         self.cells0 = [torch.cartesian_prod(torch.arange(s.shape(0)[0], device=dev), torch.arange(s.shape(0)[1], device=dev)).reshape(-1, 2)
                        for s in self.slides]
         self._host = torch.empty((len(self.slides) + 1,), dtype=torch.int64).pin_memory()      # one read-back per level: num_out | max|x| bits
         self.begin_pass()
-
-    def __len__(self):
-        return len(self.slides)
 
     def begin_pass(self):
         for s in self.slides:
@@ -914,10 +834,17 @@ class OnDemandSlideBatch:
         return self._host[:B].tolist() if num_out is not None else []
 
 
+def any_on_demand(slides) -> bool:
+    """Whether ``slides`` (a batch, or a list of slides or stand-ins) hold an on-demand slide."""
+    if isinstance(slides, _SlideBatch):
+        return slides.on_demand
+    return any(getattr(s, "on_demand", False) for s in slides)
+
+
 def slide_batch(slides):
     """The batch of a list of slides: an :class:`OnDemandSlideBatch` for :class:`OnDemandSlide`s, else a :class:`DeviceSlideBatch`
     (which refuses a mix); a batch passes through."""
-    if isinstance(slides, (DeviceSlideBatch, OnDemandSlideBatch)):
+    if isinstance(slides, _SlideBatch):
         return slides
     slides = list(slides)
     if slides and all(getattr(s, "on_demand", False) for s in slides):

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide, slide_batch
+from .data_utils.slide import DeviceSlide, DeviceSlideBatch, HostSlide, any_on_demand, mask_kernel, slide_batch
 
 OVERLAP_AGGREGATOR = os.environ.get("PATHS_OVERLAP_AGGREGATOR", "1") != "0"
 ROCTX_RANGES = os.environ.get("PATHS_ROCTX", "0") != "0"     # roctx ranges "level i: selection / aggregator / expansion" around the launches
@@ -102,7 +102,7 @@ def _checked(rec, out) -> Dict[str, torch.Tensor]:
 def _stored_batch(slides, what: str) -> DeviceSlideBatch:
     """The batch of an entry point that needs every level's rows BEFORE its first launch (recorded or captured launch sequences,
     training): resident or host-resident slides.  On-demand slides raise - their rows come from a host callback between the levels."""
-    if getattr(slides, "on_demand", False) or (not isinstance(slides, DeviceSlideBatch) and any(getattr(s, "on_demand", False) for s in slides)):
+    if any_on_demand(slides):
         raise NotImplementedError(f"{what}: on-demand slides (OnDemandSlide) are served by recurse() / inference_end2end() only - "
                                   "their rows are supplied by a host callback between the levels")
     return slides if isinstance(slides, DeviceSlideBatch) else DeviceSlideBatch(slides)
@@ -246,10 +246,9 @@ class TapedRecursion:
         if new.host_resident != self.batch.host_resident:      # (a host batch's tape stages its rows, a resident batch's does not)
             kind = lambda h: "host-resident" if h else "resident"
             raise ValueError(f"rebind: the tape serves {kind(self.batch.host_resident)} slides, the new batch is {kind(new.host_resident)}")
-        if getattr(new, "packed", False) != getattr(self.batch, "packed", False):     # (other entry points, one more table per level)
+        if new.packed != self.batch.packed:         # (other entry points, one more table per level)
             form = lambda k: "packed" if k else "dense"
-            raise ValueError(f"rebind: the tape serves {form(getattr(self.batch, 'packed', False))} slides, the new batch is "
-                             f"{form(getattr(new, 'packed', False))}")
+            raise ValueError(f"rebind: the tape serves {form(self.batch.packed)} slides, the new batch is {form(new.packed)}")
         fits = (self.tape is not None and rec is not None and len(new) == len(rec) and new.dim == rec.dim and new.device == rec.device
                 and new.num_levels >= self.levels and new.n0 <= rec.n0
                 and all(new.max_dim[l] <= rec.max_dim[l] for l in range(self.levels))
@@ -484,8 +483,7 @@ def _mask_supplied(batch, buf, want_mask: bool, stream: int):
     as DeviceSlide's, so the tissue predicate sums in the same order."""
     B, cap, D = buf.shape
     mask = torch.empty((B, cap), device=batch.device, dtype=torch.uint8) if want_mask else None
-    _lib.call("paths_tissue_mask_absmax_h16" if batch.dtype == torch.float16 else "paths_tissue_mask_absmax", buf.data_ptr(), B * cap, D,
-              _lib.ptr(mask), batch.absmax_bits.data_ptr(), stream)
+    _lib.call(mask_kernel(batch.dtype), buf.data_ptr(), B * cap, D, _lib.ptr(mask), batch.absmax_bits.data_ptr(), stream)
     return mask
 
 
@@ -539,11 +537,6 @@ def _stage_rows(batch, rows, n: int, zero_row, stream: int):
     return buf
 
 
-def _packed_args(batch, level: int) -> tuple:
-    """What a ``_packed`` entry point takes in front of its stream: the level's cell-index table of a packed batch (dense: nothing)."""
-    return (_lib.ptr(batch.index_ptrs[level]),) if getattr(batch, "packed", False) else ()
-
-
 def _rows_in_place(r) -> bool:
     """Whether the current GEMM mode reads feature rows where they live (row-pointer operands) instead of gathered fp32 copies."""
     mc, D, Dp = r.mc, r.D, r.Dp
@@ -560,9 +553,9 @@ def _level0(r) -> SimpleNamespace:
     lv.locs = torch.empty((B, N, 2), **r.i64)
     lv.parent_inds = torch.empty((B, N), **r.i64)
     lv.num_ims = torch.empty((B,), **r.i64)
-    _lib.call("paths_level0_batch" + r.sfx, p(r.batch.grid_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, r.mc.patch_size, N,
-              p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), *_packed_args(r.batch, 0), r.st)
-    if getattr(r.batch, "masked", False):        # views (DeviceSlide.with_masks): a cleared level-0 cell reads as a background cell's zero row
+    _lib.call(r.batch.entry("paths_level0_batch"), p(r.batch.grid_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, r.mc.patch_size, N,
+              p(lv.fts), p(lv.locs), p(lv.parent_inds), p(lv.num_ims), 0, p(lv.x_rows), p(r.zero_row), *r.batch.index_args(0), r.st)
+    if r.batch.masked:        # views (DeviceSlide.with_masks): a cleared level-0 cell reads as a background cell's zero row
         _lib.call("paths_level0_mask_rows", p(r.batch.mask_ptrs[0]), p(r.batch.gx[0]), p(r.batch.gy[0]), B, D, N, p(lv.fts), p(lv.x_rows),
                   p(r.zero_row), r.st)
     if r.stage_host:
@@ -620,7 +613,7 @@ def _child_step(r, i: int, lv, out, keep: int):
         nx.N, nx.num_ims, nx.locs, nx.parent_inds = Nn, num_next, locs_next, parent_next
         if batch.on_demand:          # the rows just supplied may have moved the pass to the three-plane kernels (_note_range)
             rows_in_place = r.rows_in_place = _rows_in_place(r)
-        grid, pk = p(batch.grid_ptrs[i + 1]), _packed_args(batch, i + 1)
+        gather, grid, pk = batch.entry("paths_gather_rows"), p(batch.grid_ptrs[i + 1]), batch.index_args(i + 1)
         if share_parent:
             # children only need their parent's c row (h enters through the per-parent partials)
             Hc = Dp - D
@@ -629,19 +622,19 @@ def _child_step(r, i: int, lv, out, keep: int):
                 # ... and their feature rows are not copied either: the GEMMs of the next level read them in the resident grids
                 nx.x_rows = torch.empty((B, Nn), **r.i64)
                 ops.timed("gather", lambda: _lib.call(
-                    "paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                    gather, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
                     p(src_row), Hc, p(num_next), B, Nn, None, p(c0), 0, p(nx.x_rows), p(r.zero_row), *pk, st2))
                 if r.stage_host:
                     nx.staged = _stage_rows(batch, nx.x_rows, Nn, r.zero_row, st2)
             else:
                 nx.fts = torch.empty((B, Nn, D), **r.f32)
-                _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
+                _lib.call(gather, grid, p(src_cell), D, out["ctx_patch"].data_ptr() + 4 * D, N, Dp,
                           p(src_row), Hc, p(num_next), B, Nn, p(nx.fts), p(c0), 0, None, None, *pk, st2)
             nx.parent = {"hp": hp, "hp_row": hp_row, "c0": c0}
         else:
             nx.fts = torch.empty((B, Nn, D), **r.f32)
             nx.state_prev = torch.empty((B, Nn, Dp), **r.f32)
-            _lib.call("paths_gather_rows" + r.sfx, grid, p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
+            _lib.call(gather, grid, p(src_cell), D, p(out["ctx_patch"]), N, Dp, p(src_row), Dp,
                       p(num_next), B, Nn, p(nx.fts), p(nx.state_prev), 0, None, None, *pk, st2)
         if forked:            # allocated on the expansion stream, read by the next level on the selection stream
             r.keepalive.append((nx, src_row, src_cell))
@@ -680,8 +673,7 @@ def _recurse_body(model, batch, keep_patches: Sequence[int], num_levels: int, tr
     # the host link once and nothing else does; where they are read in place, the address table is staged: the selected rows are
     # pulled into a compact HBM buffer on the stream that wrote the table and the table is pointed at the copies.
     # packed slides: the two address-forming kernels take their _packed forms (+ the cell-index table); nothing else changes
-    r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(),
-                        sfx=("_packed" if getattr(batch, "packed", False) else "") + ("_h16" if h16 else ""), f32=f32,
+    r = SimpleNamespace(mc=mc, batch=batch, B=B, D=D, Dp=Dp, st=_lib.stream(), f32=f32,
                         i32=dict(device=dev, dtype=torch.int32), i64=dict(device=dev, dtype=torch.int64),
                         lstm_pack=lstm_pack, share_parent=share_parent,
                         careful=careful, attention=attention, rollout=rollout, overlap=overlap, main_stream=main_stream,
@@ -795,8 +787,8 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
     parent = torch.empty((B, N), **i64)
     num_ims = torch.empty((B,), **i64)
     h16 = batch.dtype == torch.float16                     # fp16 grids: the gathers write fp32 copies, the training kernels are unchanged
-    _lib.call("paths_level0_batch" + ("_packed" if batch.packed else "") + ("_h16" if h16 else ""), p(batch.grid_ptrs[0]), p(batch.gx[0]),
-              p(batch.gy[0]), B, D, mc.patch_size, N, p(fts), p(locs), p(parent), p(num_ims), 1, None, None, *_packed_args(batch, 0), st)
+    _lib.call(batch.entry("paths_level0_batch"), p(batch.grid_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, mc.patch_size, N, p(fts),
+              p(locs), p(parent), p(num_ims), 1, None, None, *batch.index_args(0), st)
     if batch.masked:
         _lib.call("paths_level0_mask_rows", p(batch.mask_ptrs[0]), p(batch.gx[0]), p(batch.gy[0]), B, D, N, p(fts), None, None, st)
     state_prev, ctx_prev, ctx_hist = None, None, []
@@ -846,12 +838,12 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
             rec["keep_idx"], rec["keep_count"] = keep_idx, keep_count
         if parent_form:
             fts, c0, h_kept = pag.GatherParentFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx, keep_count,
-                                                       child_pos, D, Nn, h16, batch.index_ptrs[i + 1] if batch.packed else None)
+                                                       child_pos, D, Nn, h16, batch.index_table(i + 1))
             par = {"c0": c0, "h_kept": h_kept, "hp_row": hp_row, "child_pos": child_pos, "keep_count": keep_count, "cap": cap_keep}
             state_prev = None
         else:
             fts, state_prev = pag.GatherFn.apply(state_out, batch.grid_ptrs[i + 1], src_cell, src_row, num_next, keep_idx,
-                                                 keep_count, child_pos, D, Nn, h16, batch.index_ptrs[i + 1] if batch.packed else None)
+                                                 keep_count, child_pos, D, Nn, h16, batch.index_table(i + 1))
         locs, parent, num_ims, N = locs_next, parent_next, num_next, Nn
     return {"logits": logits, "status": status}
 

@@ -146,12 +146,8 @@ def test_argument_errors_come_before_the_device():
 
 def _host_side_slide(cls):
     """A slide object with the read surface with_masks needs, built without a device: two levels, 2 x 3 and 4 x 6."""
-    from paths_amd.data_utils import slide as S
-    s = object.__new__(cls)
-    s.grids = [torch.zeros(2, 3, 8), torch.zeros(4, 6, 8)]
-    s.masks = [torch.ones(2, 3, dtype=torch.uint8), torch.ones(4, 6, dtype=torch.uint8)]
-    s.dtype, s.patch_size, s.slide_id, s.subtype, s._absmax, s._absmax_bits = torch.float32, 256, "x", None, 1.5, None
-    return s
+    masks = [torch.ones(2, 3, dtype=torch.uint8), torch.ones(4, 6, dtype=torch.uint8)]
+    return cls._new(torch.float32, torch.device("cpu"), masks, grids=[torch.zeros(2, 3, 8), torch.zeros(4, 6, 8)], absmax=1.5, slide_id="x")
 
 
 @pytest.mark.parametrize("kind", ["DeviceSlide", "HostSlide"])

@@ -372,6 +372,7 @@ def test_scale_add_rows_replica():
 HERE = "tests/test_gpu_select.py"
 ROWS = "tests/test_gpu_row_backward.py"
 OND = "tests/test_gpu_on_demand.py"
+PACKED = "tests/test_gpu_packed_slides.py"
 SELECT_DIRECT_TESTS = {
     "paths_topk": HERE + "::test_topk_equals_the_numpy_contract",
     "paths_topk_rows": HERE + "::test_topk_equals_the_numpy_contract",
@@ -381,6 +382,10 @@ SELECT_DIRECT_TESTS = {
     "paths_gather_rows_h16": HERE + "::test_gather_kernel_equals_the_numpy_contract",
     "paths_level0_batch": HERE + "::test_level0_kernel_equals_the_numpy_contract",
     "paths_level0_batch_h16": HERE + "::test_level0_kernel_equals_the_numpy_contract",
+    "paths_gather_rows_packed": PACKED + "::test_packed_gather_equals_its_dense_twin",
+    "paths_gather_rows_packed_h16": PACKED + "::test_packed_gather_equals_its_dense_twin",
+    "paths_level0_batch_packed": PACKED + "::test_packed_level0_equals_its_dense_twin",
+    "paths_level0_batch_packed_h16": PACKED + "::test_packed_level0_equals_its_dense_twin",
     "paths_tissue_mask": HERE + "::test_tissue_kernels_on_the_special_rows",
     "paths_scale_add_rows": HERE + "::test_scale_add_rows_vs_fp64",
     "paths_tissue_mask_absmax": OND + "::test_row_predicate_over_a_candidate_buffer",
