@@ -33,6 +33,7 @@ struct TLayerParams {
   float *q, *k, *v;
   const int64_t* num_ims;
   int T, H; int do_post, do_qkv, skip_padding; float qscale, eps;
+  int nt;                          // rows [0, nt) of a slide are written (T, or max_tokens when that is smaller)
 };
 
 typedef f32x4 act_t[8];   // 128 features of 16 tokens: tile t, reg r, lane group g -> feature 16t + 4g + r
@@ -181,7 +182,7 @@ tlayer_f32_kernel(TLayerParams p) {
       x[t] = x[t] + (y[t] + b2);
     }
     layernorm_t(x, p.ln3g, p.ln3b, g4, p.eps);
-    if (tok < p.T) {
+    if (tok < p.nt) {
 #pragma unroll
       for (int t = 0; t < 8; ++t) *reinterpret_cast<f32x4*>(p.x_out + rowoff + 16 * t + 4 * g4) = x[t];
     }
@@ -201,7 +202,7 @@ tlayer_f32_kernel(TLayerParams p) {
       mm_chunk<4, 8>(smem + buf * CHUNK_FLOATS, LDA_, acc, x, ql, g4);
       float* dst = qc < 2 ? p.q : qc < 4 ? p.k : p.v;
       const float sc = qc < 2 ? p.qscale : 1.0f;
-      if (tok < p.T) {
+      if (tok < p.nt) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int f = 64 * (qc & 1) + 16 * i + 4 * g4;          // feature within q / k / v
@@ -479,12 +480,13 @@ int paths_token_layer_f32(const float* x_in, const float* attn, float* x_out,
   PATHS_REQUIRE(!skip_padding || num_ims, "token_layer: skip_padding needs num_ims");
   PATHS_REQUIRE(x_in && (!do_post || (attn && x_out && wo && w1 && w2)) && (!do_qkv || (wqkv && q && k && v)), "token_layer: null operand");
   TLayerParams p{x_in, attn, x_out, wo, bo, ln1g, ln1b, cab, ln2g, ln2b, w1, b1, w2, b2, ln3g, ln3b, wqkv, bqkv,
-                 q, k, v, num_ims, T, H, do_post, do_qkv, skip_padding, qscale, eps};
+                 q, k, v, num_ims, T, H, do_post, do_qkv, skip_padding, qscale, eps, 0};
   constexpr size_t lds_min = (2ull * CHUNK_FLOATS + DFF + 3 * DM) * sizeof(float);      // 77,312 B: two workgroups per CU
   constexpr size_t lds_solo = 84 * 1024;                                                 // > 80 KiB: one workgroup per CU
   PATHS_LDS_OPT_IN(tlayer_f32_kernel, lds_solo, "token_layer");
   // max_tokens > 0: only token rows [0, max_tokens) are needed (last layer: only token 0 is read downstream)
   const int nt = max_tokens > 0 && max_tokens < T ? max_tokens : T;
+  p.nt = nt;
   const int nblk = ((nt + 63) / 64) * B;
   // Placement (speed only): with about one workgroup per CU in the grid, two co-resident workgroups would share a CU's
   // matrix pipes while other CUs idle and the kernel lasts as long as the doubled-up CUs (measured 0.51 waves/SIMD

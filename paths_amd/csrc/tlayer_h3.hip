@@ -45,6 +45,7 @@ struct TLayerH3Params {
   int T, H; int do_post, do_qkv, skip_padding; float qscale, eps;
   char* qkv_img = nullptr;         // instead of q, k, v: the two-plane fragment images attn_x6_kernel<2> reads (attn_x6.hip), Q | K | V
   int Tp = 0;                      // T rounded up to 64 (image rows per (slide, head))
+  int nt = 0;                      // rows [0, nt) of a slide are written as fp32 (T, or max_tokens when that is smaller)
 };
 
 typedef f32x4 act_t[8];            // 128 features of 16 tokens: tile t, reg r, lane group g -> feature 16t + 4g + r
@@ -211,7 +212,7 @@ tlayer_h3_kernel(TLayerH3Params p) {
       x[t] = x[t] + (y[t] * p.inv_w2 + b2);
     }
     layernorm_t(x, s_vec + 7 * DM, s_vec + 8 * DM, g4, p.eps);
-    if (tok < p.T) {
+    if (tok < p.nt) {
 #pragma unroll
       for (int t = 0; t < 8; ++t) *reinterpret_cast<f32x4*>(p.x_out + rowoff + 16 * t + 4 * g4) = x[t];
     }
@@ -278,7 +279,7 @@ tlayer_h3_kernel(TLayerH3Params p) {
           *reinterpret_cast<u32x2*>(base + off + FRAG) = u32x2{l0, l1};
         }
         }
-      } else if (tok < p.T) {
+      } else if (tok < p.nt) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int f = 64 * (qc & 1) + 16 * i + 4 * g4;          // feature within q / k / v
@@ -367,6 +368,7 @@ int paths_token_layer_h3(const float* x_in, const float* attn, float* x_out, con
   constexpr size_t lds_solo = 84 * 1024;                                                 // > 80 KiB: one workgroup per CU
   PATHS_LDS_OPT_IN(tlayer_h3_kernel, lds_solo, "token_layer_h3");
   const int nt = max_tokens > 0 && max_tokens < T ? max_tokens : T;
+  p.nt = nt;
   const int nblk = ((nt + TOK_WG - 1) / TOK_WG) * B;
   const size_t lds = nblk <= (NWAVES == 8 ? 256 : 2 * 256) ? lds_solo : lds_min;      // spread small grids one workgroup per CU (see tlayer_f32.hip)
   hipLaunchKernelGGL(tlayer_h3_kernel, dim3((nt + TOK_WG - 1) / TOK_WG, B), dim3(NTHREADS), lds, stream, p);

@@ -14,6 +14,8 @@ Bounds (all computed in float64 from the reference's own intermediate values; U 
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 GEMM_REL = 5e-7
@@ -321,3 +323,149 @@ def linear_ref(a, w, b, act: int):
         out = torch.relu(out)
     S = a.abs() @ w.abs().T
     return out, GEMM_REL * S + U * (prod.abs() + (b.abs() if b is not None else 0.0) + out.abs()), S
+
+
+# ------------------------------------------------------------------------------------------------
+# the aggregator's decoder layers (reference model/aggregator.py:25-33, 70-75 = torch's post-LN TransformerDecoderLayer over an empty
+# memory; model/paths.py:130-139).  A layer is a dict wqkv [3d, d], bqkv, wo, bo, ln1g, ln1b, cab (the cross-attention's out_proj bias:
+# all an empty memory leaves of it), ln2g, ln2b, w1 [4d, d], b1, w2 [d, 4d], b2, ln3g, ln3b, eps - the keys of ops.pack_level's layers.
+# ------------------------------------------------------------------------------------------------
+def _lin(a, e_a, w, b, act: int = 0):
+    """(out, tol, S) of act(a W^T + b) for an input that carries the absolute error e_a per element (0.0: exact):
+    tol = e_a |W|^T + GEMM_REL S + U (|a W^T| + |b| + |out|), S = |a| |W|^T; relu is 1-Lipschitz."""
+    prod = a @ w.T
+    out = prod + b
+    S = a.abs() @ w.abs().T
+    tol = GEMM_REL * S + U * (prod.abs() + b.abs() + out.abs())
+    if torch.is_tensor(e_a):
+        tol = tol + e_a @ w.abs().T
+    return (torch.relu(out) if act else out), tol, S
+
+
+def in_proj_ref(lay: dict, x, H: int, e_x=0.0):
+    """q, k, v [B, H, T, d / H] (q UNscaled) of x [B, T, d], their bounds tol_q / tol_k / tol_v and S_q / S_k / S_v = |x| |W|^T."""
+    B, T, d = x.shape
+    qkv, tol, S = _lin(x, e_x, lay["wqkv"], lay["bqkv"])
+    heads = lambda t: t.view(B, T, H, d // H).transpose(1, 2)
+    res = {}
+    for i, n in enumerate("qkv"):
+        res[n], res["tol_" + n], res["S_" + n] = (heads(t[..., i * d:(i + 1) * d]) for t in (qkv, tol, S))
+    return res
+
+
+def special_index(num_ims, special_last: bool = False):
+    """[B] index of the special token: 0 (the reference's order) or num_ims[b] (the fused finish's: patches first)."""
+    return num_ims.long() if special_last else torch.zeros_like(num_ims.long())
+
+
+def attention_ref(q, k, v, num_ims, special_last: bool = False, query: str = "all", qk_scale=None, bounds: bool = False, errs=None):
+    """softmax(qk_scale q k^T) v per head (qk_scale: 1 / sqrt(hd), or what the caller's pre-scaled q asks for: ln 2 for a q that holds
+    log2(e) / sqrt(hd) times the projection) with keys t < num_ims[b] + 1 valid (the special token and the patches of the slide, in
+    EITHER token order: the special token is row 0, or - special_last - row num_ims[b], right behind the patches; the valid keys are
+    rows [0, num_ims[b]] both times).  q, k, v [B, H, T, hd].  query "all": o [B, T, H hd], every row's attention over the valid
+    keys (rows past the valid ones included: the kernels' contract for them differs and is stated by each test); "special": o [B, H hd],
+    the special token's row only (its index follows special_last).
+    bounds=True: (o, tol) with tol [.., H hd] = (2 delta + (log2(T) + 8) U) max_t |v_t| per (query, head, channel): a score is off by at
+    most delta = qk_scale GEMM_REL max_t(|q| . |k_t|) + ACT (the product, then the exponential), which moves every weight of the convex
+    combination by at most that relative amount in numerator and denominator; its sum passes log2(T) + 8 rounding additions.
+    errs = (e_q, e_k, e_v), the absolute errors q, k, v themselves carry (in_proj_ref's tol_q, tol_k, tol_v): delta grows by
+    qk_scale max_t(e_q . |k_t| + |q| . e_k_t) and tol by max_t e_v_t."""
+    B, H, T, hd = q.shape
+    scale = 1.0 / (hd ** 0.5) if qk_scale is None else qk_scale
+    mask = torch.arange(T, device=q.device)[None, :] > num_ims.to(q.device)[:, None]
+    if query == "special":
+        at = special_index(num_ims, special_last).to(q.device)
+        q = q[torch.arange(B, device=q.device), :, at][:, :, None]                 # [B, H, 1, hd]
+    s = (q @ k.transpose(-1, -2)) * scale
+    s = s.masked_fill(mask[:, None, None, :], float("-inf"))
+    o = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(B, q.shape[2], H * hd)
+    o = o[:, 0] if query == "special" else o
+    if not bounds:
+        return o
+    smax = ((q.abs() @ k.abs().transpose(-1, -2)) * scale).masked_fill(mask[:, None, None, :], 0.0).amax(dim=-1)       # [B, H, Q]
+    vmax = v.abs().masked_fill(mask[:, None, :, None], 0.0).amax(dim=2)                                             # [B, H, hd]
+    rel = 2 * (GEMM_REL * smax + ACT) + (math.log2(T) + 8) * U
+    tol = rel[..., None] * vmax[:, :, None, :]                                                                        # [B, H, Q, hd]
+    if errs is not None:
+        eq, ek, ev = errs
+        if query == "special":
+            eq = eq[torch.arange(B, device=q.device), :, at][:, :, None]
+        ds = ((eq @ k.abs().transpose(-1, -2) + q.abs() @ ek.transpose(-1, -2)) * scale).masked_fill(mask[:, None, None, :], 0.0).amax(dim=-1)
+        tol = tol + 2 * ds[..., None] * vmax[:, :, None, :] + ev.masked_fill(mask[:, None, :, None], 0.0).amax(dim=2)[:, :, None, :]
+    tol = tol.transpose(1, 2).reshape(B, q.shape[2], H * hd)
+    return o, (tol[:, 0] if query == "special" else tol)
+
+
+def decoder_post_ref(lay: dict, x, attn, bounds: bool = False, e_attn=0.0):
+    """x_out = norm3(x' + ffn(x')), x' = norm2(norm1(x + out_proj(attn)) + cab) over the last axis of x / attn [..., d].
+    bounds=True: (x_out, tol), every stage's bound the next one's input error (_lin, _ln; an addition rounds once at its result);
+    e_attn: the absolute error attn itself carries (0.0: an input, exact)."""
+    eps = lay["eps"]
+    y0, t0, _ = _lin(attn, e_attn, lay["wo"], lay["bo"])
+    v1 = x + y0
+    x1, t1 = _ln(v1, t0 + U * v1.abs(), lay["ln1g"], lay["ln1b"], eps)
+    v2 = x1 + lay["cab"]
+    x2, t2 = _ln(v2, t1 + U * v2.abs(), lay["ln2g"], lay["ln2b"], eps)
+    h, th, _ = _lin(x2, t2, lay["w1"], lay["b1"], 1)
+    f, tf, _ = _lin(h, th, lay["w2"], lay["b2"])
+    v3 = x2 + f
+    x3, t3 = _ln(v3, t2 + tf + U * v3.abs(), lay["ln3g"], lay["ln3b"], eps)
+    return (x3, t3) if bounds else x3
+
+
+def decoder_layer_ref(lay: dict, x, num_ims, H: int, attn=None, special_last: bool = False, query: str = "all"):
+    """One decoder layer on x [B, T, d]: in_proj, masked softmax attention (attention_ref), out_proj, norm1, + cab, norm2, FFN, norm3.
+    attn given ([B, T, d]): it stands in for the attention's output (the layer kernels take it as an input).  query "special": the
+    layer at the special token's row only (what the last layer is read at).  Returns q, k, v (+ their tol_ / S_), attn, x_out, tol_x_out
+    (the chain's bound for the attn it was given: exact when attn was passed in)."""
+    B, T, d = x.shape
+    res = in_proj_ref(lay, x, H)
+    if attn is None:
+        attn = attention_ref(res["q"], res["k"], res["v"], num_ims, special_last, query)
+    xin = x
+    if query == "special":
+        xin = x[torch.arange(B, device=x.device), special_index(num_ims, special_last).to(x.device)]
+    res["attn"] = attn
+    res["x_out"], res["tol_x_out"] = decoder_post_ref(lay, xin, attn, bounds=True)
+    return res
+
+
+def token0_tail_ref(lay: dict, lvl: dict, x, num_ims, H: int, ctx_prev=None, ctx_all=None, special_last: bool = False, qkv=None,
+                    qk_scale=None):
+    """The LAST layer at one query per slide (the special token's), decoder.norm (lvl lnfg, lnfb, lnf_eps), the slide context (ctx_prev
+    [B, d] added, or ctx_all [B, depth, d] concatenated in front) and the classifier (lvl wcls, bcls): reference model/aggregator.py:70-75,
+    model/paths.py:130-139.  qkv = (q, k, v) [B, H, T, hd] stands in for the layer's in_proj (paths_token0_tail takes them as inputs;
+    qk_scale as in attention_ref for a pre-scaled q).  Returns ctx_out [B, d], logits, tol_ctx, tol_logits (final_head_ref's bounds on top of the chain's)."""
+    B, T, d = x.shape
+    at = special_index(num_ims, special_last).to(x.device)
+    if qkv is None:
+        r = in_proj_ref(lay, x, H)
+        qkv = (r["q"], r["k"], r["v"])
+    a, ta = attention_ref(*qkv, num_ims, special_last, "special", qk_scale, bounds=True)
+    x3, t3 = decoder_post_ref(lay, x[torch.arange(B, device=x.device), at], a, bounds=True, e_attn=ta)
+    f, tf = _ln(x3, t3, lvl["lnfg"], lvl["lnfb"], lvl["lnf_eps"], (d + 63) // 64 + 6)
+    if ctx_prev is not None:
+        f = f + ctx_prev
+        tf = tf + U * f.abs()
+    inp = f if ctx_all is None else torch.cat([ctx_all.reshape(B, -1), f], dim=1)
+    logits = inp @ lvl["wcls"].T + lvl["bcls"]
+    steps = (inp.shape[1] + 63) // 64 + 8
+    tl = tf @ lvl["wcls"][:, -d:].abs().T + steps * U / 2 * (inp.abs() @ lvl["wcls"].abs().T) + U * logits.abs()
+    return f, logits, tf, tl
+
+
+def fused_token_order(tokens, num_ims):
+    """imp_proj_ref's tokens [B, N + 1, d] (special first, patch i at row i + 1) in the fused finish's order: patch i at row i and
+    `special` at row num_ims[b]; a row j behind it is padding and holds the token of the (padded) patch min(j, N - 1), the slot's own
+    patch row as the fused finish reads it.  Returns (tokens in that order, perm [B, N + 1] with out[b, j] = tokens[b, perm[b, j]])."""
+    B, T = tokens.shape[:2]
+    j = torch.arange(T, device=tokens.device)[None, :].expand(B, T)
+    n = num_ims.to(tokens.device).long()[:, None]
+    perm = torch.where(j < n, j + 1, torch.where(j == n, torch.zeros_like(j), (j + 1).clamp(max=T - 1)))
+    return torch.gather(tokens, 1, perm[:, :, None].expand_as(tokens)), perm
+
+
+# normalisation stages on each output's path (the second condition's n): the chain's three LayerNorms, decoder.norm on top for the tail
+LAYER_ACTIVATIONS = {"x_out": 3, "q": 3, "k": 3, "v": 3, "q_only": 0, "k_only": 0, "v_only": 0}
+TAIL_ACTIVATIONS = {"ctx_out": 4, "logits": 4}
+ATTN_ACTIVATIONS = {"o": 1}          # the softmax's exponential

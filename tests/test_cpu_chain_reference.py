@@ -198,3 +198,112 @@ def test_imp_proj_ref_equals_process_level_in_fp32():
                          cfg.patch_size, 2, 1)
     assert float((got["importance"].view(3, 8) - out["importance"].double()).abs().max()) < 1e-6
     assert float((got["tokens"][:, 1:] - probe["xs"].double()).abs().max()) < 1e-5
+
+
+# ------------------------------------------------------------------------------------------------
+# the decoder-layer references
+# ------------------------------------------------------------------------------------------------
+def _decoder_problem(d, H, lens, T, depth, seed):
+    """Two random layers + head in float64, as chain_ref's layer dicts AND as the oracle's state-dict keys; tokens [B, T, d]."""
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.rand(s, generator=g, dtype=F64) * 2 - 1
+    layers, p = [], {}
+    pre = "agg.transformer"
+    for l in range(2):
+        lay = {"wqkv": rnd(3 * d, d) * 0.3, "bqkv": rnd(3 * d) * 0.1, "wo": rnd(d, d) * 0.1, "bo": rnd(d) * 0.1, "cab": rnd(d) * 0.1,
+               "w1": rnd(4 * d, d) * 0.1, "b1": rnd(4 * d) * 0.1, "w2": rnd(d, 4 * d) * 0.05, "b2": rnd(d) * 0.1, "eps": 1e-5}
+        for n in ("ln1", "ln2", "ln3"):
+            lay[n + "g"], lay[n + "b"] = 1 + rnd(d) * 0.1, rnd(d) * 0.1
+        layers.append(lay)
+        q = f"{pre}.decoder.layers.{l}."
+        p.update({q + "self_attn.in_proj_weight": lay["wqkv"], q + "self_attn.in_proj_bias": lay["bqkv"], q + "self_attn.out_proj.weight": lay["wo"],
+                  q + "self_attn.out_proj.bias": lay["bo"], q + "multihead_attn.out_proj.bias": lay["cab"], q + "linear1.weight": lay["w1"],
+                  q + "linear1.bias": lay["b1"], q + "linear2.weight": lay["w2"], q + "linear2.bias": lay["b2"]})
+        for i, n in enumerate(("ln1", "ln2", "ln3")):
+            p[q + f"norm{i + 1}.weight"], p[q + f"norm{i + 1}.bias"] = lay[n + "g"], lay[n + "b"]
+    lvl = {"lnfg": 1 + rnd(d) * 0.1, "lnfb": rnd(d) * 0.1, "lnf_eps": 1e-5, "wcls": rnd(4, (depth + 1) * d) * 0.1, "bcls": rnd(4) * 0.1}
+    p[pre + ".decoder.norm.weight"], p[pre + ".decoder.norm.bias"] = lvl["lnfg"], lvl["lnfb"]
+    B = len(lens)
+    num_ims = torch.tensor([n - 1 for n in lens])
+    return layers, lvl, p, pre, rnd(B, T, d), num_ims, rnd(B, d), (rnd(B, depth, d) if depth else None)
+
+
+DECODER_LENS = (9, [1, 9, 4, 7])            # T = N + 1 = 9: a slide with 0 patches, a full one, two ragged ones
+
+
+@pytest.mark.parametrize("d,H", [(128, 4), (192, 4), (64, 2)])
+def test_decoder_layer_ref_equals_the_oracle_in_float64(d, H):
+    """in_proj + attention + out_proj against the oracle's _self_attention, a whole layer against its one-layer decoder_stack (whose
+    decoder.norm is applied on top of decoder_layer_ref's rows here), every row of every slide: the oracle computes padded query
+    rows over the valid keys like any other, and so does the reference."""
+    T, lens = DECODER_LENS
+    layers, lvl, p, pre, x, num_ims, _, _ = _decoder_problem(d, H, lens, T, 0, d + H)
+    lay = layers[0]
+    key_pad = torch.arange(T)[None, :] >= (num_ims + 1)[:, None]
+    got = R.decoder_layer_ref(lay, x, num_ims, H)
+    sa = orc._self_attention(x, lay["wqkv"], lay["bqkv"], lay["wo"], lay["bo"], H, key_pad)
+    torch.testing.assert_close(got["attn"] @ lay["wo"].T + lay["bo"], sa, rtol=0, atol=1e-13)
+    want = orc.decoder_stack(p, pre, x, key_pad, H, 1)
+    torch.testing.assert_close(F.layer_norm(got["x_out"], (d,), lvl["lnfg"], lvl["lnfb"], 1e-5), want, rtol=0, atol=1e-13)
+    # attn given: the chain alone on that input; the special-token query alone: row 0 of the full evaluation
+    again = R.decoder_layer_ref(lay, x, num_ims, H, attn=got["attn"])
+    assert torch.equal(again["x_out"], got["x_out"])
+    one = R.decoder_layer_ref(lay, x, num_ims, H, query="special")
+    torch.testing.assert_close(one["x_out"], got["x_out"][:, 0], rtol=0, atol=1e-13)
+    for k in ("q", "k", "v"):
+        assert got[k].shape == (len(lens), H, T, d // H) and got["tol_" + k].shape == got[k].shape and float(got["tol_" + k].max()) < 1e-4
+    # (the chain's bound sums worst cases through three LayerNorms and two products: loose, a few 1e-2 here; the tests' second
+    # condition is the one that binds for x_out)
+    assert got["tol_x_out"].shape == got["x_out"].shape and bool((got["tol_x_out"] > 0).all()) and float(got["tol_x_out"].max()) < 0.1
+
+
+@pytest.mark.parametrize("ctx_mode", ["residual", "concat", "none"])
+def test_token0_tail_ref_equals_the_oracle_in_float64(ctx_mode):
+    """Two layers: decoder_layer_ref, then token0_tail_ref, against the oracle's two-layer decoder_stack at token 0 and the head of
+    oracle.process_level (model/paths.py:130-139: residual adds ctx_slide[:, -1], concat puts the flattened ctx_slide in front).
+    (The bounds only have to exist here: summed worst cases through four LayerNorms and two products, they are far above any
+    error a kernel shows; the kernel tests' second condition is the one that binds behind the feed-forward.)"""
+    d, H = 128, 4
+    T, lens = DECODER_LENS
+    depth = 2 if ctx_mode == "concat" else 0
+    layers, lvl, p, pre, x, num_ims, ctx_prev, ctx_all = _decoder_problem(d, H, lens, T, depth, 17)
+    key_pad = torch.arange(T)[None, :] >= (num_ims + 1)[:, None]
+    agg = orc.decoder_stack(p, pre, x, key_pad, H, 2)[:, 0]
+    if ctx_mode == "residual":
+        agg = agg + ctx_prev
+    ft = torch.cat((torch.flatten(ctx_all, start_dim=1), agg), dim=1) if ctx_mode == "concat" else agg
+    logits = F.linear(ft, lvl["wcls"], lvl["bcls"])
+    x1 = R.decoder_layer_ref(layers[0], x, num_ims, H)["x_out"]
+    ctx, lg, tc, tl = R.token0_tail_ref(layers[1], lvl, x1, num_ims, H, ctx_prev if ctx_mode == "residual" else None, ctx_all)
+    torch.testing.assert_close(ctx, agg, rtol=0, atol=1e-13)
+    torch.testing.assert_close(lg, logits, rtol=0, atol=1e-13)
+    assert tc.shape == ctx.shape and tl.shape == lg.shape and bool((tc > 0).all()) and bool(torch.isfinite(tc).all()) and bool(torch.isfinite(tl).all())
+    # q, k, v handed in (paths_token0_tail's form) change nothing
+    r = R.in_proj_ref(layers[1], x1, H)
+    again = R.token0_tail_ref(layers[1], lvl, x1, num_ims, H, ctx_prev if ctx_mode == "residual" else None, ctx_all, qkv=(r["q"], r["k"], r["v"]))
+    assert torch.equal(again[0], ctx) and torch.equal(again[1], lg)
+
+
+def test_special_last_order_leaves_the_special_token_unchanged():
+    """fused_token_order: patch i at row i, the special token at row num_ims[b].  Masked self-attention is invariant under that
+    permutation of the valid rows, so two layers read at the special token give the same ctx_out and logits in either order."""
+    d, H = 128, 4
+    T, lens = DECODER_LENS
+    layers, lvl, p, pre, x, num_ims, ctx_prev, _ = _decoder_problem(d, H, lens, T, 0, 23)
+    xs, perm = R.fused_token_order(x, num_ims)
+    for b, n in enumerate(num_ims.tolist()):
+        assert torch.equal(xs[b, n], x[b, 0]) and torch.equal(xs[b, :n], x[b, 1:n + 1])
+        assert perm[b, :n].tolist() == list(range(1, n + 1)) and int(perm[b, n]) == 0
+        assert perm[b, n + 1:].tolist() == [min(j + 1, T - 1) for j in range(n + 1, T)]
+    assert R.special_index(num_ims, True).tolist() == num_ims.tolist() and R.special_index(num_ims).tolist() == [0] * len(lens)
+    first = R.decoder_layer_ref(layers[0], x, num_ims, H)
+    last = R.decoder_layer_ref(layers[0], xs, num_ims, H, special_last=True)
+    for b, n in enumerate(num_ims.tolist()):                     # the valid rows of the layer's output are the permuted rows
+        torch.testing.assert_close(last["x_out"][b, :n + 1], first["x_out"][b][perm[b, :n + 1]], rtol=0, atol=1e-13)
+    a = R.token0_tail_ref(layers[1], lvl, first["x_out"], num_ims, H, ctx_prev)
+    b_ = R.token0_tail_ref(layers[1], lvl, last["x_out"], num_ims, H, ctx_prev, special_last=True)
+    torch.testing.assert_close(b_[0], a[0], rtol=0, atol=1e-13)
+    torch.testing.assert_close(b_[1], a[1], rtol=0, atol=1e-13)
+    o_first = R.attention_ref(first["q"], first["k"], first["v"], num_ims, False, "special")
+    o_last = R.attention_ref(last["q"], last["k"], last["v"], num_ims, True, "special")
+    torch.testing.assert_close(o_last, o_first, rtol=0, atol=1e-13)

@@ -1,5 +1,7 @@
-"""The forward pass's two hottest kernel families, one entry point at a time, against the float64 references of tests/chain_ref.py:
-paths_lstm_cell_x6 / _h16 / paths_lstm_cell and paths_importance_proj_x6 / _h16 / paths_importance_proj.
+"""The forward pass's hottest kernel families, one entry point at a time, against the float64 references of tests/chain_ref.py:
+paths_lstm_cell_x6 / _h16 / paths_lstm_cell, paths_importance_proj_x6 / _h16 / paths_importance_proj, the fused finish
+paths_importance_qkv_x6 / _h16, paths_gemm_add_nt_x6 / _h16 and the generic forward row kernels; and the gate that keeps every
+forward entry point behind a direct test.
 
 Every output buffer is pre-filled with a NaN sentinel bit pattern, the entry point is called through _lib.call on inputs of this
 file's own, and everything is compared: valid rows against float64 under two conditions (the per-element forward-error bound of
@@ -988,14 +990,455 @@ def test_linear_f32_matches_float64(dev, M, N, K, act):
 
 
 # ================================================================================================
+# paths_importance_qkv_x6 / paths_importance_qkv_x6_h16: the split-K GEMM + the fused finish (csrc/finish_qkv.h)
+# ================================================================================================
+# (B, N, num_ims): 3x64: M = 192 has a tail block, a full slide (special token in the extra tile), an empty one (special token in slot 0);
+# 2x128: the special token as the first slot of the second tile / the last slot before the extra tile; 8x128: the smallest xcd_order shape
+FQ_LAYOUTS = {"3x64": (3, 64, (64, 0, 1)), "2x128": (2, 128, (64, 127)), "5x64": (5, 64, (63, 64, 33, 0, 64)),
+              "8x128": (8, 128, (128, 0, 65, 1, 128, 64, 127, 100))}
+# form -> (entry point, A operand, the reference's input, the paths_importance_proj_x6 form that must give the same importance bits)
+FQ_FORMS = {"matrix": ("paths_importance_qkv_x6", "matrix", "sum", "sk-add"), "rows": ("paths_importance_qkv_x6", "rows", "sum", "sk-rows-add"),
+            "h16": ("paths_importance_qkv_x6_h16", "rows16", "sum16", "h16"),
+            "rows-of-fp16-values": ("paths_importance_qkv_x6", "rows-of-fp16-values", "sum16", "sk-rows-add16")}
+FQ_MAIN_FORMS = ("matrix", "rows", "h16")
+FQ_QSCALE = math.log2(math.e) / math.sqrt(32)
+FQ_ACTIVATIONS = {"o": 2}            # the importance's sigmoid (through alpha) and the softmax's exponential
+
+
+@functools.lru_cache(maxsize=None)
+def _fq_layers():
+    """Decoder layers of the fused finish's consumers: layer 0's in_proj at 4 / sqrt(128) (attention logits spread over a few units: a
+    wrong q or k row moves the softmax visibly), the rest as in test_token_layer_ws_and_tail_ws_vs_fp64; + decoder.norm and classifier."""
+    g = torch.Generator().manual_seed(515)
+    rnd = lambda *s: (torch.rand(s, generator=g) * 2 - 1).to(DEV)
+    d = DT
+    layers = []
+    for l in range(2):
+        lay = {"wqkv": rnd(3 * d, d) * (4 / math.sqrt(d) if l == 0 else 0.15), "bqkv": rnd(3 * d) * 0.1, "wo": rnd(d, d) * 0.1, "bo": rnd(d) * 0.1,
+               "cab": rnd(d) * 0.1, "w1": rnd(4 * d, d) * 0.1, "b1": rnd(4 * d) * 0.1, "w2": rnd(d, 4 * d) * 0.05, "b2": rnd(d) * 0.1, "eps": 1e-5}
+        for n in ("ln1", "ln2", "ln3"):
+            lay[n + "g"], lay[n + "b"] = 1 + rnd(d) * 0.1, rnd(d) * 0.1
+        layers.append({k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in lay.items()})
+    return {"layers": layers, "lnfg": 1 + rnd(d) * 0.1, "lnfb": rnd(d) * 0.1, "lnf_eps": 1e-5, "wcls": (rnd(4, d) * 0.1).contiguous(), "bcls": rnd(4) * 0.1}
+
+
+def _cast_layer(lay, dtype):
+    return {k: (v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in lay.items() if "image" not in k}
+
+
+@functools.lru_cache(maxsize=None)
+def _fq_problem(layout, pe_mode):
+    """_imp_problem's weights and rows at D = 256 with the layout's own num_ims."""
+    B, N, counts = FQ_LAYOUTS[layout]
+    pr = dict(_imp_problem(256, B, N, pe_mode, 224 if pe_mode == 2 else 3))
+    pr.update(num_ims=torch.tensor(counts, dtype=torch.int64, device=DEV), refs={}, o_refs={})
+    return pr
+
+
+def _fq_refs(pr, kind, imp_mul):
+    """float64 (with bounds) and fp32 references in the FUSED token order: importance, tokens, and o = attention(in_proj(tokens))."""
+    key = (kind, imp_mul)
+    if key not in pr["o_refs"]:
+        out = []
+        lay = _fq_layers()["layers"][0]
+        for r, dt in zip(_imp_refs(pr, kind, imp_mul, True), (F64, F32)):
+            tok, _ = R.fused_token_order(r["tokens"], pr["num_ims"])
+            q = R.in_proj_ref(_cast_layer(lay, dt), tok, 4)
+            res = {"importance": r["importance"], "tokens": tok, "o": R.attention_ref(q["q"], q["k"], q["v"], pr["num_ims"])}
+            if "tol_tokens" in r:
+                res["tol_importance"], res["tol_tokens"] = r["tol_importance"], R.fused_token_order(r["tol_tokens"], pr["num_ims"])[0]
+            out.append(res)
+        pr["o_refs"][key] = tuple(out)
+    return pr["o_refs"][key]
+
+
+def _fq_buffers(pr):
+    from paths_amd import _lib
+    M, B, N = pr["M"], pr["B"], pr["N"]
+    lib = _lib.load()
+    n_ws, n_img = int(lib.paths_importance_proj_x6_workspace(M)) // 4, int(lib.paths_attention_x6_workspace(B, N + 1, 4, 32, 2)) // 4
+    return {"importance": _ffill(M + TAIL), "tokens": _ffill(B * (N + 1) * DT + TAIL), "splitk_ws": _ffill(n_ws + TAIL), "qkv_images": _ffill(n_img + TAIL)}
+
+
+def _fq_args(pr, bufs, form, imp_mul, skip, y=None, locs=None):
+    """Named arguments of paths_importance_qkv_x6 / _h16 (phases and alpha_from_importance are given per call)."""
+    from paths_amd import _lib, ops
+    entry, a_form, _, _ = FQ_FORMS[form]
+    M, D, B, N = pr["M"], pr["D"], pr["B"], pr["N"]
+    p, lay = pr["p"], _fq_layers()["layers"][0]
+    img, w_s = _imp_image(D, B, N, pr["pe_mode"], pr["patch_size"], pr["big_locs"], 2)
+    iq, sq = ops.tlayer_ws_images(lay, 1)
+    tab = _pe_table(pr["pe_mode"], 64 if pr["pe_mode"] == 2 else N)              # sized from the positions: cells < 64, or the slide's N rows
+    y = pr["y"] if y is None else y
+    locs = pr["locs"] if locs is None else locs
+    ab = _ffill(M, D + 4)
+    ab[:, :D] = pr["y_add"]
+    a = dict(y=None, ldy=D, y_rows=None, y_add=ab.data_ptr(), ldya=D + 4, w=img.data_ptr(), b1=p["b1"].data_ptr(), w2=p["w2"].data_ptr(),
+             b2=p["b2"].data_ptr(), bp=p["bp"].data_ptr(), special=p["special"].data_ptr(), pe_table=tab.data_ptr(), pe_rows=tab.shape[0],
+             locs=locs.data_ptr(), num_ims=pr["num_ims"].data_ptr(), B=B, N=N, patch_size=pr["patch_size"], pe_mode=pr["pe_mode"], imp_mul=imp_mul,
+             importance=bufs["importance"].data_ptr(), tokens=bufs["tokens"].data_ptr(), D=D, skip=skip, w_s=w_s, a_s=A_SCALE,
+             splitk_ws=bufs["splitk_ws"].data_ptr(), w_qkv=iq.data_ptr(), bqkv=lay["bqkv"].data_ptr(), s_wqkv=sq[0], qscale=FQ_QSCALE,
+             qkv_images=bufs["qkv_images"].data_ptr(), stream=_lib.stream(), keep=[ab, locs, y])
+    if a_form == "matrix":
+        yb = _ffill(M, D + 8)
+        yb[:, :D] = y
+        a.update(y=yb.data_ptr(), ldy=D + 8)
+        a["keep"].append(yb)
+    else:
+        g = torch.Generator().manual_seed(M + 1)
+        at = torch.randperm(M + 5, generator=g)[:M].to(DEV)
+        big = torch.full((M + 5, D), float("nan"), device=DEV, dtype=torch.float16 if a_form == "rows16" else F32)
+        big[at] = (y if a_form == "rows" else y.half()).to(big.dtype)
+        rows = (big.data_ptr() + at.to(torch.int64) * (D * big.element_size())).contiguous()
+        a.update(y_rows=rows.data_ptr())
+        a["keep"] += [big, rows]
+    return entry, a
+
+
+def _fq_call(entry, a, phases, afi):
+    from paths_amd import _lib
+    _lib.call(entry, a["y"], a["ldy"], a["y_rows"], a["y_add"], a["ldya"], a["w"], a["b1"], a["w2"], a["b2"], a["bp"], a["special"], a["pe_table"],
+              a["pe_rows"], a["locs"], a["num_ims"], a["B"], a["N"], a["patch_size"], a["pe_mode"], a["imp_mul"], a["importance"], a["tokens"], a["D"],
+              a["skip"], a["w_s"], a["a_s"], a["splitk_ws"], a["w_qkv"], a["bqkv"], a["s_wqkv"], a["qscale"], a["qkv_images"], phases, afi, a["stream"])
+
+
+def _fq_run(pr, form, imp_mul, skip, calls=((5, 0),), **over):
+    """One or more calls on freshly filled buffers; adds "o": paths_attention_x6 on the q | k | v images the finish wrote (planes 2,
+    images_ready 1, all queries: it reads exactly these images and is itself compared with float64 in test_attention_x6_matches_fp64)."""
+    from paths_amd import _lib
+    bufs = _fq_buffers(pr)
+    entry, a = _fq_args(pr, bufs, form, imp_mul, skip, **over)
+    for phases, afi in calls:
+        _fq_call(entry, a, phases, afi)
+    B, T = pr["B"], pr["N"] + 1
+    bufs["o"] = _ffill(B * T * DT + TAIL)
+    _lib.call("paths_attention_x6", None, None, None, bufs["o"].data_ptr(), None, pr["num_ims"].data_ptr(), B, T, 4, 32, 0, bufs["qkv_images"].data_ptr(),
+              2, 1, _lib.stream())
+    torch.cuda.synchronize()
+    return bufs
+
+
+def _fq_views(pr, bufs):
+    M, B, T = pr["M"], pr["B"], pr["N"] + 1
+    return {"importance": bufs["importance"][:M], "tokens": bufs["tokens"][:B * T * DT].view(B, T, DT), "o": bufs["o"][:B * T * DT].view(B, T, DT)}
+
+
+def _fq_masks(pr):
+    """(valid patch rows [M], token slots that hold a patch or the special token [B, N + 1], the special token's slot [B, N + 1])."""
+    M, B, N = pr["M"], pr["B"], pr["N"]
+    n = pr["num_ims"][:, None]
+    j = torch.arange(N + 1, device=DEV)[None, :]
+    return (torch.arange(M, device=DEV) % N) < pr["num_ims"].repeat_interleave(N), j <= n, (j == n).expand(B, N + 1)
+
+
+def _fq_guards(pr, bufs, label):
+    from paths_amd import _lib
+    M, B, T = pr["M"], pr["B"], pr["N"] + 1
+    lib = _lib.load()
+    n_ws, n_img = int(lib.paths_importance_proj_x6_workspace(M)) // 4, int(lib.paths_attention_x6_workspace(B, T, 4, 32, 2)) // 4
+    assert _untouched(bufs["importance"][M:]) and _untouched(bufs["tokens"][B * T * DT:]), f"{label}: written beyond importance [M] / tokens [B, N + 1, 128]"
+    assert _untouched(bufs["splitk_ws"][n_ws:]) and _untouched(bufs["qkv_images"][n_img:]), f"{label}: written beyond the workspace / the images"
+    assert _untouched(bufs["o"][B * T * DT:])
+
+
+def _fq_same_valid(pr, a, b, label):
+    """Two runs agree bit for bit on every valid row: importance of valid patches, the token slots up to the special token, o of those."""
+    valid, tokvalid, _ = _fq_masks(pr)
+    va, vb = _fq_views(pr, a), _fq_views(pr, b)
+    assert torch.equal(_bits(va["importance"])[valid], _bits(vb["importance"])[valid]), f"{label}: importance of a valid row differs"
+    for name in ("tokens", "o"):
+        assert torch.equal(_bits(va[name])[tokvalid], _bits(vb[name])[tokvalid]), f"{label}: {name} of a valid slot differs"
+
+
+@pytest.mark.parametrize("form", FQ_MAIN_FORMS)
+@pytest.mark.parametrize("layout", sorted(FQ_LAYOUTS))
+def test_importance_qkv_matches_float64(dev, layout, form):
+    """paths_importance_qkv_x6 / _h16 on inputs of its own (D 256, trans_dim 128, 4 heads, Hi 128; pe_mode and imp_mul alternate over
+    the (layout, form) grid so that every form meets every pair; skip_padding 0 and 1 in every case; splitk_ws starts as NaN, so a
+    finish that multiplied a skipped tile's slab by zero would show):
+      * importance against imp_proj_ref(splitk) under both conditions; padded rows bitwise +0.0 (skip_padding 0) or that / the sentinel (1);
+        bit-identical to paths_importance_proj_x6's split-K form on the same problem;
+      * tokens [B, N + 1, 128] in the fused order (patch i at slot i, `special` at slot num_ims[b]) against the permuted reference under
+        both conditions, the special slot a bitwise copy, the slots behind it finite (skip_padding 0), nothing behind the tensor;
+      * the q | k | v images through paths_attention_x6(images_ready): every valid row of o against float64 tokens -> in_proj -> attention
+        under 4 err32 + 2 ACT (err32: the same chain in torch fp32 on the device);
+      * phases 5 = 3 then 4 with alpha_from_importance = 1 = 1, 2, 4 in three calls, in every byte of every buffer (skip_padding 1:
+        in every byte but the importance of padded rows, which is +0.0 or untouched: the two finishes skip different tiles);
+      * _h16 bit-identical to the fp32 row form on rows holding the same fp16 values;
+      * matrix form: +-3e4 in the padded rows of y (their products overflow the fp16 planes) leaves every valid row bit-identical;
+      * row form, pe_mode 2: padded rows' positions beyond the table (up to 2^24 - 1 px) are clamped: valid rows bit-identical, padded
+        slots finite;
+      * 8x128 meets the three conditions of the finish's XCD-ordered workgroup mapping.
+    Measured maxima on an MI355X (max |err|, fraction of the per-element bound, fraction of 4 err32 + n ACT): importance 8.0e-8 .013
+    .15, tokens 6.4e-7 .15 .11, o 1.2e-5 - .27 (the same for the matrix, row and fp16-row forms to within a tenth)."""
+    B, N, counts = FQ_LAYOUTS[layout]
+    idx = 3 * sorted(FQ_LAYOUTS).index(layout) + FQ_MAIN_FORMS.index(form)
+    pe_mode, imp_mul = 2 - idx % 2, (idx // 2) % 2
+    pr = _fq_problem(layout, pe_mode)
+    M, T = pr["M"], N + 1
+    if layout == "8x128":
+        assert B % 8 == 0 and M % 128 == 0 and (M // 128) % 8 == 0, "the smallest shape with xcd_order = 1 (csrc/gemm_x6.hip importance_qkv_x6)"
+    else:
+        assert not (B % 8 == 0 and M % 128 == 0 and (M // 128) % 8 == 0)
+    label = f"qkv {form} {layout} pe {pe_mode} imp_mul {imp_mul}"
+    kind, twin = FQ_FORMS[form][2], FQ_FORMS[form][3]
+    r64, r32 = _fq_refs(pr, kind, imp_mul)
+    valid, tokvalid, special = _fq_masks(pr)
+    full = _fq_run(pr, form, imp_mul, 0)
+    v = _fq_views(pr, full)
+    _report(label, "importance", v["importance"], r64["importance"], r64["tol_importance"], r32["importance"], R.IMP_ACTIVATIONS["importance"])
+    assert bool((_bits(v["importance"])[~valid] == 0).all()), f"{label}: importance of a padded row is not +0.0"
+    same_problem = _imp_run(pr, twin, True, imp_mul, 0, False)
+    assert torch.equal(_bits(same_problem["importance"][:M]), _bits(v["importance"])), f"{label}: importance differs from paths_importance_proj_x6 ({twin})"
+    _report(label, "tokens", v["tokens"][tokvalid], r64["tokens"][tokvalid], r64["tol_tokens"][tokvalid], r32["tokens"][tokvalid], R.IMP_ACTIVATIONS["tokens"])
+    assert torch.equal(_bits(v["tokens"])[special], _bits(pr["p"]["special"].expand(B, DT))), f"{label}: the special token's slot is no copy"
+    assert bool(torch.isfinite(v["tokens"]).all()), f"{label}: a slot behind the special token is not finite"
+    assert bool(torch.isfinite(v["o"][tokvalid]).all()), f"{label}: o"
+    err = (v["o"].double() - r64["o"]).abs()[tokvalid]
+    e, e32 = float(err.max()), float((r32["o"].double() - r64["o"]).abs()[tokvalid].max())
+    bound2 = 4 * e32 + FQ_ACTIVATIONS["o"] * R.ACT
+    print(f"[chain] {label} o: max err {e:.3e} = {e / bound2:.3f} of 4 * err32 ({e32:.3e}) + 2 ACT")
+    assert e <= bound2, f"{label} o: err {e:.3e} > 4 * {e32:.3e} + 2 ACT"
+    _fq_guards(pr, full, label)
+    # skip_padding 1: whole 128-row GEMM tiles and 64-token finish tiles of padding are skipped
+    skipped = _fq_run(pr, form, imp_mul, 1)
+    _fq_same_valid(pr, full, skipped, label + " skip_padding")
+    b1, b0 = _bits(_fq_views(pr, skipped)["importance"]), _bits(v["importance"])
+    assert bool(((b1 == b0) | (b1 == NAN_FILL))[~valid].all()), f"{label}: importance of a padded row is neither +0.0 nor the sentinel"
+    _fq_guards(pr, skipped, label + " skip_padding")
+    # the phase split, on buffers pre-filled alike
+    for skip, one in ((0, full), (1, skipped)):
+        for calls in (((3, 0), (4, 1)), ((1, 0), (2, 0), (4, 0))):
+            what = f"{label} skip_padding {skip} phases {[c[0] for c in calls]}"
+            other = _fq_run(pr, form, imp_mul, skip, calls)
+            # skip_padding 1 leaves a padded row's importance "+0.0 or untouched", and the two finishes skip different tiles: the
+            # importance-only one (bit 2) drops a tile without a valid patch, the tokens one (bit 4) still runs a tile that holds
+            # nothing but the special token and writes its zeros (num_ims a multiple of 64).  Every other byte is the same.
+            _same_buffers(one, other, what, skip=("importance",) if skip else ())
+            bo = _bits(other["importance"])
+            assert torch.equal(bo[:M][valid], _bits(one["importance"])[:M][valid]) and _untouched(other["importance"][M:]), what
+            assert bool(((bo[:M] == 0) | (bo[:M] == NAN_FILL))[~valid].all()), f"{what}: importance of a padded row is neither +0.0 nor the sentinel"
+    if form == "h16":
+        _same_buffers(full, _fq_run(pr, "rows-of-fp16-values", imp_mul, 0), label + " against fp32 rows")
+    if form == "matrix":
+        g = torch.Generator().manual_seed(M)
+        wild = torch.where(torch.rand((M, pr["D"]), generator=g) > 0.5, 3e4, -3e4).to(DEV)
+        y = torch.where(valid[:, None], pr["y"], wild)
+        for skip, one in ((0, full), (1, skipped)):
+            other = _fq_run(pr, form, imp_mul, skip, y=y)
+            _fq_same_valid(pr, one, other, f"{label} skip_padding {skip}, +-3e4 in the padded rows of y")
+            if skip == 0:
+                assert bool((_bits(_fq_views(pr, other)["importance"])[~valid] == 0).all()) and bool(torch.isfinite(_fq_views(pr, other)["tokens"]).all())
+    if form == "rows" and pe_mode == 2:
+        g = torch.Generator().manual_seed(M + 9)
+        far = torch.randint(64 * pr["patch_size"], 1 << 24, (M, 2), generator=g)
+        far[::3, 0] = (1 << 24) - 1
+        locs = torch.where(valid[:, None], pr["locs"], far.to(DEV)).contiguous()
+        other = _fq_run(pr, form, imp_mul, 0, locs=locs)
+        _fq_same_valid(pr, full, other, label + " padded positions beyond the table")
+        assert bool(torch.isfinite(_fq_views(pr, other)["tokens"]).all()), f"{label}: a clamped padded slot is not finite"
+        _fq_guards(pr, other, label + " clamp")
+
+
+@pytest.mark.parametrize("layout", sorted(FQ_LAYOUTS))
+def test_importance_qkv_feeds_the_special_last_aggregator(dev, layout):
+    """tokens and qkv_images of the fused finish into ops._aggregator_forward(qkv_img = ...): paths_attention_h3_img, paths_token_layer_ws
+    and paths_token0_tail_ws with special_last = 1 on two random layers; ctx_slide and logits against decoder_layer_ref +
+    token0_tail_ref (special-last order) in float64 at the bars of test_token_layer_ws_and_tail_ws_vs_fp64 (1e-5)."""
+    from paths_amd import ops
+    if ops.GEMM_MODE != "h3":
+        pytest.skip("default-mode kernels")
+    B, N, counts = FQ_LAYOUTS[layout]
+    i = sorted(FQ_LAYOUTS).index(layout)
+    pe_mode, imp_mul = 2 - i % 2, (i // 2 + 1) % 2
+    pr = _fq_problem(layout, pe_mode)
+    bufs = _fq_run(pr, "matrix", imp_mul, 1)
+    lvl = _fq_layers()
+    g = torch.Generator().manual_seed(B)
+    ctx_prev = (torch.rand((B, DT), generator=g) * 2 - 1).to(DEV)
+
+    class MC:
+        trans_dim, trans_heads, trans_layers, slide_ctx_mode, importance_mlp_hidden_dim = DT, 4, 2, "residual", HI
+    out = ops._aggregator_forward(MC, lvl, _fq_views(pr, bufs)["tokens"], pr["num_ims"], ctx_prev, None, qkv_img=bufs["qkv_images"])
+    torch.cuda.synchronize()
+    r64, _ = _fq_refs(pr, "sum", imp_mul)
+    l64 = [_cast_layer(lay, F64) for lay in lvl["layers"]]
+    lvl64 = {k: (v.double() if torch.is_tensor(v) else v) for k, v in lvl.items() if k != "layers"}
+    x1 = R.decoder_layer_ref(l64[0], r64["tokens"], pr["num_ims"], 4, special_last=True)["x_out"]
+    ctx, logits, _, _ = R.token0_tail_ref(l64[1], lvl64, x1, pr["num_ims"], 4, ctx_prev.double(), None, special_last=True)
+    ec, el = float((out["ctx_slide"].double() - ctx).abs().max()), float((out["logits"].double() - logits).abs().max())
+    print(f"[chain] special-last aggregator {layout} pe {pe_mode} imp_mul {imp_mul}: ctx_slide max err {ec:.3e}, logits {el:.3e} (bars 1e-5)")
+    assert ec < 1e-5 and el < 1e-5
+
+
+def test_importance_qkv_refusals_launch_nothing(dev):
+    from paths_amd import _lib
+    pr = _fq_problem("3x64", 2)
+
+    def refused(what, form="matrix", phases=5, **change):
+        bufs = _fq_buffers(pr)
+        entry, a = _fq_args(pr, bufs, form, 1, 0)
+        for k, v in change.items():
+            a[k] = v(a) if callable(v) else v
+        with pytest.raises(_lib.PathsHipError):
+            _fq_call(entry, a, phases, 0)
+        torch.cuda.synchronize()
+        assert all(_untouched(t) for t in bufs.values()), what
+
+    refused("N = 96 is no multiple of 64", B=2, N=96)
+    refused("D = 192", D=192)
+    refused("pe_table NULL", pe_table=None)
+    refused("phases 0", phases=0)
+    refused("phases 8", phases=8)
+    refused("splitk_ws off by 4 bytes", splitk_ws=lambda a: a["splitk_ws"] + 4)
+    refused("both y and y_rows", y_rows=lambda a: a["y"])
+    refused("_h16 with y given", form="h16", y=lambda a: a["y_rows"])
+    refused("ldya = D + 5", ldya=256 + 5)
+
+
+# ================================================================================================
+# paths_gemm_add_nt_x6 / paths_gemm_add_nt_x6_h16
+# ================================================================================================
+# (M, N, Npad, K): Npad 384 / 192 take the 128 x 192 tiles, 256 / 512 the 128 x 256 ones; every M has a tail block
+GEMM_ADD_SHAPES = {"300x320p384k256": (300, 320, 384, 256), "131x256p256k128": (131, 256, 256, 128), "257x300p512k256": (257, 300, 512, 256),
+                   "260x164p192k512": (260, 164, 192, 512)}
+GEMM_ADD_FORMS = ("matrix", "rows", "h16")
+
+
+@functools.lru_cache(maxsize=None)
+def _gemm_add_problem(M, N, Npad, K, a16):
+    """a in +-1.7 (a16: fp16 values), a_add in +-1, W at 1 / sqrt(K), bias +-0.5; the float64 references of both act values, with and
+    without bias, are computed once."""
+    from paths_amd import ops
+    g = torch.Generator().manual_seed(M + 3 * N + K)
+    a = (torch.rand((M, K), generator=g) * 2 - 1) * 1.7
+    if a16:
+        a = a.half().float()
+    add = torch.rand((M, K), generator=g) * 2 - 1
+    w = ((torch.rand((N, K), generator=g) * 2 - 1) / math.sqrt(K)).to(DEV).contiguous()
+    pr = {"a": a.to(DEV), "add": add.to(DEV), "w": w, "b": (torch.rand((N,), generator=g) - 0.5).to(DEV), "shape": (M, N, Npad, K)}
+    pr["img"], pr["w_scale"] = ops.x6_pack(w, n_pad=Npad, planes=2)
+    s64 = pr["a"].double() + pr["add"].double()
+    s32 = pr["a"] + pr["add"]
+    pr["ref"] = {}
+    for act in (0, 1):
+        for bias in (False, True):
+            r64, t64, S = R.linear_ref(s64, w.double(), pr["b"].double() if bias else None, act)
+            # the kernel sums a + a_add in fp32 while it stages the operand: one rounding, <= U / 2 |a + a_add|, times |W|
+            pr["ref"][act, bias] = (r64, t64 + R.U / 2 * S, S, R.linear_ref(s32, w, pr["b"] if bias else None, act)[0])
+    return pr
+
+
+def _gemm_add_run(pr, form, act, bias, num_ims=None, rps=0, **change):
+    """One call; returns the [M + guard, N + 4] output buffer (pre-filled with the sentinel)."""
+    from paths_amd import _lib
+    M, N, Npad, K = pr["shape"]
+    out = _ffill(M + GUARD_ROWS, N + 4)
+    addb = _ffill(M, K + 4)
+    addb[:, :K] = pr["add"]
+    a = dict(a=None, lda=K, a_rows=None, a_add=addb.data_ptr(), ld_add=K + 4, w=pr["img"].data_ptr(), Kp=K, b=pr["b"].data_ptr() if bias else None,
+             out=out.data_ptr(), ldo=N + 4, M=M, N=N, Npad=Npad, K=K, act=act, num_ims=None if num_ims is None else num_ims.data_ptr(), rps=rps,
+             w_s=pr["w_scale"], a_s=A_SCALE)
+    if form == "matrix":
+        ab = _ffill(M, K + 8)
+        ab[:, :K] = pr["a"]
+        a.update(a=ab.data_ptr(), lda=K + 8)
+    else:                                # the rows in scrambled order in a larger NaN-filled buffer (fp32, or fp16 for the _h16 entry point)
+        g = torch.Generator().manual_seed(M + 2)
+        at = torch.randperm(M + 5, generator=g)[:M].to(DEV)
+        big = torch.full((M + 5, K), float("nan"), device=DEV, dtype=torch.float16 if form == "h16" else F32)
+        big[at] = pr["a"].to(big.dtype)
+        rows = (big.data_ptr() + at.to(torch.int64) * (K * big.element_size())).contiguous()
+        a.update(a_rows=rows.data_ptr())
+    for k, v in change.items():
+        a[k] = v(a) if callable(v) else v
+    _lib.call("paths_gemm_add_nt_x6_h16" if form == "h16" else "paths_gemm_add_nt_x6", a["a"], a["lda"], a["a_rows"], a["a_add"], a["ld_add"], a["w"],
+              a["Kp"], a["b"], a["out"], a["ldo"], a["M"], a["N"], a["Npad"], a["K"], a["act"], a["num_ims"], a["rps"], a["w_s"], a["a_s"],
+              _lib.stream())
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("form", GEMM_ADD_FORMS)
+@pytest.mark.parametrize("shape", sorted(GEMM_ADD_SHAPES))
+def test_gemm_add_matches_float64(dev, shape, form):
+    """out = act((A + A_add) W^T + b) against linear_ref on the float64 sum, under test_linear_f32_matches_float64's two conditions (the
+    per-element bound - plus the fp32 sum's one rounding, U / 2 S - and err / S <= 4 err32 / S + 1e-7); A as a matrix (lda = K + 8), as
+    fp32 row addresses, as fp16 row addresses; a_add at ld_add = K + 4, out at ldo = N + 4.  act and the bias alternate over the
+    (shape, form) grid and the other act runs without / with the bias the first one had.  Guard columns and rows beyond M stay
+    untouched; _h16 is bit-identical to the fp32 row form on rows holding the same fp16 values.
+    Measured maxima on an MI355X: max |err| 1.7e-6 = .29 of the element bound; err / S 1.8e-7 = .17 of 4 * torch's fp32 (2.9e-7) + 1e-7."""
+    M, N, Npad, K = GEMM_ADD_SHAPES[shape]
+    pr = _gemm_add_problem(M, N, Npad, K, form == "h16")
+    i, j = sorted(GEMM_ADD_SHAPES).index(shape), GEMM_ADD_FORMS.index(form)
+    first = ((i + j) % 2, bool((i + j // 2) % 2))
+    for act, bias in (first, (1 - first[0], not first[1])):
+        out = _gemm_add_run(pr, form, act, bias)
+        r64, t64, S, r32 = pr["ref"][act, bias]
+        got = out[:M, :N]
+        assert bool(torch.isfinite(got).all())
+        err = (got.double() - r64).abs()
+        ratio, rel, rel32 = float((err / t64).max()), float((err / S).max()), float(((r32.double() - r64).abs() / S).max())
+        print(f"[chain] gemm_add {shape} {form} act {act} bias {bias}: max err {float(err.max()):.3e} = {ratio:.3f} of its element bound; "
+              f"err / S {rel:.3e} = {rel / (4 * rel32 + 1e-7):.3f} of 4 * fp32 torch ({rel32:.3e}) + 1e-7")
+        assert ratio <= 1.0 and rel <= 4 * rel32 + 1e-7
+        assert _untouched(out[:, N:]) and _untouched(out[M:]), "guard columns / rows beyond M"
+        if form == "h16":
+            assert torch.equal(_bits(out), _bits(_gemm_add_run(pr, "rows", act, bias))), "_h16 against fp32 rows of the same fp16 values"
+
+
+@pytest.mark.parametrize("form", GEMM_ADD_FORMS)
+@pytest.mark.parametrize("N,Npad", [(320, 384), (300, 512)])
+def test_gemm_add_skips_whole_tiles_of_padding(dev, N, Npad, form):
+    """num_ims = [128, 0, 5] at rows_per_slide 128: the second 128-row tile is all padding.  Valid rows are bit-identical to the run
+    without num_ims, the others are the value or still the sentinel, and some are skipped."""
+    M, K = 384, 256
+    pr = _gemm_add_problem(M, N, Npad, K, form == "h16")
+    full = _gemm_add_run(pr, form, 1, True)
+    num_ims = torch.tensor([128, 0, 5], dtype=torch.int64, device=DEV)
+    skip = _gemm_add_run(pr, form, 1, True, num_ims, 128)
+    valid = (torch.arange(M, device=DEV) % 128) < num_ims.repeat_interleave(128)
+    a, b = _bits(full[:M, :N]), _bits(skip[:M, :N])
+    assert bool((a == b)[valid].all()), "a valid row changed with num_ims"
+    assert bool(((a == b) | (b == NAN_FILL))[~valid].all()), "a padded row is neither the value nor the sentinel"
+    assert int((b == NAN_FILL)[~valid].sum()) > 0, "the empty slide was meant to leave a whole tile of padding"
+    assert _untouched(skip[:, N:]) and _untouched(skip[M:])
+    r64, t64, _, _ = pr["ref"][1, True]
+    assert float(((full[:M, :N].double() - r64).abs() / t64).max()) <= 1.0
+
+
+def test_gemm_add_refusals_launch_nothing(dev):
+    from paths_amd import _lib
+    pr = _gemm_add_problem(131, 256, 256, 128, False)
+
+    # (_gemm_add_run allocates the output inside: hand it a buffer of this test's to look at afterwards)
+    out = _ffill(131 + GUARD_ROWS, 256 + 4)
+    mine = dict(out=out.data_ptr())
+
+    def refused(form, what, **change):
+        with pytest.raises(_lib.PathsHipError):
+            _gemm_add_run(pr, form, 0, True, **change)
+        torch.cuda.synchronize()
+        assert _untouched(out), what
+
+    refused("matrix", "both a and a_rows", a_rows=lambda a: a["a"], **mine)
+    refused("matrix", "neither a nor a_rows", a=None, **mine)
+    refused("rows", "K != Kpacked", K=64, **mine)
+    refused("matrix", "Npad = 320", Npad=320, **mine)
+    refused("matrix", "unaligned a_add", a_add=lambda a: a["a_add"] + 4, **mine)
+    refused("matrix", "ld_add no multiple of 4", ld_add=128 + 5, **mine)
+    refused("h16", "_h16 with a given", a=lambda a: a["a_rows"], **mine)
+
+
+# ================================================================================================
 # coverage: every entry point a forward pass launches has a direct test
 # ================================================================================================
 HERE = "tests/test_gpu_chain_forward.py"
 SELECT = "tests/test_gpu_select.py"
 PARITY = "tests/test_gpu_parity.py"
-HALF = "tests/test_gpu_half_grids.py"
 ROWBWD = "tests/test_gpu_row_backward.py"
 BWD = "tests/test_gpu_backward.py"
+AGG = "tests/test_gpu_aggregator_forward.py"
 # entry point -> a test that calls it on inputs of its own and compares it with something no project kernel computed
 DIRECT_TESTS = {
     "paths_lstm_cell_x6": HERE + "::test_lstm_cell_matches_float64",
@@ -1014,6 +1457,14 @@ DIRECT_TESTS = {
     "paths_final_head": HERE + "::test_final_heads_match_float64",
     "paths_pe_table": HERE + "::test_pe_table_matches_the_fp32_angle_contract",
     "paths_linear_f32": HERE + "::test_linear_f32_matches_float64",
+    "paths_importance_qkv_x6": HERE + "::test_importance_qkv_matches_float64",
+    "paths_importance_qkv_x6_h16": HERE + "::test_importance_qkv_matches_float64",
+    "paths_gemm_add_nt_x6": HERE + "::test_gemm_add_matches_float64",
+    "paths_gemm_add_nt_x6_h16": HERE + "::test_gemm_add_matches_float64",
+    "paths_token_layer_f32": AGG + "::test_token_layer_kernels_match_float64",
+    "paths_token_layer_ws_rows": AGG + "::test_token_layer_kernels_match_float64",
+    "paths_token0_tail": AGG + "::test_token0_tail_matches_float64",
+    "paths_attention_h3_any_img": AGG + "::test_attention_h3_any_img_matches_float64",
     # existing direct tests in other files
     "paths_topk": SELECT + "::test_topk_equals_the_numpy_contract",
     "paths_topk_rows": SELECT + "::test_topk_equals_the_numpy_contract",
@@ -1037,17 +1488,8 @@ DIRECT_TESTS = {
     "paths_token0_pack_ws_d": PARITY + "::test_token_layer_ws_and_tail_ws_vs_fp64",
     "paths_attention_h3_img": PARITY + "::test_token_layer_ws_and_tail_ws_vs_fp64",
 }
-# entry points no test calls directly yet: the end-to-end test that covers each, and why it is not direct.  Open debt.
-KNOWN_INDIRECT = {
-    "paths_importance_qkv_x6": (PARITY + "::test_fused_importance_qkv_finish_equals_the_separate_launches",
-                                "compared with the separate launches (paths_importance_proj_x6 + the in_proj layer), not with float64"),
-    "paths_importance_qkv_x6_h16": (HALF + "::test_fp16_recursion_is_bitwise_its_fp32_twin", "bitwise against the fp32-row recursion only"),
-    "paths_gemm_add_nt_x6": (PARITY + "::test_single_level_variants", "the (x + h1) W^T product of the generic widths: whole levels only"),
-    "paths_attention_h3_any_img": (PARITY + "::test_single_level_variants", "attention on operand images of trans_dim 192: whole levels only"),
-    "paths_token_layer_ws_rows": (PARITY + "::test_single_level_variants", "the row form of the decoder-layer chain: whole levels only"),
-    "paths_token_layer_f32": (PARITY + "::test_single_level_vs_reference_golden", "the training forward's decoder layer: goldens and gradients only"),
-    "paths_token0_tail": (PARITY + "::test_single_level_vs_reference_golden", "the f32 token-0 tail: goldens only"),
-}
+# entry points no test calls directly: the end-to-end test that covers each, and why it is not direct.  Empty, and meant to stay so.
+KNOWN_INDIRECT = {}
 # csrc/runtime.hip: events, stream waits, memset, stop events (no arithmetic to compare)
 EXEMPT = {"paths_stream_wait", "paths_set_stop_event", "paths_flush_stop_event", "paths_stream_wait_event", "paths_record_event",
           "paths_event_destroy", "paths_memset_zero", "paths_clear_stop_event", "paths_stop_event_pending", "paths_event_create",
@@ -1071,7 +1513,13 @@ FORWARD_CONFIGS = {"shipped_k16": ({}, False, {"paths_lstm_cell_x6", "paths_impo
                                            {"paths_importance_rows", "paths_tokens_assemble", "paths_final_head_any"}),
                    # Hc = 64: below the split-operand kernel's K >= 128, the dispatcher takes the f32 kernels
                    "hc64": (HC64, False, {"paths_lstm_cell", "paths_importance_proj"}),
-                   "training_forward": ({}, False, {"paths_lstm_cell_x6", "paths_importance_proj_x6"})}
+                   "training_forward": ({}, False, {"paths_lstm_cell_x6", "paths_importance_proj_x6"}),
+                   # top-K 64 on a 16 x 16 base: every level has N = 256, a multiple of 64 - the fused finish, what the benchmark's levels run
+                   "shipped_k64": ({}, False, {"paths_lstm_cell_x6", "paths_importance_qkv_x6"}),
+                   "fp16_grids_k64": ({}, True, {"paths_lstm_cell_x6_h16", "paths_importance_qkv_x6_h16"}),
+                   "td192_fp16_grids": ({"model_config": {"trans_dim": 192}}, True, {"paths_lstm_cell_x6_h16", "paths_gemm_add_nt_x6_h16"})}
+# (top-K, base grid) of a configuration's recursion; the others run K = 16 on a 6 x 7 base
+FORWARD_SIZES = {"shipped_k64": (64, (16, 16)), "fp16_grids_k64": (64, (16, 16))}
 
 
 def _exempt(name):
@@ -1094,8 +1542,10 @@ def test_direct_test_map_names_real_tests():
 @pytest.mark.parametrize("cfg", list(FORWARD_CONFIGS))
 def test_every_forward_entry_point_has_a_direct_test(dev, cfg):
     """One small inference recursion (K = 16 on a 6 x 7 base, three slides, five levels) per configuration - the shipped one, fp16
-    grids, trans_dim 192, lstm false, td64 / one head / hidden 36 without the LSTM - and the forward half of one training step launch
-    only entry points listed in DIRECT_TESTS or KNOWN_INDIRECT: a new forward kernel needs a direct test before it ships."""
+    grids, trans_dim 192 (on fp32 and on fp16 grids), lstm false, td64 / one head / hidden 36 without the LSTM, and the shipped one
+    on fp32 and fp16 grids at top-K 64 on a 16 x 16 base, where the fused importance / in_proj finish runs - and the forward half of
+    one training step launch only entry points listed in DIRECT_TESTS or KNOWN_INDIRECT: a new forward kernel needs a direct test
+    before it ships."""
     from paths_amd import utils as putils
     from paths_amd.data_utils.slide import DeviceSlide
     from tests import helpers as H
@@ -1109,9 +1559,10 @@ def test_every_forward_entry_point_has_a_direct_test(dev, cfg):
             out = putils.recurse_train(model, batch["slide"], c.top_k_patches, 5)
             putils.loss_from_logits(out["logits"], batch, "survival")
     else:
-        c, model, _ = build_model(dev, 3, over, top_k_patches=[16] * 4)
+        top_k, base = FORWARD_SIZES.get(cfg, (16, (6, 7)))
+        c, model, _ = build_model(dev, 3, over, top_k_patches=[top_k] * 4)
         kw = {"dtype": torch.float16} if half else {}
-        slides = [DeviceSlide.synthetic(14, sid, (6, 7), p_bg=0.1, device=dev, **kw) for sid in range(3)]
+        slides = [DeviceSlide.synthetic(14, sid, base, p_bg=0.1, device=dev, **kw) for sid in range(3)]
         with H.spy_calls() as calls, torch.no_grad():
             putils.recurse(model, slides, c.top_k_patches, 5)
     torch.cuda.synchronize()
@@ -1144,5 +1595,30 @@ def test_hc64_recursion_takes_the_f32_lstm_kernel_and_matches_the_oracle(dev):
     with torch.no_grad():
         hz, _ = orc.inference_end2end(params, ocfg, [orc.LazyGrids(s.synthetic_spec) for s in slides], None, otrace)
     assert "paths_lstm_cell" in calls and not {"paths_lstm_cell_x6", "paths_lstm_cell_x6_h16"} & set(calls)
+    res = compare_recursion(trace, otrace, torch.sigmoid(out["logits"]), hz, imp_tol=STATE_TOL, hazard_tol=LOGIT_TOL)
+    assert res["problems"] == [], res["problems"]
+
+
+def test_trans_dim_192_recursion_on_fp16_grids_matches_the_oracle(dev):
+    """trans_dim 192 (a generic aggregator geometry) on fp16 slide grids: the [W1 ; Wp] product reads the fp16 feature rows in place
+    through paths_gemm_add_nt_x6_h16 (ops.importance_proj_generic_add).  A three-slide, three-level recursion launches it, launches no
+    fp32-row twin, and agrees with the oracle on the fp16 pyramids through the shared checker at the suite's level tolerances."""
+    from oracle import paths_oracle as orc
+    from oracle.compare import compare_recursion
+    from paths_amd import utils as putils
+    from paths_amd.data_utils.slide import DeviceSlide
+    from tests import helpers as H
+    from tests.test_gpu_parity import LOGIT_TOL, STATE_TOL, build_model
+    keeps = [12, 5]
+    over = {"model_config": {"trans_dim": 192}, "num_levels": 3}
+    cfg, model, params = build_model(dev, 77, over, top_k_patches=keeps)
+    ocfg = H.oracle_config(over, top_k_patches=keeps)
+    slides = [DeviceSlide.synthetic(640, sid, (4, 5), num_levels=3, p_bg=0.3, device=dev, dtype=torch.float16) for sid in range(3)]
+    trace, otrace = [], []
+    with H.spy_calls() as calls, torch.no_grad():
+        out = putils.recurse(model, slides, keeps, 3, trace=trace)
+    with torch.no_grad():
+        hz, _ = orc.inference_end2end(params, ocfg, [orc.LazyGrids(s.synthetic_spec) for s in slides], None, otrace)
+    assert "paths_gemm_add_nt_x6_h16" in calls and "paths_gemm_add_nt_x6" not in calls and "paths_lstm_cell_x6_h16" in calls, sorted(set(calls))
     res = compare_recursion(trace, otrace, torch.sigmoid(out["logits"]), hz, imp_tol=STATE_TOL, hazard_tol=LOGIT_TOL)
     assert res["problems"] == [], res["problems"]

@@ -895,24 +895,16 @@ def test_token_layer_ws_and_tail_ws_vs_fp64(dev, T, lens, d, ctx_mode):
     ctx_all = rnd(B, depth, d) if depth else None
     out = ops._aggregator_forward(MC, lvl, tokens, num_ims, ctx_prev, ctx_all)
     torch.cuda.synchronize()
-    ln = lambda x, g_, b_: torch.nn.functional.layer_norm(x, (d,), g_.double(), b_.double(), 1e-5)
-    D = lambda t: t.double()
-    for b, n in enumerate(lens):
-        x = D(tokens[b, :n])
-        for li, lay in enumerate(layers):
-            qkv = x @ D(lay["wqkv"]).T + D(lay["bqkv"])
-            q, k, v = (t.view(n, Hh, hd).transpose(0, 1) for t in qkv.split(d, dim=1))
-            if li == 1:
-                q = q[:, :1]
-            a = (torch.softmax(q @ k.transpose(1, 2) / math.sqrt(hd), dim=-1) @ v).transpose(0, 1).reshape(-1, d)
-            xin = x if li == 0 else x[:1]
-            y = ln(xin + a @ D(lay["wo"]).T + D(lay["bo"]), lay["ln1g"], lay["ln1b"])
-            y = ln(y + D(lay["cab"]), lay["ln2g"], lay["ln2b"])
-            y = ln(y + torch.relu(y @ D(lay["w1"]).T + D(lay["b1"])) @ D(lay["w2"]).T + D(lay["b2"]), lay["ln3g"], lay["ln3b"])
-            x = y
-        ctx = ln(x[0], lvl["lnfg"], lvl["lnfb"]) + (D(ctx_prev[b]) if ctx_mode == "residual" else 0)
-        feat = ctx if ctx_mode == "residual" else torch.cat([D(ctx_all[b]).reshape(-1), ctx])
-        logits = feat @ D(lvl["wcls"]).T + D(lvl["bcls"])
+    from tests import chain_ref as R
+    D = lambda t: t.double() if torch.is_tensor(t) else t
+    l64 = [{k: D(v) for k, v in lay.items()} for lay in layers]
+    lvl64 = {k: D(v) for k, v in lvl.items() if k != "layers"}
+    for b, n in enumerate(lens):                 # slide by slide over its valid rows (float64 scores of T = 8193 are 2 GB per slide)
+        nb = num_ims[b:b + 1]
+        x1 = R.decoder_layer_ref(l64[0], D(tokens[b:b + 1, :n]), nb, Hh)["x_out"]
+        ctx, logits, _, _ = R.token0_tail_ref(l64[1], lvl64, x1, nb, Hh, D(ctx_prev[b:b + 1]) if ctx_mode == "residual" else None,
+                                              D(ctx_all[b:b + 1]) if depth else None)
+        ctx, logits = ctx[0], logits[0]
         assert float((D(out["ctx_slide"][b]) - ctx).abs().max()) < 1e-5, (b, n)
         assert float((D(out["logits"][b]) - logits).abs().max()) < 1e-5, (b, n)
 
