@@ -23,6 +23,74 @@
  *     bf16 planes (6 x v_mfma_f32_32x32x16_bf16, no range limits).  The entry points without suffix use the f32-input
  *     matrix cores (v_mfma_f32_32x32x2_f32 / 16x16x4_f32: a k-ordered fp32 FMA chain).  Measured error of all three vs
  *     fp64 is that of an fp32 FMA chain.
+ *
+ * UNDEFINED MEMORY.  What a buffer may hold on entry where its contents are not an operand: rows of padding (row index within the
+ * slide >= num_ims[b]; token rows >= num_ims[b] + 1), pad columns between a row's width and its leading dimension, workspaces and
+ * operand images, zones a kernel may read behind a buffer.  Four phrases, each with the meaning tests/test_gpu_undefined_memory.py
+ * asserts (the defined part of every output is BIT-identical whatever such memory held; no float atomics anywhere):
+ *   never read                     the bytes are not loaded, or every byte that is loaded was written by this call first;
+ *   read, any bit pattern          loaded, and no defined output depends on them: NaN, Inf and 0xff bytes included;
+ *   read, must be finite           loaded and multiplied by exact zeros: any finite value leaves every defined output as it is,
+ *                                  a NaN or an infinity does not;
+ *   must be zero on entry          (written by ...): a precondition.
+ * OUTPUT rows of padding are what each entry point says below; where it says nothing they are not defined (written from whatever the
+ * padded input rows held, or not written at all when tiles of padding are skipped).  Pad columns [width, ld) of every strided
+ * operand: never read, never written.  Rows past the M / B * T rows of an operand: never read unless stated.
+ *
+ * attention, forward
+ *   paths_attention_x6 / _x6_dropout   q, k, v rows of padding: read, any bit pattern (they enter the operand images as zeros - the
+ *                                      keys because they are masked, the queries because their scores share the wave-wide votes of
+ *                                      the deferred rescale with valid queries); workspace on entry (images_ready = 0): never read;
+ *                                      images_ready != 0: the images of paths_token_layer_h3 / _ws / paths_importance_qkv_x6, whose
+ *                                      writers zero the same rows in every 64-token tile that holds a valid token (other tiles:
+ *                                      never read); o / lse rows of padded queries: not defined
+ *   paths_attention_f32                q, k, v rows of padding: read, any bit pattern
+ *   paths_attention_any / _any_train / _h3_any / paths_attention_token0_any / paths_attention_fp8 / _fp8_qkv / paths_attention_token0_fwd
+ *                                      q | k | v rows of padding: read, any bit pattern; workspace on entry: never read
+ *   paths_attention_wide_fwd           qkv rows of padding: read, must be finite (O = P V multiplies v by the zero probabilities of
+ *                                      masked keys); the 128 rows behind qkv: read, any bit pattern; workspace on entry: never read
+ * attention, backward (dqkv: must be zero on entry, written by the caller, for every entry point)
+ *   paths_attention_bwd_f32 / _f32_dropout     k, v, lse rows of padding: read, any bit pattern; q, o, d_o rows of padding: read, must
+ *                                              be finite (D = sum dO o of a padded query and its q and dO rows meet zero
+ *                                              probabilities inside the matrix products); ws_dsum on entry: never read
+ *   paths_attention_bwd_x6_planes / _x6_dropout  q, k, v, lse rows of padding: read, any bit pattern; o, d_o rows of padding: read,
+ *                                              must be finite; ws_dsum, images on entry: never read
+ *   paths_attention_bwd_any / paths_attention_token0_bwd   every input's rows of padding: read, any bit pattern; ws_dsum / ws: never read
+ *   paths_attention_wide_bwd           qkv and d_o rows of padding: read, must be finite; o, lse rows of padding: never read; the
+ *                                      128 rows behind qkv: read, any bit pattern; workspace on entry: never read
+ *   The training step computes rows of padding instead of skipping them (paths_amd/utils.py:recurse_train), so every saved row is finite.
+ * token-layer chain
+ *   paths_token_layer_f32 / _h3 / _ws / _ws_rows   x_in and attn rows of padded tokens: read, any bit pattern (skip_padding 0: each is
+ *                                      computed into the same row of the outputs; 1: 64-token tiles of padding are skipped);
+ *                                      qkv_images, q, k, v, qkv_rows, x_out on entry: never read
+ *   paths_attention_h3_img / paths_attention_h3_any_img   o_img / o on entry: never read; workspace: the producer's images
+ *   paths_token0_tail                  x_in, q, k, v rows of padded tokens: read, any bit pattern; ws_partials on entry: never read
+ *   paths_token0_tail_ws               x1 rows of padded tokens: read, any bit pattern; partials on entry: never read; counters: must
+ *                                      be zero on entry (written by the caller once; every launch leaves them zero)
+ * gate and importance GEMMs
+ *   paths_lstm_cell_x6 / _h16 with num_ims    rows of x (or the rows x_rows addresses), h0, c0 of padded patches: read, any bit
+ *                                      pattern; ws_o and every output on entry: never read; every row of hp counts
+ *   paths_importance_proj_x6 / _h16, paths_importance_qkv_x6 / _h16   rows of y (or the rows y_rows addresses) and y_add of padded
+ *                                      patches: read, any bit pattern; splitk_ws, qkv_images on entry: never read; importance of a
+ *                                      padded row is +0.0 (skip_padding 0) or not written (1)
+ *   paths_gemm_add_nt_x6 / _h16 with num_ims  rows of a (a_rows) and a_add of padded patches: read, any bit pattern
+ *   paths_gemm_rows_nt_x6              every address of a_rows is read: none is padding
+ * reductions over rows (they sum over M without a mask, by design)
+ *   paths_gemm_tn_f32 / _tn_x6, paths_colsum_f32, paths_reduce_slabs_f32, paths_layernorm_bwd_sums / _any
+ *                                      EVERY row of a, b0 | b1, dy, xhat, rstd and every slab counts: the caller hands over defined
+ *                                      (for padding: zero) rows; workspace / slabs / dx on entry: never read; out with
+ *                                      accumulate = 0: never read
+ * row backward kernels
+ *   paths_lstm_bwd_a / _b              dh1, dh1b, o, tc, dc1_h, dc1_ext, frm, c0 rows of padded patches: read, any bit pattern
+ *   paths_importance_bwd / _any        dtok rows of padded patches and of the special token: read, any bit pattern; pproj, hid: saved
+ *                                      activations, finite in every row
+ *   paths_importance_rows_bwd / _any   dz_rows and x rows of padded patches: read, any bit pattern
+ * packers and pack kernels
+ *   paths_x6_pack_weights / _t, paths_tlayer_pack_ws, paths_tlayer_pack_h3, paths_token0_pack_ws / _d, paths_fp8_pack_weight
+ *                                      write EVERY byte of an image of the queried size (padding rows and columns as zeros): out on
+ *                                      entry: never read, and a consumer never sees what the buffer held
+ *   paths_pack_flags / _index / _rows  flags, index, count, partials, rows on entry: never read (flags is written in full by
+ *                                      paths_pack_flags before paths_pack_index counts it)
  */
 #ifndef PATHS_HIP_H
 #define PATHS_HIP_H

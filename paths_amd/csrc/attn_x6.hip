@@ -9,7 +9,7 @@
 //     [16 l, 16 l + 16) = its 8 k-values.  Q and K fragments: rows = tokens, k = the 32 head dims.  V fragments are
 //     TRANSPOSED (rows = 16 head dims, k = 32 keys) and key-PERMUTED, k-slot (g, j) <-> key 4g + (j&3) + 16 (j>>2), which is
 //     the order in which the S^T accumulators of two 16-key tiles sit in a lane - so P never leaves the registers.
-//     Keys that are masked (or beyond T) are written as zeros.
+//     Keys that are masked (or beyond T) are written as zeros, and so are the queries of padded tokens.
 //  2. attn_x6_kernel: one wave = 32 queries (two 16-query tiles) of one (slide, head); a 4-wave workgroup shares 64-key
 //     K / V^T fragment sets through LDS (plain 16-byte copies, double-buffered).  Per 32-key group and wave:
 //        S^T[key][q] = K Q^T          2 key tiles x 2 query tiles x 6 MFMAs (A = K fragment, B = Q fragment in registers)
@@ -59,7 +59,9 @@ attn_x6_prep_kernel(const float* __restrict__ q, const float* __restrict__ k, co
   {
     const int tl = tid >> 2, g = tid & 3, tok = t0 + tl;
     float xq[8], xk[8];
-    const bool kvalid = tok < len, qvalid = tok < T && tok < nq;
+    // (a padded query is written as zeros like a masked key: its scores sit in the same wave as valid queries' and take part in
+    // the wave-wide votes of the deferred rescale, so whatever its q row held would reach the valid rows' rounding)
+    const bool kvalid = tok < len, qvalid = tok < len && tok < nq;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       xk[i] = kvalid ? k[base + (int64_t)tok * HD + 8 * g + i] : 0.f;

@@ -240,7 +240,9 @@ tlayer_h3_kernel(TLayerH3Params p) {
         // 4x4 exchange inside the lane quad) on lane & 15, so every piece is one 8-byte store per plane.
         const int which = qc >> 1;
         const int len = p.num_ims ? min((int)p.num_ims[b] + 1, p.T) : p.T;
-        const bool live = which == 0 ? tok < p.T : tok < len;          // masked keys: K = 0, V = 0 (0 * garbage would poison O)
+        // masked keys: K = 0, V = 0 (0 * garbage would poison O); padded queries: Q = 0 (their scores vote in the attention kernel's
+        // deferred rescale beside valid queries of the same wave: garbage there would reach the valid rows' rounding)
+        const bool live = tok < len;
         const int64_t img = (int64_t)gridDim.y * p.H * p.Tp * 128;     // bytes of one of the three images (32 dims x 2 planes x 2 B)
         const int tokb = t0 + wave * 16;                               // first token of this wave's tile
 #pragma unroll

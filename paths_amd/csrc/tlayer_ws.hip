@@ -632,7 +632,9 @@ tlayer_ws_kernel(WsParams p) {
 #pragma unroll
       for (int tt = 0; tt < TT; ++tt) {
         const int tok = t0 + 16 * tt + ql;
-        const bool live = which == 0 ? tok < p.T : tok < len;    // masked keys: K = 0 (V = 0 below: 0 * garbage would poison O)
+        // masked keys: K = 0 (V = 0 below: 0 * garbage would poison O); padded queries: Q = 0 (their scores vote in the attention
+        // kernel's deferred rescale beside valid queries of the same wave: garbage there would reach the valid rows' rounding)
+        const bool live = tok < len;
 #pragma unroll
         for (int kk = 0; kk < NKB; ++kk) {
           float v[8];

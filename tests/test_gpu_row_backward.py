@@ -6,7 +6,8 @@ Per case:
   accuracy      element-wise outputs: max|g - ref| / max|ref| per slide (LayerNorm: per row family) and per output; sums (dgamma,
                 dbeta, colsum(dx), colsum, slab partials, da): |g - ref| / sum|terms|, so a cancelling sum is judged by its
                 conditioning and not by how small its result is;
-  padding       padded rows come back zero while their inputs hold large finite garbage, and what the contract leaves alone keeps a
+  padding       padded rows come back zero while their inputs hold large finite garbage - and, in the *_ignores_what_padded_rows_hold
+                tests, bit-identical outputs when they hold NaN / Inf instead (hostile_rows) - and what the contract leaves alone keeps a
                 sentinel (the other kernel's columns of dG, the h half of d_state_prev, rows of parents that were not kept);
   determinism   two launches give bit-identical outputs (no atomics here: a difference is a race);
   sensitivity   the same outputs measured against a wrong reference (the longest slide's num_ims cut by one, r / m planes swapped,
@@ -115,10 +116,115 @@ def garbage_rows(x, valid):
     return torch.where(valid.view(-1, *([1] * (x.dim() - 1))), x, gar)
 
 
+def hostile_rows(x, valid):
+    """x with the padded rows (dim 0) replaced by the hostile pattern of tests/poison.py: NaN, +Inf, -Inf and 3e38 in a cycle.  Finite
+    garbage passes whether a kernel masks with a select or with a multiplication; this passes only with a select."""
+    from tests import poison
+    bad = poison.fill_(torch.zeros_like(x).contiguous(), "H")
+    return torch.where(valid.view(-1, *([1] * (x.dim() - 1))), x, bad)
+
+
 def gen(dev, seed):
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
     return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the padded rows of every input: finite garbage and the hostile pattern give the same bits
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _same(label, a, b):
+    for i, (x, y) in enumerate(zip(a, b)):
+        if x is None:
+            assert y is None
+            continue
+        assert torch.isfinite(y).all(), f"{label}: output {i} is not finite with NaN / Inf in the padded rows"
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32)), f"{label}: output {i} depends on what the padded rows hold"
+
+
+@pytest.mark.parametrize("N,D,Hc", [(7, 1024, 32), (160, 1536, 96)])
+def test_lstm_bwd_ignores_what_padded_rows_hold(dev, N, D, Hc):
+    """paths_lstm_bwd_a / _b with d_state_out and a strided c0 / dc0: dy, o, tc, f|r|m, dc1, d_state_out and state_prev rows behind a
+    slide's last patch hold large finite values, then NaN / Inf.  Every output (padded rows exactly zero) is bit-identical."""
+    L = _lib()
+    st = L.stream()
+    g = gen(dev, N + D + Hc)
+    num_ims = [N - 1, 0, N, 1]
+    B = len(num_ims)
+    M, Dp, G = B * N, D + Hc, 3 * Hc + D
+    nims = torch.tensor(num_ims, device=dev, dtype=torch.int64)
+    valid = R.valid_rows(nims, N)
+    clean = {"dy": rnd(g, M, D), "o": rnd(g, M, D, lo=0.0), "tc": rnd(g, M, D), "frm": rnd(g, M, 3 * Hc), "dc1_h": rnd(g, M, Hc),
+             "dso": rnd(g, M, Dp), "sp": rnd(g, M, Dp)}
+
+    def run(rows):
+        t = {k: rows(v, valid).contiguous() for k, v in clean.items()}
+        dG, dpre_h, dsp = (torch.full(s, SENTINEL, device=dev) for s in ((M, G), (M, D), (M, Dp)))
+        L.call("paths_lstm_bwd_a", P(t["dy"]), D, P(t["dso"]), Dp, P(t["o"]), P(t["tc"]), P(nims), N, M, D, P(dG) + 4 * 3 * Hc, G, P(dpre_h), st)
+        L.call("paths_lstm_bwd_b", P(t["dc1_h"]), P(t["dso"]) + 4 * D, Dp, P(t["frm"]), P(t["sp"]) + 4 * D, Dp, P(nims), N, M, Hc, P(dG), G,
+               P(dsp) + 4 * D, Dp, st)
+        sync()
+        return dG, dpre_h, dsp[:, D:].contiguous()
+
+    fin, hos = run(garbage_rows), run(hostile_rows)
+    _same(f"lstm_bwd N={N}", fin, hos)
+    assert not hos[0][~valid].any() and not hos[1][~valid].any() and not hos[2][~valid].any()
+
+
+@pytest.mark.parametrize("Hi,d,extra,imp_mul,N", [(128, 128, 0, 1, 160), (128, 128, 0, 0, 7), (36, 64, 0, 1, 160), (96, 192, 32, 0, 7)])
+def test_importance_bwd_ignores_what_padded_rows_hold(dev, Hi, d, extra, imp_mul, N):
+    """paths_importance_bwd / _any: the dtok rows of padded patches and of the special token, as in test_importance_bwd_vs_fp64 (pproj
+    and hid are saved activations, finite in every row; alpha is 0 in padded rows by the forward's mask)."""
+    L = _lib()
+    st = L.stream()
+    g = gen(dev, Hi + d + N)
+    num_ims = [N - 1, 0, N, 1]
+    M, nims, valid, hid, alpha, w2 = _imp_inputs(g, dev, num_ims, N, Hi, d)
+    B = len(num_ims)
+    fast = (Hi, d, extra) == (128, 128, 0)
+    U = (Hi + d + 31) // 32 * 32 + extra
+    tv = torch.cat((torch.zeros(B, 1, dtype=torch.bool, device=dev), valid.view(B, N)), 1).reshape(-1)      # row 0 of dtok: the special token's, not read
+    dtok0, pproj0 = rnd(g, B * (N + 1), d), rnd(g, M, d)
+
+    def run(rows):
+        dtok, pproj, h = rows(dtok0, tv).contiguous(), pproj0, hid
+        du, da, dah = (torch.full(s, SENTINEL, device=dev) for s in ((M, U), (M,), (M, Hi)))
+        if fast:
+            L.call("paths_importance_bwd", P(dtok), P(pproj), P(h), P(alpha), P(w2), P(nims), N, M, imp_mul, P(du), P(da), P(dah), st)
+        else:
+            L.call("paths_importance_bwd_any", P(dtok), P(pproj), P(h), P(alpha), P(w2), P(nims), N, M, imp_mul, Hi, d, U, P(du), P(da), P(dah), st)
+        sync()
+        return du, da, dah
+
+    fin, hos = run(garbage_rows), run(hostile_rows)
+    _same(f"importance_bwd Hi={Hi} d={d}", fin, hos)
+    assert not hos[0][~valid].any() and not hos[1][~valid].any() and not hos[2][~valid].any()
+
+
+@pytest.mark.parametrize("Hi,D,N", [(128, 1024, 160), (128, 1028, 7), (36, 132, 160), (200, 1024, 1)])
+def test_importance_rows_bwd_ignores_what_padded_rows_hold(dev, Hi, D, N):
+    """paths_importance_rows_bwd / _any: the dZ and X rows of padded patches, as in test_importance_rows_bwd_vs_fp64 - the kernel reads
+    every row's dot product and must SELECT zero for a padded row, not multiply by it."""
+    L = _lib()
+    st = L.stream()
+    g = gen(dev, Hi + D + N)
+    num_ims = [N - 1, 0, N, 1]
+    M, nims, valid, hid, alpha, w2 = _imp_inputs(g, dev, num_ims, N, Hi, D)
+    dz0, x0 = rnd(g, M, D), rnd(g, M, D)
+
+    def run(rows):
+        dz, x, h = rows(dz0, valid).contiguous(), rows(x0, valid).contiguous(), hid
+        dh, da, dah = (torch.full(s, SENTINEL, device=dev) for s in ((M, Hi), (M,), (M, Hi)))
+        if Hi == 128:
+            L.call("paths_importance_rows_bwd", P(dz), P(x), D, P(h), P(alpha), P(w2), P(nims), N, M, P(dh), P(da), P(dah), st)
+        else:
+            L.call("paths_importance_rows_bwd_any", P(dz), P(x), D, P(h), P(alpha), P(w2), P(nims), N, M, Hi, P(dh), P(da), P(dah), st)
+        sync()
+        return dh, da, dah
+
+    fin, hos = run(garbage_rows), run(hostile_rows)
+    _same(f"importance_rows_bwd Hi={Hi} D={D}", fin, hos)
+    assert not hos[0][~valid].any() and not hos[1][~valid].any() and not hos[2][~valid].any()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
