@@ -12,6 +12,12 @@
  *     -3 unsupported configuration); paths_last_error() returns a thread-local message;
  *   - never allocates, frees or synchronises; launches on the caller's stream (hipStream_t passed as
  *     void*); no global mutable state, callable from any host thread;
+ *   - paths_stream_t is void* for every consumer.  A translation unit that has the HIP runtime's types may define
+ *     PATHS_STREAM_T (as hipStream_t) before it includes this header; the library's own sources do (csrc/common.h), so the
+ *     compiler checks every definition against the declaration here.  The ABI is the same either way: one pointer.  This header
+ *     is also the only statement of the signatures: the Python binding (paths_amd/_lib.py) reads argument and return types from
+ *     it, so a declaration is `<int | int64_t | void* | const char*> paths_name(<parameters>);` with named parameters of type
+ *     int, int64_t, float, uint32_t, uint64_t, size_t, a pointer or paths_stream_t;
  *   - all floating-point buffers are fp32, row-major, 16-byte aligned, leading dimensions in elements
  *     and multiples of 4; integer fields follow the reference's dtypes (int64 locs / num_ims /
  *     parent_inds);
@@ -102,7 +108,10 @@
 extern "C" {
 #endif
 
-typedef void* paths_stream_t; /* hipStream_t */
+#ifndef PATHS_STREAM_T
+#define PATHS_STREAM_T void*
+#endif
+typedef PATHS_STREAM_T paths_stream_t; /* hipStream_t */
 
 const char* paths_last_error(void);
 const char* paths_build_info(void);

@@ -1,170 +1,79 @@
-"""ctypes binding of ``libpaths_hip.so`` (C ABI in include/paths_hip.h).
+"""ctypes binding of ``libpaths_hip.so`` (C ABI in include/paths_hip.h, which this module reads the signatures from).
 
 The product path has NO fallback: if the shared library is missing or a kernel launch fails this
-module raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` (or
-``make -C paths_amd/csrc``).
+module raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PATHS_HIP_LIB") or os.path.join(_HERE, "libpaths_hip.so")
-
-_i64, _i32, _f32, _vp, _u32, _u64 = C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_uint32, C.c_uint64
-
-# name -> argtypes (mirrors include/paths_hip.h; tests/test_cpu_surface.py::test_library_exports_every_declared_symbol_at_abi_3 checks both against the .so exports)
-SIGNATURES = {
-    "paths_lstm_cell": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                        _i32, _i32, _i32, _vp, _i32, _i32, _vp],
-    "paths_pe_table": [_vp, _i32, _i32, _i32, _vp, _vp],
-    "paths_importance_proj": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
-                              _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_gemm_nt_f32": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp],
-    "paths_x6_pack_weights": [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
-    "paths_x6_pack_weights_t": [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_lstm_cell_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                           _i32, _i32, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
-    "paths_importance_proj_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
-                                 _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp],
-    "paths_importance_qkv_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
-                                _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _f32, _f32, _vp, _i32, _i32, _vp],
-    "paths_gemm_nt_x6": [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
-                         _i32, _f32, _f32, _vp],
-    "paths_gemm_add_nt_x6": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _f32, _vp],
-    "paths_gemm_tn_f32": [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_attention_fp8": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_gemm_tn_x6": [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
-    "paths_colsum_f32": [_vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
-    "paths_transpose_f32": [_vp, _i64, _i32, _i32, _vp, _i64, _vp],
-    "paths_attention_wide_fwd": [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _u64, _f32, _vp, _vp],
-    "paths_attention_wide_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _u64, _f32, _vp, _vp],
-    "paths_sibling_sum": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp],
-    "paths_scatter_kept_rows": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
-    "paths_adamw_multi": [_vp, _vp, _vp, _i32, _vp, _vp, _f32, _i32, _f32, _f32, _f32, _f32, _i32, _vp],
-    "paths_lstm_bwd_a": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp],
-    "paths_lstm_bwd_b": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
-    "paths_importance_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp],
-    "paths_layernorm_fwd_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
-    "paths_attention_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_token0_any": [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
-    "paths_attention_token0_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _f32, _vp],
-    "paths_attention_token0_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _f32, _vp],
-    "paths_token0_attention": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_rollout_prepare": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_rollout_seed": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp],
-    "paths_attention_rollout_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_relevance_seed": [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp,
-                                       _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_relevance_step": [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                                       _i32, _i32, _i32, _i32, _vp],
-    "paths_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    "paths_layernorm_bwd_sums": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "paths_reduce_slabs_f32": [_vp, _i32, _i32, _vp, _i32, _vp],
-    "paths_defer_reductions": [_i32],
-    "paths_flush_reductions": [_vp, _vp],
-    "paths_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "paths_attention_x6": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp],
-    "paths_tlayer_pack_h3": [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp],
-    "paths_token_layer_h3": [_vp] * 16 + [_f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp],
-    "paths_tlayer_pack_ws": [_i32, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _i32, _vp],
-    "paths_token_layer_ws": [_vp] * 17 + [_f32, _f32, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _i32, _vp],
-    "paths_token_layer_ws_rows": [_vp] * 16 + [_f32, _f32, _f32, _f32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
-    "paths_token0_pack_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
-    "paths_token0_pack_ws_d": [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp],
-    "paths_token0_tail_ws": [_vp] * 16 + [_vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp],
-    "paths_attention_any": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
-    "paths_attention_any_train": [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _u64, _f32, _vp],
-    "paths_layernorm_fwd_stats_any": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
-    "paths_layernorm_bwd_any": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
-    "paths_layernorm_bwd_sums_any": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "paths_importance_bwd_any": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
-    "paths_importance_rows_bwd_any": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp],
-    "paths_attention_bwd_any": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _u64, _f32, _vp],
-    "paths_fp8_scale": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _vp],
-    "paths_fp8_pack_weight": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp],
-    "paths_fp8_quantize": [_vp, _i64, _i32, _i32, _vp, _vp, _vp],
-    "paths_gemm_nt_fp8_out8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "paths_gemm_nt_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    "paths_attention_fp8_qkv": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
-    "paths_attention_h3_any": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
-    "paths_attention_h3_any_img": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_layernorm_rows": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp],
-    "paths_layernorm2_rows": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp],
-    "paths_importance_rows": [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp],
-    "paths_importance_tokens_rows": [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp],
-    "paths_tokens_assemble": [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_final_head_any": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp],
-    "paths_attention_h3_img": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_token_layer_f32": [_vp] * 21 + [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp],
-    "paths_token0_tail": [_vp] * 20 + [_vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
-    "paths_final_head": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp],
-    "paths_layernorm_f32": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
-    "paths_topk": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
-    "paths_topk_rows": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
-    "paths_gemm_rows_nt_x6": [_vp, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
-    "paths_expand_children": [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "paths_candidate_children": [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
-    "paths_admit_children": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "paths_gather_kept_rows": [_vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp],
-    "paths_gather_rows_bwd": [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp],
-    "paths_fallback_all_cells": [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "paths_gather_rows": [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
-    "paths_level0_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
-    "paths_scale_add_rows": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp],
-    "paths_importance_rows_bwd": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
-    "paths_dropout_rows": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _u64, _f32, _vp],
-    "paths_dropout_mask": [_vp, _i64, _u64, _f32, _vp],
-    "paths_attention_x6_dropout": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _u64, _f32, _vp],
-    "paths_attention_bwd_f32_dropout": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _f32, _vp],
-    "paths_attention_bwd_x6_dropout": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _f32, _vp],
-    "paths_attention_bwd_x6_planes": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _f32, _i32, _vp],
-    "paths_stream_wait": [_vp, _vp, _vp],
-    "paths_set_stop_event": [_vp],
-    "paths_flush_stop_event": [_vp],
-    "paths_stream_wait_event": [_vp, _vp],
-    "paths_record_event": [_vp, _vp],
-    "paths_event_destroy": [_vp],
-    "paths_memset_zero": [_vp, C.c_size_t, _vp],
-    "paths_tissue_mask": [_vp, _i64, _i32, _vp, _vp],
-    "paths_tissue_mask_absmax": [_vp, _i64, _i32, _vp, _vp, _vp],
-    "paths_synth_grid": [_vp, _i32, _i32, _i32, _u32, _i32, _u64, _vp],
-    "paths_stage_rows": [_vp, _i64, _i32, _vp, _vp, _vp],
-    "paths_saliency_rows": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    "paths_path_points": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_path_accumulate": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
-    "paths_rank_joint": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    "paths_path_mask_points": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_removal_masks": [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
-    "paths_visited_overlap": [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "paths_level0_mask_rows": [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp],
-}
-# fp16 slide grids (DeviceSlide dtype torch.float16): the same arguments as the fp32 entry points above
-for _n in ("paths_lstm_cell_x6", "paths_importance_proj_x6", "paths_importance_qkv_x6", "paths_gemm_add_nt_x6", "paths_gather_rows",
-           "paths_level0_batch", "paths_tissue_mask_absmax", "paths_synth_grid"):
-    SIGNATURES[_n + "_h16"] = SIGNATURES[_n]
-# tissue-only (packed) slides: the twins' arguments + index_ptrs in front of the stream; the pack passes (csrc/pack_rows.hip)
-for _n in ("paths_gather_rows", "paths_level0_batch"):
-    for _s in ("", "_h16"):
-        SIGNATURES[_n + "_packed" + _s] = SIGNATURES[_n][:-1] + [_vp, _vp]
-for _s in ("", "_h16"):
-    SIGNATURES["paths_pack_flags" + _s] = [_vp, _i64, _i32, _vp, _vp]
-    SIGNATURES["paths_pack_rows" + _s] = [_vp, _i64, _i32, _vp, _i64, _vp, _vp]
-SIGNATURES["paths_pack_index"] = [_vp, _i64, _vp, _vp, _vp, _vp]
-_PLAIN = {"paths_gemm_tn_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_x6_packed_bytes": (C.c_int64, [_i32, _i32, _i32]), "paths_tlayer_h3_image_bytes": (C.c_int64, [_i32]), "paths_tlayer_ws_image_bytes": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes": (C.c_int64, []), "paths_token0_ws_partials": (C.c_int64, [_i32, _i32]), "paths_token0_ws_image_bytes_d": (C.c_int64, [_i32]), "paths_token0_ws_partials_d": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_ws_supported": (_i32, [_i32, _i32, _i32, _i32]), "paths_attention_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32, _i32]), "paths_attention_fp8_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_bwd_x6_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_token0_workspace": (C.c_int64, [_i32, _i32, _i32]), "paths_token0_attention_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_rollout_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_attention_h3_any_workspace": (C.c_int64, [_i32, _i32, _i32, _i32]), "paths_importance_proj_x6_workspace": (C.c_int64, [_i32]), "paths_last_error": (C.c_char_p, []), "paths_build_info": (C.c_char_p, []), "paths_abi_version": (_i32, []), "paths_stop_event_pending": (_i32, []), "paths_clear_stop_event": (_i32, []), "paths_adamw_chunk": (_i32, []), "paths_rank_joint_tile": (_i32, []), "paths_attention_wide_workspace": (C.c_int64, [_i32, _i32]), "paths_event_create": (_vp, []), "paths_stream_create_masked": (_vp, [_vp, _i32]),
-          "paths_pack_index_partials": (C.c_int64, [_i64])}
-
-ABI_VERSION = 3     # include/paths_hip.h: paths_abi_version() of the library this binding was written against
-_lib: Optional[C.CDLL] = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "paths_hip.h")
 
 
 class PathsHipError(RuntimeError):
     pass
+
+
+# The signatures are stated once, in include/paths_hip.h: the library's sources are compiled against it (csrc/common.h includes
+# it, so a definition that disagrees does not build) and this binding reads every argtypes / restype from it.  A new entry point
+# is defined in csrc/ and declared in the header; nothing is added here.
+_PARAMS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+           "size_t": C.c_size_t, "paths_stream_t": C.c_void_p}
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "void *": C.c_void_p, "const char *": C.c_char_p}
+_NAMED = re.compile(r"\b(paths_[a-z0-9_]+)\s*\(")
+_DECLARATION = re.compile(r"([A-Za-z_][\w \t]*[\w*][ \t*]*)" + _NAMED.pattern + r"([^;{()]*)\)\s*;")
+
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every function a C header declares.  Parameters: int, int64_t, float, uint32_t, uint64_t,
+    size_t, paths_stream_t and any pointer (c_void_p); returns: int, int64_t, void*, const char*.  Anything else raises, and so does a
+    ``paths_name(`` in the text (comments apart) that is not part of a declaration this reads: no function stays silently unbound."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    out = {}
+    for ret, name, params in _DECLARATION.findall(text):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret not in _RETURNS:
+            raise PathsHipError(f"declaration of {name}: return type '{ret}' is none of {sorted(_RETURNS)}")
+        if name in out:
+            raise PathsHipError(f"{name} is declared twice")
+        args = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = [w for w in p.replace("*", " * ").split() if w != "const"]
+            if "*" in words:
+                args.append(C.c_void_p)
+            elif len(words) == 2 and words[0] in _PARAMS:             # type and name
+                args.append(_PARAMS[words[0]])
+            else:
+                raise PathsHipError(f"declaration of {name}: parameter '{p.strip()}' is neither a pointer nor one of {sorted(_PARAMS)}")
+        out[name] = (_RETURNS[ret], args)
+    named = _NAMED.findall(text)
+    if len(named) != len(out):
+        raise PathsHipError(f"{len(named)} functions are named but {len(out)} declarations could be read: check "
+                            f"{sorted(set(named) - set(out)) or 'for a name used twice'}")
+    return out
+
+
+def _read_header() -> dict:
+    if not os.path.isfile(HEADER_PATH):
+        raise PathsHipError(f"{HEADER_PATH} not found: the binding reads every signature from the C header of the source tree")
+    with open(HEADER_PATH) as f:
+        try:
+            return parse_header(f.read())
+        except PathsHipError as e:
+            raise PathsHipError(f"{HEADER_PATH}: {e}") from None
+
+
+DECLARATIONS = _read_header()                                              # name -> (restype, [argtypes]), read once
+SIGNATURES = {name: args for name, (_, args) in DECLARATIONS.items()}      # name -> [argtypes]
+ABI_VERSION = 3     # include/paths_hip.h: paths_abi_version() of the library this binding was written against
+_lib: Optional[C.CDLL] = None
 
 
 def load() -> C.CDLL:
@@ -175,14 +84,11 @@ def load() -> C.CDLL:
             raise PathsHipError(f"{LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build()); "
                                 "paths_amd has no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        lib.paths_abi_version.restype = _i32
+        lib.paths_abi_version.restype = C.c_int
         if lib.paths_abi_version() != ABI_VERSION:
             raise PathsHipError(f"{LIB_PATH} has ABI version {lib.paths_abi_version()}, this binding needs {ABI_VERSION}: rebuild it "
                                 "(__graft_entry__.build())")
-        for name, args in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _i32
-        for name, (res, args) in _PLAIN.items():
+        for name, (res, args) in DECLARATIONS.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, res
         _lib = lib
@@ -227,23 +133,26 @@ def call(name: str, *args):
             fb.taken_at = len(TAPE) - 1                  # this call's kernel carries the block's stop event
 
 
+def _next_event():
+    """The event of the next tape position: taken from the recorder's pool, created when the pool has none left."""
+    pool = TAPE_EVENTS if TAPE_EVENTS is not None else [[], 0]
+    if pool[1] == len(pool[0]):
+        ev = load().paths_event_create()
+        if not ev:
+            raise PathsHipError("paths_event_create failed")
+        pool[0].append(ev)
+    pool[1] += 1
+    return pool[0][pool[1] - 1]
+
+
 def stream_wait(dst: "torch.cuda.Stream", src: "torch.cuda.Stream"):
     """``dst.wait_stream(src)``; recorded on the launch tape (as a paths_stream_wait with its own event) when one is being built."""
     dst.wait_stream(src)
     if TAPE is not None:
-        lib = load()
-        pool = TAPE_EVENTS if TAPE_EVENTS is not None else [[], 0]
-        if pool[1] == len(pool[0]):
-            ev = lib.paths_event_create()
-            if not ev:
-                raise PathsHipError("paths_event_create failed")
-            pool[0].append(ev)
-        ev = pool[0][pool[1]]
-        pool[1] += 1
-        TAPE.append((lib.paths_stream_wait, (dst.cuda_stream, src.cuda_stream, ev), "paths_stream_wait"))
+        TAPE.append((load().paths_stream_wait, (dst.cuda_stream, src.cuda_stream, _next_event()), "paths_stream_wait"))
 
 
-STOP_EVENTS = __import__("os").environ.get("PATHS_STOP_EVENTS", "1") != "0"
+STOP_EVENTS = os.environ.get("PATHS_STOP_EVENTS", "1") != "0"
 
 
 # entries of a launch tape that are not kernel launches on the block's stream (fork_behind looks for the block's LAST launch)
@@ -272,15 +181,7 @@ class fork_behind:
 
     def __enter__(self):
         if TAPE is not None and STOP_EVENTS:
-            lib = load()
-            pool = TAPE_EVENTS if TAPE_EVENTS is not None else [[], 0]
-            if pool[1] == len(pool[0]):
-                e = lib.paths_event_create()
-                if not e:
-                    raise PathsHipError("paths_event_create failed")
-                pool[0].append(e)
-            self.ev = pool[0][pool[1]]
-            pool[1] += 1
+            self.ev = _next_event()
             call("paths_set_stop_event", self.ev)
             self.prev, fork_behind.active = fork_behind.active, self
         return self

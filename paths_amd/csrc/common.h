@@ -7,6 +7,11 @@
 #include <stdio.h>
 #include <type_traits>
 
+// the public C ABI: every extern "C" definition in csrc/*.hip is compiled against its declaration (a mismatch is a
+// "conflicting types" error); inside the library paths_stream_t is the HIP type it stands for
+#define PATHS_STREAM_T hipStream_t
+#include "../../include/paths_hip.h"
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

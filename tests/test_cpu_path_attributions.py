@@ -1,8 +1,7 @@
 """CPU side of the attributions along the frozen path (paths_amd/saliency.py: integrated_gradients / smooth_grad): the
 restated Gaussian generator's statistics, the quadrature rules, the oracle-along-a-recorded-path reference (tests/path_ref.py) and
 its completeness, the argument checks, the header / binding of the two entry points and their host-side argument validation."""
-import os
-import re
+import ctypes
 import types
 
 import numpy as np
@@ -12,7 +11,6 @@ import torch
 from tests import helpers as H
 from tests import path_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ((1, 0), (2, 0), (0x1234, 7), (99, 3), (5, 5), (123456789, 42))        # (key_lo, key_hi)
 IG_STEPS = 8         # fixed by test_reference_completeness_fixes_the_steps; tests/test_gpu_path_attributions.py uses it
 
@@ -229,11 +227,10 @@ def test_heatmap_passes_the_new_keys_through():
 # ------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_points_and_the_binding_matches():
     from paths_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "paths_hip.h")).read(), flags=re.S)
     for name, nargs in (("paths_path_points", 13), ("paths_path_accumulate", 16)):
-        m = re.search(r"\bint\s+" + name + r"\s*\((.*?)\);", text, flags=re.S)
-        assert m, f"{name} is not declared in include/paths_hip.h"
-        assert len([a for a in m.group(1).split(",") if a.strip()]) == len(_lib.SIGNATURES[name]) == nargs
+        assert name in _lib.DECLARATIONS, f"{name} is not declared in include/paths_hip.h"
+        res, args = _lib.DECLARATIONS[name]
+        assert res is ctypes.c_int and len(args) == len(_lib.SIGNATURES[name]) == nargs
     assert _lib.ABI_VERSION == 3                                      # no existing signature changed
     import __graft_entry__ as g
     assert "path_rows.hip" in g.SOURCES

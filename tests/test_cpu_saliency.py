@@ -1,8 +1,8 @@
 """CPU side of the gradient x input attributions (paths_amd/saliency.py): target parsing against float64, the float64 row reference
 (tests/saliency_ref.py), the rasters of paths_amd.heatmap.saliency_map, the lstm=false rejection, the backward's weight-gradient
 switch and the host-side argument checks of paths_saliency_rows (no launch)."""
+import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -138,10 +138,9 @@ def test_weight_gradient_switch_nests_and_restores():
 
 def test_header_declares_the_symbol_and_the_binding_matches():
     from paths_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "paths_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+paths_saliency_rows\s*\((.*?)\);", text, flags=re.S)
-    assert m, "paths_saliency_rows is not declared in include/paths_hip.h"
-    assert len([a for a in m.group(1).split(",") if a.strip()]) == len(_lib.SIGNATURES["paths_saliency_rows"]) == 11
+    assert "paths_saliency_rows" in _lib.DECLARATIONS, "paths_saliency_rows is not declared in include/paths_hip.h"
+    res, args = _lib.DECLARATIONS["paths_saliency_rows"]
+    assert res is ctypes.c_int and len(args) == len(_lib.SIGNATURES["paths_saliency_rows"]) == 11
     assert _lib.ABI_VERSION == 3
 
 

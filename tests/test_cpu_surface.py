@@ -21,55 +21,126 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(paths_[a-z0-9_]+)\s*\(", text)))
 
 
-_C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "uint32_t": ctypes.c_uint32,
-            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t}
-
-
-def _ctype(decl: str, ret: bool = False):
-    """ctypes type of one C parameter (``const float* x``) or return type: pointers and paths_stream_t are c_void_p."""
-    words = decl.replace("*", " * ").split()
-    if "*" in words:
-        return ctypes.c_char_p if (ret and "char" in words) else ctypes.c_void_p
-    words = [w for w in words if w != "const"]
-    if not ret:
-        assert len(words) == 2, decl          # type and name
-    return ctypes.c_void_p if words[0] == "paths_stream_t" else _C_TYPES[words[0]]
-
-
-def header_declarations():
-    """name -> (return ctype, [parameter ctypes]) of every function declared in include/paths_hip.h."""
-    text = open(os.path.join(ROOT, "include", "paths_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    out = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t]*[\w*][ \t*]*)\b(paths_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text):
-        params = [a.strip() for a in params.split(",") if a.strip() and a.strip() != "void"]
-        assert name not in out, name
-        out[name] = (_ctype(ret, ret=True), [_ctype(a) for a in params])
-    return out
-
-
-def test_library_exports_every_declared_symbol_at_abi_3():
+def _built_library():
     from paths_amd import _lib
     if not os.path.isfile(_lib.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
+    return _lib
+
+
+_vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+# hand-written (return type, parameter types) of a few entry points per return type, read off include/paths_hip.h by eye
+EXPECTED = {
+    "paths_topk": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "paths_memset_zero": (_i, [_vp, ctypes.c_size_t, _vp]),
+    "paths_synth_grid": (_i, [_vp, _i, _i, _i, ctypes.c_uint32, _i, ctypes.c_uint64, _vp]),
+    "paths_dropout_mask": (_i, [_vp, _i64, ctypes.c_uint64, _f, _vp]),
+    "paths_abi_version": (_i, []),
+    "paths_x6_packed_bytes": (_i64, [_i, _i, _i]),
+    "paths_pack_index_partials": (_i64, [_i64]),
+    "paths_token0_ws_image_bytes": (_i64, []),
+    "paths_event_create": (_vp, []),
+    "paths_stream_create_masked": (_vp, [_vp, _i]),
+    "paths_last_error": (ctypes.c_char_p, []),
+    "paths_build_info": (ctypes.c_char_p, []),
+}
+
+
+def test_library_exports_every_declared_symbol_at_abi_3():
+    _lib = _built_library()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
     syms = header_symbols()
     assert len(syms) >= 16
     for s in syms:
-        assert hasattr(lib, s), f"{s} declared in include/paths_hip.h but not exported"
-    # every declared function is bound with exactly the declared parameter and return types, and nothing is bound that is not declared
-    decls = header_declarations()
-    assert sorted(decls) == syms
-    bound = {name: (ctypes.c_int, list(args)) for name, args in _lib.SIGNATURES.items()}
-    assert not set(bound) & set(_lib._PLAIN), "a function is bound twice"
-    bound.update({name: (res, list(args)) for name, (res, args) in _lib._PLAIN.items()})
-    assert sorted(bound) == syms, sorted(set(bound) ^ set(syms))
-    for name, (res, args) in bound.items():
-        assert (res, args) == decls[name], f"{name}: bound as {(res, args)}, declared as {decls[name]}"
-    lib.paths_abi_version.restype = ctypes.c_int
+        assert hasattr(raw, s), f"{s} declared in include/paths_hip.h but not exported"
+    # the binding binds exactly the declared names ...
+    assert sorted(_lib.DECLARATIONS) == sorted(_lib.SIGNATURES) == syms, sorted(set(_lib.DECLARATIONS) ^ set(syms))
+    # ... and the loaded library carries, for every one of them, the declared parameter and return types
+    lib = _lib.load()
+    for name in syms:
+        fn = getattr(lib, name)
+        res, args = _lib.DECLARATIONS[name]
+        assert res in (_i, _i64, _vp, ctypes.c_char_p), name
+        assert (fn.restype, list(fn.argtypes)) == (res, args) and args == _lib.SIGNATURES[name], name
+    for name, (res, args) in EXPECTED.items():
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == (res, args), f"{name}: bound as {(fn.restype, fn.argtypes)}, declared as {(res, args)}"
     assert lib.paths_abi_version() == 3
+
+
+def test_library_exports_nothing_the_header_does_not_declare():
+    """The direction the compiler cannot check: a function that is defined (and exported) but never declared."""
+    import shutil
+    _lib = _built_library()
+    readelf = "/opt/rocm/llvm/bin/llvm-readelf"
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    elif os.path.exists(readelf):
+        out = subprocess.run([readelf, "--dyn-syms", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+        out = "\n".join(l for l in out.splitlines() if " FUNC " in l and " UND " not in l)
+    else:
+        pytest.skip("neither nm nor llvm-readelf to list the dynamic symbols with")
+    exported = sorted(set(re.findall(r"\b(paths_[a-z0-9_]+)$", out, flags=re.M)))
+    assert exported == header_symbols(), sorted(set(exported) ^ set(header_symbols()))
+
+
+INLINE_HEADER = """
+/* paths_in_a_comment(int x); and a stray ( */
+#ifndef PATHS_STREAM_T
+#define PATHS_STREAM_T void*
+#endif
+typedef PATHS_STREAM_T paths_stream_t; // paths_other_comment(void);
+const char* paths_text(void);
+void* paths_handle(const uint32_t* mask, int words);
+int64_t paths_bytes(int a, size_t b);   /* bytes of ( */
+int paths_launch(const float* x, int64_t ld, float eps, uint32_t u, uint64_t key,
+                 int* const* rows,
+                 paths_stream_t stream);
+"""
+
+
+def test_header_parser_reads_the_declaration_forms_and_fails_loudly():
+    from paths_amd._lib import PathsHipError, parse_header
+    assert parse_header(INLINE_HEADER) == {
+        "paths_text": (ctypes.c_char_p, []),
+        "paths_handle": (_vp, [_vp, _i]),
+        "paths_bytes": (_i64, [_i, ctypes.c_size_t]),
+        "paths_launch": (_i, [_vp, _i64, _f, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp]),
+    }
+    with pytest.raises(PathsHipError, match="paths_odd.*double d"):            # a parameter type outside the list
+        parse_header(INLINE_HEADER + "int paths_odd(int a, double d);\n")
+    with pytest.raises(PathsHipError, match="paths_odd.*float"):               # a return type outside the list
+        parse_header(INLINE_HEADER + "float paths_odd(int a);\n")
+    with pytest.raises(PathsHipError, match="paths_odd"):                      # an unnamed parameter
+        parse_header(INLINE_HEADER + "int paths_odd(int);\n")
+    with pytest.raises(PathsHipError, match="6 functions.*5 declarations.*paths_cut"):    # no ';': caught by the count
+        parse_header(INLINE_HEADER + "int paths_cut(int a)\nint paths_next(int a);\n")
+    with pytest.raises(PathsHipError, match="twice"):
+        parse_header(INLINE_HEADER + "const char* paths_text(void);\n")
+
+
+TOPK_DEFINITION = """#include "common.h"
+extern "C" int paths_topk(const float* scores, %s ld, const int64_t* num_ims, int B, int n_max, int keep,
+                          int* keep_idx, int64_t ldk, int* keep_count, hipStream_t stream) { return 0; }
+"""
+
+
+def test_a_definition_that_disagrees_with_the_header_does_not_compile(tmp_path):
+    """Every source reaches csrc/common.h, which includes include/paths_hip.h: the compiler compares each definition with it."""
+    import __graft_entry__ as g
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    runs = {}
+    for ld_type in ("int", "int64_t"):
+        src = tmp_path / f"topk_{ld_type}.hip"
+        src.write_text(TOPK_DEFINITION % ld_type)
+        runs[ld_type] = subprocess.run([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-fsyntax-only", "-I", g.CSRC, str(src)],
+                                       capture_output=True, text=True)
+    bad, good = runs["int"], runs["int64_t"]
+    assert bad.returncode != 0 and "conflicting types" in bad.stderr and "paths_topk" in bad.stderr, bad.stderr
+    assert good.returncode == 0, good.stderr
 
 
 def test_invalid_arguments_are_reported_not_launched():
