@@ -97,6 +97,11 @@
  *                                      entry: never read, and a consumer never sees what the buffer held
  *   paths_pack_flags / _index / _rows  flags, index, count, partials, rows on entry: never read (flags is written in full by
  *                                      paths_pack_flags before paths_pack_index counts it)
+ * heat-map rasters
+ *   paths_raster_index                 locs rows of padding: never read; index: must be -1 on entry, status: must be zero on entry
+ *                                      (both written by the caller)
+ *   paths_raster_maps                  value rows of padding: never read (only rows an index grid names are); out on entry: never
+ *                                      read, every element of the padded allocation is written
  */
 #ifndef PATHS_HIP_H
 #define PATHS_HIP_H
@@ -897,6 +902,36 @@ int paths_visited_overlap(const uint8_t* bitmap, int64_t ldb, const int* gx, con
                           int patch_size, int Nm, int B, int C, int* overlap, paths_stream_t stream);
 int paths_level0_mask_rows(const int64_t* mask_ptrs, const int* gx, const int* gy, int B, int D, int64_t n0, float* fts, int64_t* row_ptrs,
                            const float* zero_row, paths_stream_t stream);
+
+/* Heat-map rasters on the device, a whole batch per call (paths_amd/heatmap.py:rasterize; csrc/raster.hip; the data of
+ * reference heatmap_visualise.py:147-171).  A raster is in finest cells: with L levels, f = 2^(L-1), slide b covers
+ * [gx[b] f, gy[b] f] cells of the batch's padded [GX f, GY f] (gx / gy: DEVICE tables [B] int32 of the LEVEL-0 grids, clamped to
+ * [0, GX] / [0, GY] by the kernels; GX / GY: the batch maxima); the patch of level l that covers finest cell (x, y) sits at cell
+ * (x >> (L-1-l), y >> (L-1-l)) of that level's grid [GX << l, GY << l].
+ *
+ * paths_raster_index: the map from cell to visited row of ONE level.  locs [B, N, 2] int64 in pixels (cell = locs / patch_size),
+ * num_ims [B] int64 (clamped to [0, N]).  index: int32 [B, GX << level, ldi] (ldi >= GY << level), every element -1 on entry
+ * (written by the caller, pad columns included).  For every row i < num_ims[b] whose cell lies inside slide b's own grid
+ * (gx[b] << level, gy[b] << level): index[b, cx, cy] = max(index[b, cx, cy], i) (integer atomicMax: of two rows on one cell the
+ * later one stays, whatever the schedule).  A valid row with a negative location or a cell outside its slide's grid is skipped and
+ * sets bit `level` of *status (int32, zeroed by the caller).  Rows of padding of locs (i >= num_ims[b]): never read.
+ *
+ * paths_raster_maps: all levels and slides in one launch, one thread per four consecutive finest cells of a raster row.
+ * table: DEVICE table [L][4] int64 = (address of level l's index grid, its row stride ldi_l, address of level l's value rows,
+ * their slide stride in elements): the value of row i of slide b is values_l[b * stride_l + i], fp32 (value_f64 = 0) or fp64 (1).
+ * offset_w: DEVICE [2] fp64 = (offset, w).  With idx = index_l[b, x >> (L-1-l), y >> (L-1-l)]:
+ *     v_l = idx >= 0 ? (double)(values_l[b, idx] + offset) : 0      the sum rounded in the VALUE's type (fp32 values: an fp32 add of
+ *                                                                   the fp32-rounded offset, what NumPy computes for float32 + float)
+ *     fold = 0 (planes):  out[b, l, x, y] = v_l                     out: [B, L, GX f, ldo]
+ *     fold = 1:           for l = L-2 .. 0: v_l += w * v_{l+1} wherever the folded v_{l+1} != 0;  out[b, x, y] = v_0     out: [B, GX f, ldo]
+ * in fp64, multiply and add rounded separately (no FMA); rounded once to the output type on the store: fp32 (out_f64 = 0) or fp64.
+ * ldo >= GY f, a multiple of 4; out 16-byte aligned: every store is 16 bytes, columns [GY f, ldo) and all cells outside a slide's
+ * own extent are written as +0.  Only rows an index grid names are read from the value rows (rows of padding: never read).  No
+ * atomics, no LDS, a launch shape fixed by (B, GX, ldo, L): bit-identical on repeat.  1 <= L <= 8, B <= 65535. */
+int paths_raster_index(const int64_t* locs, const int64_t* num_ims, const int* gx, const int* gy, int level, int patch_size, int N, int B,
+                       int GX, int GY, int* index, int64_t ldi, int* status, paths_stream_t stream);
+int paths_raster_maps(const int64_t* table, const int* gx, const int* gy, int L, int B, int GX, int GY, int value_f64, int out_f64, int fold,
+                      const double* offset_w, void* out, int64_t ldo, paths_stream_t stream);
 
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */

@@ -13,12 +13,18 @@ the mean over heads), one raster per level and no fold across levels; ``rollout_
 ``saliency_map`` for the gradient attributions and ``removed_map`` for the cells a member of
 :func:`paths_amd.saliency.removal_curves` turned to background.  Rasters are in units of the FINEST level's patches (one
 cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch_size / 2**(L-1)``.
+
+The functions above work on host records, one slide and one patch at a time, and define the contract.  :func:`rasterize` computes the
+same rasters on the device for all slides of a trace at once, without the host copies (csrc/raster.hip; ``removed_map`` excepted).
 """
 from __future__ import annotations
 
 from typing import Dict, List, Optional
 
 import numpy as np
+import torch
+
+from . import _lib
 
 
 # per-row attributions a saliency trace may carry: input_gradients', integrated_gradients' and smooth_grad's
@@ -156,7 +162,8 @@ def removed_map(levels: List[Dict[str, np.ndarray]], base_grid, count: int, orde
     """One [X0 * f, Y0 * f] uint8 map per level (f = magnification_factor**(L-1)): 1 over the footprint of every cell the member of
     :func:`paths_amd.saliency.removal_curves` that removes ``count`` patches (``out["counts"][s, slide]``) turned to background at
     that level - the patches of joint rank below ``count`` in ``order`` ("morf" / "lerf") -, 0 elsewhere; no fold across levels.
-    ``levels`` from :func:`hierarchy_from_trace` of the trace removal_curves returns."""
+    ``levels`` from :func:`hierarchy_from_trace` of the trace removal_curves returns.  NumPy only: :func:`rasterize` has no form of
+    this map (uint8, a predicate on the rank instead of a value)."""
     key = "removal_rank_" + order
     if key not in REMOVAL_RANKS:
         raise ValueError("order must be 'morf' or 'lerf', got %r" % (order,))
@@ -172,3 +179,137 @@ def removed_map(levels: List[Dict[str, np.ndarray]], base_grid, count: int, orde
         _paint(raster, lv["locs"][gone], np.ones(int(gone.sum()), np.uint8), magnification_factor ** (L - 1 - depth), patch_size)
         maps.append(raster)
     return maps
+
+
+# ---- the same rasters on the device, a whole batch per call (csrc/raster.hip) ----------------------------------------
+
+RASTER_KINDS = ("importance", "attention", "rollout", "attention_relevance") + SALIENCY_KINDS
+MAX_RASTER_LEVELS = 8          # include/paths_hip.h: paths_raster_maps
+_NO_KEY = {"attention": "level %d carries no attention: run recurse(..., attention=True)",
+           "rollout": "level %d carries no rollout: run recurse(..., rollout=True)",
+           "attention_relevance": "level %d carries no attention relevance: run saliency.attention_relevance"}
+
+
+def _level0_grids(base_grids, B: int) -> List[tuple]:
+    """One (X0, Y0) per slide from a list of pairs, a slide batch or a list of slides (``shape(0)``)."""
+    items = list(getattr(base_grids, "slides", base_grids))
+    if len(items) != B:
+        raise ValueError("base_grids: %d grids for the %d slides of the trace" % (len(items), B))
+    grids = [tuple(int(v) for v in (g.shape(0) if callable(getattr(g, "shape", None)) else g)) for g in items]
+    if any(len(g) != 2 or g[0] < 1 or g[1] < 1 for g in grids):
+        raise ValueError("base_grids: every grid is a pair of positive extents, got %r" % (grids,))
+    return grids
+
+
+def _raster_values(lv: dict, kind: str, layer: int, head: Optional[int]) -> torch.Tensor:
+    """The [B, N] value rows of one level (last stride 1; a view where the record already holds them that way)."""
+    if kind == "attention":
+        a = lv["attention"]                                                   # [B, layers, H, N]
+        v = a[:, layer].to(torch.float64).mean(dim=1) if head is None else a[:, layer, head]
+    else:
+        v = lv[kind]
+    if v.dtype not in (torch.float32, torch.float64):
+        v = v.to(torch.float32)
+    return v if v.stride(-1) == 1 else v.contiguous()
+
+
+def rasterize(trace: List[dict], base_grids, kind: str = "importance", *, layer: int = -1, head: Optional[int] = None, fold=None,
+              offset: Optional[float] = None, patch_size: int = 256, magnification_factor: int = 2, dtype: torch.dtype = torch.float32,
+              check: bool = True) -> List[torch.Tensor]:
+    """The rasters of the functions above for every slide of ``trace`` at once, on the device: two kernels (csrc/raster.hip) instead of
+    the per-slide host copies of :func:`hierarchy_from_trace` and the per-patch loop of ``_paint``.
+
+    ``trace``: the per-level records with their device tensors as ``recurse(..., trace=[])`` (with ``attention=`` / ``rollout=``),
+    ``saliency.input_gradients`` / ``integrated_gradients`` / ``smooth_grad`` / ``attention_relevance`` leave them.  ``base_grids``: one
+    level-0 ``(X0, Y0)`` per slide, or the slide batch / list of slides itself.  ``kind``: "importance", "attention" (decoder layer
+    ``layer``, head ``head`` or None = the mean over heads, taken in fp64), "rollout", "attention_relevance" or one of SALIENCY_KINDS.
+
+    Returns one tensor per slide, with f = 2**(L-1):
+      fold = w      ``[X0 f, Y0 f]``: ``value + offset`` per level, deeper levels folded upwards with weight w wherever they are non-zero
+                    (:func:`importance_map`'s rule for any kind);
+      fold = False  ``[L, X0 f, Y0 f]``: ``value + offset`` per level, 0 where the level did not visit (the ``*_map`` functions, stacked).
+    Defaults: "importance" fold = 0.5, offset = 1e-4 (= :func:`importance_map`); every other kind fold = False, offset = 0 (= its
+    ``*_map`` function).  ``dtype`` float64 gives the NumPy functions' values bit for bit, float32 (default) those rounded once.  The
+    tensors are views, narrowed to each slide's extent, of one allocation padded to the batch's largest grid.
+
+    ``check`` reads the kernels' status word (one host synchronise) and raises PathsHipError when a recorded location lies outside its
+    slide's grid; with ``check=False`` such rows are skipped silently.  Only ``magnification_factor`` 2 exists: the recursion expands a
+    patch into 2 x 2 children.  Host records stay with the NumPy functions: there is no CPU fallback here."""
+    if kind not in RASTER_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(repr(k) for k in RASTER_KINDS), kind))
+    if magnification_factor != 2:
+        raise ValueError("rasterize: magnification_factor must be 2 (the recursion's child expansion is 2 x 2), got %r" % (magnification_factor,))
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("rasterize: dtype must be torch.float32 or torch.float64, got %r" % (dtype,))
+    if isinstance(fold, bool) and fold:
+        raise ValueError("rasterize: fold is a weight, False or None")
+    if int(patch_size) < 1:
+        raise ValueError("rasterize: patch_size must be positive, got %r" % (patch_size,))
+    L = len(trace)
+    if not 1 <= L <= MAX_RASTER_LEVELS:
+        raise ValueError("rasterize: a trace of 1 to %d levels expected, got %d" % (MAX_RASTER_LEVELS, L))
+    B = int(trace[0]["locs"].shape[0])
+    for depth, lv in enumerate(trace):
+        if kind not in lv:
+            if kind in SALIENCY_KINDS:
+                raise KeyError("level %d carries no %s: take the trace from saliency.input_gradients / integrated_gradients / smooth_grad"
+                               % (depth, kind))
+            raise KeyError(_NO_KEY[kind] % depth if kind in _NO_KEY else kind)
+        if tuple(lv["locs"].shape) != (B, lv[kind].shape[-1], 2) or lv[kind].shape[0] != B or tuple(lv["num_ims"].shape) != (B,):
+            raise ValueError("rasterize: level %d: locs %s, num_ims %s and %s %s do not describe the same [B, N] rows"
+                             % (depth, tuple(lv["locs"].shape), tuple(lv["num_ims"].shape), kind, tuple(lv[kind].shape)))
+    grids = _level0_grids(base_grids, B)
+    if kind == "attention":
+        for depth, lv in enumerate(trace):
+            n_layers, n_heads = int(lv["attention"].shape[1]), int(lv["attention"].shape[2])
+            if not -n_layers <= layer < n_layers:
+                raise IndexError("rasterize: layer %d out of range for the %d decoder layers of level %d" % (layer, n_layers, depth))
+            if head is not None and not 0 <= head < n_heads:
+                raise IndexError("rasterize: head %d out of range for the %d heads of level %d" % (head, n_heads, depth))
+    for lv in trace:                                       # last of the checks, so that the others can be met without a GPU
+        _lib.require_cuda(lv["locs"], lv["num_ims"], lv[kind])
+    folded = (kind == "importance") if fold is None else fold is not False
+    w = 0.5 if fold is None or fold is False else float(fold)
+    off = (1e-4 if kind == "importance" else 0.0) if offset is None else float(offset)
+
+    dev = trace[0]["locs"].device
+    f = 1 << (L - 1)
+    GX, GY = max(g[0] for g in grids), max(g[1] for g in grids)
+    with torch.cuda.device(dev):
+        locs = [lv["locs"].to(torch.int64).contiguous() for lv in trace]                      # (no copies for a trace's own tensors)
+        num_ims = [lv["num_ims"].to(torch.int64).contiguous() for lv in trace]
+        values = [_raster_values(lv, kind, layer, head) for lv in trace]
+        if len({v.dtype for v in values}) > 1:
+            values = [v.to(torch.float64) for v in values]
+        # index grids of all levels in one allocation, filled with -1 once; rows padded to four cells (16-byte loads at the finest level)
+        ldi = [((GY << l) + 3) // 4 * 4 for l in range(L)]
+        sizes = [B * (GX << l) * ldi[l] for l in range(L)]
+        index = torch.full((sum(sizes),), -1, dtype=torch.int32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        ldo = (GY * f + 3) // 4 * 4
+        out = torch.empty((B, GX * f, ldo) if folded else (B, L, GX * f, ldo), dtype=dtype, device=dev)
+        # one host -> device copy: the per-level table, (offset, w) and the level-0 extents
+        host = np.zeros(4 * L + 2 + B, dtype=np.int64)
+        at = index.data_ptr()
+        for l in range(L):
+            host[4 * l:4 * l + 4] = (at, ldi[l], values[l].data_ptr(), values[l].stride(0))
+            at += 4 * sizes[l]
+        host[4 * L:4 * L + 2].view(np.float64)[:] = (off, w)
+        host[4 * L + 2:].view(np.int32)[:B] = [g[0] for g in grids]
+        host[4 * L + 2:].view(np.int32)[B:2 * B] = [g[1] for g in grids]
+        tables = torch.from_numpy(host).to(dev)
+        p_table = tables.data_ptr()
+        p_offw, p_gx = p_table + 8 * 4 * L, p_table + 8 * (4 * L + 2)
+        p_gy = p_gx + 4 * B
+        stream = _lib.stream()
+        for l in range(L):
+            _lib.call("paths_raster_index", locs[l].data_ptr(), num_ims[l].data_ptr(), p_gx, p_gy, l, int(patch_size), int(locs[l].shape[1]), B,
+                      GX, GY, int(host[4 * l]), ldi[l], status.data_ptr(), stream)
+        _lib.call("paths_raster_maps", p_table, p_gx, p_gy, L, B, GX, GY, int(values[0].dtype == torch.float64), int(dtype == torch.float64),
+                  int(folded), p_offw, out.data_ptr(), ldo, stream)
+        if check:
+            bits = int(status.item())
+            if bits:
+                raise _lib.PathsHipError("rasterize: level(s) %s hold a location outside their slide's grid (base_grids or patch_size do not "
+                                         "belong to this trace)" % ", ".join(str(l) for l in range(L) if bits >> l & 1))
+    return [out[b, :g[0] * f, :g[1] * f] if folded else out[b, :, :g[0] * f, :g[1] * f] for b, g in enumerate(grids)]
