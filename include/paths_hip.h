@@ -136,7 +136,7 @@ void* paths_stream_create_masked(const uint32_t* cu_mask, int words);
 int paths_event_destroy(void* event);
 int paths_stream_wait(paths_stream_t dst, paths_stream_t src, void* event);
 /* Stop events: paths_set_stop_event(ev) makes the next stop-capable launch of this host thread (the importance / projection finish
- * kernel of paths_importance_proj_x6, the kernel of paths_topk / paths_topk_rows) carry ev as its completion event - no event-record
+ * kernel of paths_importance_proj_x6, the kernel of paths_topk / paths_topk_rows and of their _tiled forms) carry ev as its completion event - no event-record
  * packet of its own in the launching queue; paths_flush_stop_event(src) records it on src the ordinary way if no launch took it;
  * paths_stream_wait_event(dst, ev): dst waits for ev.  paths_stop_event_pending(): 1 while the armed event has not been taken;
  * paths_clear_stop_event(): disarm without recording (error paths); paths_record_event(ev, s): plain hipEventRecord - the caller
@@ -662,6 +662,20 @@ int paths_topk(const float* scores, int64_t ld, const int64_t* num_ims, int B, i
 int paths_topk_rows(const float* scores, int64_t ld, const int64_t* num_ims, int B, int n_max, int keep,
                     int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t slide_rows,
                     int64_t* kept_rows, const float* zero_row, paths_stream_t stream);
+/* The same two selections for levels of more than 8,192 patches (csrc/topk_tiled.hip): same parameters, same outputs byte for byte,
+ * same key.  The twins above hold all keys of a slide in LDS, which ends at n_max = 8,192; these stream them through a fixed 16-KiB
+ * LDS tile, so n_max and ldk go up to PATHS_TOPK_TILED_MAX - the most patches the token-0 attention entries take (65,536 tokens, one of
+ * them the special token); past it n^2 rank counting stops being a small share of a level.  n_max <= 8,192 is accepted too (the two
+ * families can be compared on one input).  num_ims[b] is clamped to [0, n_max].  Return -1 without launching unless B > 0,
+ * 1 <= n_max <= PATHS_TOPK_TILED_MAX, keep is -1 or > 0, (keep < 0 ? n_max : min(keep, n_max)) <= ldk <= PATHS_TOPK_TILED_MAX,
+ * ld >= n_max and no required pointer is null; the _rows form also needs row_ld > 0 and slide_rows >= n_max.  One launch each, which
+ * carries a pending stop event like the twins' (paths_set_stop_event). */
+#define PATHS_TOPK_TILED_MAX 65535
+int paths_topk_tiled(const float* scores, int64_t ld, const int64_t* num_ims, int B, int n_max, int keep,
+                     int* keep_idx, int64_t ldk, int* keep_count, paths_stream_t stream);
+int paths_topk_rows_tiled(const float* scores, int64_t ld, const int64_t* num_ims, int B, int n_max, int keep,
+                          int* keep_idx, int64_t ldk, int* keep_count, const float* row_base, int64_t row_ld, int64_t slide_rows,
+                          int64_t* kept_rows, const float* zero_row, paths_stream_t stream);
 
 /* 4-child expansion, bounds + background filter, stable compaction (reference data_utils/slide.py:303-331).
  *   mask_ptrs[b] -> uint8 [X*Y] tissue mask of the NEXT level (1 = row sum != 0).  status bit0: a slide

@@ -1,4 +1,5 @@
-// The 64-bit key of the rank-counting kernels (select.hip: paths_topk / paths_topk_rows; perturb_rows.hip: paths_rank_joint).
+// The 64-bit key of the rank-counting kernels (select.hip: paths_topk / paths_topk_rows; topk_tiled.hip: their _tiled forms;
+// perturb_rows.hip: paths_rank_joint).
 #pragma once
 #include <stdint.h>
 

@@ -424,6 +424,17 @@ def _child_capacity(n: int, keep: int):
     return cap_keep, 4 * cap_keep
 
 
+TOPK_LDS_MAX = 8192       # csrc/select.hip TOPK_MAX: the most keys paths_topk / paths_topk_rows hold in LDS
+
+
+def topk_entry(N: int, rows: bool) -> str:
+    """The top-K entry point for a level of ``N`` (padded) patches: the LDS-resident kernel up to 8,192, above that its tiled form
+    (csrc/topk_tiled.hip; same arguments, same outputs), which refuses N above PATHS_TOPK_TILED_MAX = 65,535 itself.  ``rows``: the
+    form that also writes the kept rows' addresses."""
+    name = "paths_topk_rows" if rows else "paths_topk"
+    return name if N <= TOPK_LDS_MAX else name + "_tiled"
+
+
 def _level_sizes(n0: int, keep_patches, num_levels: int) -> List[int]:
     """Padded patch count of every level of the optimistic pass (the careful path may grow a level: _expand_children)."""
     sizes = [n0]
@@ -600,10 +611,10 @@ def _child_step(r, i: int, lv, out, keep: int):
         if rows_in_place:
             # ... with the addresses of the kept parents' h rows (row b, i -> ctx_patch[b, keep_idx[b, i], :D]) for the parent GEMM
             kept_rows = torch.empty((B, cap_keep), **r.i64)
-            ops.timed("topk", lambda: _lib.call("paths_topk_rows", p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep,
+            ops.timed("topk", lambda: _lib.call(topk_entry(N, True), p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep,
                                                 p(keep_count), p(out["ctx_patch"]), Dp, N, p(kept_rows), p(r.zero_row), st))
         else:
-            _lib.call("paths_topk", p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
+            _lib.call(topk_entry(N, False), p(out["importance"]), N, p(lv.num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
     hp = ops.parent_partials(r.lstm_pack, out["ctx_patch"], keep_idx, keep_count, kept_rows) if share_parent else None
     st2 = r.par_stream.cuda_stream if forked else st
     nx = SimpleNamespace(fts=None, x_rows=None, staged=None, state_prev=None, parent=None)
@@ -831,7 +842,7 @@ def _recurse_train_body(model, batch, keep_patches, num_levels, careful, trace=N
         else:
             keep_idx = torch.empty((B, cap_keep), **i32)
             keep_count = torch.empty((B,), **i32)
-            _lib.call("paths_topk", p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
+            _lib.call(topk_entry(N, False), p(importance), N, p(num_ims), B, N, keep, p(keep_idx), cap_keep, p(keep_count), st)
         Nn, num_next, locs_next, parent_next, src_row, src_cell, child_pos, hp_row = _expand_children(
             batch, i + 1, mc.patch_size, keep_idx, keep_count, locs, N, Nn, status, st, careful, True, parent_form)
         if rec is not None:
