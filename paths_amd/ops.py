@@ -106,8 +106,13 @@ def split_planes() -> int:
     return 2 if GEMM_MODE == "h3" else 3
 
 
+def a_scale_of(planes: int) -> float:
+    """The activation scale of a split-operand launch: A_SCALE for the two fp16 planes, 1 for every bf16 split."""
+    return A_SCALE if planes == 2 else 1.0
+
+
 def a_scale() -> float:
-    return A_SCALE if GEMM_MODE == "h3" else 1.0
+    return a_scale_of(2 if GEMM_MODE == "h3" else 3)
 
 
 def x6_pack(w: torch.Tensor, n_pad: Optional[int] = None, planes: Optional[int] = None, w_scale: Optional[float] = None):
@@ -233,20 +238,30 @@ def token0_counters(dev, B: int) -> torch.Tensor:
     return t
 
 
+def weight_image(cache: Dict[str, object], key: str, w, planes: int, n_pad: Optional[int] = None, lagged: bool = False):
+    """(image, w_scale) of the fp32 weight ``w`` [N, K] for the split ``planes``, its rows padded to ``n_pad``: packed on first use
+    and cached in ``cache`` (a pack dict, rebuilt when weights change) once per (key, planes, n_pad).  ``lagged`` (training,
+    two-plane split): see :func:`_pow2_scale_lagged`."""
+    k6 = f"{key}_split{planes}" + ("" if n_pad is None else f"_pad{n_pad}")
+    if k6 not in cache:
+        ws = _pow2_scale_lagged(w, cache["_owner"], key) if (lagged and planes == 2) else None
+        cache[k6] = x6_pack(w, n_pad=n_pad, planes=planes, w_scale=ws)
+    return cache[k6]
+
+
 def _x6_of(pack: Dict[str, object], key: str, planes: Optional[int] = None, lagged: bool = False):
-    """(image, w_scale) of pack[key] for the given (default: current) split, built on first use and cached beside it (the pack
-    dict is rebuilt when weights change).  ``lagged`` (training, two-plane split): see :func:`_pow2_scale_lagged`."""
-    planes = split_planes() if planes is None else planes
-    k6 = f"{key}_split{planes}"
-    if k6 not in pack:
-        ws = _pow2_scale_lagged(pack[key], pack["_owner"], key) if (lagged and planes == 2) else None
-        pack[k6] = x6_pack(pack[key], planes=planes, w_scale=ws)
-    return pack[k6]
+    """:func:`weight_image` of pack[key] for the given (default: current) split."""
+    return weight_image(pack, key, pack[key], split_planes() if planes is None else planes, lagged=lagged)
 
 
-def pe_table(lvl_pack: Dict[str, object], pe_mode: int, d: int, rows: int) -> torch.Tensor:
+def pe_operands(mc, lvl_pack: Dict[str, object]):
+    """(pe_mode, div): 2 / 1 for the 2-D / 1-D positional encoding and that mode's frequency vector (:func:`_pe_divs`)."""
+    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    return pe_mode, lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]
+
+
+def pe_table(pe_mode: int, div: torch.Tensor, d: int, rows: int) -> torch.Tensor:
     """[cap >= rows, d/2 or d] table of the positional-encoding sin/cos values (paths_pe_table), cached beside the weights."""
-    div = lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]
     key = (pe_mode, d, div.device)
     tab = _PE_TABLES.get(key)
     if tab is None or tab.shape[0] < rows:
@@ -327,6 +342,16 @@ def pack_lstm(lstm) -> Dict[str, torch.Tensor]:
     return packed
 
 
+def _pack_aggregator_entries(agg) -> Dict[str, object]:
+    """What :func:`pack_level` and :func:`pack_aggregator` both hold of an aggregator: the decoder layers, the final norm, the special
+    token, proj_in's bias and the positional-encoding constants."""
+    c = lambda t: t.detach().float().contiguous()
+    div_1d, div_2d = _pe_divs(agg.dim, agg.proj_in.weight.device)
+    return {"layers": _pack_decoder_layers(agg), "lnfg": c(agg.transformer.decoder.norm.weight), "lnfb": c(agg.transformer.decoder.norm.bias),
+            "lnf_eps": float(agg.transformer.decoder.norm.eps), "special": c(agg.special_token), "bp": c(agg.proj_in.bias),
+            "div_1d": div_1d, "div_2d": div_2d}
+
+
 def pack_level(proc) -> Dict[str, object]:
     """Per-level tensors in the layout the kernels read.  Dead encoder / cross-attention matrices are
     never touched (only ``multihead_attn.out_proj.bias`` is live)."""
@@ -339,11 +364,8 @@ def pack_level(proc) -> Dict[str, object]:
         return packed
     with torch.no_grad():
         c = lambda t: t.detach().float().contiguous()
-        d = agg.dim
-        layers = _pack_decoder_layers(agg)
-        dev = agg.proj_in.weight.device
-        div_1d, div_2d = _pe_divs(d, dev)
         packed = {
+            **_pack_aggregator_entries(agg),
             "w_ip": torch.cat([proc.importance_mlp[0].weight, agg.proj_in.weight], dim=0).float().contiguous(),
             # forward kernels: rows interleaved in blocks of 64 so that each column half of a workgroup owns 64 hidden units
             # and 64 token channels (csrc/gemm_epi.h EpiImpProj)
@@ -351,11 +373,6 @@ def pack_level(proc) -> Dict[str, object]:
                                    proc.importance_mlp[0].weight[64:], agg.proj_in.weight[64:]], dim=0).float().contiguous(),
             "b1": c(proc.importance_mlp[0].bias), "w2": c(proc.importance_mlp[2].weight.view(-1)),
             "b2": c(proc.importance_mlp[2].bias.view(-1)),        # read on the device (a .item() here was a host sync per re-pack)
-            "bp": c(agg.proj_in.bias), "special": c(agg.special_token),
-            "div_1d": div_1d, "div_2d": div_2d,
-            "layers": layers,
-            "lnfg": c(agg.transformer.decoder.norm.weight), "lnfb": c(agg.transformer.decoder.norm.bias),
-            "lnf_eps": float(agg.transformer.decoder.norm.eps),
             "wcls": c(proc.classification_layer.weight), "bcls": c(proc.classification_layer.bias),
             "_owner": proc,
         }
@@ -419,10 +436,7 @@ def pack_aggregator(agg) -> Dict[str, object]:
         c = lambda t: t.detach().float().contiguous()
         d = agg.dim
         dev = agg.proj_in.weight.device
-        div_1d, div_2d = _pe_divs(d, dev)
-        packed = {"layers": _pack_decoder_layers(agg), "lnfg": c(agg.transformer.decoder.norm.weight), "lnfb": c(agg.transformer.decoder.norm.bias),
-                  "lnf_eps": float(agg.transformer.decoder.norm.eps), "special": c(agg.special_token), "bp": c(agg.proj_in.bias),
-                  "wp": c(agg.proj_in.weight), "div_1d": div_1d, "div_2d": div_2d,
+        packed = {**_pack_aggregator_entries(agg), "wp": c(agg.proj_in.weight),
                   "wcls": torch.zeros((1, d), device=dev, dtype=torch.float32), "bcls": torch.zeros((1,), device=dev, dtype=torch.float32),
                   "_owner": agg}
     agg._paths_pack = (key, packed)
@@ -467,11 +481,10 @@ def check_aggregator_geometry(d: int, H: int):
 def check_supported(mc, training: bool = False):
     """Configurations this build runs on the HIP path; everything else is rejected loudly."""
     if not fast_path(mc):
-        d, H, Hi = mc.trans_dim, mc.trans_heads, mc.importance_mlp_hidden_dim
-        if d % 32 or d > 2048 or H < 1 or d % H or padded_head_dim(d // H) > 1024 or H * padded_head_dim(d // H) > 2048 or Hi < 1 or Hi > 1024:
-            raise NotImplementedError("the shape-generic aggregator kernels need trans_dim % 32 == 0 (<= 2048, also after padding its heads to 16 / 32 / 48 / 64 "
-                                      "or a multiple of 32), trans_dim % trans_heads == 0 and importance_mlp_hidden_dim <= 1024 "
-                                      f"(got trans_dim {d}, trans_heads {H}, importance hidden {Hi})")
+        Hi = mc.importance_mlp_hidden_dim
+        check_aggregator_geometry(mc.trans_dim, mc.trans_heads)
+        if Hi < 1 or Hi > 1024:
+            raise NotImplementedError(f"the shape-generic importance kernels need 1 <= importance_mlp_hidden_dim <= 1024 (got {Hi})")
         if training and Hi % 4:
             raise NotImplementedError("training at aggregator geometries other than trans_dim=128 / 4 heads / importance hidden 128 needs "
                                       f"importance_mlp_hidden_dim % 4 == 0 (got {Hi}); inference runs")
@@ -511,6 +524,13 @@ def generic_pack(lvl_pack: Dict[str, object], mc) -> Dict[str, object]:
 GENERIC_SPLIT = os.environ.get("PATHS_GENERIC_SPLIT", "1") != "0"   # shape-generic INFERENCE: big GEMMs on the split-fp16 matrix-core kernel
 
 
+def generic_add_route(mc, D: int, Hc: Optional[int]) -> bool:
+    """A level of an aggregator geometry other than the shipped one runs the tuned LSTM kernels and takes the importance / projection
+    products from x + h1 summed while it is staged (:func:`importance_proj_generic_add`): the only generic form that reads feature
+    rows at their addresses.  ``Hc``: the LSTM's hidden width."""
+    return bool(not fast_path(mc) and mc.lstm and use_x6(D, Hc) and split_planes() == 2 and GENERIC_ADD and GENERIC_SPLIT and D % 128 == 0)
+
+
 def gemm_f32(a, lda: int, w_pad: torch.Tensor, bias, out, ldo: int, M: int, N: int, K: int, act: int = 0, residual=None, ldr: int = 0,
              split=None):
     """out[M, N] = act(a[M, K] w^T + bias) (+ residual) on the f32-input matrix cores (exact fp32 FMA chains).
@@ -520,10 +540,7 @@ def gemm_f32(a, lda: int, w_pad: torch.Tensor, bias, out, ldo: int, M: int, N: i
     ptr = _lib.ptr
     if split is not None and GENERIC_SPLIT and GEMM_MODE != "f32" and M >= 1024 and K >= 128 and K % 32 == 0:
         cache, key = split
-        k6 = f"{key}_x6_{split_planes()}"
-        if k6 not in cache:
-            cache[k6] = x6_pack(w_pad[:N].contiguous(), n_pad=(N + 255) // 256 * 256)
-        img, ws = cache[k6]
+        img, ws = weight_image(cache, key, w_pad[:N].contiguous(), split_planes(), n_pad=(N + 255) // 256 * 256)
         _lib.call("paths_gemm_nt_x6", ptr(a), lda, img.data_ptr(), K, 0, ptr(bias), ptr(out), ldo, M, N, (N + 255) // 256 * 256, K, act,
                   ptr(residual), ldr, None, 0, 0, split_planes(), ws, a_scale(), _lib.stream())
         return
@@ -550,9 +567,9 @@ def importance_proj_generic(mc, lvl_pack, src, ld_src: int, locs, num_ims, B: in
     if not train:
         pproj = torch.empty((M, d), device=dev, dtype=torch.float32)
     gemm_f32(src, ld_src, gp["wp"], None, pproj, d, M, d, D, split=None if train else (gp, "wp"))
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    pe_mode, div = pe_operands(mc, lvl_pack)
     _lib.call("paths_tokens_assemble", p(pproj), d, p(imp_out), imp_mul, p(lvl_pack["bp"]), p(lvl_pack["special"]),
-              p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), p(locs), N, mc.patch_size, pe_mode, d, B, p(tokens), st)
+              p(div), p(locs), N, mc.patch_size, pe_mode, d, B, p(tokens), st)
 
 
 def importance_proj(mc, lvl_pack, src, x_rows, add, locs, num_ims, pe_tab, imp_mul: int, imp_out, tokens, hid, pproj, B: int, N: int, D: int,
@@ -564,10 +581,10 @@ def importance_proj(mc, lvl_pack, src, x_rows, add, locs, num_ims, pe_tab, imp_m
     ``splitk``: two k halves on twice the blocks + an epilogue launch (M / 128 blocks fill half the chip at K = 2048 x 8 slides).
     ``hid`` / ``pproj`` (training): keep relu(src W1^T + b1) and src Wp^T for the backward; ``lagged``: see :func:`_x6_of`."""
     p = _lib.ptr
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    pe_mode, div = pe_operands(mc, lvl_pack)
     M = B * N
     common = (p(lvl_pack["b1"]), p(lvl_pack["w2"]), p(lvl_pack["b2"]),
-              p(lvl_pack["bp"]), p(lvl_pack["special"]), p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]),
+              p(lvl_pack["bp"]), p(lvl_pack["special"]), p(div),
               p(pe_tab), pe_tab.shape[0] if pe_tab is not None else 0, p(locs),
               p(num_ims), N, mc.patch_size, pe_mode, imp_mul, p(imp_out), p(tokens), p(hid), p(pproj),
               M, D, mc.importance_mlp_hidden_dim, mc.trans_dim, 1 if skip_padding else 0)
@@ -580,7 +597,7 @@ def importance_proj(mc, lvl_pack, src, x_rows, add, locs, num_ims, pe_tab, imp_m
     if splitk:
         splitk_ws = torch.empty((int(_lib.load().paths_importance_proj_x6_workspace(M)),), device=locs.device, dtype=torch.uint8)
     _lib.call("paths_importance_proj_x6" + (h16 if src is None else ""), p(src), D, p(x_rows) if src is None else None, p(add),
-              add.stride(1) if add is not None else 0, p(wip), *common, planes, wip_s, A_SCALE if planes == 2 else 1.0,
+              add.stride(1) if add is not None else 0, p(wip), *common, planes, wip_s, a_scale_of(planes),
               p(splitk_ws), _lib.stream())
 
 
@@ -601,19 +618,17 @@ def importance_proj_generic_add(mc, lvl_pack, src, x_rows, add, locs, num_ims, B
     # twice the column tiles fills it once.  The relu of the hidden layer moves into paths_importance_rows (relu = 1).
     n = Hi + d
     n_pad = min((n + 255) // 256 * 256, (n + 191) // 192 * 192)      # (128 x 256 or 128 x 192 tiles, whichever pads less: 320 -> 384, not 512)
-    k6 = f"w1p_x6_{split_planes()}"
-    if k6 not in gp:
+    if "w1p" not in gp:
         gp["w1p"] = torch.cat([gp["w1"][:Hi], gp["wp"][:d]], dim=0).contiguous()
         gp["b1p"] = torch.cat([lvl_pack["b1"], torch.zeros((d,), device=dev, dtype=torch.float32)])
-        gp[k6] = x6_pack(gp["w1p"], n_pad=n_pad)
-    img, ws = gp[k6]
+    img, ws = weight_image(gp, "w1p", gp["w1p"], split_planes(), n_pad=n_pad)
     # (skipped tiles of padding stay undefined: paths_importance_rows writes 0 for padded rows without looking at them and
     # paths_tokens_assemble selects on that 0 - only when the importance does not multiply the tokens does the buffer need a fill;
     # _lib.zeros: the fill is repeated when a recorded launch tape is replayed)
     hp_ = (_lib.zeros if (skip_padding and not imp_mul) else torch.empty)((M, n), device=dev, dtype=torch.float32)
     _lib.call("paths_gemm_add_nt_x6_h16" if x_rows_h16 else "paths_gemm_add_nt_x6", p(src) if x_rows is None else None, D, p(x_rows), p(add), add.stride(1), img.data_ptr(), D, p(gp["b1p"]), p(hp_), n,
               M, n, n_pad, D, 0, nim, N, ws, a_scale(), st)
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    pe_mode, div = pe_operands(mc, lvl_pack)
     if pe_tab is not None and FUSE_IMPORTANCE_TOKENS:
         # importance + tokens in one pass over the product's rows, sin / cos from the table (csrc/generic.hip: 6.5 + 13.8 us -> one launch)
         _lib.call("paths_importance_tokens_rows", p(hp_), n, p(lvl_pack["w2"]), p(lvl_pack["b2"]), p(num_ims), N, M, Hi, p(imp_out), 1, imp_mul,
@@ -621,7 +636,7 @@ def importance_proj_generic_add(mc, lvl_pack, src, x_rows, add, locs, num_ims, B
         return
     _lib.call("paths_importance_rows", p(hp_), n, p(lvl_pack["w2"]), p(lvl_pack["b2"]), p(num_ims), N, M, Hi, p(imp_out), 1, st)
     _lib.call("paths_tokens_assemble", hp_.data_ptr() + 4 * Hi, n, p(imp_out), imp_mul, p(lvl_pack["bp"]), p(lvl_pack["special"]),
-              p(lvl_pack["div_2d" if pe_mode == 2 else "div_1d"]), p(locs), N, mc.patch_size, pe_mode, d, B, p(tokens), st)
+              p(div), p(locs), N, mc.patch_size, pe_mode, d, B, p(tokens), st)
 
 
 def fp8_pack(lvl_pack: Dict[str, object], mc) -> Dict[str, object]:
@@ -722,14 +737,20 @@ def slide_ctx_operands(lvl_pack, ctx_prev, ctx_all, B: int, d: int, dev, mode: O
     return res, cat, cat.shape[1] if cat is not None else 0, ctx_out, logits
 
 
+def _head_args(lvl_pack, head):
+    """The twelve arguments every kernel with a level's head takes for it: decoder.norm, the slide-context residual / concat, the
+    classifier and both outputs; ``head`` = :func:`slide_ctx_operands`."""
+    p = _lib.ptr
+    res, cat, depth, ctx_out, logits = head
+    return (p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res), res.stride(0) if res is not None else 0, p(cat), depth,
+            p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits))
+
+
 def final_head(lvl_pack, x, ldx: int, head, B: int, d: int, any_width: bool):
     """decoder.norm of the rows ``x`` (row stride ldx) + slide-context residual / concat + classifier (reference model/aggregator.py:75,
     model/paths.py:130-139); ``head`` = :func:`slide_ctx_operands`.  ``any_width``: the shape-generic kernel (csrc/generic.hip)."""
-    p = _lib.ptr
-    res, cat, depth, ctx_out, logits = head
-    _lib.call("paths_final_head_any" if any_width else "paths_final_head", p(x), ldx, p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res),
-              res.stride(0) if res is not None else 0, p(cat), depth, p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1],
-              lvl_pack["wcls"].shape[1], p(ctx_out), p(logits), B, d, lvl_pack["lnf_eps"], _lib.stream())
+    _lib.call("paths_final_head_any" if any_width else "paths_final_head", _lib.ptr(x), ldx, *_head_args(lvl_pack, head),
+              B, d, lvl_pack["lnf_eps"], _lib.stream())
 
 
 def token0_tail_ws(lvl_pack, x, num_ims, head, status, B: int, T: int, d: int, H: int, qscale: float, special_last: int):
@@ -738,15 +759,13 @@ def token0_tail_ws(lvl_pack, x, num_ims, head, status, B: int, T: int, d: int, H
     ``special_last``: the special token sits at index num_ims[b] instead of 0 (token order of the fused finish)."""
     p = _lib.ptr
     w = lvl_pack["layers"][-1]
-    res, cat, depth, ctx_out, logits = head
     img = token0_ws_image(w, qscale)
     part = torch.empty((int(_lib.load().paths_token0_ws_partials_d(B, T, d)),), device=x.device, dtype=torch.float32)
     cnt = token0_counters(x.device, B)
     _lib.call(
         "paths_token0_tail_ws", p(x), p(num_ims), p(img), w["bqkv"].data_ptr() + 4 * 2 * d, p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
         p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["b1"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-        p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res), res.stride(0) if res is not None else 0, p(cat), depth,
-        p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
+        *_head_args(lvl_pack, head),
         p(part), p(cnt), p(status), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], special_last, _lib.stream())
 
 
@@ -755,13 +774,11 @@ def token0_tail(lvl_pack, x, q, k, v, num_ims, head, B: int, T: int, d: int, H: 
     single-query attention from fp32 q, k, v, the row chain, decoder.norm, the slide-context residual and the classifier."""
     p = _lib.ptr
     w = lvl_pack["layers"][-1]
-    res, cat, depth, ctx_out, logits = head
     ws_part = torch.empty((B * H * 16 * 36,), device=x.device, dtype=torch.float32)
     _lib.call(
         "paths_token0_tail", p(x), p(q), p(k), p(v), p(num_ims), p(w["wo"]), p(w["bo"]), p(w["ln1g"]), p(w["ln1b"]),
         p(w["cab"]), p(w["ln2g"]), p(w["ln2b"]), p(w["w1"]), p(w["b1"]), p(w["w2"]), p(w["b2"]), p(w["ln3g"]), p(w["ln3b"]),
-        p(lvl_pack["lnfg"]), p(lvl_pack["lnfb"]), p(res), res.stride(0) if res is not None else 0, p(cat), depth,
-        p(lvl_pack["wcls"]), p(lvl_pack["bcls"]), logits.shape[1], lvl_pack["wcls"].shape[1], p(ctx_out), p(logits),
+        *_head_args(lvl_pack, head),
         p(ws_part), B, T, d, H, w["eps"], lvl_pack["lnf_eps"], _lib.stream())
 
 
@@ -781,11 +798,30 @@ def token_layer_f32(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B: int, T: i
 
 
 def _tlayer_ws_biases(post, nxt):
-    """The eleven bias / LayerNorm vectors of the weight-stationary token-layer kernels: ten of the chain of ``post``, in_proj's of ``nxt``."""
+    """The eleven bias / LayerNorm vectors of the image-fed token-layer kernels: ten of the chain of ``post``, in_proj's of ``nxt``."""
     p = _lib.ptr
     g = lambda dct, key: p(dct[key]) if dct is not None else None
     return (g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
             g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"))
+
+
+def tlayer_operands(post, nxt, kind: str):
+    """(ip, sp, iq, sq): :func:`_tlayer_images` of the chain of ``post`` and of the in_proj of ``nxt`` for paths_token_layer_<kind>;
+    a side that is None gets no image and the neutral scales."""
+    ip, sp = _tlayer_images(post, 0, kind) if post is not None else (None, (1.0, 1.0, 1.0))
+    iq, sq = _tlayer_images(nxt, 1, kind) if nxt is not None else (None, (1.0,))
+    return ip, sp, iq, sq
+
+
+def token_layer_h3(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B: int, T: int, d: int, H: int, qscale: float, max_tokens: int = 0,
+                   qkv_images=None):
+    """:func:`token_layer_f32` on the two-plane split-operand kernel (csrc/tlayer_h3.hip), padded token rows skipped;
+    ``qkv_images``: the in_proj of ``nxt`` also writes q | k | v into the attention's operand images."""
+    p = _lib.ptr
+    ip, sp, iq, sq = tlayer_operands(post, nxt, "h3")
+    _lib.call("paths_token_layer_h3", p(x_in), p(attn) if post else None, p(x_out) if post else None, p(ip), p(iq),
+              *_tlayer_ws_biases(post, nxt), sp[0], sp[1], sp[2], sq[0], p(q), p(k), p(v), p(num_ims), B, T, d, H,
+              1 if post else 0, 1 if nxt else 0, 1, qscale, (post or nxt)["eps"], max_tokens, p(qkv_images), _lib.stream())
 
 
 def token_layer_ws(x_in, x_out, o_img, post, nxt, qkv_img, num_ims, B: int, T: int, d: int, H: int, qscale: float):
@@ -793,8 +829,7 @@ def token_layer_ws(x_in, x_out, o_img, post, nxt, qkv_img, num_ims, B: int, T: i
     writes ``x_out``; the in_proj of ``nxt`` writes q | k | v straight into the attention's operand images ``qkv_img``.  Either of
     ``post`` / ``nxt`` may be None."""
     p = _lib.ptr
-    ip, sp = tlayer_ws_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
-    iq, sq = tlayer_ws_images(nxt, 1) if nxt is not None else (None, (1.0,))
+    ip, sp, iq, sq = tlayer_operands(post, nxt, "ws")
     _lib.call("paths_token_layer_ws", p(x_in), None, p(o_img) if post is not None else None, p(x_out) if post is not None else None,
               p(ip), p(iq), *_tlayer_ws_biases(post, nxt), sp[0], sp[1], sp[2], sq[0], p(qkv_img) if nxt is not None else None,
               p(num_ims), B, T, d, H, 1 if post is not None else 0, 1 if nxt is not None else 0, 1, qscale, (post or nxt)["eps"], None, 0,
@@ -807,9 +842,8 @@ def token_layer_ws_rows(x_in, attn, post, nxt, num_ims, B: int, T: int, d: int, 
     (the chain's output rows or None, the q | k | v rows or None)."""
     p = _lib.ptr
     f32 = dict(device=x_in.device, dtype=torch.float32)
-    ip, sp = tlayer_ws_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
+    ip, sp, iq, sq = tlayer_operands(post, nxt, "ws")
     x_out = torch.empty((B * T, d), **f32) if post is not None else None
-    iq, sq = tlayer_ws_images(nxt, 1) if nxt is not None else (None, (1.0,))
     if nxt is not None and qkv is None:
         qkv = torch.empty((B * T, 3 * d), **f32)
     _lib.call("paths_token_layer_ws_rows", p(x_in), p(attn) if post is not None else None, p(x_out), p(ip), p(iq), *_tlayer_ws_biases(post, nxt),
@@ -1013,7 +1047,8 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
     locs = locs.contiguous()
     num_ims = num_ims.contiguous()
     assert locs.dtype == torch.int64 and num_ims.dtype == torch.int64
-    pe_mode = 2 if mc.pos_encoding_mode == "2d" else 1
+    pe_mode, pe_div = pe_operands(mc, lvl_pack)
+    imp_mul = 1 if mc.importance_mode == "mul" else 0
     tokens = torch.empty((B, T, d), **f32)
 
     x6 = use_x6(D, lstm_pack["Hc"] if mc.lstm else None)
@@ -1026,7 +1061,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
         # from the batch's largest position - one host sync, in a call that is synchronous anyway (level_forward reads the status word)
         top = int(locs.max().item()) // int(mc.patch_size) + 1 if locs.numel() else 0
         pe_rows = top if 0 < top <= (1 << 16) else 0
-    pe_tab = pe_table(lvl_pack, pe_mode, d, pe_rows) if pe_rows > 0 else None
+    pe_tab = pe_table(pe_mode, pe_div, d, pe_rows) if pe_rows > 0 else None
 
     generic = not fast_path(mc)
     # default inference form of the shipped geometry: in_proj of decoder layer 0 inside the importance / projection finish (FUSE_QKV)
@@ -1034,7 +1069,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
                 and L > 1 and pe_tab is not None and not (ATTN_FP8 or AGG_FP8) and D % 64 == 0 and D >= 256 and N % 64 == 0 and TAIL_WS)
     fused: Dict[str, object] = {}
     # any aggregator geometry on the tuned LSTM kernels: the importance / projection products take x + h1 summed while staged
-    generic_add = generic and x6 and split_planes() == 2 and mc.lstm and GENERIC_ADD and GENERIC_SPLIT and D % 128 == 0
+    generic_add = generic_add_route(mc, D, lstm_pack["Hc"] if mc.lstm else None)
 
     def imp_proj(src, imp_mul, imp_out, add=None):
         """tokens / importance from ``src`` (+ ``add``: x6 only, the GEMM input is src + add, row stride of add arbitrary)."""
@@ -1095,12 +1130,12 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
             timed("lstm_mem_to_out", lambda: lstm(4))
         if generic_add:
             timed("importance_proj", lambda: importance_proj_generic_add(mc, lvl_pack, fts, x_rows, state_out, locs, num_ims, B, N, D,
-                                                                         1 if mc.importance_mode == "mul" else 0, importance, tokens, skip_padding, pe_tab=pe_tab,
+                                                                         imp_mul, importance, tokens, skip_padding, pe_tab=pe_tab,
                                                                          x_rows_h16=x_rows_h16))
         elif x6 and not generic:
-            timed("importance_proj", lambda: imp_proj(fts, 1 if mc.importance_mode == "mul" else 0, importance, add=state_out))
+            timed("importance_proj", lambda: imp_proj(fts, imp_mul, importance, add=state_out))
         else:
-            timed("importance_proj", lambda: imp_proj(y, 1 if mc.importance_mode == "mul" else 0, importance))
+            timed("importance_proj", lambda: imp_proj(y, imp_mul, importance))
         del ws_o
     else:
         # lstm=false (reference model/paths.py:95-109): alpha from X; Z = alpha*X (+ hctx_mlp(previous Z) on valid rows);
@@ -1118,7 +1153,7 @@ def selection_forward(mc, lstm_pack, lvl_pack, fts, locs, num_ims, state_prev, s
             _lib.call("paths_linear_f32", p(hid), Hh, p(lvl_pack["wh2"]), p(lvl_pack["bh2"]), p(hctx), D, M, D, D, Hh, 0, st)
         state_out = torch.empty((B, N, D), **f32)
         _lib.call("paths_scale_add_rows", p(fts), p(importance), p(hctx) if hctx is not None else None, p(num_ims), N, D, M,
-                  1 if mc.importance_mode == "mul" else 0, p(state_out), st)
+                  imp_mul, p(state_out), st)
         scratch_imp = torch.empty((B, N), **f32)
         imp_proj(state_out, 0, scratch_imp)                      # pass 2: tokens = proj_in(Z) + PE
 
@@ -1164,7 +1199,7 @@ def lstm_cell(lstm_pack, fts, x_rows, prev, state_out, y, o, frm, tc, N: int, nu
         (wg, wg_s), (wm, wm_s) = _x6_of(lstm_pack, "w_gates", planes, lagged=lagged), _x6_of(lstm_pack, "w_mem", planes, lagged=lagged)
         _lib.call("paths_lstm_cell_x6" + h16, p(fts), D, p(x_rows), h0, ld, c0, ld, p(wg), p(lstm_pack["b_gates"]), p(wm), p(lstm_pack["b_mem"]),
                   p(state_out), Dp, p(y), D, p(o), p(frm), p(tc), hp, hp_row, M, D, Hc, p(num_ims), N, phases,
-                  planes, wg_s, wm_s, A_SCALE if planes == 2 else 1.0, _lib.stream())
+                  planes, wg_s, wm_s, a_scale_of(planes), _lib.stream())
     else:
         _lib.call("paths_lstm_cell", p(fts), D, h0, ld, c0, ld, p(lstm_pack["w_gates"]), p(lstm_pack["b_gates"]),
                   p(lstm_pack["w_mem"]), p(lstm_pack["b_mem"]), p(state_out), Dp, p(y), D,
@@ -1181,7 +1216,7 @@ def parent_gate_product(lstm_pack, hk, hp, planes: int = 0, lagged: bool = False
     if planes and G % 256 == 0:
         wg, wg_s = _x6_of(lstm_pack, "w_gates", planes, lagged=lagged)
         _lib.call("paths_gemm_nt_x6", p(hk), D, p(wg), 2 * D, D, None, p(hp), G, rows, G, G, D, 0, None, 0, None, 0, 0, planes, wg_s,
-                  A_SCALE if planes == 2 else 1.0, _lib.stream())
+                  a_scale_of(planes), _lib.stream())
     elif G % 128 == 0:
         _lib.call("paths_gemm_nt_f32", p(hk), D, lstm_pack["w_gates"].data_ptr() + 4 * D, 2 * D, None, p(hp), G, rows, G, G, D, 0,
                   None, 0, None, 0, 0, _lib.stream())
@@ -1399,14 +1434,7 @@ def _aggregator_forward(mc, lvl_pack, tokens, num_ims, ctx_prev, ctx_all, status
     def token_layer(x_in, x_out, post, nxt, max_tokens=0, qkv_images=None):
         if GEMM_MODE != "h3":
             return token_layer_f32(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B, T, d, H, qscale, 1, max_tokens)
-        g = lambda dct, key: p(dct[key]) if dct is not None else None
-        ip, sp = tlayer_h3_images(post, 0) if post is not None else (None, (1.0, 1.0, 1.0))
-        iq, sq = tlayer_h3_images(nxt, 1) if nxt is not None else (None, (1.0,))
-        _lib.call("paths_token_layer_h3", p(x_in), p(attn) if post else None, p(x_out) if post else None, p(ip), p(iq),
-                  g(post, "bo"), g(post, "ln1g"), g(post, "ln1b"), g(post, "cab"), g(post, "ln2g"), g(post, "ln2b"),
-                  g(post, "b1"), g(post, "b2"), g(post, "ln3g"), g(post, "ln3b"), g(nxt, "bqkv"),
-                  sp[0], sp[1], sp[2], sq[0], p(q), p(k), p(v), p(num_ims), B, T, d, H,
-                  1 if post else 0, 1 if nxt else 0, 1, qscale, (post or nxt)["eps"], max_tokens, p(qkv_images), st)
+        token_layer_h3(x_in, x_out, post, nxt, attn, q, k, v, num_ims, B, T, d, H, qscale, max_tokens, qkv_images)
 
     def tail_f32(x, in_proj: bool):
         """The last layer at token 0 + head from that layer's fp32 q, k, v; ``in_proj``: project them first (the weight-stationary

@@ -552,7 +552,7 @@ def _rows_in_place(r) -> bool:
     """Whether the current GEMM mode reads feature rows where they live (row-pointer operands) instead of gathered fp32 copies."""
     mc, D, Dp = r.mc, r.D, r.Dp
     return bool(r.share_parent and ops.use_x6(D, Dp - D) and ops.split_planes() == 2 and ROWS_IN_PLACE
-                and (ops.fast_path(mc) or (ops.GENERIC_ADD and ops.GENERIC_SPLIT and D % 128 == 0)))
+                and (ops.fast_path(mc) or ops.generic_add_route(mc, D, Dp - D)))
 
 
 def _level0(r) -> SimpleNamespace:

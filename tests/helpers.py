@@ -29,6 +29,28 @@ def oracle_params(cfg: orc.OracleConfig, wseed: int):
     return {k: torch.from_numpy(v) for k, v in sd.items()}
 
 
+def build_model(dev, wseed, cfg_over=None, **top):
+    """(config, model on ``dev`` in eval mode, its parameters): the sample config + overrides, seeded weights through the oracle's
+    state-dict shapes."""
+    import os
+    from paths_amd.config import Config
+    root = os.path.join(os.path.dirname(__file__), "golden", "sample")
+    cfg = Config.load(root, test_mode=True)
+    over = dict(cfg_over or {})
+    for k, v in over.pop("model_config", {}).items():
+        setattr(cfg.model_config, k, v)
+    for k, v in over.items():
+        setattr(cfg, k, v)
+    for k, v in top.items():
+        setattr(cfg, k, v)
+    cfg.model_config.dropout = 0.0
+    model = cfg.get_model()
+    ocfg = oracle_config(cfg_over)
+    sd = syn.make_state_dict(wseed, orc.state_dict_shapes(ocfg))
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return cfg, model.to(dev).eval(), {k: torch.from_numpy(v) for k, v in sd.items()}
+
+
 def level_inputs(dseed, depth, B, N, num_ims, D, d, pd_dim, patch_size):
     """Same construction as tools/make_goldens.py:level_inputs (inputs are functions of seeds only)."""
     fts = np.zeros((B, N, D), np.float32)
@@ -102,3 +124,15 @@ def spy_calls():
         yield calls
     finally:
         _lib.call = orig
+
+
+def twin_runs(model, keep, a, b, levels=5, **kw):
+    """The recursion on the slides ``a``, then on their twins ``b``: (trace a, trace b, outputs a, outputs b, C entry points of a, of b)."""
+    from paths_amd import utils as putils
+    ta, tb = [], []
+    with spy_calls() as calls, torch.no_grad():
+        oa = putils.recurse(model, a, keep, levels, trace=ta, **kw)
+        n = len(calls)
+        ob = putils.recurse(model, b, keep, levels, trace=tb, **kw)
+    torch.cuda.synchronize()
+    return ta, tb, oa, ob, calls[:n], calls[n:]

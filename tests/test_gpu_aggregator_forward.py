@@ -133,9 +133,7 @@ def _layer_call(kernel, pr, bufs, mode, skip, max_tokens=0, **change):
                   g(post, "ln3b", do_post), g(nxt, "wqkv", do_qkv), g(nxt, "bqkv", do_qkv), *(p(bufs[n]) if do_qkv else None for n in "qkv"),
                   *tail, a["H"], do_post, do_qkv, a["skip"], a["qscale"], a["eps"], a["max_tokens"], _lib.stream())
         return
-    kind = "h3" if kernel == "h3" else "ws"
-    ip, sp = ops._tlayer_images(post, 0, kind) if do_post else (None, (1.0, 1.0, 1.0))
-    iq, sq = ops._tlayer_images(nxt, 1, kind) if do_qkv else (None, (1.0,))
+    ip, sp, iq, sq = ops.tlayer_operands(post if do_post else None, nxt if do_qkv else None, "h3" if kernel == "h3" else "ws")
     biases = vecs + [g(post, k, do_post) for k in ("b1", "b2", "ln3g", "ln3b")] + [g(nxt, "bqkv", do_qkv)]
     if kernel == "h3":
         _lib.call("paths_token_layer_h3", a["x_in"], a["attn"], a["x_out"], p(ip), p(iq), *biases, sp[0], sp[1], sp[2], sq[0],

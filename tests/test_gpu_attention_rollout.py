@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.helpers import build_model
 from tests import rollout_ref as R
 from tests.conftest import load_golden
 
@@ -22,25 +23,6 @@ def dev():
     from paths_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def build_model(dev, wseed, cfg_over=None, **top):
-    """The model of tests/test_gpu_parity.py:build_model (seeded weights through the oracle's state-dict shapes), with its params."""
-    import os
-    from oracle import paths_oracle as orc
-    from paths_amd import synthetic as syn
-    from paths_amd.config import Config
-    cfg = Config.load(os.path.join(os.path.dirname(__file__), "golden", "sample"), test_mode=True)
-    over = dict(cfg_over or {})
-    for k, v in over.pop("model_config", {}).items():
-        setattr(cfg.model_config, k, v)
-    for k, v in list(over.items()) + list(top.items()):
-        setattr(cfg, k, v)
-    cfg.model_config.dropout = 0.0
-    model = cfg.get_model()
-    sd = syn.make_state_dict(wseed, orc.state_dict_shapes(H.oracle_config(cfg_over)))
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return cfg, model.to(dev).eval(), {k: torch.from_numpy(v) for k, v in sd.items()}
 
 
 SMALL = {"num_levels": 3, "top_k_patches": [16, 16]}           # the smoke() case

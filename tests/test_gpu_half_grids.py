@@ -22,13 +22,6 @@ def fp32_twin(s):
     return DeviceSlide([g.float() for g in s.grids], patch_size=s.patch_size, slide_id=s.slide_id + "-fp32")
 
 
-def spy_calls(monkeypatch):
-    from paths_amd import _lib
-    calls, real = [], _lib.call
-    monkeypatch.setattr(_lib, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
-    return calls
-
-
 def assert_same_recursion(ta, tb, oa, ob):
     """Per level: num_ims, locations, parents and kept indices identical; logits, importance, ctx_slide bit-identical."""
     assert len(ta) == len(tb)
@@ -81,15 +74,14 @@ def k2048(dev):
     return cfg, model, params, slides
 
 
-def test_fp16_recursion_is_bitwise_its_fp32_twin(dev, k2048, monkeypatch):
+def test_fp16_recursion_is_bitwise_its_fp32_twin(dev, k2048):
     """8 slides at K = 2048 x 5 levels, top-K 512, stored fp16, against the same values stored fp32: the one-plane gate GEMMs drop only
     the lo*hi product, which is exactly zero for fp16 operands, and the fp16-row importance / projection GEMM stages the same fp32 sum."""
     from paths_amd import utils as putils
     cfg, model, _, slides = k2048
     twins = [fp32_twin(s) for s in slides]
-    calls = spy_calls(monkeypatch)
     ta, tb = [], []
-    with torch.no_grad():
+    with H.spy_calls() as calls, torch.no_grad():
         oa = putils.recurse(model, slides, cfg.top_k_patches, 5, trace=ta)
         n16 = len(calls)
         ob = putils.recurse(model, twins, cfg.top_k_patches, 5, trace=tb)
@@ -189,7 +181,7 @@ def test_fp16_training_steps_are_bitwise_the_fp32_twin(dev):
     assert all(torch.equal(pa[n], pb[n]) for n in pa)
 
 
-def test_fp16_out_of_range_slide_takes_the_fallback(dev, monkeypatch):
+def test_fp16_out_of_range_slide_takes_the_fallback(dev):
     """Features near 30,000 leave the fp16-split range of the default mode ((max|x| + margin) * A_SCALE >= 65504): the recursion runs on
     the exact bf16 kernels over fp32 gathered copies of the fp16 rows - the fp32 twin's path exactly."""
     from paths_amd import ops
@@ -200,10 +192,9 @@ def test_fp16_out_of_range_slide_takes_the_fallback(dev, monkeypatch):
     big = [DeviceSlide([g * 16384 for g in s.grids]) for s in small]          # exact in fp16 (a power of two), max|x| ~ 28,400
     assert 28000 < big[0].feature_absmax() < 30000 and not ops.h3_in_range(big[0].feature_absmax())
     twins = [fp32_twin(s) for s in big]
-    calls = spy_calls(monkeypatch)
     before = ops.RANGE_FALLBACKS[0]
     ta, tb = [], []
-    with torch.no_grad():
+    with H.spy_calls() as calls, torch.no_grad():
         oa = putils.recurse(model, big, cfg.top_k_patches, 5, trace=ta)
         ob = putils.recurse(model, twins, cfg.top_k_patches, 5, trace=tb)
     torch.cuda.synchronize()

@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import helpers as H
 from tests import stage_ref
-from tests.test_gpu_half_grids import BASE, assert_same_recursion, spy_calls
+from tests.test_gpu_half_grids import BASE, assert_same_recursion
 from tests.test_gpu_parity import build_model, dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -142,20 +143,8 @@ def test_pageable_grids_never_reach_the_pointer_table(dev):
 # ------------------------------------------------------------------------------------------------
 # 3. the recursion on pinned grids is its resident twin, bit for bit
 # ------------------------------------------------------------------------------------------------
-def _twin_runs(model, keep, host, twins, monkeypatch, levels=5, **kw):
-    from paths_amd import utils as putils
-    ta, tb = [], []
-    with monkeypatch.context() as mp, torch.no_grad():
-        calls = spy_calls(mp)
-        oa = putils.recurse(model, host, keep, levels, trace=ta, **kw)
-        n = len(calls)
-        ob = putils.recurse(model, twins, keep, levels, trace=tb, **kw)
-    torch.cuda.synchronize()
-    return ta, tb, oa, ob, calls[:n], calls[n:]
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, F16])
-def test_host_recursion_is_bitwise_its_resident_twin(dev, dtype, monkeypatch):
+def test_host_recursion_is_bitwise_its_resident_twin(dev, dtype):
     """Two slides at K = 1024 x 5 levels, top-K 256, default mode: every trace field of every level and the outputs; one staging
     launch per level on the host batch, none on the twin; the same with the attention and rollout exports."""
     from paths_amd.data_utils.slide import DeviceSlideBatch, HostSlide
@@ -167,13 +156,13 @@ def test_host_recursion_is_bitwise_its_resident_twin(dev, dtype, monkeypatch):
     hb, tb_ = DeviceSlideBatch(host), DeviceSlideBatch(twins)
     assert hb.host_resident and not tb_.host_resident and hb.dtype == dtype
     assert hb.grid_ptrs[4].cpu().tolist() == [s.grids[4].data_ptr() for s in host]
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, hb, tb_, monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, hb, tb_)
     assert ca.count("paths_stage_rows") == 5 and "paths_stage_rows" not in cb
     sfx = "_h16" if dtype == F16 else ""
     assert {"paths_level0_batch" + sfx, "paths_gather_rows" + sfx} <= set(ca) & set(cb)
     assert int(oa["status"].item()) == 0
     assert_same_recursion(ta, tb, oa, ob)
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, hb, tb_, monkeypatch, attention=True, rollout=True)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, hb, tb_, attention=True, rollout=True)
     assert ca.count("paths_stage_rows") == 5 and "paths_stage_rows" not in cb
     assert_same_recursion(ta, tb, oa, ob)
     for l, (a, b) in enumerate(zip(ta, tb)):
@@ -201,9 +190,10 @@ def test_host_recursion_other_branches_bitwise(dev, variant, monkeypatch):
         monkeypatch.setattr(ops, "GEMM_MODE", variant)
     cfg, model, _ = build_model(dev, 5, over, top_k_patches=[12] * 4)
     host, twins = _small_pair(dev, 41, range(2), (7, 6))
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, host, twins, monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, host, twins)
     assert_same_recursion(ta, tb, oa, ob)
-    if variant == "td192" and ops.GEMM_MODE == "h3" and ops.GENERIC_ADD and ops.GENERIC_SPLIT:
+    mc = cfg.model_config
+    if variant == "td192" and ops.generic_add_route(mc, mc.patch_embed_dim, mc.hierarchical_ctx_mlp_hidden_dim):
         assert ca.count("paths_stage_rows") == 5        # generic geometry, rows still read in place: staged
     if variant in ("x6", "f32", "nolstm"):
         # rows are copied by the gathers themselves (fp32 fts): the only kernels that read a host address; nothing is staged
@@ -213,7 +203,7 @@ def test_host_recursion_other_branches_bitwise(dev, variant, monkeypatch):
     free_pinned()
 
 
-def test_host_zero_children_fallback_bitwise(dev, monkeypatch):
+def test_host_zero_children_fallback_bitwise(dev):
     """The careful re-run (paths_fallback_all_cells) on host slides: its rows go through the same staging."""
     from paths_amd import utils as putils
     cfg, model, _ = build_model(dev, 9, None, top_k_patches=[2] * 4)
@@ -221,7 +211,7 @@ def test_host_zero_children_fallback_bitwise(dev, monkeypatch):
     with torch.no_grad():
         fast = putils._recurse(model, host, cfg.top_k_patches, 5, None, careful=False)
     assert int(fast["status"].item()) & 1, "test slides should trigger the fallback (pick another seed otherwise)"
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, host, twins, monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, host, twins)
     assert "paths_fallback_all_cells" in ca and "paths_fallback_all_cells" in cb
     assert ca.count("paths_stage_rows") == 10 and "paths_stage_rows" not in cb           # optimistic pass + careful re-run
     assert_same_recursion(ta, tb, oa, ob)

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from tests import on_demand_ref as R
-from tests.test_gpu_half_grids import assert_same_recursion, spy_calls
+from tests.helpers import spy_calls
+from tests.test_gpu_half_grids import assert_same_recursion
 from tests.test_gpu_parity import LOGIT_TOL, build_model, dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -163,13 +164,12 @@ def _slides(dev, dtype=torch.float32, seed=41, ids=range(2), shape=(7, 6), **kw)
     return [OnDemandSlide.from_slide(s) for s in res], res
 
 
-def _twin_runs(model, keep, od, res, monkeypatch, levels=5, **kw):
+def _twin_runs(model, keep, od, res, levels=5, **kw):
     from paths_amd import utils as putils
     ta, tb = [], []
     with torch.no_grad():                    # the weight images are packed once per model and mode: keep those launches out of both lists
         putils.recurse(model, res, keep, levels, trace=[] if kw else None, **kw)
-    with monkeypatch.context() as mp, torch.no_grad():
-        calls = spy_calls(mp)
+    with spy_calls() as calls, torch.no_grad():
         ob = putils.recurse(model, res, keep, levels, trace=tb, **kw)
         n = len(calls)
         oa = putils.recurse(model, od, keep, levels, trace=ta, **kw)
@@ -197,7 +197,7 @@ def _check_requests(od, tb, keep, patch=256):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, F16])
-def test_on_demand_recursion_is_bitwise_its_resident_twin(dev, dtype, monkeypatch):
+def test_on_demand_recursion_is_bitwise_its_resident_twin(dev, dtype):
     """Two synthetic slides, base (7, 6), top-12, 5 levels, default mode: every trace field of every level and the outputs; the same
     with the attention and rollout exports; what the encoder was asked; the launches of each side."""
     from paths_amd.data_utils.slide import OnDemandSlideBatch, slide_batch
@@ -209,7 +209,7 @@ def test_on_demand_recursion_is_bitwise_its_resident_twin(dev, dtype, monkeypatc
     batch = slide_batch(od)
     assert isinstance(batch, OnDemandSlideBatch) and batch.n0 == 42 and batch.dim == res[0].dim and batch.dtype == dtype
     assert batch.max_dim == [7 << l for l in range(5)] and batch.gx[2].cpu().tolist() == [28, 28] and batch.gy[4].cpu().tolist() == [96, 96]
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, batch, res, monkeypatch)
+    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, batch, res)
     assert_same_recursion(ta, tb, oa, ob)
     assert sorted((sid, l) for sid, l, _ in seen) == sorted((s.slide_id, l) for s in od for l in range(5)), "encode sees each level once"
     _check_requests(od, tb, cfg.top_k_patches)
@@ -220,7 +220,7 @@ def test_on_demand_recursion_is_bitwise_its_resident_twin(dev, dtype, monkeypatc
     assert not {"paths_candidate_children", "paths_admit_children"} & set(cb)
     others = lambda c: [n for n in c if n not in ("paths_candidate_children", "paths_admit_children", "paths_expand_children", "paths_tissue_mask_absmax" + sfx)]
     assert others(ca) == others(cb), "everything around the expansion is the resident launch sequence"
-    ta, tb, oa, ob, _, _ = _twin_runs(model, cfg.top_k_patches, od, res, monkeypatch, attention=True, rollout=True)
+    ta, tb, oa, ob, _, _ = _twin_runs(model, cfg.top_k_patches, od, res, attention=True, rollout=True)
     assert_same_recursion(ta, tb, oa, ob)
     for l, (a, b) in enumerate(zip(ta, tb)):
         for key in ("attention", "attention_self", "rollout", "rollout_self"):
@@ -237,7 +237,7 @@ def test_on_demand_recursion_other_branches_bitwise(dev, variant, monkeypatch):
         monkeypatch.setattr(ops, "GEMM_MODE", variant)
     cfg, model, _ = build_model(dev, 5, over, top_k_patches=[12] * 4)
     od, res = _slides(dev)
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, od, res, monkeypatch)
+    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, od, res)
     assert_same_recursion(ta, tb, oa, ob)
     assert ca.count("paths_admit_children") == 4 and "paths_expand_children" not in ca
     _check_requests(od, tb, cfg.top_k_patches)
@@ -257,7 +257,7 @@ def test_on_demand_inference_end2end(dev):
 # ------------------------------------------------------------------------------------------------
 # 3. what is refused, the range contract, and that nothing else moved
 # ------------------------------------------------------------------------------------------------
-def test_no_tissue_among_the_children_is_refused(dev, monkeypatch):
+def test_no_tissue_among_the_children_is_refused(dev):
     """The slides of the careful-path test (seed 57, (4, 4), p_bg 0.93, top-2): the resident run falls back to every cell of the next
     grid; an on-demand slide would have to encode that whole grid, so the pass raises, naming the slide, and launches nothing more."""
     from paths_amd import _lib, utils as putils
@@ -266,8 +266,7 @@ def test_no_tissue_among_the_children_is_refused(dev, monkeypatch):
     with torch.no_grad():
         fast = putils._recurse(model, res, cfg.top_k_patches, 5, None, careful=False)
         assert int(fast["status"].item()) & 1, "test slides should trigger the fallback (pick another seed otherwise)"
-        calls = spy_calls(monkeypatch)
-        with pytest.raises(_lib.PathsHipError, match=r"on-demand slide .*synthetic-57-.*every cell"):
+        with spy_calls() as calls, pytest.raises(_lib.PathsHipError, match=r"on-demand slide .*synthetic-57-.*every cell"):
             putils.recurse(model, od, cfg.top_k_patches, 5)
     assert calls[-1] == "paths_admit_children", "no launch follows the raise"
     torch.cuda.synchronize()
@@ -336,7 +335,7 @@ def test_bad_encode_results_raise_on_the_device_too(dev):
     assert OnDemandSlide.on_demand
 
 
-def test_nothing_else_moved(dev, monkeypatch):
+def test_nothing_else_moved(dev):
     """Resident and host-resident recursions launch neither new entry point; the stored-launch and training entry points refuse
     on-demand slides."""
     from paths_amd import saliency, utils as putils
@@ -346,8 +345,7 @@ def test_nothing_else_moved(dev, monkeypatch):
     keep = cfg.top_k_patches
     od, res = _slides(dev)
     host = [HostSlide.synthetic(41, sid, (7, 6), device=dev) for sid in range(2)]
-    calls = spy_calls(monkeypatch)
-    with torch.no_grad():
+    with spy_calls() as calls, torch.no_grad():
         putils.recurse(model, res, keep, 5)
         putils.recurse(model, host, keep, 5)
     torch.cuda.synchronize()

@@ -9,7 +9,7 @@ import torch
 
 from tests import helpers as H
 from tests import pack_ref as R
-from tests.test_gpu_half_grids import assert_same_recursion, spy_calls
+from tests.test_gpu_half_grids import assert_same_recursion
 from tests.test_gpu_parity import LOGIT_TOL, build_model, dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -287,21 +287,9 @@ def _slides(dev, kind, dtype, seed=99, ids=range(3), base=(9, 11), p_bg=0.6, **k
     return dense, [s.pack() for s in dense]
 
 
-def _twin_runs(model, keep, a, b, monkeypatch, levels=5, **kw):
-    from paths_amd import utils as putils
-    ta, tb = [], []
-    with monkeypatch.context() as mp, torch.no_grad():
-        calls = spy_calls(mp)
-        oa = putils.recurse(model, a, keep, levels, trace=ta, **kw)
-        n = len(calls)
-        ob = putils.recurse(model, b, keep, levels, trace=tb, **kw)
-    torch.cuda.synchronize()
-    return ta, tb, oa, ob, calls[:n], calls[n:]
-
-
 @pytest.mark.parametrize("kind", ["device", "host"])
 @pytest.mark.parametrize("dtype", [F32, F16], ids=["f32", "f16"])
-def test_packed_recursion_is_bitwise_its_dense_twin(dev, dtype, kind, monkeypatch):
+def test_packed_recursion_is_bitwise_its_dense_twin(dev, dtype, kind):
     from paths_amd.data_utils.slide import DeviceSlideBatch
     cfg, model, _ = build_model(dev, 77, None, top_k_patches=[24] * 4)
     dense, packed = _slides(dev, kind, dtype)
@@ -320,8 +308,8 @@ def test_packed_recursion_is_bitwise_its_dense_twin(dev, dtype, kind, monkeypatc
         DeviceSlideBatch([dense[0], packed[1]])
     sfx = "_h16" if dtype == F16 else ""
     for kw in ({}, dict(attention=True, rollout=True)):
-        _twin_runs(model, cfg.top_k_patches, pb, db, monkeypatch, **kw)       # (the first pass also builds the cached weight images)
-        ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, pb, db, monkeypatch, **kw)
+        H.twin_runs(model, cfg.top_k_patches, pb, db, **kw)       # (the first pass also builds the cached weight images)
+        ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, pb, db, **kw)
         assert ca.count("paths_level0_batch_packed" + sfx) == 1 and ca.count("paths_gather_rows_packed" + sfx) == 4
         assert not (set(cb) & PACKED_NAMES), "a dense run launches no packed entry point"
         assert cb.count("paths_level0_batch" + sfx) == 1 and cb.count("paths_gather_rows" + sfx) == 4
@@ -343,7 +331,7 @@ def test_packed_recursion_with_gathered_copies(dev, kind, monkeypatch):
     monkeypatch.setattr(putils, "ROWS_IN_PLACE", False)
     cfg, model, _ = build_model(dev, 77, None, top_k_patches=[24] * 4)
     dense, packed = _slides(dev, kind, F16)
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, packed, dense, monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, packed, dense)
     assert "paths_stage_rows" not in ca and ca.count("paths_gather_rows_packed_h16") == 4 and not (set(cb) & PACKED_NAMES)
     assert_same_recursion(ta, tb, oa, ob)
     del dense, packed
@@ -372,21 +360,21 @@ def test_packed_recursion_vs_oracle(dev):
 # 4. zero-children fallback, masked views, on-demand replay
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["device", "host"])
-def test_packed_zero_children_fallback_bitwise(dev, kind, monkeypatch):
+def test_packed_zero_children_fallback_bitwise(dev, kind):
     from paths_amd import utils as putils
     cfg, model, _ = build_model(dev, 9, None, top_k_patches=[2] * 4)
     dense, packed = _slides(dev, kind, F32, seed=57, ids=range(4), base=(4, 4), p_bg=0.93)
     with torch.no_grad():
         fast = putils._recurse(model, packed, cfg.top_k_patches, 5, None, careful=False)
     assert int(fast["status"].item()) & 1, "test slides should trigger the fallback (pick another seed otherwise)"
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, packed, dense, monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, packed, dense)
     assert "paths_fallback_all_cells" in ca and "paths_fallback_all_cells" in cb and not (set(cb) & PACKED_NAMES)
     assert_same_recursion(ta, tb, oa, ob)
     del dense, packed
     free_pinned()
 
 
-def test_packed_masked_view_bitwise(dev, monkeypatch):
+def test_packed_masked_view_bitwise(dev):
     """with_masks on a packed slide: cleared cells at level 0 (read as zero rows) and deeper (dropped by the child filter)."""
     cfg, model, _ = build_model(dev, 77, None, top_k_patches=[24] * 4)
     dense, packed = _slides(dev, "device", F32, p_bg=0.3)
@@ -398,7 +386,7 @@ def test_packed_masked_view_bitwise(dev, monkeypatch):
         views[0].append(d.with_masks(masks))
         views[1].append(p.with_masks(masks))
     assert all(v.packed and v.masked_view and v.rows is p.rows for v, p in zip(views[1], packed))
-    ta, tb, oa, ob, ca, cb = _twin_runs(model, cfg.top_k_patches, views[1], views[0], monkeypatch)
+    ta, tb, oa, ob, ca, cb = H.twin_runs(model, cfg.top_k_patches, views[1], views[0])
     assert "paths_level0_mask_rows" in ca and "paths_level0_mask_rows" in cb
     assert_same_recursion(ta, tb, oa, ob)
     # the view of the packed slide packs / unpacks to a view
@@ -482,7 +470,7 @@ def test_packed_tape_rebind_pipeline_and_graph(dev):
 # 6. training and attribution
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["device", "host"])
-def test_packed_training_steps_are_bitwise_the_dense_twin(dev, kind, monkeypatch):
+def test_packed_training_steps_are_bitwise_the_dense_twin(dev, kind):
     from paths_amd import utils as putils
     from paths_amd.data_utils.slide import DeviceSlideBatch
     from paths_amd.optim import HipAdamW
@@ -495,8 +483,7 @@ def test_packed_training_steps_are_bitwise_the_dense_twin(dev, kind, monkeypatch
         model.train()
         opt = HipAdamW(model.parameters(), lr=1e-4)
         losses, grads = [], []
-        with monkeypatch.context() as mp:
-            calls = spy_calls(mp)
+        with H.spy_calls() as calls:
             for _ in range(3):
                 losses.append(float(putils.train_step(model, opt, batch, 5, cfg.top_k_patches)))
                 grads.append({n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None})

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.helpers import build_model
 from tests.conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -26,28 +27,6 @@ def dev():
     from paths_amd import _lib
     _lib.load()          # fail loudly if the HIP extension is missing
     return torch.device("cuda:0")
-
-
-def build_model(dev, wseed, cfg_over=None, **top):
-    import os
-    from paths_amd import synthetic as syn
-    from paths_amd.config import Config
-    from oracle import paths_oracle as orc
-    root = os.path.join(os.path.dirname(__file__), "golden", "sample")
-    cfg = Config.load(root, test_mode=True)
-    over = dict(cfg_over or {})
-    for k, v in over.pop("model_config", {}).items():
-        setattr(cfg.model_config, k, v)
-    for k, v in over.items():
-        setattr(cfg, k, v)
-    for k, v in top.items():
-        setattr(cfg, k, v)
-    cfg.model_config.dropout = 0.0
-    model = cfg.get_model()
-    ocfg = H.oracle_config(cfg_over)
-    sd = syn.make_state_dict(wseed, orc.state_dict_shapes(ocfg))
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    return cfg, model.to(dev).eval(), {k: torch.from_numpy(v) for k, v in sd.items()}
 
 
 def run_single(dev, name):
@@ -89,13 +68,8 @@ def test_single_level_other_aggregator_geometries(dev, tag):
     """g12 (reference config.py:30-36: the dataclass DEFAULT is trans_dim 192 = head_dim 48 with the 1-D encoding): aggregator
     geometries other than the shipped 128 / 4 / 128 run on the shape-generic kernels (csrc/generic.hip + the f32 GEMM), same bars."""
     import paths_amd.ops as O
-    calls = []
-    orig = O._lib.call
-    O._lib.call = lambda cname, *a: (calls.append(cname), orig(cname, *a))[1]
-    try:
+    with H.spy_calls() as calls:
         g, info, out = run_single(dev, f"g12_{tag}_level1")
-    finally:
-        O._lib.call = orig
     attn = {"paths_attention_h3_any", "paths_attention_token0_any"} if (O.GEMM_MODE == "h3" and O.GENERIC_SPLIT) else {"paths_attention_any"}
     if tag.startswith("td192") and "paths_attention_h3_any" in attn and O.WS_CHAIN_192 and O.WS_IMAGES_192:
         # trans_dim 192 / 4 heads: the first in_proj writes the attention's head_dim-48 operand images itself (csrc/tlayer_ws.hip), no prep launch
@@ -476,14 +450,8 @@ def test_single_level_wide_heads(dev, tag):
     """g14 (VERDICT r3 missing 2): head_dim above 64 - trans_dim 256 / 2 heads = 128 and the stress row's own form trans_dim 1536 / 4
     heads = 384 - on csrc/attn_wide.hip (scores through the f32-input MFMA GEMMs, score matrix in scratch), against the
     fixtures captured from the reference; same bars as every other geometry."""
-    import paths_amd.ops as O
-    calls = []
-    orig = O._lib.call
-    O._lib.call = lambda cname, *a: (calls.append(cname), orig(cname, *a))[1]
-    try:
+    with H.spy_calls() as calls:
         g, info, out = run_single(dev, f"g14_{tag}_level1")
-    finally:
-        O._lib.call = orig
     assert "paths_attention_wide_fwd" in calls and not {"paths_attention_any", "paths_attention_h3_any"} & set(calls)
     np.testing.assert_allclose(out["logits"].numpy(), g["logits"], atol=LOGIT_TOL, rtol=0)
     np.testing.assert_allclose(out["ctx_slide"].numpy(), g["ctx_slide"], atol=LOGIT_TOL, rtol=0)
@@ -800,21 +768,13 @@ def test_wave_pair_attention_in_the_chain(dev, name, monkeypatch):
 def _spy_calls(dev, name, **flags):
     """Run one golden level and return (golden, outputs, names of the C entry points it went through)."""
     import paths_amd.ops as O
-    calls = []
-    orig = O._lib.call
-
-    def spy(cname, *a):
-        calls.append(cname)
-        return orig(cname, *a)
-
     saved = {k: getattr(O, k) for k in flags}
     for k, v in flags.items():
         setattr(O, k, v)
-    O._lib.call = spy
     try:
-        g, _, out = run_single(dev, name)
+        with H.spy_calls() as calls:
+            g, _, out = run_single(dev, name)
     finally:
-        O._lib.call = orig
         for k, v in saved.items():
             setattr(O, k, v)
     return g, out, calls
