@@ -102,6 +102,10 @@
  *                                      (both written by the caller)
  *   paths_raster_maps                  value rows of padding: never read (only rows an index grid names are); out on entry: never
  *                                      read, every element of the padded allocation is written
+ * row cache of on-demand slides
+ *   paths_cache_probe                  cells beyond n[b]: never read; src, miss_count, miss_cells, status on entry: never read
+ *   paths_cache_fill / _h16            src beyond n[b], store rows at and beyond count[b], out on entry: never read; every row of out
+ *                                      is written
  */
 #ifndef PATHS_HIP_H
 #define PATHS_HIP_H
@@ -712,6 +716,42 @@ int paths_admit_children(const int* cand_count, const int64_t* cand_cells, const
                          const int* keep_idx, int64_t ldk, const int* keep_count, int patch_size, int B, int64_t n_next,
                          int64_t* num_out, int64_t* locs_out, int64_t* parent_out, int* src_row, int* src_cell, int* status,
                          int* child_pos, int* hp_row, paths_stream_t stream);
+
+/* The row cache of on-demand slides that keep what their encoder produced (paths_amd/data_utils/slide.py:CachedOnDemandSlide;
+ * csrc/row_cache.hip; no reference equivalent - RawSlide.recurse encodes every visit anew).  Per slide b and level the cache
+ * is a cell index (int32 [X, Y]: the row of a cell in the store, or -1) and a row store [capacity[b], D] with count[b] rows in use.
+ * Every per-slide argument is a DEVICE table [B]: int64 addresses (cells_ptrs: the request, int64 [n[b], 2] cell coordinates; index_ptrs;
+ * enc_ptrs: the rows the caller's encoder returned for the misses, [miss_count[b], D], never dereferenced without a miss; store_ptrs),
+ * int64 n / count / capacity, int32 gx / gy (the level's grid).  n[b] is clamped to [0, n_max]; n[b] = 0 is a slide without a request.
+ * Rows are D fp32 (paths_cache_fill) or fp16 (_h16) elements; store, encoder rows and out are 16-byte aligned.  One launch each for the
+ * whole batch; integers and copies only, no atomics, no workspace: a rerun on the same inputs writes the same bytes.  Both return -1
+ * and launch nothing unless B > 0, n_max > 0, D is a positive multiple of 4 and no pointer is null.  Contract: tests/cache_ref.py.
+ *
+ * paths_cache_probe - one workgroup per slide, the request in chunks of PATHS_CACHE_PROBE_CHUNK cells.  For i < n[b]:
+ *   src[b, i] = the store row (>= 0) of a cell the index holds;  -1 - j for the j-th cell it does not hold, in request order;
+ *   PATHS_CACHE_SRC_NONE for a cell outside the gx[b] x gy[b] grid (it reads as a zero row and is not a miss).
+ *   miss_count[b] = the number of misses m_b, miss_cells[b, 0:m_b] = their coordinates in request order (what to hand the encoder),
+ *   status[b] = 1 if the request names a cell outside the grid, else 0.  src [B, n_max] beyond n[b] and miss_cells [B, n_max, 2] beyond
+ *   m_b are left untouched; nothing is read beyond n[b].  D is the cache's row width (checked only).
+ * paths_cache_fill / _h16 - one wave per row of out [B, n_max, D], the buffer the recursion reads (a hit row moves once).  For i < n[b]:
+ *   src >= 0 (and < count[b]):  out[b, i] = store_b[src];
+ *   src = -1 - j (j < miss_count[b]):  out[b, i] = enc_b[j]; if count[b] + j < capacity[b] also store_b[count[b] + j] = enc_b[j] and
+ *   index_b[cell i] = count[b] + j - the first capacity[b] - count[b] misses in request order are kept, the rest pass through;
+ *   anything else (PATHS_CACHE_SRC_NONE, a src no store row or encoder row stands behind): out[b, i] = +0.
+ *   Rows n[b] <= i < n_max of out are +0.  count itself is the caller's to advance (by min(m_b, capacity[b] - count[b])).
+ *   A request must not name a cell twice (the recursion's candidates never do): both copies would be misses with rows of their own,
+ *   and which of them the index then names is not defined.  The fill of a probe's src must follow it with the index unchanged.
+ * Undefined memory: src / miss_cells / out on entry: never read; store rows at and beyond count[b]: never read. */
+#define PATHS_CACHE_PROBE_CHUNK 1024
+#define PATHS_CACHE_SRC_NONE (-2147483647 - 1)
+int paths_cache_probe(const int64_t* cells_ptrs, const int64_t* n, const int64_t* index_ptrs, const int* gx, const int* gy, int B, int n_max,
+                      int D, int* src, int* miss_count, int64_t* miss_cells, int* status, paths_stream_t stream);
+int paths_cache_fill(const int64_t* cells_ptrs, const int64_t* n, const int* src, const int* miss_count, const int64_t* enc_ptrs,
+                     const int64_t* store_ptrs, const int64_t* count, const int64_t* capacity, const int64_t* index_ptrs, const int* gx,
+                     const int* gy, int B, int n_max, int D, float* out, paths_stream_t stream);
+int paths_cache_fill_h16(const int64_t* cells_ptrs, const int64_t* n, const int* src, const int* miss_count, const int64_t* enc_ptrs,
+                         const int64_t* store_ptrs, const int64_t* count, const int64_t* capacity, const int64_t* index_ptrs, const int* gx,
+                         const int* gy, int B, int n_max, int D, void* out, paths_stream_t stream);
 
 /* Rare fallback of reference data_utils/slide.py:336-352 for slides with num_out[b] == 0 after paths_expand_children:
  * continue with every tissue cell of the next grid (every cell if it has no tissue), zero patch context (src_row = -1),

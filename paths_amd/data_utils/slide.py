@@ -18,7 +18,8 @@ live on the device, and the recursion fetches just the rows it selects over the 
 masks - a slide with some of its tissue turned to background, at the cost of the masks alone (saliency.removal_curves).
 
 :class:`OnDemandSlide` holds no grid at all: the recursion asks the caller's ``encode`` for the features of exactly the cells it is
-about to visit (reference ``RawSlide.recurse``, data_utils/slide.py:173-198).
+about to visit (reference ``RawSlide.recurse``, data_utils/slide.py:173-198).  :class:`CachedOnDemandSlide` keeps what
+the encoder has produced on the device across passes and hands the visited part over as a packed :class:`DeviceSlide`.
 
 PACKED slides (``slide.pack()``, ``packed=True``, ``from_patches``) leave the background out: per level the kept rows
 ``rows[l]`` [n_l, D] behind a cell index ``index[l]`` (int32 [X, Y] on the device: the row of a cell, or -1).  Only rows that are all
@@ -683,6 +684,7 @@ class OnDemandSlide:
 
     on_demand = True
     host_resident = False
+    caching = False                 # (CachedOnDemandSlide: keeps the rows its encoder has produced)
 
     def __init__(self, shapes: Sequence[Tuple[int, int]], encode: Callable, dim: int, device, patch_size: int = 256,
                  dtype=torch.float32, slide_id: str = "", subtype=None):
@@ -726,6 +728,10 @@ class OnDemandSlide:
         if self.requested[level] is not None:
             raise RuntimeError(f"OnDemandSlide {self.slide_id!r}: level {level} was already requested in this pass")
         self.requested[level] = cells
+        return self._encode(level, cells)
+
+    def _encode(self, level: int, cells: torch.Tensor) -> Optional[torch.Tensor]:
+        """``encode(level, cells)`` with its result checked (ValueError); n = 0: nothing is asked, None."""
         n = int(cells.shape[0])
         if n == 0:
             return None
@@ -739,8 +745,8 @@ class OnDemandSlide:
             raise ValueError(f"OnDemandSlide {self.slide_id!r}: encode(level {level}) returned rows on {rows.device}, the slide lives on {self.device}")
         return rows
 
-    @staticmethod
-    def from_slide(slide) -> "OnDemandSlide":
+    @classmethod
+    def from_slide(cls, slide, **kw) -> "OnDemandSlide":
         """A :class:`DeviceSlide` or :class:`HostSlide` behind the on-demand interface: ``encode`` indexes its grids (a preprocessed
         cohort replayed through this path; the twin of the tests and of tools/on_demand_time.py).  Anything with a slide's read surface
         will do: ``packed`` and ``synthetic_spec`` are read tolerantly."""
@@ -760,17 +766,171 @@ class OnDemandSlide:
             c = cells.to(g.device)
             return g[c[:, 0], c[:, 1]].to(dev)
 
-        s = OnDemandSlide([slide.shape(l) for l in range(slide.num_levels)], encode, slide.dim, dev, patch_size=slide.patch_size,
-                          dtype=slide.dtype, slide_id=slide.slide_id, subtype=slide.subtype)
+        s = cls([slide.shape(l) for l in range(slide.num_levels)], encode, slide.dim, dev, patch_size=slide.patch_size,
+                dtype=slide.dtype, slide_id=slide.slide_id, subtype=slide.subtype, **kw)
         s.synthetic_spec = getattr(slide, "synthetic_spec", None)
         return s
+
+
+class CachedOnDemandSlide(OnDemandSlide):
+    """An :class:`OnDemandSlide` that KEEPS what its encoder has produced, on the device, across passes: a second
+    ``recurse`` (with ``attention=True``, under the next fold's model, in a later epoch) pays the encoder only for cells no earlier
+    pass has visited.  Same constructor plus ``max_rows`` - an int, or one int per level: the most rows the cache stores per level;
+    None: no bound.
+
+    Per level ``l`` it owns ``index[l]`` (int32 [X, Y] on the device: the row of a cell in the store, or -1; allocated when the level
+    is first reached) and ``store[l]`` ([capacity, D] in the slide's dtype, ``count[l]`` rows in use, grown by doubling).  A row is
+    stored exactly as ``encode`` returned it, an all-zero background row like any other.  At K = 2,048 x 5 levels that is at most
+    34,816 rows = 142.6 MB per slide in fp32 (half in fp16) and 2.8 MB of indices.
+
+    The contract towards ``encode`` changes in one word: it is called with the cells the cache does NOT hold, in request order
+    (n >= 1), and not at all for a level whose cells are all held.  ``requested[l]`` is still what the recursion asked;
+    ``encoded[l]`` is what the encoder was asked in the last pass (an empty [0, 2] tensor: all held; None: level not reached).
+    ``stats`` counts requests, hits, misses and stored rows per level over the cache's life; :meth:`clear` empties the cache.  When
+    ``max_rows[l]`` is reached the first ``max_rows[l] - count[l]`` misses in request order are stored and the rest pass through:
+    encoded, used, not stored, asked again next time - results never depend on ``max_rows``.  Rows are never rewritten: a row the
+    encoder got wrong (a NaN that made the pass raise) stays until :meth:`clear`.
+
+    It stays ``on_demand``: whatever refuses an on-demand slide refuses this one.  :meth:`visited` hands the stored part over as an
+    ordinary packed :class:`DeviceSlide`, on which every stored-slide entry point works."""
+
+    caching = True
+
+    def __init__(self, shapes: Sequence[Tuple[int, int]], encode: Callable, dim: int, device, patch_size: int = 256,
+                 dtype=torch.float32, slide_id: str = "", subtype=None, max_rows=None):
+        super().__init__(shapes, encode, dim, device, patch_size, dtype, slide_id, subtype)
+        L = len(self.shapes)
+        per_level = list(max_rows) if isinstance(max_rows, (list, tuple)) else [max_rows] * L
+        if len(per_level) != L or any(m is not None and (isinstance(m, bool) or not isinstance(m, int) or m < 0) for m in per_level):
+            raise ValueError(f"CachedOnDemandSlide: max_rows is None, a non-negative int or one per level ({L}), got {max_rows}")
+        self.max_rows: List[Optional[int]] = per_level
+        self.encoded: List[Optional[torch.Tensor]] = [None] * L
+        self.clear()
+
+    def clear(self):
+        """Empty the cache: every index, store and count (``stats`` start again too)."""
+        L = len(self.shapes)
+        for t in list(getattr(self, "index", ())) + list(getattr(self, "store", ())):
+            if t is not None and t.is_cuda:         # (a pass on another stream may still read them: not reused before that stream gets there)
+                t.record_stream(torch.cuda.current_stream(t.device))
+        self.index: List[Optional[torch.Tensor]] = [None] * L
+        self.store: List[Optional[torch.Tensor]] = [None] * L
+        self.count: List[int] = [0] * L
+        self.stats = {k: [0] * L for k in ("requests", "hits", "misses", "stored")}
+
+    def begin_pass(self):
+        super().begin_pass()
+        self.encoded = [None] * len(self.shapes)
+
+    def row_limit(self, level: int) -> int:
+        """The most rows level ``level`` can ever store: its cells, or ``max_rows[level]`` if that is fewer."""
+        X, Y = self.shapes[level]
+        m = self.max_rows[level]
+        return X * Y if m is None else min(m, X * Y)
+
+    def capacity(self, level: int) -> int:
+        return 0 if self.store[level] is None else int(self.store[level].shape[0])
+
+    def cell_index(self, level: int) -> torch.Tensor:
+        """``index[level]``, allocated (all -1) on first use."""
+        if self.index[level] is None:
+            self.index[level] = torch.full(self.shapes[level], -1, dtype=torch.int32, device=self.device)
+        return self.index[level]
+
+    def reserve(self, level: int, more: int):
+        """Room for ``more`` further rows at ``level``, as far as :meth:`row_limit` allows: the store is regrown by doubling (a copy
+        enqueued on the current stream; the rows a running pass reads are the copies in its batch buffer, never these)."""
+        need = min(self.count[level] + int(more), self.row_limit(level))
+        cap = self.capacity(level)
+        if need <= cap:
+            return
+        new = torch.empty((min(max(need, 2 * cap, 64), self.row_limit(level)), self._dim), dtype=self.dtype, device=self.device)
+        old = self.store[level]
+        if old is not None:
+            new[:self.count[level]].copy_(old[:self.count[level]])
+            old.record_stream(torch.cuda.current_stream(self.device))
+        self.store[level] = new
+
+    def request_misses(self, level: int, cells: torch.Tensor, misses: torch.Tensor) -> Optional[torch.Tensor]:
+        """:meth:`request` for a level of which the cache holds all but ``misses`` (a subset of ``cells`` in request order): the encoder
+        is asked for those alone, with the same checks.  The rows come back contiguous and 16-byte aligned (what paths_cache_fill reads)."""
+        if self.requested[level] is not None:
+            raise RuntimeError(f"OnDemandSlide {self.slide_id!r}: level {level} was already requested in this pass")
+        self.requested[level], self.encoded[level] = cells, misses
+        n, m = int(cells.shape[0]), int(misses.shape[0])
+        for k, v in (("requests", n), ("hits", n - m), ("misses", m)):
+            self.stats[k][level] += v
+        rows = self._encode(level, misses)
+        if rows is not None and (not rows.is_contiguous() or rows.data_ptr() % 16 != 0):
+            rows = rows.clone(memory_format=torch.contiguous_format)
+        return rows
+
+    def note_stored(self, level: int, misses: int):
+        """Host bookkeeping behind paths_cache_fill: the first ``capacity - count`` of ``misses`` rows are in the store now."""
+        self.count[level] += max(0, min(int(misses), self.capacity(level) - self.count[level]))
+        self.stats["stored"][level] = self.count[level]
+
+    def export_patches(self):
+        """``(coords, features, shapes)`` in :meth:`DeviceSlide.from_patches`' format: per level the stored cells (int64 [n_l, 2] device
+        tensors) and their rows in insertion order.  ``features[l]`` is a VIEW of the store's first ``count[l]`` rows - they are never
+        rewritten, so a slide built from them may share them; writing the lists to disk is the caller's."""
+        coords, features = [], []
+        for l, (X, Y) in enumerate(self.shapes):
+            n = self.count[l]
+            if n == 0:
+                coords.append(torch.empty((0, 2), dtype=torch.int64, device=self.device))
+                features.append(torch.empty((0, self._dim), dtype=self.dtype, device=self.device))
+                continue
+            coords.append(stored_cells(self.index[l], n))
+            features.append(self.store[l][:n])
+        return coords, features, list(self.shapes)
+
+    def visited(self, packed: bool = True) -> "DeviceSlide":
+        """The visited part of the slide as an ordinary stored slide (``DeviceSlide.from_patches`` of :meth:`export_patches`;
+        ``packed=False``: its dense twin).  Cells no pass has asked for are background, stored background is what ``from_patches`` makes
+        of all-zero rows (a row whose tissue mask is 0).
+
+        With the model that filled the cache a free ``recurse`` on it takes the same path and gives the same results bit for bit -
+        every cell it can reach was requested - and so do ``saliency.input_gradients`` / ``attention_relevance`` and the frozen-path
+        functions given that pass's trace.  THE LIMIT: with OTHER weights (the next fold's model, a model after further training) the
+        selection may leave the cached set, and those cells read as background, silently.  :func:`uncached_children` is the guard: all
+        zeros for a pass's trace means the pass saw everything the full slide would have shown it.  With ``max_rows`` set the cache
+        may not hold every requested cell, and the same guard tells.  Training an on-demand slide end to end stays out of scope."""
+        coords, features, shapes = self.export_patches()
+        s = DeviceSlide.from_patches(coords, features, shapes, self.device, self.dtype, self.patch_size, self.slide_id, self.subtype)
+        s.synthetic_spec = self.synthetic_spec
+        return s if packed else s.to_dense()
+
+    def uncached_children(self, trace, keep_patches, patch_size: Optional[int] = None) -> torch.Tensor:
+        """:func:`uncached_children` for the trace of a one-slide pass: int64 [levels]."""
+        return uncached_children([self], trace, keep_patches, patch_size)[0]
+
+    @classmethod
+    def from_slide(cls, slide, max_rows=None) -> "CachedOnDemandSlide":
+        """:meth:`OnDemandSlide.from_slide` with a cache in front of the stored slide's rows (the twin of the tests and of
+        tools/on_demand_cache_time.py)."""
+        return super().from_slide(slide, max_rows=max_rows)
+
+
+def stored_cells(index: torch.Tensor, n: int) -> torch.Tensor:
+    """int64 [n, 2] coordinates of the cells a cache index [X, Y] names, in the order of their rows 0 .. n - 1."""
+    flat = index.reshape(-1)
+    cells = torch.nonzero(flat >= 0).flatten()
+    if int(cells.numel()) != int(n):
+        raise RuntimeError(f"the cache index names {int(cells.numel())} cells for {n} stored rows (was a cell requested twice?)")
+    lin = cells[torch.argsort(flat[cells])]
+    Y = index.shape[1]
+    return torch.stack([lin // Y, lin % Y], dim=1)
 
 
 class OnDemandSlideBatch(_SlideBatch):
     """The batch type of :class:`OnDemandSlide`, beside :class:`DeviceSlideBatch`: the static per-level tables come from the shapes
     (``gx`` / ``gy`` / ``max_dim`` / ``n0`` / ``dim`` / ``dtype``); what a resident batch knows up front and this one cannot - the rows'
     addresses (``grid_ptrs[l]``: per slide, the first of the rows supplied for level ``l``) and max|x| (``feat_absmax``, of the rows
-    supplied so far) - is per-pass state, filled by :meth:`supply` as the recursion goes (paths_amd/utils.py)."""
+    supplied so far) - is per-pass state, filled by :meth:`supply` as the recursion goes (paths_amd/utils.py).
+
+    A batch is all plain or all caching (:class:`CachedOnDemandSlide`; ``caching``): a caching batch serves :meth:`supply` from the
+    slides' row caches and asks the encoders for the misses only (:meth:`_supply_cached`)."""
 
     on_demand = True
 
@@ -780,6 +940,10 @@ class OnDemandSlideBatch(_SlideBatch):
         if not all(getattr(s, "on_demand", False) for s in self.slides):
             raise ValueError("OnDemandSlideBatch: slides of one batch are all on-demand (OnDemandSlide); resident and host-resident "
                              "slides go into a DeviceSlideBatch")
+        kinds = {bool(getattr(s, "caching", False)) for s in self.slides}
+        if len(kinds) != 1:
+            raise ValueError("OnDemandSlideBatch: slides of one batch are all caching (CachedOnDemandSlide) or all plain (OnDemandSlide)")
+        self.caching = kinds.pop()
         dev = self.slides[0].device
         if dev.type != "cuda":
             raise _lib.PathsHipError("paths_amd runs on the GPU only: the slides of a batch live on a GPU device (no CPU fallback)")
@@ -790,6 +954,8 @@ class OnDemandSlideBatch(_SlideBatch):
         self.cells0 = [torch.cartesian_prod(torch.arange(s.shape(0)[0], device=dev), torch.arange(s.shape(0)[1], device=dev)).reshape(-1, 2)
                        for s in self.slides]
         self._host = torch.empty((len(self.slides) + 1,), dtype=torch.int64).pin_memory()      # one read-back per level: num_out | max|x| bits
+        if self.caching:        # the per-slide tables of the cache kernels: cells | n | index, and encoder rows | store | count | capacity
+            self._tables_host = torch.empty((7, len(self.slides)), dtype=torch.int64).pin_memory()
         self.begin_pass()
 
     def begin_pass(self):
@@ -806,21 +972,49 @@ class OnDemandSlideBatch(_SlideBatch):
     def supply(self, level: int, cells: Sequence[torch.Tensor], cap: int) -> torch.Tensor:
         """Ask slide b for ``cells[b]`` of ``level`` and put what it returns into rows [b, 0:n_b] of one ``[B, cap, D]`` buffer (the
         rest zero); ``grid_ptrs[level]`` then holds the address of every slide's first row.  Everything is enqueued on the current
-        stream: the encoder's work is ordered before whatever the caller launches there next."""
+        stream: the encoder's work is ordered before whatever the caller launches there next.  A caching batch fills the same buffer
+        from the slides' caches and asks for the misses only (:meth:`_supply_cached`)."""
         B, D = len(self.slides), self.dim
         buf = torch.empty((B, cap, D), dtype=self.dtype, device=self.device)
-        for b, s in enumerate(self.slides):
-            n = int(cells[b].shape[0])
-            assert n <= cap
-            rows = s.request(level, cells[b])
-            if rows is not None:
-                buf[b, :n].copy_(rows)
-            if n < cap:
-                buf[b, n:].zero_()
+        if self.caching:
+            self._supply_cached(level, cells, buf)
+        else:
+            for b, s in enumerate(self.slides):
+                n = int(cells[b].shape[0])
+                assert n <= cap
+                rows = s.request(level, cells[b])
+                if rows is not None:
+                    buf[b, :n].copy_(rows)
+                if n < cap:
+                    buf[b, n:].zero_()
         self.supplied.append(buf)
         # (base + b * slide stride, computed on the device: torch.tensor(list) would be a blocking upload)
         self.grid_ptrs[level] = torch.arange(B, device=self.device, dtype=torch.int64) * (cap * D * buf.element_size()) + buf.data_ptr()
         return buf
+
+    def _supply_cached(self, level: int, cells: Sequence[torch.Tensor], buf: torch.Tensor):
+        """:meth:`supply` for caching slides, all on the current stream: probe every slide's index -> ONE host read of the B
+        miss counts -> ``encode`` per slide with misses, on its miss cells -> regrow the stores that need it -> fill ``buf`` (hit rows
+        from the store, miss rows from the encoder and, while there is room, into the store and the index; the rest zero).  Each
+        pinned table is rewritten only after a host synchronisation that follows its upload: the miss-count read here, :meth:`read_back`
+        behind every supply."""
+        B, cap, D = buf.shape
+        with torch.cuda.device(self.device):
+            tab, src, cnt, misses = _cache_probe(self.slides, level, cells, cap, D, self.gx[level], self.gy[level], self._tables_host[:3])
+            enc = [s.request_misses(level, cells[b], misses[b]) for b, s in enumerate(self.slides)]
+            for s, m in zip(self.slides, misses):
+                s.reserve(level, int(m.shape[0]))
+            host = self._tables_host[3:]
+            host.copy_(torch.tensor([[0 if r is None else r.data_ptr() for r in enc],
+                                     [0 if s.store[level] is None else s.store[level].data_ptr() for s in self.slides],
+                                     [s.count[level] for s in self.slides], [s.capacity(level) for s in self.slides]], dtype=torch.int64))
+            tab2 = torch.empty((4, B), dtype=torch.int64, device=self.device)
+            tab2.copy_(host, non_blocking=True)
+            p = lambda t: t.data_ptr()
+            _lib.call(entry_name("paths_cache_fill", self.dtype == torch.float16), p(tab[0]), p(tab[1]), p(src), p(cnt[0]), p(tab2[0]), p(tab2[1]),
+                      p(tab2[2]), p(tab2[3]), p(tab[2]), p(self.gx[level]), p(self.gy[level]), B, cap, D, p(buf), _lib.stream())
+            for s, m in zip(self.slides, misses):
+                s.note_stored(level, int(m.shape[0]))
 
     def read_back(self, num_out: Optional[torch.Tensor]) -> List[int]:
         """ONE host synchronisation with the current stream: max|x| of the rows supplied so far goes into ``feat_absmax`` (inf for an
@@ -839,6 +1033,79 @@ def any_on_demand(slides) -> bool:
     if isinstance(slides, _SlideBatch):
         return slides.on_demand
     return any(getattr(s, "on_demand", False) for s in slides)
+
+
+def _cache_probe(slides, level: int, cells: Sequence[torch.Tensor], n_max: int, D: int, gx: torch.Tensor, gy: torch.Tensor,
+                 host: Optional[torch.Tensor] = None):
+    """paths_cache_probe of ``cells[b]`` (int64 [n_b, 2], contiguous, n_b <= n_max) against the ``level`` index of every caching slide,
+    on the current stream, and ONE host read of the miss counts.  ``host``: a pinned int64 [3, B] staging table (None: a blocking
+    upload).  Returns (the device table [3, B] cells | n | index, src [B, n_max], (miss_count | status) [2, B], the per-slide miss
+    cells as views [m_b, 2]).  A cell outside its grid raises PathsHipError."""
+    B, dev = len(slides), slides[0].device
+    rows = torch.tensor([[c.data_ptr() for c in cells], [int(c.shape[0]) for c in cells],
+                         [s.cell_index(level).data_ptr() for s in slides]], dtype=torch.int64)
+    assert all(c.dtype == torch.int64 and c.is_contiguous() and int(c.shape[0]) <= n_max for c in cells)
+    if host is None:
+        tab = rows.to(dev)
+    else:
+        host.copy_(rows)
+        tab = torch.empty((3, B), dtype=torch.int64, device=dev)
+        tab.copy_(host, non_blocking=True)
+    src = torch.empty((B, n_max), dtype=torch.int32, device=dev)
+    miss_cells = torch.empty((B, n_max, 2), dtype=torch.int64, device=dev)
+    cnt = torch.empty((2, B), dtype=torch.int32, device=dev)
+    p = lambda t: t.data_ptr()
+    _lib.call("paths_cache_probe", p(tab[0]), p(tab[1]), p(tab[2]), p(gx), p(gy), B, n_max, D, p(src), p(cnt[0]), p(miss_cells), p(cnt[1]),
+              _lib.stream())
+    counts, status = cnt.cpu().tolist()                     # the host read: waits for the current stream, i.e. for the probe
+    bad = [b for b in range(B) if status[b]]
+    if bad:
+        names = ", ".join(repr(slides[b].slide_id or f"#{b}") for b in bad)
+        raise _lib.PathsHipError(f"on-demand slide {names}: a cell requested at level {level} lies outside its grid")
+    return tab, src, cnt, [miss_cells[b, :counts[b]] for b in range(B)]
+
+
+def uncached_children(slides, trace, keep_patches, patch_size: Optional[int] = None) -> torch.Tensor:
+    """The guard of :meth:`CachedOnDemandSlide.visited`: how many of the cells a pass WOULD have asked a full slide for the caches of
+    ``slides`` (caching slides, or their batch) do not hold.  ``trace``: the pass's trace (``recurse(..., trace=[])``) over slides in
+    the same order - e.g. of a pass run on the ``visited()`` slides under other weights.  Column 0 counts the level-0 cells; for every
+    further level of the trace the existing paths_candidate_children runs on the level above's kept patches and paths_cache_probe on
+    its candidates.  Returns the miss counts, int64 [B, len(trace)] on the host; all zeros: the pass saw everything the full slides
+    would have shown it.  ``keep_patches``: the pass's (one entry per step of the trace); ``patch_size``: the model's (default: the
+    slides').  One host read per level; the caches are left as they are."""
+    slides = list(slides.slides) if isinstance(slides, _SlideBatch) else list(slides)
+    if not slides or not all(getattr(s, "caching", False) for s in slides):
+        raise ValueError("uncached_children: the slides are CachedOnDemandSlides")
+    L, B, dev = len(trace), len(slides), slides[0].device
+    if L < 1 or L > min(s.num_levels for s in slides) or L - 1 > len(keep_patches):
+        raise ValueError(f"uncached_children: a trace of {L} levels does not fit the slides' levels / the {len(keep_patches)} keep_patches entries")
+    ps = int(slides[0].patch_size if patch_size is None else patch_size)
+    out = torch.zeros((B, L), dtype=torch.int64)
+    p = lambda t: t.data_ptr()
+    with torch.cuda.device(dev):
+        for l in range(L):
+            gx, gy = (torch.tensor([s.shape(l)[k] for s in slides], dtype=torch.int32, device=dev) for k in (0, 1))
+            if l == 0:
+                cells = [torch.cartesian_prod(torch.arange(s.shape(0)[0], device=dev), torch.arange(s.shape(0)[1], device=dev)).reshape(-1, 2)
+                         for s in slides]
+            else:
+                t = trace[l - 1]
+                keep_idx, keep_count = t["keep_idx"].to(torch.int32).contiguous(), t["keep_count"].to(torch.int32).contiguous()
+                locs = t["locs"].to(torch.int64).contiguous()
+                if keep_idx.shape[0] != B or locs.shape[0] != B:
+                    raise ValueError(f"uncached_children: the trace holds {keep_idx.shape[0]} slides, {B} were given")
+                ldk = int(keep_idx.shape[1])
+                cand_count = torch.empty((B,), dtype=torch.int32, device=dev)
+                cand_cells = torch.empty((B, 4 * ldk, 2), dtype=torch.int64, device=dev)
+                cand_slot = torch.empty((B, 4 * ldk), dtype=torch.int32, device=dev)
+                _lib.call("paths_candidate_children", p(keep_idx), ldk, p(keep_count), p(locs), int(locs.shape[1]), ps, p(gx), p(gy), B,
+                          p(cand_count), p(cand_cells), p(cand_slot), _lib.stream())
+                counts = cand_count.cpu().tolist()
+                cells = [cand_cells[b, :counts[b]] for b in range(B)]
+            n_max = max(1, max(int(c.shape[0]) for c in cells))
+            misses = _cache_probe(slides, l, cells, n_max, slides[0].dim, gx, gy)[3]
+            out[:, l] = torch.tensor([int(m.shape[0]) for m in misses])
+    return out
 
 
 def slide_batch(slides):
