@@ -2,12 +2,18 @@
 
 The product path has NO fallback: if the shared library is missing or a kernel launch fails this
 module raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"``.
+
+Launches go through :func:`call`.  A :class:`LaunchTape` records them for replay and owns all the state of that: its entries, its HIP
+events, the open :class:`fork_behind` block and the recording thread.  The module keeps one name for it, ``TAPE``: the tape that is
+recording, or None.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import re
+import threading
 from typing import Optional
 
 import torch
@@ -115,9 +121,86 @@ def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-TAPE = None        # a list while paths_amd.utils.TapedRecursion records: every launch is executed AND appended as (fn, args, name)
-TAPE_EVENTS = None # the recorder's event pool: [events, next index]; events are created once per tape position and re-used when a
-                   # tape is recorded again (a weight changed), so re-recording does not leak HIP events
+TAPE = None        # the LaunchTape that is recording (LaunchTape.record), else None: launches are only executed
+
+
+class LaunchTape:
+    """Everything one launch tape needs: the recorded entries ``(fn, args, name)``, the pool of HIP events its stream joins use (one per
+    tape position, created once and re-used when the tape is recorded again - a weight changed - so re-recording leaks none), the
+    :class:`fork_behind` block open on it and the thread that records.  While ``with tape.record():`` runs, ``TAPE`` is this object and
+    every launch of the recording thread (:func:`call`, :func:`stream_wait`, :func:`zeros`) is executed AND appended; an entry from any
+    other thread raises.  :meth:`converted` / :meth:`play` replay it, :meth:`close` destroys the events."""
+
+    def __init__(self):
+        self.entries, self.events, self.cursor, self.block, self.thread = None, [], 0, None, None
+
+    @contextlib.contextmanager
+    def record(self):
+        """Record into fresh entries from the first event of the pool.  Refuses to start while another tape records or a stop event is
+        pending; on every way out ``TAPE`` is None again, after an exception with nothing armed."""
+        global TAPE
+        if TAPE is not None:
+            raise PathsHipError("a launch tape is already being recorded")
+        lib = load()
+        if lib.paths_stop_event_pending():
+            raise PathsHipError("a stop event is pending: a launch tape cannot start recording behind it")
+        self.entries, self.cursor, self.block, self.thread = [], 0, None, threading.get_ident()
+        TAPE = self
+        try:
+            yield self
+        except BaseException:
+            lib.paths_clear_stop_event()
+            raise
+        finally:
+            TAPE, self.block, self.thread = None, None, None
+
+    def append(self, fn, args, name):
+        if threading.get_ident() != self.thread:
+            raise PathsHipError(f"{name} was launched from another thread while a launch tape records: it is not part of the tape")
+        self.entries.append((fn, args, name))
+
+    def next_event(self):
+        """The event of the next tape position: taken from the pool, created when the pool has none left.  Only while recording."""
+        if threading.get_ident() != self.thread:         # (None when not recording)
+            raise PathsHipError("next_event: this launch tape is not recording on this thread")
+        if self.cursor == len(self.events):
+            ev = load().paths_event_create()
+            if not ev:
+                raise PathsHipError("paths_event_create failed")
+            self.events.append(ev)
+        self.cursor += 1
+        return self.events[self.cursor - 1]
+
+    def converted(self) -> list:
+        """The entries with their arguments converted to their ctypes types, once: a replayed call then skips ctypes' per-argument
+        conversion."""
+        self.entries = [(fn, tuple(a if a is None else t(a) for t, a in zip(fn.argtypes, args)), name) for fn, args, name in self.entries]
+        return self.entries
+
+    @staticmethod
+    def play(entries):
+        """Replay ``entries`` in order.  The first one that fails ends it: the stop event is cleared (a failure between
+        paths_set_stop_event and the kernel that takes it leaves nothing armed) and PathsHipError names the entry."""
+        for fn, args, name in entries:
+            if fn(*args) != 0:
+                lib = load()
+                msg = lib.paths_last_error().decode()
+                lib.paths_clear_stop_event()
+                raise PathsHipError(f"{name} failed during tape replay: {msg}")
+
+    def close(self, device=None):
+        """Drop the entries and destroy every event, once (a second call finds none); ``device`` is synchronised first, so that no replay
+        in flight still waits on them.  Safe at interpreter shutdown, when the runtime may be gone already."""
+        evs, self.events, self.cursor, self.entries = self.events, [], 0, None
+        if evs:
+            try:
+                if device is not None:
+                    torch.cuda.synchronize(device)
+                lib = load()
+                for ev in evs:
+                    lib.paths_event_destroy(ev)
+            except Exception:
+                pass
 
 
 def call(name: str, *args):
@@ -127,29 +210,17 @@ def call(name: str, *args):
     if rc != 0:
         raise PathsHipError(f"{name} failed ({rc}): {lib.paths_last_error().decode()}")
     if TAPE is not None:
-        TAPE.append((fn, args, name))
-        fb = fork_behind.active
+        TAPE.append(fn, args, name)
+        fb = TAPE.block
         if fb is not None and fb.taken_at is None and name != "paths_set_stop_event" and not lib.paths_stop_event_pending():
-            fb.taken_at = len(TAPE) - 1                  # this call's kernel carries the block's stop event
-
-
-def _next_event():
-    """The event of the next tape position: taken from the recorder's pool, created when the pool has none left."""
-    pool = TAPE_EVENTS if TAPE_EVENTS is not None else [[], 0]
-    if pool[1] == len(pool[0]):
-        ev = load().paths_event_create()
-        if not ev:
-            raise PathsHipError("paths_event_create failed")
-        pool[0].append(ev)
-    pool[1] += 1
-    return pool[0][pool[1] - 1]
+            fb.taken_at = len(TAPE.entries) - 1          # this call's kernel carries the block's stop event
 
 
 def stream_wait(dst: "torch.cuda.Stream", src: "torch.cuda.Stream"):
     """``dst.wait_stream(src)``; recorded on the launch tape (as a paths_stream_wait with its own event) when one is being built."""
     dst.wait_stream(src)
     if TAPE is not None:
-        TAPE.append((load().paths_stream_wait, (dst.cuda_stream, src.cuda_stream, _next_event()), "paths_stream_wait"))
+        TAPE.append(load().paths_stream_wait, (dst.cuda_stream, src.cuda_stream, TAPE.next_event()), "paths_stream_wait")
 
 
 STOP_EVENTS = os.environ.get("PATHS_STOP_EVENTS", "1") != "0"
@@ -170,9 +241,10 @@ class fork_behind:
     assumed: the C call that owns the stop-capable kernel is the one during which ``paths_stop_event_pending()`` falls to 0
     (:func:`call` notes it); if any launch was recorded after it the event is recorded again behind the block the ordinary way
     (``paths_record_event``: waiters then wait for the later record), so a launch added behind the finish / top-K kernel cannot let
-    ``dst`` start early on a replayed tape."""
+    ``dst`` start early on a replayed tape.
 
-    active = None        # the block being recorded (call() reports to it)
+    The library arms ONE event per host thread, so a tape has one block open at a time (``LaunchTape.block``): entering a second one, or
+    entering while an event is still pending, raises before anything is armed."""
 
     def __init__(self, dsts, src):
         self.dsts, self.src = list(dsts), src
@@ -181,19 +253,23 @@ class fork_behind:
 
     def __enter__(self):
         if TAPE is not None and STOP_EVENTS:
-            self.ev = _next_event()
+            if TAPE.block is not None:
+                raise PathsHipError("fork_behind inside another fork_behind: the library arms one stop event at a time")
+            if load().paths_stop_event_pending():
+                raise PathsHipError("fork_behind: a stop event is already pending")
+            self.ev = TAPE.next_event()
             call("paths_set_stop_event", self.ev)
-            self.prev, fork_behind.active = fork_behind.active, self
+            TAPE.block = self
         return self
 
     def __exit__(self, et, ev, tb):
         if self.ev is not None:
-            fork_behind.active = self.prev
+            TAPE.block = None
             if et is not None:
                 load().paths_clear_stop_event()         # an exception inside the block: leave nothing armed for an unrelated launch
                 return False
             call("paths_flush_stop_event", self.src.cuda_stream)
-            if self.taken_at is not None and any(nm not in _TAPE_PLUMBING for _, _, nm in TAPE[self.taken_at + 1:]):
+            if self.taken_at is not None and any(nm not in _TAPE_PLUMBING for _, _, nm in TAPE.entries[self.taken_at + 1:]):
                 call("paths_record_event", self.ev, self.src.cuda_stream)     # launches followed the stop-capable kernel: cover them
             for d in self.dsts:
                 call("paths_stream_wait_event", d.cuda_stream, self.ev)
@@ -207,7 +283,7 @@ def zeros(shape, **kw) -> torch.Tensor:
     """``torch.zeros`` whose fill is repeated on every replay of a launch tape (status words, importance of padding rows)."""
     t = torch.zeros(shape, **kw)
     if TAPE is not None:
-        TAPE.append((load().paths_memset_zero, (t.data_ptr(), t.numel() * t.element_size(), stream()), "paths_memset_zero"))
+        TAPE.append(load().paths_memset_zero, (t.data_ptr(), t.numel() * t.element_size(), stream()), "paths_memset_zero")
     return t
 
 

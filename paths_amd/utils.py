@@ -26,7 +26,6 @@ ROCTX_RANGES = os.environ.get("PATHS_ROCTX", "0") != "0"     # roctx ranges "lev
                                                              # of each level (rocprofv3 --marker-trace; torch.cuda.nvtx = roctx on ROCm)
 ROWS_IN_PLACE = os.environ.get("PATHS_ROWS_IN_PLACE", "1") != "0"
 TRAIN_PARENT = os.environ.get("PATHS_TRAIN_PARENT", "1") != "0"      # training: h half of the LSTM gates once per kept parent
-STREAM_LANE = 0      # which stream triple _recurse uses (TapedRecursion(lane=k) records each lane on its own streams)
 _STREAMS: Dict[int, tuple] = {}
 
 
@@ -159,8 +158,8 @@ class TapedRecursion:
 
     The optimistic pass is sync-free with static capacities, resident slides and cached weight images: a step is a fixed sequence
     of ~70 kernel launches, a dozen cross-stream joins and two zero fills on three HIP streams.  The first call runs it eagerly
-    while ``paths_amd._lib`` records every C call with its final arguments (device pointers, sizes, the stream handle); a replay
-    is then a tight loop over that list - no tensor allocation, no pack look-ups, no Python-side shape logic - on the SAME three
+    while a ``_lib.LaunchTape`` records every C call with its final arguments (device pointers, sizes, the stream handle); a replay
+    is then its tight loop over that list - no tensor allocation, no pack look-ups, no Python-side shape logic - on the SAME three
     streams with the same joins, so the overlap of the eager schedule is kept (a captured HIP graph loses most of it on ROCm 7.2,
     see GraphedRecursion) while the host's share of a step drops from ~0.65 to ~0.15.  Outputs live in the buffers of the recorded
     pass and are overwritten by every replay.
@@ -168,7 +167,11 @@ class TapedRecursion:
     Validity: the tape holds the weight images current at recording time; ``replay()`` records again when any parameter's version
     counter has moved.  Like the eager fast path it does not handle the zero-children fallback itself: :meth:`run` checks the
     status word and hands such a batch to ``recurse()``.  ``slide_ctx_mode="concat"`` stacks contexts with a torch op per level
-    and is not taped (eager path)."""
+    and is not taped (eager path).
+
+    This class is a client of the tape: it keeps the memory pool, the private table copy, the parameter versions and ``tape``, the
+    plain list of ``(fn, ctypes_args, name)`` that is replayed (None before recording; replaceable).  Recording, the events, the replay
+    loop and their clean-up are the ``LaunchTape``'s.  ``lane`` picks the stream triple the pass is recorded on and replays on."""
 
     def __init__(self, model, slides, keep_patches: Sequence[int], num_levels: int, lane: int = 0):
         self.model, self.keep, self.levels, self.lane = model, list(keep_patches), int(num_levels), int(lane)
@@ -176,7 +179,7 @@ class TapedRecursion:
         self.tape, self.out, self.versions, self.stream_handle = None, None, None, None
         self._unjoined = False               # a replay(join=False) whose streams the caller stream has not waited for yet
         self._rec_batch = None               # private copy of the recorded batch's table TENSORS: what the tape addresses (rebind() re-points them)
-        self._events = [[], 0]               # HIP events of the tape's stream joins, re-used when the tape is recorded again
+        self._tape = _lib.LaunchTape()       # records the pass; owns the HIP events of its stream joins across re-recordings
         # The tape holds raw device addresses of every intermediate of the recorded pass.  Those tensors are freed when the pass
         # returns; from the default caching allocator their blocks would be handed to whoever allocates next, and a replay would
         # then write into memory somebody else owns.  So the recorded pass allocates from a pool of its own: freed blocks stay in
@@ -188,45 +191,23 @@ class TapedRecursion:
     def close(self):
         """Drop the tape and destroy the HIP events of its stream joins (a service that records one tape per batch would otherwise
         accumulate about a dozen events per tape).  Called by __del__; the tape can be recorded again afterwards."""
-        evs = (getattr(self, "_events", None) or [[], 0])[0]      # (__init__ may have raised before _events existed)
-        self._events = [[], 0]
         self.tape = None
-        if evs:
-            try:
-                torch.cuda.synchronize(self.batch.device)       # no replay in flight still waits on them
-                lib = _lib.load()
-                for ev in evs:
-                    lib.paths_event_destroy(ev)
-            except Exception:                                    # interpreter shutdown: the runtime may be gone already
-                pass
+        if hasattr(self, "_tape"):                               # (__init__ may have raised before _tape existed)
+            self._tape.close(self.batch.device)
 
     def __del__(self):
         self.close()
 
     def record(self):
-        global STREAM_LANE
-        saved_lane, STREAM_LANE = STREAM_LANE, self.lane
-        try:
-            with torch.no_grad():
-                tab = self.batch.clone_tables()                  # the tape's OWN table tensors (rebind() re-points them)
-                _recurse(self.model, tab, self.keep, self.levels, None, careful=False)      # warm-up: builds cached images / tables
-                torch.cuda.synchronize(self.batch.device)
-                assert _lib.TAPE is None, "a launch tape is already being recorded"
-                self.out = None                                   # (a re-recording re-uses the pool's blocks: drop the old outputs first)
-                _lib.TAPE = tape = []
-                self._events[1] = 0
-                _lib.TAPE_EVENTS = self._events
-                try:
-                    with torch.cuda.use_mem_pool(self._pool, device=self.batch.device):
-                        out = _recurse(self.model, tab, self.keep, self.levels, None, careful=False)
-                finally:
-                    _lib.TAPE, _lib.TAPE_EVENTS = None, None
-                torch.cuda.synchronize(self.batch.device)
-        finally:
-            STREAM_LANE = saved_lane
-        # arguments pre-converted to their ctypes types once: a replayed call then skips ctypes' per-argument conversion
-        tape = [(fn, tuple(a if a is None else t(a) for t, a in zip(fn.argtypes, args)), name) for fn, args, name in tape]
-        self.tape, self.out, self.versions = tape, out, _param_versions(self.model)
+        with torch.no_grad():
+            tab = self.batch.clone_tables()                  # the tape's OWN table tensors (rebind() re-points them)
+            _recurse(self.model, tab, self.keep, self.levels, None, careful=False, lane=self.lane)      # warm-up: builds cached images / tables
+            torch.cuda.synchronize(self.batch.device)
+            self.out = None                                   # (a re-recording re-uses the pool's blocks: drop the old outputs first)
+            with self._tape.record(), torch.cuda.use_mem_pool(self._pool, device=self.batch.device):
+                out = _recurse(self.model, tab, self.keep, self.levels, None, careful=False, lane=self.lane)
+            torch.cuda.synchronize(self.batch.device)
+        self.tape, self.out, self.versions = self._tape.converted(), out, _param_versions(self.model)
         self.stream_handle = torch.cuda.current_stream(self.batch.device).cuda_stream
         self._rec_batch = tab
         return self
@@ -277,14 +258,6 @@ class TapedRecursion:
         self.batch = new                 # (keeps the bound slides alive; run()'s fallback recurses on them)
         return self
 
-    def _play(self, ops_):
-        for fn, args, name in ops_:
-            if fn(*args) != 0:
-                lib = _lib.load()
-                msg = lib.paths_last_error().decode()
-                lib.paths_clear_stop_event()      # a failure between paths_set_stop_event and the kernel that takes it: leave nothing armed
-                raise _lib.PathsHipError(f"{name} failed during tape replay: {msg}")
-
     def replay(self, join: bool = True) -> Dict[str, torch.Tensor]:
         """join=False leaves out the tape's last entry (the caller stream waiting for this lane's streams): several lanes
         (sub-batches recorded on different stream triples) are then enqueued back to back and run CONCURRENTLY; call
@@ -293,12 +266,12 @@ class TapedRecursion:
             self.record()
         assert torch.cuda.current_stream(self.batch.device).cuda_stream == self.stream_handle, "replay on the stream the tape was recorded on"
         assert self.tape[-1][2] == "paths_stream_wait"
-        self._play(self.tape if join else self.tape[:-1])
+        self._tape.play(self.tape if join else self.tape[:-1])
         self._unjoined = not join
         return self.out
 
     def join(self):
-        self._play(self.tape[-1:])
+        self._tape.play(self.tape[-1:])
         self._unjoined = False
 
     def run(self) -> Dict[str, torch.Tensor]:
@@ -347,11 +320,11 @@ class _Range:
         return False
 
 
-def _streams(dev, lane: Optional[int] = None):
-    """(selection-chain stream, aggregator stream, parent-partials stream) of a device.  The selection chain is the critical path of the recursion,
+def _streams(dev, lane: int = 0):
+    """(selection-chain stream, aggregator stream, parent-partials stream) of a device, one triple per ``lane``.  The selection chain is the critical path of the recursion,
     so it gets the high-priority queue: its workgroups are dispatched first and the aggregator fills what is left."""
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (idx, STREAM_LANE if lane is None else lane)
+    key = (idx, lane)
     if key not in _STREAMS:
         hi = -1 if os.environ.get("PATHS_STREAM_PRIORITIES", "1") != "0" else 0
         agg = torch.cuda.Stream(device=idx, priority=0)
@@ -376,7 +349,7 @@ def _streams(dev, lane: Optional[int] = None):
 
 
 def _recurse(model, slides, keep_patches: Sequence[int], num_levels: int,
-             trace: Optional[list] = None, careful: bool = False, attention: bool = False, rollout: bool = False) -> Dict[str, torch.Tensor]:
+             trace: Optional[list] = None, careful: bool = False, attention: bool = False, rollout: bool = False, lane: int = 0) -> Dict[str, torch.Tensor]:
     batch = slide_batch(slides)
     if batch.on_demand:
         # max|x| is only known as the rows arrive: every level whose rows raise it enters a range_guard of its own on this stack
@@ -386,21 +359,21 @@ def _recurse(model, slides, keep_patches: Sequence[int], num_levels: int,
             batch.guards = guards
             guards.callback(batch.end_pass)
             try:
-                return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout)
+                return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout, lane)
             except BaseException:
                 # (a refused slide, a bad encode() result, inf / NaN rows: the pass's streams have not been joined - nothing of it
                 # is in flight any more when its buffers are dropped and the error leaves)
                 torch.cuda.synchronize(batch.device)
                 raise
     with ops.range_guard(batch.feat_absmax):       # out-of-range features run on the exact bf16 split (no fp16 overflow)
-        return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout)
+        return _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention, rollout, lane)
 
 
-def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention=False, rollout=False):
+def _recurse_streams(model, batch, keep_patches, num_levels, trace, careful, attention=False, rollout=False, lane=0):
     if not (OVERLAP_AGGREGATOR and batch.device.type == "cuda"):
         return _recurse_body(model, batch, keep_patches, num_levels, trace, careful, None, None, attention, rollout)
     caller = torch.cuda.current_stream(batch.device)
-    sel_stream, agg_stream, par_stream = _streams(batch.device)
+    sel_stream, agg_stream, par_stream = _streams(batch.device, lane)
     if torch.cuda.is_current_stream_capturing():
         # HIP graph capture (GraphedRecursion): on ROCm 7.2 a stream that forks from an already-forked stream crashes
         # hipStreamEndCapture, so every side stream forks from the capture's origin stream: the selection chain runs on the origin

@@ -1085,6 +1085,40 @@ def test_two_batches_in_flight_give_the_single_lane_results(dev):
         pipe.close()
 
 
+def test_tapes_on_explicit_lanes_leave_the_eager_pass_on_lane_0(dev, monkeypatch):
+    """The stream lane is an argument of the pass, not module state: two tapes of one batch recorded one after the other on lanes 1 and 2
+    join only their own lane's streams, replayed alternately they give the eager results bit for bit, and a plain recurse() made in
+    between asks for lane 0's streams - recording on a lane leaves nothing behind."""
+    from paths_amd import utils as putils
+    from paths_amd.data_utils.slide import DeviceSlide, DeviceSlideBatch
+    cfg, model, _ = build_model(dev, 3, None, top_k_patches=[8] * 4)
+    slides = DeviceSlideBatch([DeviceSlide.synthetic(41, sid, (5, 6), p_bg=0.1, device=dev) for sid in range(2)])
+    with torch.no_grad():
+        ref = {k: v.clone() for k, v in putils.recurse(model, slides, cfg.top_k_patches, 5).items()}
+    asked, real_streams = [], putils._streams
+    monkeypatch.setattr(putils, "_streams", lambda d, lane=0: asked.append(lane) or real_streams(d, lane))
+    tapes = [putils.TapedRecursion(model, slides, cfg.top_k_patches, 5, lane=lane).record() for lane in (1, 2)]
+    assert asked == [1, 1, 2, 2]                          # (warm-up and recorded pass of each)
+    handles = lambda lane: {s.cuda_stream for s in real_streams(slides.device, lane)}
+    caller = torch.cuda.current_stream(dev).cuda_stream
+    val = lambda x: int(getattr(x, "value", x) or 0)
+    assert len(handles(0) | handles(1) | handles(2)) == 9
+    for t, lane in zip(tapes, (1, 2)):
+        joined = {val(a[i]) for _, a, name in t.tape if name == "paths_stream_wait" for i in (0, 1)}
+        assert joined == handles(lane) | {caller}, lane
+    for rnd in range(3):
+        for t in tapes:
+            out = t.run()
+            assert torch.equal(out["logits"], ref["logits"]) and torch.equal(out["ctx_slide"], ref["ctx_slide"]), (rnd, t.lane)
+        del asked[:]
+        with torch.no_grad():
+            eager = putils.recurse(model, slides, cfg.top_k_patches, 5)
+        assert asked == [0] and torch.equal(eager["logits"], ref["logits"]) and torch.equal(eager["ctx_slide"], ref["ctx_slide"])
+    assert torch.equal(tapes[0].out["logits"], tapes[1].out["logits"]) and torch.equal(tapes[0].out["ctx_slide"], tapes[1].out["ctx_slide"])
+    for t in tapes:
+        t.close()
+
+
 def test_tape_rebinds_to_other_batches(dev):
     """TapedRecursion.rebind (missing 6): ONE recorded tape pointed at other resident batches by copying their table
     tensors into the tape's own - same results as the eager recursion of each batch bit for bit, in any order, including a batch of

@@ -31,7 +31,7 @@ lo, hi = idx[3], idx[6]
 level = [c for c in tr.tape[lo:hi] if c[2] not in ("paths_expand_children", "paths_gather_rows")]
 print("level-1 calls:", [n for _, _, n in level])
 torch.cuda.synchronize()
-tr._play(tr.tape[:hi]); torch.cuda.synchronize()
+tr._tape.play(tr.tape[:hi]); torch.cuda.synchronize()
 
 
 def t_of(calls):
@@ -40,7 +40,7 @@ def t_of(calls):
         torch.cuda.Event(enable_timing=True).record()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        tr._play(calls)
+        tr._tape.play(calls)
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b) * 1e3)
