@@ -102,6 +102,10 @@
  *                                      (both written by the caller)
  *   paths_raster_maps                  value rows of padding: never read (only rows an index grid names are); out on entry: never
  *                                      read, every element of the padded allocation is written
+ *   paths_render_range                 raster cells no drawn index grid names: never read; partial, range, status on entry: never
+ *                                      read (status is written, not accumulated)
+ *   paths_render_rgb                   raster cells no drawn index grid names, thumbnail bytes outside a slide's extent: never read;
+ *                                      out on entry: never read, every byte of the padded allocation is written
  * row cache of on-demand slides
  *   paths_cache_probe                  cells beyond n[b]: never read; src, miss_count, miss_cells, status on entry: never read
  *   paths_cache_fill / _h16            src beyond n[b], store rows at and beyond count[b], out on entry: never read; every row of out
@@ -986,6 +990,38 @@ int paths_raster_index(const int64_t* locs, const int64_t* num_ims, const int* g
                        int GX, int GY, int* index, int64_t ldi, int* status, paths_stream_t stream);
 int paths_raster_maps(const int64_t* table, const int* gx, const int* gy, int L, int B, int GX, int GY, int value_f64, int out_f64, int fold,
                       const double* offset_w, void* out, int64_t ldo, paths_stream_t stream);
+
+/* Overlays: a raster of the two entries above as 8-bit RGB pixels (paths_amd/heatmap.py:render; csrc/raster.hip; the
+ * drawing of reference heatmap_visualise.py:148-181).  table, gx, gy, L, B, GX, GY as paths_raster_maps (the value columns of table are
+ * not read); raster: the allocation paths_raster_maps wrote, fp32 (raster_f64 = 0) or fp64, row stride ldo; level = -1: its fold form
+ * [B, GX f, ldo], level = l: plane l of its planes form [B, L, GX f, ldo].  The DRAWN levels are all levels for level = -1, else
+ * level l alone.  A finest cell is VISITED when an index grid of a drawn level names a row on the cell that covers it and the
+ * raster's value there is finite; the raster is read on cells an index grid of a drawn level names, and nowhere else.
+ *
+ * paths_render_range: range [B][2] fp64 = (vmin, vmax) per slide over its visited cells.  center = NULL: (min + 0.0, max + 0.0) of
+ * the value (a -0 extreme becomes +0); center: DEVICE [1] fp64 z: m = max |value - z|, (z - m, z + m).  (0, 0) for a slide without a
+ * visited cell.  status [B] int32: 1 when a cell a drawn index grid names holds a non-finite value, else 0.  Two launches of fixed
+ * shape (64 partial blocks per slide, then one thread per slide), no atomics: min / max of finite values do not depend on the
+ * order, so the result is bit-identical on repeat.  partial: workspace of B * 64 * 3 fp64.
+ *
+ * paths_render_rgb: out uint8 [B, GX f c, ldp], c = cell_px in [1, 64], ldp a multiple of 16 and at least GY f c * 3 bytes, out
+ * 16-byte aligned; pixel (u, v) of slide b at bytes [3 v, 3 v + 3) of row u shows finest cell (u / c, v / c).  All slides in one
+ * launch, one thread per 16 consecutive pixels of a row (three 16-byte stores).  With (vmin, vmax) = range[b], in fp64 with every
+ * operation rounded separately:
+ *     t256 = (value - vmin) / (vmax - vmin) * 256.0;  k = t256 >= 255 ? 255 : t256 > 0 ? (int)t256 : 0;  k = 0 when vmax == vmin
+ *     visited pixel:  (alpha255 * colours[k] + (255 - alpha255) * under + 127) / 255 per channel, in integers
+ *     other pixels of the slide's extent:  under
+ * colours: DEVICE [256] uint32 = r | g << 8 | b << 16; under = background (same packing), or with thumbs != NULL the pixel of the
+ * slide's thumbnail: thumbs DEVICE [B][2] int64 = (address of a uint8 image [gx[b] f c, gy[b] f c, 3] with pixel stride 3, its row
+ * stride in bytes).  Outlines, painted last and opaque, whatever the value: for every level l of the bit mask outline_levels whose index
+ * grid names a row on the cell covering a pixel, the pixel takes outline_rgb when it lies in the first or last pixel row or column of
+ * that cell (which spans c << (L-1-l) pixels).  Pixels outside a slide's own extent and the pad bytes of every row are written as 0:
+ * every byte of out is written, none is read.  No atomics, no LDS: bit-identical on repeat. */
+int paths_render_range(const int64_t* table, const int* gx, const int* gy, int L, int B, int GX, int GY, int level, const void* raster,
+                       int raster_f64, int64_t ldo, const double* center, double* partial, double* range, int* status, paths_stream_t stream);
+int paths_render_rgb(const int64_t* table, const int* gx, const int* gy, int L, int B, int GX, int GY, int level, const void* raster,
+                     int raster_f64, int64_t ldo, const double* range, const uint32_t* colours, const int64_t* thumbs, int cell_px, int alpha255,
+                     int outline_levels, uint32_t outline_rgb, uint32_t background, uint8_t* out, int64_t ldp, paths_stream_t stream);
 
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */

@@ -1,4 +1,5 @@
-"""Heat-map export (the data consumed by reference heatmap_visualise.py:113-175; drawing is out of scope).
+"""Heat-map export (the data consumed by reference heatmap_visualise.py:113-175) and the overlay drawn from it (:func:`render`, its
+lines 148-181); figure layout - viewport, colour bar, annotations - is out of scope.
 
 ``hierarchy_from_trace`` pulls one slide's per-level patch locations / importances / selected indices (and, from a
 ``recurse(..., attention=True)`` trace, the special token's attention; from a ``recurse(..., rollout=True)`` trace, its attention
@@ -16,15 +17,21 @@ cell = one patch of the last level), i.e. level-0 pixel space divided by ``patch
 
 The functions above work on host records, one slide and one patch at a time, and define the contract.  :func:`rasterize` computes the
 same rasters on the device for all slides of a trace at once, without the host copies (csrc/raster.hip; ``removed_map`` excepted).
+:func:`render` turns one of them into 8-bit RGB pixels there: colour table, blend over a thumbnail, one outline per visited patch;
+:func:`save_png` writes such an image with the standard library alone.
 """
 from __future__ import annotations
 
+import struct
+import zlib
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from .colormaps import colour_table
 
 
 # per-row attributions a saliency trace may carry: input_gradients', integrated_gradients' and smooth_grad's
@@ -235,6 +242,17 @@ def rasterize(trace: List[dict], base_grids, kind: str = "importance", *, layer:
     ``check`` reads the kernels' status word (one host synchronise) and raises PathsHipError when a recorded location lies outside its
     slide's grid; with ``check=False`` such rows are skipped silently.  Only ``magnification_factor`` 2 exists: the recursion expands a
     patch into 2 x 2 children.  Host records stay with the NumPy functions: there is no CPU fallback here."""
+    plan = _raster_plan(trace, base_grids, kind, layer, head, fold, offset, patch_size, magnification_factor, dtype)
+    for lv in trace:                                       # last of the checks, so that the others can be met without a GPU
+        _lib.require_cuda(lv["locs"], lv["num_ims"], lv[kind])
+    run = _raster_run(trace, plan)
+    if check:
+        _raise_outside(int(run.status[0].item()), plan.L)
+    return run.views
+
+
+def _raster_plan(trace, base_grids, kind, layer, head, fold, offset, patch_size, magnification_factor, dtype) -> SimpleNamespace:
+    """Every check of :func:`rasterize` that needs no device, and what they settle: L, B, grids, folded, w, off."""
     if kind not in RASTER_KINDS:
         raise ValueError("kind must be one of %s, got %r" % (", ".join(repr(k) for k in RASTER_KINDS), kind))
     if magnification_factor != 2:
@@ -266,12 +284,25 @@ def rasterize(trace: List[dict], base_grids, kind: str = "importance", *, layer:
                 raise IndexError("rasterize: layer %d out of range for the %d decoder layers of level %d" % (layer, n_layers, depth))
             if head is not None and not 0 <= head < n_heads:
                 raise IndexError("rasterize: head %d out of range for the %d heads of level %d" % (head, n_heads, depth))
-    for lv in trace:                                       # last of the checks, so that the others can be met without a GPU
-        _lib.require_cuda(lv["locs"], lv["num_ims"], lv[kind])
     folded = (kind == "importance") if fold is None else fold is not False
     w = 0.5 if fold is None or fold is False else float(fold)
     off = (1e-4 if kind == "importance" else 0.0) if offset is None else float(offset)
+    return SimpleNamespace(L=L, B=B, grids=grids, folded=folded, w=w, off=off, kind=kind, layer=layer, head=head, patch_size=int(patch_size),
+                           dtype=dtype)
 
+
+def _raise_outside(bits: int, L: int):
+    if bits:
+        raise _lib.PathsHipError("rasterize: level(s) %s hold a location outside their slide's grid (base_grids or patch_size do not "
+                                 "belong to this trace)" % ", ".join(str(l) for l in range(L) if bits >> l & 1))
+
+
+def _raster_run(trace: List[dict], plan: SimpleNamespace, more_status: int = 0) -> SimpleNamespace:
+    """The launches of :func:`rasterize` (one paths_raster_index per level, one paths_raster_maps) on the current stream of the trace's
+    device; the status word is read by the caller.  ``more_status``: further zeroed int32 words behind it, for the caller's own kernels."""
+    L, B, grids, folded, w, off, kind, dtype, patch_size = (plan.L, plan.B, plan.grids, plan.folded, plan.w, plan.off, plan.kind, plan.dtype,
+                                                            plan.patch_size)
+    layer, head = plan.layer, plan.head
     dev = trace[0]["locs"].device
     f = 1 << (L - 1)
     GX, GY = max(g[0] for g in grids), max(g[1] for g in grids)
@@ -285,7 +316,7 @@ def rasterize(trace: List[dict], base_grids, kind: str = "importance", *, layer:
         ldi = [((GY << l) + 3) // 4 * 4 for l in range(L)]
         sizes = [B * (GX << l) * ldi[l] for l in range(L)]
         index = torch.full((sum(sizes),), -1, dtype=torch.int32, device=dev)
-        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        status = torch.zeros((1 + more_status,), dtype=torch.int32, device=dev)
         ldo = (GY * f + 3) // 4 * 4
         out = torch.empty((B, GX * f, ldo) if folded else (B, L, GX * f, ldo), dtype=dtype, device=dev)
         # one host -> device copy: the per-level table, (offset, w) and the level-0 extents
@@ -307,9 +338,171 @@ def rasterize(trace: List[dict], base_grids, kind: str = "importance", *, layer:
                       GX, GY, int(host[4 * l]), ldi[l], status.data_ptr(), stream)
         _lib.call("paths_raster_maps", p_table, p_gx, p_gy, L, B, GX, GY, int(values[0].dtype == torch.float64), int(dtype == torch.float64),
                   int(folded), p_offw, out.data_ptr(), ldo, stream)
+    views = [out[b, :g[0] * f, :g[1] * f] if folded else out[b, :, :g[0] * f, :g[1] * f] for b, g in enumerate(grids)]
+    # (tables and index stay referenced: a caller's further kernels read them through p_table)
+    return SimpleNamespace(views=views, out=out, status=status, tables=tables, index=index, p_table=p_table, p_gx=p_gx, p_gy=p_gy, GX=GX, GY=GY,
+                           ldo=ldo, dev=dev)
+
+
+# ---- the overlay: a raster as pixels (csrc/raster.hip: paths_render_range / paths_render_rgb) ---------------------------
+
+MAX_CELL_PX = 64               # include/paths_hip.h: paths_render_rgb
+MIN_OUTLINED_SPAN = 4          # a cell narrower than this many pixels gets no outline: it would be all outline
+
+
+def _rgb_word(rgb, name: str) -> int:
+    c = tuple(int(v) for v in rgb)
+    if len(c) != 3 or any(not 0 <= v <= 255 for v in c):
+        raise ValueError("render: %s is three integers in [0, 255], got %r" % (name, rgb))
+    return c[0] | c[1] << 8 | c[2] << 16
+
+
+def _per_slide(v, B: int, name: str) -> np.ndarray:
+    a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+        raise ValueError("render: %s is a scalar or one value per slide (%d), got shape %r" % (name, B, tuple(a.shape)))
+    if not np.isfinite(a).all():
+        raise ValueError("render: %s must be finite" % name)
+    return np.broadcast_to(a, (B,))
+
+
+def render(trace: List[dict], base_grids, kind: str = "importance", *, level: Optional[int] = None, layer: int = -1, head: Optional[int] = None,
+           fold=None, offset: Optional[float] = None, thumbnails=None, cell_px: int = 4, cmap="viridis", alpha: float = 0.5, vmin=None,
+           vmax=None, center: Optional[float] = None, outline=True, outline_rgb=(0, 0, 0), background=(255, 255, 255), patch_size: int = 256,
+           dtype: torch.dtype = torch.float32, check: bool = True) -> List[torch.Tensor]:
+    """One uint8 RGB overlay ``[X0 f c, Y0 f c, 3]`` per slide of ``trace``, on the device (f = 2**(L-1), c = ``cell_px`` in 1..64): the
+    picture reference heatmap_visualise.py:148-181 draws - the map through a colour table, at ``alpha`` over the slide where a patch was
+    visited, one rectangle per visited patch and level.  The first axis is the locations' first coordinate, as in the rasters; pixel
+    (u, v) shows finest cell (u // c, v // c).
+
+    ``trace``, ``base_grids``, ``kind``, ``layer``, ``head``, ``offset``, ``patch_size``, ``dtype``: as in :func:`rasterize`, whose
+    launches compute the drawn VALUE: with ``level=None`` the folded map ``rasterize(..., fold=w)``, w = ``fold`` (0.5 by default, for
+    every kind); with ``level=l`` plane l of ``rasterize(..., fold=False)`` (``fold`` must then stay None).
+
+    VISITED is a finest cell on which an index grid of a drawn level names a row (all levels for the folded map - a deeper cell without
+    a level-0 parent counts, as in :func:`importance_map` -, else level l alone), never ``value != 0``.
+
+    RANGE, per slide: ``vmin`` / ``vmax`` where given (a scalar or one value per slide); else with ``center=None`` the minimum / maximum of
+    the value over the slide's visited cells (for the folded importance map the reference's rule: zeros filled with the smallest positive
+    value, then autoscaled), with ``center=z`` ``z -+ max |value - z|`` (the signed kinds under a diverging table); 0, 0 for a slide
+    without a visited cell.  A non-finite value on a visited cell is left out of the range and drawn as not visited; with ``check`` it
+    raises PathsHipError naming the slides (the same synchronise reads :func:`rasterize`'s status), with ``check=False`` nothing more.
+
+    COLOUR, in fp64 (fp32 values convert exactly): ``t256 = (value - vmin) / (vmax - vmin) * 256.0``, ``k = clamp(int(t256), 0, 255)``,
+    k = 0 when ``vmax == vmin``; ``cmap``: "viridis", "bwr" (:mod:`paths_amd.colormaps`) or a uint8 ``[256, 3]`` array / tensor.
+    BLEND, in integers: ``a = round(alpha * 255)``; a visited pixel is ``(a * colour + (255 - a) * under + 127) // 255`` per channel, any
+    other pixel ``under``: the pixel of ``thumbnails[b]`` (uint8 device tensors ``[X0 f c, Y0 f c, 3]``, last strides (3, 1), any row
+    stride) or ``background``.  OUTLINE: True (all levels), a sequence of levels, or False.  A cell of level l spans
+    ``s = c << (L-1-l)`` pixels; where s >= 4, every pixel (u, v) inside a cell that level visited takes ``outline_rgb``, opaque and last,
+    when ``min(u % s, v % s) == 0 or max(u % s, v % s) == s - 1``.
+
+    Departures from the reference's drawing: nearest-neighbour pixels instead of a resampled image; integer blending; one-pixel outlines
+    instead of anti-aliased half-point lines; no viewport crop, colour bar or annotation polygons, which stay with whoever lays out the
+    figure.  The tensors are views, narrowed to each slide's extent, of one allocation padded to the batch's largest grid with every row
+    starting 16-byte aligned; bytes outside the slides' extents are 0.  No CPU fallback."""
+    if level is not None and fold is not None:
+        raise ValueError("render: fold is the weight of the folded map (level=None); a single level has none")
+    if isinstance(fold, bool):
+        raise ValueError("render: fold is a weight or None")
+    plan = _raster_plan(trace, base_grids, kind, layer, head, False if level is not None else (0.5 if fold is None else fold), offset, patch_size,
+                        2, dtype)
+    L, B, grids = plan.L, plan.B, plan.grids
+    if level is not None and (isinstance(level, bool) or not 0 <= int(level) < L):
+        raise ValueError("render: level %r out of range for a trace of %d levels" % (level, L))
+    if isinstance(cell_px, bool) or int(cell_px) != cell_px or not 1 <= int(cell_px) <= MAX_CELL_PX:
+        raise ValueError("render: cell_px is an integer in [1, %d], got %r" % (MAX_CELL_PX, cell_px))
+    c = int(cell_px)
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("render: alpha must lie in [0, 1], got %r" % (alpha,))
+    a255 = int(round(float(alpha) * 255))
+    colours = colour_table(cmap)                                         # uint8 [256, 3], or ValueError
+    words = colours[:, 0].astype(np.uint32) | colours[:, 1].astype(np.uint32) << 8 | colours[:, 2].astype(np.uint32) << 16
+    line, back = _rgb_word(outline_rgb, "outline_rgb"), _rgb_word(background, "background")
+    if outline is True:
+        outlined = list(range(L))
+    elif outline is False or outline is None:
+        outlined = []
+    else:
+        outlined = [int(l) for l in outline]
+        if any(not 0 <= l < L for l in outlined):
+            raise ValueError("render: outline names level(s) %s, the trace has levels 0 to %d" % ([l for l in outlined if not 0 <= l < L], L - 1))
+    outline_bits = sum(1 << l for l in set(outlined) if c << (L - 1 - l) >= MIN_OUTLINED_SPAN)
+    given = [None if v is None else _per_slide(v, B, name) for v, name in ((vmin, "vmin"), (vmax, "vmax"))]
+    if center is not None and not np.isfinite(float(center)):
+        raise ValueError("render: center must be finite, got %r" % (center,))
+    f = 1 << (L - 1)
+    if thumbnails is not None:
+        thumbnails = list(thumbnails)
+        if len(thumbnails) != B:
+            raise ValueError("render: %d thumbnails for the %d slides of the trace" % (len(thumbnails), B))
+        for b, (t, g) in enumerate(zip(thumbnails, grids)):
+            want = (g[0] * f * c, g[1] * f * c, 3)
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != want or tuple(t.stride()[1:]) != (3, 1):
+                raise ValueError("render: thumbnail %d must be a uint8 tensor %r with last strides (3, 1), got %s" % (
+                    b, want, "%s %r strides %r" % (t.dtype, tuple(t.shape), tuple(t.stride())) if torch.is_tensor(t) else type(t).__name__))
+    for lv in trace:                                       # last of the checks, so that the others can be met without a GPU
+        _lib.require_cuda(lv["locs"], lv["num_ims"], lv[kind])
+    if thumbnails is not None:
+        _lib.require_cuda(*thumbnails)
+        if any(t.device != trace[0]["locs"].device for t in thumbnails):
+            raise _lib.PathsHipError("render: the thumbnails are not on the trace's device")
+
+    run = _raster_run(trace, plan, more_status=B)
+    dev, GX, GY = run.dev, run.GX, run.GY
+    lvl = -1 if level is None else int(level)
+    f64 = int(plan.dtype == torch.float64)
+    with torch.cuda.device(dev):
+        ldp = (GY * f * c * 3 + 15) // 16 * 16
+        out = torch.empty((B, GX * f * c, ldp), dtype=torch.uint8, device=dev)
+        # one host -> device copy: thumbnails [B][2], the colour words, the centre, the given range [B][2]
+        host = np.zeros(2 * B + 128 + 1 + 2 * B, dtype=np.int64)
+        if thumbnails is not None:
+            host[:2 * B] = [v for t in thumbnails for v in (t.data_ptr(), t.stride(0))]
+        host[2 * B:2 * B + 128].view(np.uint32)[:] = words
+        host[2 * B + 128:2 * B + 129].view(np.float64)[:] = 0.0 if center is None else float(center)
+        for j in (0, 1):
+            if given[j] is not None:
+                host[2 * B + 129:].view(np.float64)[j::2] = given[j]
+        table = torch.from_numpy(host).to(dev)
+        p_thumbs = table.data_ptr() if thumbnails is not None else None
+        p_colours, p_center = table.data_ptr() + 8 * 2 * B, table.data_ptr() + 8 * (2 * B + 128)
+        asked = table[2 * B + 129:].view(torch.float64).view(B, 2)
+        stream = _lib.stream()
+        if check or given[0] is None or given[1] is None:
+            rng = torch.empty((B, 2), dtype=torch.float64, device=dev)
+            partial = torch.empty((B * 64 * 3,), dtype=torch.float64, device=dev)
+            _lib.call("paths_render_range", run.p_table, run.p_gx, run.p_gy, L, B, GX, GY, lvl, run.out.data_ptr(), f64, run.ldo,
+                      p_center if center is not None else None, partial.data_ptr(), rng.data_ptr(), run.status.data_ptr() + 4, stream)
+            for j in (0, 1):
+                if given[j] is not None:
+                    rng[:, j] = asked[:, j]
+        else:
+            rng = asked
+        _lib.call("paths_render_rgb", run.p_table, run.p_gx, run.p_gy, L, B, GX, GY, lvl, run.out.data_ptr(), f64, run.ldo, rng.data_ptr(),
+                  p_colours, p_thumbs, c, a255, outline_bits, line, back, out.data_ptr(), ldp, stream)
         if check:
-            bits = int(status.item())
-            if bits:
-                raise _lib.PathsHipError("rasterize: level(s) %s hold a location outside their slide's grid (base_grids or patch_size do not "
-                                         "belong to this trace)" % ", ".join(str(l) for l in range(L) if bits >> l & 1))
-    return [out[b, :g[0] * f, :g[1] * f] if folded else out[b, :, :g[0] * f, :g[1] * f] for b, g in enumerate(grids)]
+            bits = run.status.cpu().tolist()
+            _raise_outside(bits[0], L)
+            if any(bits[1:]):
+                raise _lib.PathsHipError("render: slide(s) %s hold a non-finite %s on a visited cell" % (
+                    ", ".join(str(b) for b in range(B) if bits[1 + b]), kind))
+    return [out[b, :g[0] * f * c, :g[1] * f * c * 3].unflatten(-1, (g[1] * f * c, 3)) for b, g in enumerate(grids)]
+
+
+def _png_chunk(tag: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def save_png(path, image) -> None:
+    """Write a uint8 ``[H, W, 3]`` image - a device tensor (one ``.cpu()``) or a NumPy array - as an 8-bit RGB PNG: filter type 0 on every
+    row, one IDAT chunk from ``zlib.compress``.  Standard library only, so that a :func:`render` result can be looked at anywhere."""
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("save_png: a uint8 [H, W, 3] image expected, got %s %r" % (a.dtype, tuple(a.shape)))
+    h, w = int(a.shape[0]), int(a.shape[1])
+    rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)                       # a filter byte (0 = None) in front of every row
+    rows[:, 1:] = a.reshape(h, 3 * w)
+    png = (b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+           _png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+    with open(path, "wb") as fh:
+        fh.write(png)
