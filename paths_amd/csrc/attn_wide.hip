@@ -40,9 +40,12 @@ __device__ __forceinline__ float wave_sum_desc(float v) {
 }
 
 // One wave per query row of S [nq, Tp] (in place): P[c] = exp2(qscale S[c] - lse) for c < len, 0 for len <= c < Tp.
-// lse_in == nullptr: the softmax statistics are computed here (and written to lse_out if given); otherwise the saved ones are used
-// (the backward's recompute).  drop.thr != 0 and `dropped`: the probabilities that enter the PV product, P * mask / (1 - p), are
-// written to `dropped` [nq, Tp] (may alias S: the forward only needs those); the backward passes a second buffer and keeps both.
+// lse_in == nullptr: the softmax statistics are computed here (and written to lse_out if given) and P is normalised by the sum
+// itself, exp2(qscale S[c] - max) / sum: through lse = max + log2(sum) the rounding of lse - half an ulp of a maximum of several
+// hundred, and the exponent is one fused multiply-add of the unrounded product - reached every P of the row (1e-5 relative at a
+// maximum of 400).  Otherwise the saved lse is used (the backward's recompute).
+// drop.thr != 0 and `dropped`: the probabilities that enter the PV product, P * mask / (1 - p), are written to `dropped` [nq, Tp]
+// (may alias S: the forward only needs those); the backward passes a second buffer and keeps both.
 __global__ void __launch_bounds__(256)
 wide_softmax_kernel(float* __restrict__ S, int Tp, int nq, const int64_t* __restrict__ num_ims, int b, float qscale, const float* __restrict__ lse_in,
                     float* __restrict__ lse_out, float* __restrict__ dropped, DropSite drop, uint64_t site_base /* ((b*H + h)*T) */, int T) {
@@ -55,7 +58,7 @@ wide_softmax_kernel(float* __restrict__ S, int Tp, int nq, const int64_t* __rest
     if (lse_in == nullptr && lse_out != nullptr && lane == 0) lse_out[r] = 0.f;
     return;
   }
-  float L;
+  float L, inv = 1.f;                                  // P = exp2(qscale S - L) * inv
   if (lse_in != nullptr) {
     L = lse_in[r];
   } else {
@@ -65,13 +68,14 @@ wide_softmax_kernel(float* __restrict__ S, int Tp, int nq, const int64_t* __rest
     float l = 0.f;
     for (int c = lane; c < len; c += 64) l += __builtin_amdgcn_exp2f(row[c] * qscale - m);
     l = wave_sum_desc(l);
-    L = m + __builtin_amdgcn_logf(l);                  // v_log_f32 = log2
-    if (lse_out != nullptr && lane == 0) lse_out[r] = L;
+    if (lse_out != nullptr && lane == 0) lse_out[r] = m + __builtin_amdgcn_logf(l);       // v_log_f32 = log2
+    L = m;
+    inv = 1.0f / l;
   }
   const uint64_t mrow = (site_base + (uint64_t)r) * drop_attn_stride(T);
   float* drow = dropped != nullptr ? dropped + (int64_t)r * Tp : nullptr;
   for (int c = lane; c < Tp; c += 64) {
-    const float p = c < len ? __builtin_amdgcn_exp2f(row[c] * qscale - L) : 0.f;
+    const float p = c < len ? __builtin_amdgcn_exp2f(row[c] * qscale - L) * inv : 0.f;
     if (drow != nullptr) {
       const float m = (drop.thr != 0u && c < len) ? drop_mult(drop, mrow + (uint64_t)c) : 1.f;
       if (drow != row) row[c] = p;
