@@ -110,6 +110,15 @@
  *   paths_cache_probe                  cells beyond n[b]: never read; src, miss_count, miss_cells, status on entry: never read
  *   paths_cache_fill / _h16            src beyond n[b], store rows at and beyond count[b], out on entry: never read; every row of out
  *                                      is written
+ * pixels to encoder input
+ *   paths_grey_histogram               image bytes behind a row's cols * 3 (row padding): never read; partials, counts, status on entry:
+ *                                      never read
+ *   paths_tile_tissue                  tile bytes outside the P x 3P window (row padding, neighbouring tiles): never read; counts, flags
+ *                                      on entry: never read
+ *   paths_tile_compact                 order, m, slot, status on entry: never read; order at and beyond m: not written
+ *   paths_tiles_to_input               tile bytes outside the P x 3P window: never read; order outside [first, first + count), so every
+ *                                      entry beyond m: never read; out on entry: never read, every element is written
+ *   paths_scatter_rows                 enc rows at and beyond m: never read; out on entry: never read, every row is written
  */
 #ifndef PATHS_HIP_H
 #define PATHS_HIP_H
@@ -756,6 +765,50 @@ int paths_cache_fill(const int64_t* cells_ptrs, const int64_t* n, const int* src
 int paths_cache_fill_h16(const int64_t* cells_ptrs, const int64_t* n, const int* src, const int* miss_count, const int64_t* enc_ptrs,
                          const int64_t* store_ptrs, const int64_t* count, const int64_t* capacity, const int64_t* index_ptrs, const int* gx,
                          const int* gy, int B, int n_max, int D, void* out, paths_stream_t stream);
+
+/* From decoded pixels to encoder input and back to feature rows (paths_amd/pixels.py; csrc/tiles.hip; the tissue decision,
+ * to_tensor / Normalize and the scatter of reference preprocess/preprocess.py:27-110 and data_utils/slide.py:80-161).  Contract:
+ * tests/tiles_ref.py, bit for bit.  Integer and table work only: no float arithmetic but the one cast of paths_scatter_rows, no global
+ * atomics; a rerun on the same inputs writes the same bytes.
+ *
+ * Pixels are uint8 RGB with pixel stride 3; grey g = (4899 R + 9617 G + 1868 B + 8192) >> 14 (OpenCV's 8-bit RGB2GRAY).
+ * IMAGES are named by a DEVICE table [n_images][4] int64 = (address of the first byte, row stride in bytes, rows, cols); TILES by a
+ * DEVICE table [n][2] int64 = (address of the tile's first byte, its row stride in bytes): tile k is the P x P window whose row r is the
+ * 3 P bytes at address + r * stride - a [n, P, P, 3] batch and windows into a resident image alike.  Addresses and strides are
+ * multiples of 16, a stride is at least the row's bytes; P % 16 == 0, 16 <= P <= PATHS_TILE_MAX_P, n <= PATHS_TILES_MAX.  What the host
+ * can see is refused with -1 before any launch; a table entry that breaks the rule is never followed: the image counts nothing
+ * and paths_grey_histogram sets *status, the tile gets count -1 and flag 0 (paths_tile_compact reports it in *status) and reads as
+ * zero bytes in paths_tiles_to_input.
+ *
+ * paths_grey_histogram - counts [256] int64 = the number of pixels of every grey value over all images, jointly.  PATHS_HIST_BLOCKS
+ *   workgroups per image keep their counts in LDS (integer adds: the order does not matter) and write them to partials
+ *   (paths_grey_histogram_workspace(n_images) bytes); a second launch of one workgroup sums the partials in a fixed order.
+ *   n_images in [1, PATHS_HIST_MAX_IMAGES]; an image holds fewer than 2^31 pixels.  *status (int32) = 1 if any image entry was
+ *   refused (misaligned address or stride, a stride shorter than the row, no or too many pixels), else 0.
+ * paths_tile_tissue - counts[k] int32 = the number of lattice pixels (i s + s / 2, j s + s / 2), 0 <= i, j < P / s, s = stride, P % s == 0,
+ *   with g < threshold (strict; threshold in [0, 256]); flags[k] uint8 = counts[k] >= pass_count (the host's integer form of
+ *   count / size > tissue_threshold; 0 <= pass_count <= (P / s)^2 + 1).  One workgroup per tile.
+ * paths_tile_compact - one workgroup: order[0 .. m) int32 = the tiles with a set flag in request order, *m = their number, slot[k] =
+ *   the position of tile k in order, or -1; *status = 1 if any counts[k] < 0 (a refused table entry), else 0.
+ * paths_tiles_to_input - out [count, 3, P, P] of elem_bytes-wide elements (2: fp16 or bf16, 4: fp32): out[i, c, r, x] =
+ *   table[c * 256 + byte c of pixel (r, x) of tile order[first + i]], table [3][256] of the same element type (held in LDS; a copy of
+ *   bits, so the result is what indexing the table gives).  A thread owns 16 consecutive pixels of a row: three 16-byte loads, then
+ *   16-byte stores per channel plane.  An order entry outside [0, n) reads as zero bytes.  count >= 1, first >= 0.
+ * paths_scatter_rows - out [n, dim] fp32 (out_f16 = 0) or fp16 (1): row k = enc[slot[k]] (enc [m, dim] fp32 or fp16 (enc_f16), cast once,
+ *   round to nearest even) when 0 <= slot[k] < m, else +0.  dim % 4 == 0; enc (may be NULL when m = 0) and out 16-byte aligned; 16-byte
+ *   stores (the last 8 bytes of an fp16 output of odd n * dim / 4 apart). */
+#define PATHS_TILES_MAX 65536
+#define PATHS_TILE_MAX_P 1024
+#define PATHS_HIST_BLOCKS 64
+#define PATHS_HIST_MAX_IMAGES 1024
+int64_t paths_grey_histogram_workspace(int n_images);
+int paths_grey_histogram(const int64_t* images, int n_images, uint32_t* partials, int64_t* counts, int* status, paths_stream_t stream);
+int paths_tile_tissue(const int64_t* tiles, int n, int P, int stride, int threshold, int pass_count, int* counts, uint8_t* flags,
+                      paths_stream_t stream);
+int paths_tile_compact(const uint8_t* flags, const int* counts, int n, int* order, int* m, int* slot, int* status, paths_stream_t stream);
+int paths_tiles_to_input(const int64_t* tiles, int n, const int* order, int first, int count, int P, const void* table, int elem_bytes,
+                         void* out, paths_stream_t stream);
+int paths_scatter_rows(const void* enc, int enc_f16, int m, const int* slot, int n, int dim, int out_f16, void* out, paths_stream_t stream);
 
 /* Rare fallback of reference data_utils/slide.py:336-352 for slides with num_out[b] == 0 after paths_expand_children:
  * continue with every tissue cell of the next grid (every cell if it has no tissue), zero patch context (src_row = -1),

@@ -680,7 +680,8 @@ class OnDemandSlide:
     rows.  It is never asked for a cell outside the level's grid and never twice for the same cell within one pass; ``requested[l]``
     holds the cells asked of level ``l`` during the last pass (None: level not reached).
 
-    WSI reading, tissue masking of pixels and the encoder are the caller's.  Inference only."""
+    WSI reading and the encoder are the caller's; the tissue masking of pixels and the hand-over to the
+    encoder are ``paths_amd.pixels.TileEncoder``, an ``encode`` built from a tile reader and a model.  Inference only."""
 
     on_demand = True
     host_resident = False
