@@ -118,6 +118,9 @@
  *   paths_tile_compact                 order, m, slot, status on entry: never read; order at and beyond m: not written
  *   paths_tiles_to_input               tile bytes outside the P x 3P window: never read; order outside [first, first + count), so every
  *                                      entry beyond m: never read; out on entry: never read, every element is written
+ *   paths_tiles_resize_to_input        tile bytes outside the P x 3P window: never read; order outside [first, first + count): never
+ *                                      read; bounds / coef: whatever they hold, only bytes of the window and LDS the workgroup wrote
+ *                                      are read; out on entry: never read, every element is written
  *   paths_scatter_rows                 enc rows at and beyond m: never read; out on entry: never read, every row is written
  */
 #ifndef PATHS_HIP_H
@@ -809,6 +812,34 @@ int paths_tile_compact(const uint8_t* flags, const int* counts, int n, int* orde
 int paths_tiles_to_input(const int64_t* tiles, int n, const int* order, int first, int count, int P, const void* table, int elem_bytes,
                          void* out, paths_stream_t stream);
 int paths_scatter_rows(const void* enc, int enc_f16, int m, const int* slot, int n, int dim, int out_f16, void* out, paths_stream_t stream);
+
+/* Resize and centre crop in front of the table (csrc/tile_resize.hip; pixels.encoder_input(resize=...); contract
+ * tests/resize_ref.py, bit for bit): what Resize(S, bicubic | bilinear) -> CenterCrop(C) -> ToTensor -> Normalize give for a decoded
+ * square tile when the resize is Pillow's, as in timm's and torchvision's transforms of PIL images.  out [count, 3, C, C] of
+ * elem_bytes-wide elements: out[i, c, r, x] = table[c * 256 + o_c[off + r][off + x]], o the S x S resize of tile order[first + i] and
+ * off = int(round((S - C) / 2.0)) (half to even: S = 17, C = 16 gives 0).  Tiles, order, first, count, table and the treatment of an
+ * order entry outside [0, n) or a refused tile entry (zero bytes: the output is table[c][0] everywhere) are paths_tiles_to_input's.
+ *
+ * The resize is Pillow's ImagingResample for 8-bit images, in integers.  bounds [S][2] int32 = (lo, cnt) and coef [S][taps] int32
+ * (22 fractional bits; zero at and beyond cnt) are DEVICE tables for one axis - tiles are square, one table serves both -, built by
+ * pixels.resize_coefficients.  Horizontal pass first, into a BYTE image: h[r][j] = clip((2^21 + sum_t px[r][lo_j + t] coef_j[t]) >> 22,
+ * 0, 255) (arithmetic shift), then o[i][j] = clip((2^21 + sum_t h[lo_i + t][j] coef_i[t]) >> 22, 0, 255), per channel.  The sums are
+ * int32 (255 sum|coef| + 2^21 < 2^31 per row) and the products 24-bit multiplies (|coef| < 2^23): the builder of the tables checks both.
+ * The host cannot inspect the tables: the kernel clamps cnt into [0, taps] and every source row and column into the window it
+ * staged, so whatever they hold it reads only bytes of the tile's P x 3P window and LDS it wrote (the values are then meaningless).
+ *
+ * Domain: P as above; 16 <= C <= S <= PATHS_RESIZE_MAX, C % 16 == 0 (an output row is whole 16-byte stores); P <= 4 S, so that
+ * taps <= PATHS_RESIZE_MAX_TAPS; taps = ceil(f max(P / S, 1)) * 2 + 1 for f = 1 (bilinear) or f = 2 (bicubic).  A workgroup takes one
+ * tile and a band of R of the C output rows; it keeps in LDS
+ *   768 elem_bytes + 4 (C (taps + 2) + 2 R + R taps) + 3 rows (P + C) bytes, rows = min((R - 1) P / S + taps + 1, P)
+ * (the table, the coefficient rows of the cropped columns and of the band, the staged input rows as byte planes and their horizontal
+ * results; 2 R and R taps rounded up to multiples of 4).  R is the largest band within 64 KiB (two workgroups per compute unit),
+ * divided evenly; if not even R = 1 fits, within 160 KiB; a shape whose R = 1 exceeds that is refused.  Everything outside the domain
+ * is refused with -1 before any launch. */
+#define PATHS_RESIZE_MAX 1024
+#define PATHS_RESIZE_MAX_TAPS 17
+int paths_tiles_resize_to_input(const int64_t* tiles, int n, const int* order, int first, int count, int P, int S, int C, const int* bounds,
+                                const int* coef, int taps, const void* table, int elem_bytes, void* out, paths_stream_t stream);
 
 /* Rare fallback of reference data_utils/slide.py:336-352 for slides with num_out[b] == 0 after paths_expand_children:
  * continue with every tissue cell of the next grid (every cell if it has no tissue), zero patch context (src_row = -1),

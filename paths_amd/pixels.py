@@ -12,6 +12,11 @@ tissue    a pixel is tissue when ``g < t`` (strict: the reference's own quirk); 
 input     ``[m, 3, P, P]`` for the tissue tiles in request order, ``table[c][v]`` for byte ``v`` of channel ``c``
           (:func:`encoder_input`; :func:`to_tensor_table` is ``to_tensor``, :func:`normalize_table` is ``to_tensor`` followed by
           ``Normalize``, both built here with torch, so the kernel's result is torch's by construction);
+resize    with ``resize=S`` (and ``crop=C``, default ``S``) the input is ``[m, 3, C, C]``: the tile's BYTES resized to ``S x S`` as Pillow
+          resizes an 8-bit image (antialiased bicubic or bilinear, integer coefficients, a byte image between the horizontal and the
+          vertical pass), the centre ``C x C`` of it (torchvision's ``CenterCrop``), then the same table - what ``Resize(S)`` ->
+          ``CenterCrop(C)`` -> ``ToTensor`` -> ``Normalize`` of timm's and torchvision's transforms give for the decoded tile, byte for
+          byte (csrc/tile_resize.hip; :func:`resize_coefficients`, :func:`crop_offset`; the contract is tests/resize_ref.py);
 rows      ``[n, dim]`` in the slide's dtype: the encoder's row of a tissue tile, all +0.0 for every other tile
           (:func:`scatter_rows`).
 
@@ -25,8 +30,10 @@ approximated.
 :class:`TileEncoder` puts the pieces behind the ``encode(level, cells)`` contract of ``OnDemandSlide`` / ``CachedOnDemandSlide``.
 
 Out of scope: reading and decoding WSI files, any resampling (the reference's mask of a resampled low-power read belongs to the WSI
-reader; here the lattice samples the tile's own pixels), resizing transforms (they stay inside the caller's ``model``), the encoder
-network, ``RawSlide``'s per-load joint fit and its halve-the-threshold fallback, tiles in pinned host memory, training."""
+reader; here the lattice samples the tile's own pixels), resizes other than the one above (torch's own uint8 resize, which is within
+one byte of it; a float resize; non-square images; nearest, lanczos and box filters; ``RandomResizedCrop`` and every other training
+augmentation: they stay inside the caller's ``model``), the encoder network, ``RawSlide``'s per-load joint fit and its
+halve-the-threshold fallback, tiles in pinned host memory, training."""
 from __future__ import annotations
 
 import math
@@ -42,7 +49,10 @@ from .data_utils.slide import check_grid_dtype
 MAX_TILES = 65536            # include/paths_hip.h: PATHS_TILES_MAX
 MAX_PATCH = 1024             # PATHS_TILE_MAX_P
 MAX_IMAGES = 1024            # PATHS_HIST_MAX_IMAGES
+MAX_RESIZE = 1024           # PATHS_RESIZE_MAX
+MAX_TAPS = 17                # PATHS_RESIZE_MAX_TAPS
 INPUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+INTERPOLATIONS = {"bicubic": 2.0, "bilinear": 1.0}       # the filters' supports
 
 Tissue = namedtuple("Tissue", "counts flags order m slots tiles")
 
@@ -132,6 +142,59 @@ def normalize_table(mean: Sequence[float], std: Sequence[float], dtype=torch.flo
     return v.sub(m).div(s).to(_input_dtype(dtype)).contiguous()
 
 
+def _bicubic(x: float) -> float:
+    a, x = -0.5, abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _bilinear(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def resize_coefficients(P: int, S: int, interpolation: str = "bicubic"):
+    """``(bounds, coef, taps)`` (CPU): int32 ``[S, 2]`` = (lo, cnt) and int32 ``[S, taps]`` with 22 fractional bits, zero at and beyond
+    ``cnt`` - Pillow's ``precompute_coeffs`` and ``normalize_coeffs_8bpc`` for one axis from ``P`` to ``S`` pixels, in Python floats.
+    Output ``i`` is ``clip((2^21 + sum_t px[lo_i + t] coef_i[t]) >> 22, 0, 255)``.  Raises if a row's sum could leave int32 or a
+    coefficient the kernel's 24-bit multiplier (neither happens for these filters)."""
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation is one of {sorted(INTERPOLATIONS)}, got {interpolation!r}")
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in (P, S)) or S > MAX_RESIZE or P > 4 * S:
+        raise ValueError(f"resize_coefficients: P and S are positive integers, S <= {MAX_RESIZE}, P <= 4 S; got {P!r}, {S!r}")
+    f, support = (_bicubic if interpolation == "bicubic" else _bilinear), INTERPOLATIONS[interpolation]
+    scale = P / S
+    fs = max(scale, 1.0)
+    support = support * fs
+    taps = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    bounds, coef = [], []
+    for i in range(S):
+        center = (i + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        cnt = min(int(center + support + 0.5), P) - lo
+        w = [f((t + lo - center + 0.5) * ss) for t in range(cnt)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        k = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in w]
+        if not 0 < cnt <= taps or 255 * sum(abs(v) for v in k) + (1 << 21) >= 1 << 31 or any(abs(v) >= 1 << 23 for v in k):
+            raise ValueError(f"resize_coefficients: row {i} of {P} -> {S} ({interpolation}) leaves the kernel's integer range")
+        bounds.append((lo, cnt))
+        coef.append(k + [0] * (taps - cnt))
+    return torch.tensor(bounds, dtype=torch.int32), torch.tensor(coef, dtype=torch.int32), taps
+
+
+def crop_offset(S: int, C: int) -> int:
+    """Where torchvision's ``CenterCrop(C)`` starts in ``S`` pixels: ``int(round((S - C) / 2.0))``, half to even, on both axes."""
+    return int(round((int(S) - int(C)) / 2.0))
+
+
 # ------------------------------------------------------------------------------------------------
 # argument checks (all of them before any launch, none of them needs a GPU)
 # ------------------------------------------------------------------------------------------------
@@ -142,6 +205,47 @@ def check_patch(patch_size, stride=None) -> int:
     if stride is not None and (isinstance(stride, bool) or not isinstance(stride, int) or stride < 1 or P % stride != 0):
         raise ValueError(f"stride must be a positive integer that divides patch_size {P}, got {stride!r}")
     return P
+
+
+def _check_resize(P: int, resize, crop, interpolation):
+    """``(P, S, C)`` of a resize, or ValueError: what csrc/tile_resize.hip takes."""
+    for name, v in (("resize", resize), ("crop", crop)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 16 <= v <= MAX_RESIZE:
+            raise ValueError(f"{name} must be an integer in [16, {MAX_RESIZE}], got {v!r}")
+    if interpolation not in INTERPOLATIONS:
+        raise ValueError(f"interpolation is one of {sorted(INTERPOLATIONS)}, got {interpolation!r}")
+    if isinstance(P, bool) or not isinstance(P, int) or P < 1:
+        raise ValueError(f"the tile's size must be a positive integer, got {P!r}")
+    if crop % 16 != 0:
+        raise ValueError(f"crop must be a multiple of 16 (an output row is whole 16-byte stores), got {crop}")
+    if crop > resize:
+        raise ValueError(f"crop ({crop}) must not exceed resize ({resize})")
+    if P > 4 * resize:
+        raise ValueError(f"a {P}-pixel tile is more than 4 times resize ({resize}): at most {MAX_TAPS} taps")
+    return P, resize, crop
+
+
+def _resize_args(P: int, resize, crop, interpolation):
+    """None without a resize, else the checked ``(S, C, interpolation)``; ``crop`` defaults to ``resize``."""
+    if resize is None:
+        if crop is not None:
+            raise ValueError(f"crop ({crop!r}) needs resize: the centre crop follows the resize")
+        if interpolation not in INTERPOLATIONS:
+            raise ValueError(f"interpolation is one of {sorted(INTERPOLATIONS)}, got {interpolation!r}")
+        return None
+    return _check_resize(P, resize, resize if crop is None else crop, interpolation)[1:] + (interpolation,)
+
+
+_resize_tables = {}
+
+
+def _device_resize_tables(P: int, S: int, interpolation: str, device):
+    """The device copies of :func:`resize_coefficients`, built once per shape, filter and device."""
+    key = (P, S, interpolation, str(device))
+    if key not in _resize_tables:
+        bounds, coef, taps = resize_coefficients(P, S, interpolation)
+        _resize_tables[key] = (bounds.to(device), coef.to(device), taps)
+    return _resize_tables[key]
 
 
 def _check_image(t, who: str):
@@ -261,12 +365,18 @@ def tile_tissue(tiles, threshold: int, tissue_threshold: float = 0.1, stride: in
     return Tissue(counts, flags, order, int(m), slots, t)
 
 
-def encoder_input(tiles, order: torch.Tensor, first: int, count: int, table: torch.Tensor, patch_size: Optional[int] = None) -> torch.Tensor:
+def encoder_input(tiles, order: torch.Tensor, first: int, count: int, table: torch.Tensor, patch_size: Optional[int] = None, *,
+                  resize: Optional[int] = None, crop: Optional[int] = None, interpolation: str = "bicubic") -> torch.Tensor:
     """``[count, 3, P, P]`` in ``table``'s dtype: tiles ``order[first .. first + count)`` through ``table`` (``[3, 256]`` fp32, fp16 or
-    bf16 on the tiles' device).  Every element is written; entries of ``order`` outside the range are not read."""
+    bf16 on the tiles' device).  Every element is written; entries of ``order`` outside the range are not read.
+
+    ``resize=S``: ``[count, 3, C, C]`` instead, ``C = crop`` (default ``S``) - the tiles' bytes resized to ``S x S`` as Pillow does
+    (``interpolation``: "bicubic" or "bilinear", antialiased), centre-cropped, then through ``table``; one launch, the ``P x P`` float
+    tensor is never formed.  ``16 <= crop <= resize <= 1024``, ``crop % 16 == 0``, ``P <= 4 resize``."""
     if not torch.is_tensor(table) or tuple(table.shape) != (3, 256) or table.dtype not in INPUT_DTYPES or not table.is_contiguous():
         raise ValueError("encoder_input: table is a contiguous [3, 256] tensor in float32, float16 or bfloat16")
     t = _tiles(tiles, patch_size, "encoder_input")
+    resized = _resize_args(t.P, resize, crop, interpolation)
     first, count = int(first), int(count)
     if not torch.is_tensor(order) or order.dtype != torch.int32 or tuple(order.shape) != (t.n,) or not order.is_contiguous():
         raise ValueError(f"encoder_input: order is a contiguous int32 tensor [{t.n}]")
@@ -277,6 +387,13 @@ def encoder_input(tiles, order: torch.Tensor, first: int, count: int, table: tor
     if order.device != t.device or table.device != t.device:
         raise _lib.PathsHipError("encoder_input: order and table must be on the tiles' device")
     with torch.cuda.device(t.device):
+        if resized is not None:
+            S, C, interpolation = resized
+            bounds, coef, taps = _device_resize_tables(t.P, S, interpolation, t.device)
+            out = torch.empty((count, 3, C, C), dtype=table.dtype, device=t.device)
+            _lib.call("paths_tiles_resize_to_input", tiles_table.data_ptr(), t.n, order.data_ptr(), first, count, t.P, S, C, bounds.data_ptr(),
+                      coef.data_ptr(), taps, table.data_ptr(), table.element_size(), out.data_ptr(), _lib.stream())
+            return out
         out = torch.empty((count, 3, t.P, t.P), dtype=table.dtype, device=t.device)
         _lib.call("paths_tiles_to_input", tiles_table.data_ptr(), t.n, order.data_ptr(), first, count, t.P, table.data_ptr(), table.element_size(),
                   out.data_ptr(), _lib.stream())
@@ -341,11 +458,16 @@ class TileEncoder:
     under ``torch.no_grad()``; ``model`` returns ``[count, dim]`` in fp32 or fp16.  The call returns ``[n, dim]`` in ``dtype``, the
     all-zero row for every tile without tissue - and for a tissue tile whose embedding is exactly zero, as in the reference.
 
+    ``resize`` / ``crop`` / ``interpolation``: the resize and centre crop of :func:`encoder_input`; ``model`` then receives ``[count,
+    3, crop, crop]`` (an encoder that wants 224: ``resize=224``).  The tissue decision still looks at the tile's own pixels; the
+    device coefficient tables are built once per shape, filter and device, at the first call.
+
     It works on the current stream and costs one host read (of ``m``) per call; ``model`` is not called when ``m == 0``.  ``stats``
     counts, per level, the requested tiles, the tissue tiles and the model calls."""
 
     def __init__(self, read: Callable, model: Callable, dim: int, threshold: int, patch_size: int = 256, tissue_threshold: float = 0.1,
-                 stride: int = 4, table: Optional[torch.Tensor] = None, input_dtype=torch.float16, batch: int = 256, dtype=torch.float32):
+                 stride: int = 4, table: Optional[torch.Tensor] = None, input_dtype=torch.float16, batch: int = 256, dtype=torch.float32,
+                 resize: Optional[int] = None, crop: Optional[int] = None, interpolation: str = "bicubic"):
         if not callable(read) or not callable(model):
             raise ValueError("TileEncoder: read(level, cells) and model(input) must be callable")
         self.read, self.model = read, model
@@ -364,6 +486,10 @@ class TileEncoder:
         elif not torch.is_tensor(table) or tuple(table.shape) != (3, 256) or table.dtype not in INPUT_DTYPES:
             raise ValueError("TileEncoder: table is a [3, 256] tensor in float32, float16 or bfloat16")
         self.table = table.contiguous()
+        resized = _resize_args(self.patch_size, resize, crop, interpolation)
+        self.resize, self.crop, self.interpolation = resized if resized is not None else (None, None, interpolation)
+        if resized is not None:
+            resize_coefficients(self.patch_size, self.resize, interpolation)     # (the range check, before any launch)
         self.stats = {"requested": {}, "tissue": {}, "model_calls": {}}
 
     @classmethod
@@ -394,7 +520,8 @@ class TileEncoder:
             with torch.no_grad():
                 for first in range(0, ts.m, self.batch):
                     count = min(self.batch, ts.m - first)
-                    rows = self.model(encoder_input(ts.tiles, ts.order, first, count, self.table))
+                    rows = self.model(encoder_input(ts.tiles, ts.order, first, count, self.table, resize=self.resize, crop=self.crop,
+                                                    interpolation=self.interpolation))
                     self._count("model_calls", level, 1)
                     if not torch.is_tensor(rows) or tuple(rows.shape) != (count, self.dim) or rows.dtype not in (torch.float32, torch.float16) \
                             or rows.device != dev:
