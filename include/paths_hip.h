@@ -106,6 +106,11 @@
  *                                      read (status is written, not accumulated)
  *   paths_render_rgb                   raster cells no drawn index grid names, thumbnail bytes outside a slide's extent: never read;
  *                                      out on entry: never read, every byte of the padded allocation is written
+ * annotation polygons
+ *   paths_polygon_cover                words between the packed arrays (behind verts[V], poly_off[P], slide_poly[B]): never read; out on
+ *                                      entry: never read, every element of the padded allocation is written
+ *   paths_polygon_outline              words between the packed arrays and cum behind cum[V]: never read; image bytes: never read;
+ *                                      bytes of pixels no edge paints, row padding included: never written
  * row cache of on-demand slides
  *   paths_cache_probe                  cells beyond n[b]: never read; src, miss_count, miss_cells, status on entry: never read
  *   paths_cache_fill / _h16            src beyond n[b], store rows at and beyond count[b], out on entry: never read; every row of out
@@ -1106,6 +1111,45 @@ int paths_render_range(const int64_t* table, const int* gx, const int* gy, int L
 int paths_render_rgb(const int64_t* table, const int* gx, const int* gy, int L, int B, int GX, int GY, int level, const void* raster,
                      int raster_f64, int64_t ldo, const double* range, const uint32_t* colours, const int64_t* thumbs, int cell_px, int alpha255,
                      int outline_levels, uint32_t outline_rgb, uint32_t background, uint8_t* out, int64_t ldp, paths_stream_t stream);
+
+/* Annotation polygons (paths_amd/annotations.py; csrc/polygons.hip; the polygons reference heatmap_visualise.py:21-48,
+ * 123-135 draws beside the heat map).  The NumPy statement of both entries is tests/polygon_ref.py; the kernels equal it bit for bit.
+ *
+ * FIXED POINT.  A coordinate is an int32 with 16 fractional bits per FINEST cell (one cell of a raster above = 65536), (row, col) with
+ * row along the grid's X.  verts int32 [V][2]; polygon k owns vertices poly_off[k] .. poly_off[k+1] - 1 (poly_off int32 [P + 1],
+ * ascending, at least 3 each) and is closed implicitly: its edges run a -> b from each vertex to the next and from the last to the
+ * first; slide b owns polygons slide_poly[b] .. slide_poly[b+1] - 1 (int32 [B + 1]).  The kernels clamp every offset into its array,
+ * so no table can make them read outside verts.  gx / gy: DEVICE [B] int32, the slide's own extent in FINEST cells, clamped to [0, X] /
+ * [0, Y].  Bounds the host keeps (annotations.Polygons refuses, never clamps): |coordinate| <= 2^29, extents <= 8192 cells = 2^29,
+ * V <= 2^20.  A sample point lies in [0, 2^29), so every difference of two coordinates is at most 2^30 in magnitude, each of the
+ * two products of t below at most 2^60 and t itself below 2^61: exact in int64.
+ *
+ * paths_polygon_cover: out int32 [B, X, ld] (ld >= Y); out[b, x, y] = the number of the s x s sample points of finest cell (x, y),
+ * s = samples in {1, 2, 4, 8, 16}, that lie inside the union of slide b's polygons; sample (i, j) is the point
+ * p = ((x << 16) + o_i, (y << 16) + o_j), o_i = ((2 i + 1) << 15) >> log2 s.  Polygon k contains p by the even-odd rule: the parity
+ * of its edges a -> b with (a.r > p.r) != (b.r > p.r) whose crossing lies beyond p.c, i.e. with d = b.r - a.r and
+ * t = (p.c - a.c) * d - (p.r - a.r) * (b.c - a.c) in int64: t < 0 when d > 0, t > 0 when d < 0.  A sample is inside when any polygon
+ * contains it (holes by parity within a polygon, none between polygons).  Cells outside the slide's own extent and columns [Y, ld)
+ * are written as 0: every element of out is written, none is read.  One launch for the batch: a workgroup owns 16 x 16 cells and
+ * streams the slide's edges, polygon by polygon, through one LDS tile of 256 edges, keeping an edge only when its row span meets the
+ * tile's sample rows and it does not lie wholly on the near side of the tile's sample columns (where no crossing can lie beyond p.c);
+ * an edge wholly beyond a cell's sample columns costs that cell the row test alone.  No atomics, no workspace; parity and union are
+ * order-free, so the result is bit-identical on repeat.  B <= 65535, X, Y <= 8192.
+ *
+ * paths_polygon_outline: draws every edge in place on uint8 RGB images, images DEVICE [B][2] int64 = (address of slide b's image
+ * [gx[b] c, gy[b] c, 3] with pixel stride 3, its row stride in bytes), c = cell_px in [1, 64].  An endpoint's pixel is
+ * floor(coordinate * c / 65536) per axis.  With (du, dv) the difference of the endpoint pixels and n = max(|du|, |dv|), the edge
+ * paints k = 0 .. n at (u0 + floor((2 k du + n) / (2 n)), v0 + floor((2 k dv + n) / (2 n))), for n = 0 the pixel (u0, v0) alone.  A
+ * painted pixel (u, v) is the square [u - width / 2, u - width / 2 + width) x [v - width / 2, ...) (integer division; width in
+ * [1, 7]), clipped to the slide's own extent, every byte triple of it = rgb (r | g << 8 | b << 16), opaque.  cum: DEVICE int32
+ * [V + 1], cum[e] = the sum of n + 1 over the edges before edge e (edge e starts at vertex e), steps = cum[V] < 2^31 - 256: one
+ * thread per (edge, step), one launch for the batch.  Every writer of a byte writes the same value, so the order of the writers
+ * cannot matter and the image is bit-identical on repeat; plain byte stores, no atomics.  Bytes no edge paints are neither read nor
+ * written. */
+int paths_polygon_cover(const int* verts, int V, const int* poly_off, int P, const int* slide_poly, const int* gx, const int* gy, int B, int X,
+                        int Y, int samples, int* out, int64_t ld, paths_stream_t stream);
+int paths_polygon_outline(const int* verts, int V, const int* poly_off, int P, const int* slide_poly, const int* gx, const int* gy, int B,
+                          const int* cum, int64_t steps, const int64_t* images, int cell_px, int width, uint32_t rgb, paths_stream_t stream);
 
 /* z = alpha * x (+ h on valid rows): importance scaling and the non-LSTM hierarchical-context add
  * (reference model/paths.py:96-109). */

@@ -397,8 +397,8 @@ def render(trace: List[dict], base_grids, kind: str = "importance", *, level: Op
     when ``min(u % s, v % s) == 0 or max(u % s, v % s) == s - 1``.
 
     Departures from the reference's drawing: nearest-neighbour pixels instead of a resampled image; integer blending; one-pixel outlines
-    instead of anti-aliased half-point lines; no viewport crop, colour bar or annotation polygons, which stay with whoever lays out the
-    figure.  The tensors are views, narrowed to each slide's extent, of one allocation padded to the batch's largest grid with every row
+    instead of anti-aliased half-point lines; no viewport crop or colour bar, which stay with whoever lays out the figure (annotation
+    polygons are drawn on the returned images by :func:`paths_amd.annotations.draw`).  The tensors are views, narrowed to each slide's extent, of one allocation padded to the batch's largest grid with every row
     starting 16-byte aligned; bytes outside the slides' extents are 0.  No CPU fallback."""
     if level is not None and fold is not None:
         raise ValueError("render: fold is the weight of the folded map (level=None); a single level has none")
